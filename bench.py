@@ -59,7 +59,43 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-workloads", action="store_true", help="skip the bounded C3 / C4-shaped 1-GPU measurements reported beside the headline")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32; rank 0's slab when item-sharded): "
+                         "the per-sub-epoch D and G losses, phase C's fake pairs and the model's tensors after the step; an array above "
+                         "%d values keeps a fixed, seeded sample of its rows" % DUMP_MAX_VALUES)
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if a.dump_outputs:
+        a.dump_outputs = os.path.abspath(a.dump_outputs)      # (the rank processes of N > 1 run from the repository root)
+    return a
+
+
+DUMP_MAX_VALUES = 1 << 19          # per array: 2 MB of float32, so the at most 32 arrays of a dump stay under 64 MB
+
+
+def dump_outputs(out_dir, tr, eng, data):
+    """--dump-outputs: the arrays a caller of the timed path holds after its last step, as float32 .npy files.  The inputs are seeded
+    (data, initial weights, shuffle order, RNG counters), so two builds run with the same arguments can be compared file by file."""
+    gen_names = ("W_q0", "W_q1", "W_p0", "W_p1", "b_q0", "b_q1", "b_p0", "b_p1")
+    arrays = {"d_losses": tr.d_losses, "g_losses": tr.g_losses,
+              "fake_cnt": data.fake_cnt, "fake_gen": data.fake_gen, "fake_pop": data.fake_pop}
+    arrays.update(("gen_" + n, t) for n, t in zip(gen_names, eng.generator_params_tf()))     # (flushes the lazy Adam clock of W_q0)
+    arrays.update(("disc_%d" % i, t) for i, t in enumerate(eng.discriminator_params_tf()))
+    assert len(arrays) <= 32
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        x = t.detach().float().cpu().numpy()
+        rows = x.reshape(x.shape[0], -1) if x.ndim else x.reshape(1, 1)
+        if rows.size > DUMP_MAX_VALUES:
+            keep = max(1, DUMP_MAX_VALUES // rows.shape[1])
+            pick = np.sort(np.random.default_rng(20240607).choice(rows.shape[0], keep, replace=False))
+            x = rows[pick]
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        total += x.nbytes
+        np.save(os.path.join(out_dir, name + ".npy"), x)
+    assert total <= 64 << 20, total
 
 
 def load_workload(name, batch_size, device, users=None):
@@ -516,6 +552,8 @@ def self_launch(a):
     # --rdzv-endpoint 127.0.0.1:0 lets the launcher's own store pick a free port (no bind-then-close race in this process)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(a.gpus), "--rdzv-backend", "c10d",
            "--rdzv-endpoint", "127.0.0.1:0", "--local-addr", "127.0.0.1", os.path.abspath(__file__)] + sys.argv[1:]
+    if a.dump_outputs:
+        cmd += ["--dump-outputs", a.dump_outputs]      # (absolute: the ranks run from the repository root)
     proc = subprocess.Popen(cmd, stdout=subprocess.PIPE, text=True, env=env, cwd=ROOT)
     last_json = None
     for line in proc.stdout:
@@ -780,6 +818,8 @@ def main():
         barrier()
         dt = time.perf_counter() - t0
         tr.probe_hook = None
+        if a.dump_outputs and rank == 0:
+            dump_outputs(a.dump_outputs, tr, eng, data)
         if world > 1:
             t = torch.tensor([dt], dtype=torch.float64, device=device)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)

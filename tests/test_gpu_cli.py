@@ -111,6 +111,25 @@ def test_train_cli_under_torchrun_item_sharded(tmp_path):
     assert "Restored" in out.stdout and "global-epoch: 1 Data Creation Finished" in out.stdout
 
 
+def test_bench_dump_outputs_of_the_timed_step(tmp_path):
+    """--dump-outputs DIR: after the timed steps bench.py writes the last step's losses, fake pairs and model tensors as float32 .npy files
+    (under 64 MB), and --steps sets the number of timed steps that ms_per_step divides."""
+    import json
+    import numpy as np
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--sub-epochs", "2", "--no-probe",
+                          "--no-cpu-baseline", "--no-other-workloads", "--dump-outputs", str(tmp_path / "dump")],
+                         capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-3000:]
+    d = json.loads(out.stdout.strip().splitlines()[-1])
+    assert d["steps"] == 2 and d["ms_per_step"] > 0 and abs(d["value"] * d["ms_per_step"] * 1e-3 - d["config"]["users"]) < 1e-6 * d["config"]["users"]
+    files = {p.name: np.load(p) for p in (tmp_path / "dump").iterdir()}
+    assert {"d_losses.npy", "g_losses.npy", "fake_cnt.npy", "fake_gen.npy", "gen_W_q0.npy", "disc_0.npy"} <= set(files)
+    assert all(x.dtype == np.float32 for x in files.values()) and sum(x.nbytes for x in files.values()) <= 64 << 20
+    assert files["d_losses.npy"].shape == (2, 8) and np.all(np.isfinite(files["d_losses.npy"][:, 0])) and np.all(np.isfinite(files["g_losses.npy"][:, :3]))
+    assert files["fake_cnt.npy"].shape == (d["config"]["batches"],) and files["fake_cnt.npy"].sum() > 0
+    assert files["gen_W_q0.npy"].shape[1] == 600 and np.all(np.isfinite(files["gen_W_q0.npy"]))
+
+
 def test_bench_contract_one_json_line():
     """bench.py prints ONE JSON line (the last line of stdout) carrying the driver's keys plus roofline and cpu_baseline."""
     import json

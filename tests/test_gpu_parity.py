@@ -293,6 +293,18 @@ def _g_step_case(precision, I, B, path, warm):
     batch = _upload_batch(eng, X, with_csc=True)
     acts = eng.new_acts(B)
     eng.adam_t = t0  # exercise the shared counter
+    if path.startswith("one-call") and not q:
+        # ltg_g_step_sharded serves the bf16 decoder path only: an fp32 engine is refused before any launch (a trainer then takes
+        # ltg_g_step), and that step is held to the same oracle below
+        from ltgan._cabi import LtgError
+        assert not eng.sharded_step_ok(B)
+        before = [t.clone() for t in eng.g_p]
+        with pytest.raises(LtgError, match="ltg_g_step_sharded"):
+            eng.g_step_sharded(batch, fake, acts, eng.g_opts(cnt_t, anneal, lam, keep, 1.0, dkeep, step, dstep), Pipe(eng, B))
+        torch.cuda.synchronize()
+        assert all(torch.equal(a, b) for a, b in zip(before, eng.g_p))     # refused: no launch, the model is untouched
+        eng.adam_t = t0                      # (g_opts drew the shared counter for a step that never ran)
+        path = "step"
     if path.startswith("one-call"):
         assert eng.sharded_step_ok(B)
         pipe = Pipe(eng, B)
@@ -338,11 +350,8 @@ def test_g_step_parity(precision, I, B, path):
     """path "step": ltg_g_step.  "one-call": ltg_g_step_sharded without a communicator (the G step of every large item slab:
     bias + tanh and the tanh derivative folded into operand loaders, weight update and clock slice forked) -- same oracle, same
     tolerances.  I = 6 000: the middle-layer fast path without the streaming decoder kernels (4 096 < I < 8 192); I = 25 024: the
-    slab one of eight ranks owns at 200 000 items.  "-config-d": config.ini's discriminator sizes inside the G step."""
-    if I >= 20000 and precision != "bf16":
-        pytest.skip("BASELINE configs 3 / 4 run the bf16 decoder path")
-    if path.startswith("one-call") and precision != "bf16":
-        pytest.skip("ltg_g_step_sharded serves the bf16 decoder path")
+    slab one of eight ranks owns at 200 000 items.  "-config-d": config.ini's discriminator sizes inside the G step.  fp32: the one-call
+    step refuses the engine and ltg_g_step is checked instead; at I >= 20 000 the fp32 decoder (BASELINE configs 3 / 4 run bf16) is checked too."""
     _g_step_case(precision, I, B, path, warm=False)
 
 
@@ -363,9 +372,8 @@ def test_g_step_adam_quotient_from_warm_moments(precision, I, B, path):
 @pytest.mark.parametrize("nr,nf", [(900, 950), (33, 7), (1, 0), (0, 5), (260, 250)])
 def test_d_step_parity(nr, nf, d_arith):
     """d_arith (ltg_config.d_arith): the exact fp32 MFMA and the six-term bf16 split of the same fp32 operands -- SAME bounds (the split leaves
-    out 2^-26 per product, below fp32's own rounding); the wide sizes (260, 250) do not take the latency-path kernels: one arithmetic"""
-    if d_arith != "fp32" and nr == 260:
-        pytest.skip("config-5 sizes run the LDS-staged kernels: d_arith does not apply")
+    out 2^-26 per product, below fp32's own rounding); the wide sizes (260, 250) do not take the latency-path kernels: one arithmetic, so
+    either setting must meet the fp32 bounds there"""
     _d_step_case(nr, nf, warm=False, d_arith=d_arith)
 
 
@@ -386,9 +394,7 @@ def test_d_step_parity_of_the_generic_kernels(nr, nf):
 @pytest.mark.parametrize("nr,nf", [(900, 950), (33, 7), (260, 250)])
 def test_d_step_adam_quotient_from_warm_moments(nr, nf, d_arith):
     """The D step from injected non-zero Adam moments at shared step t = 212 (train.py:160-163): the flat Adam sweep's theta move,
-    m and v element-wise against oracle.SharedAdam."""
-    if d_arith != "fp32" and nr == 260:
-        pytest.skip("config-5 sizes run the LDS-staged kernels: d_arith does not apply")
+    m and v element-wise against oracle.SharedAdam (config-5 sizes: the LDS-staged kernels whatever d_arith says)."""
     _d_step_case(nr, nf, warm=True, d_arith=d_arith)
 
 

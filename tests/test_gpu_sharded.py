@@ -33,28 +33,30 @@ def test_two_rank_item_sharding_matches_unsharded(workload, users, precision, mo
     assert out.returncode == 0 and "SHARDED_OK" in out.stdout, out.stdout[-3000:] + out.stderr[-6000:]
 
 
-@pytest.mark.parametrize("workload,users,precision,mode", [("c4", 200, "bf16", ""), ("ml20m", 200, "bf16", ""), ("c4", 200, "bf16", "wide_fp8_full"),
-                                                           ("custom:65600", 200, "bf16", "")])
-def test_eight_rank_item_sharding_matches_unsharded(workload, users, precision, mode):
-    """World size 8 -- the node the split is built for -- on the rig a 1-GPU box allows: eight gloo ranks sharing cuda:0, every rank also
-    running the unsharded trainer it is compared with.  c4: 200 000 items = seven slabs of 25 024 and one of 24 832 (the uneven last
-    slab), `rowpart_all [8][B][5]`, the one-call step on every rank; with "wide_fp8_full" config 5's discriminator pair-split over 8
-    ranks.  ml20m: 20 000 items = 2 560-item slabs, below the one-call step's 8 192 -- every rank agrees on the cut-point sequence
-    (the worker asserts which path ran).  custom:65600: slabs of 8 256 items and a last one of 7 808 < 8 192 -- ONE rank's slab is too
-    small for the one-call step, so all eight must agree on the cut-point sequence (`ShardedTrainer._init_sharded_step`)."""
+@pytest.mark.parametrize("workload,users,precision,mode", [("custom:99904", 200, "bf16", ""), ("custom:99904", 200, "bf16", "wide_fp8_full"),
+                                                           ("ml20m", 200, "bf16", ""), ("custom:32896", 200, "bf16", "")])
+def test_four_rank_item_sharding_matches_unsharded(workload, users, precision, mode):
+    """Four gloo ranks sharing cuda:0 (the suite keeps at most four rank processes on one GPU), every rank also running the unsharded trainer
+    it is compared with.  custom:99904: three slabs of 25 024 items and one of 24 832 -- the slabs of an 8-rank run of BASELINE config 4's
+    200 000 items, uneven last slab included -- with the one-call step on every rank; with "wide_fp8_full" config 5's discriminator
+    pair-split over the ranks.  ml20m: 20 000 items = 5 056-item
+    slabs, below the one-call step's 8 192 -- every rank agrees on the cut-point sequence (the worker asserts which path ran).
+    custom:32896: three slabs of 8 256 items and a last one of 8 128 < 8 192 -- ONE rank's slab is too small for the one-call step, so all
+    four must agree on the cut-point sequence (`ShardedTrainer._init_sharded_step`)."""
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="2")
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
-           "--master-port", "29581", os.path.join(ROOT, "tests", "dist_shard_worker.py"), workload, str(users), precision] + ([mode] if mode else [])
-    out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=2400)      # fresh children only
-    assert out.returncode == 0 and "SHARDED_OK world=8" in out.stdout, out.stdout[-3000:] + out.stderr[-6000:]
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr", "127.0.0.1",
+           "--master-port", "29587", os.path.join(ROOT, "tests", "dist_shard_worker.py"), workload, str(users), precision] + ([mode] if mode else [])
+    out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=1500)      # fresh children only
+    assert out.returncode == 0 and "SHARDED_OK world=4" in out.stdout, out.stdout[-3000:] + out.stderr[-6000:]
 
 
-@pytest.mark.parametrize("world,workload,users", [(2, "c4", 200), (8, "c4", 200)])
+@pytest.mark.parametrize("world,workload,users", [(2, "c4", 200), (4, "custom:99904", 200)])
 def test_one_shot_exchange_equals_the_rank_ordered_host_transport(world, workload, users):
     """The second transport behind ltg_comm (csrc/ltg_oneshot.h, ltgan._rccl.OneShotComm; SURVEY 8/e1's one-shot exchange for the <= 240-KB
     messages): every rank's staging buffer mapped into every peer through HIP IPC, one kernel per exchange, contributions added in rank order.
     Against host callbacks that add in the same order the two-epoch run must leave the same bits on every rank -- fake pairs, losses, every
-    generator tensor and Adam moment -- at world sizes 2 and 8 (c4: 100 000-item slabs / seven slabs of 25 024 items and one of 24 832).
+    generator tensor and Adam moment -- at world sizes 2 and 4 (c4: 100 000-item slabs / custom:99904: three slabs of 25 024 items and one of
+    24 832, the slabs and message sizes of an 8-rank run of c4).
     Correctness only: RCCL stays the transport of every measurement."""
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="2", LTGAN_ONESHOT_LIMIT_MS="20000")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",

@@ -571,6 +571,21 @@ int ltg_rank_counts(const ltg_config* cfg, const float* logits, const ltg_batch*
 int ltg_rank_finish(const ltg_batch* te, const int32_t* counts, int32_t k_ndcg, int32_t k_r1, int32_t k_r2,
                     float* out, ltg_stream stream);
 
+/* Top-K recommendations on device (the reference ranks users' items only to score them, Codes/test.py:135-171).
+ * ltg_topk: per row of logits [n_rows][cfg->n_items] (this rank's slab; global id = cfg->item_lo + column) the k best
+ * items, fold-in items of tr (LOCAL column ids, like ltg_rank_metrics; ascending per row; tr may be NULL = no fold-in)
+ * excluded: score_out [n_rows][k] = the logits, id_out [n_rows][k] = GLOBAL ids.  Order: score descending, equal scores
+ * lower global id first (the rank ltg_rank_metrics counts, so Recall@k from the ids equals its Recall@k); -0.0 == +0.0;
+ * -inf logits are eligible; a row with fewer than k eligible items is padded with id -1 / score -inf; NaN logits are
+ * outside the contract.  1 <= k <= 1024, n_items <= 360 448; bit-identical from run to run.
+ * ltg_topk_merge: the top-k of the union of n_parts lists per row, score_in / id_in [n_parts][n_rows][k_in], each list
+ * sorted and padded as ltg_topk writes it, over disjoint item sets (the slabs of an item-sharded run, gathered): for
+ * slabs cut from one row it equals ltg_topk on the whole row bit for bit.  1 <= k_in, k <= 1024. */
+int ltg_topk(const ltg_config* cfg, const float* logits, const ltg_batch* tr, int32_t n_rows, int32_t k, float* score_out,
+             int32_t* id_out, ltg_stream stream);
+int ltg_topk_merge(int32_t n_parts, int32_t n_rows, int32_t k_in, const float* score_in, const int32_t* id_in, int32_t k,
+                   float* score_out, int32_t* id_out, ltg_stream stream);
+
 /* Verification helper of the LTG_PREC_FP8 mode: out[i] = the value the fp8 GEMM operands carry for in[i]
  * (clamp to +-448, round to nearest-even OCP e4m3) -- lets a test pin its CPU model of the rounding to the hardware. */
 int ltg_fp8_roundtrip(const float* in, float* out, int32_t n, ltg_stream stream);

@@ -171,6 +171,7 @@ __global__ __launch_bounds__(64) void k_gate_set(LtgGate g, LtgGate g2 = LTG_NO_
 #include "ltg_gstep.h"
 #include "ltg_clock.h"
 #include "ltg_sampler.h"
+#include "ltg_topk.h"
 
 // ---------------------------------------------------------------------------------------------
 // host side
@@ -1791,6 +1792,36 @@ int ltg_rank_metrics(const ltg_config* cfg, const float* logits, const ltg_batch
     if (lds > 64 * 1024) return LTG_EINVAL;
     hipLaunchKernelGGL(k_rank_metrics, dim3(tr->n_rows), dim3(NT), lds, (hipStream_t)stream, cfg->n_items, cfg->item_lo, logits,
                        tr->indptr, tr->indices, te->indptr, te->indices, (const float*)nullptr, (int32_t*)nullptr, k_ndcg, k_r1, k_r2, out);
+    return check_launch();
+}
+
+int ltg_topk(const ltg_config* cfg, const float* logits, const ltg_batch* tr, int32_t n_rows, int32_t k, float* score_out, int32_t* id_out,
+             ltg_stream stream) {
+    clear_errors();
+    if (!cfg || !logits || !score_out || !id_out || cfg->n_items <= 0 || n_rows < 0 || k < 1 || k > 1024) return LTG_EINVAL;
+    if (tr && (!tr->indptr || !tr->indices || tr->n_rows != n_rows)) return LTG_EINVAL;
+    if (n_rows == 0) return LTG_OK;
+    // dynamic LDS: the fold-in bitset, then the candidate buffer (64-bit words; the largest power of two <= 4096 that fits, >= 1024)
+    const size_t bits = (size_t)((cfg->n_items + 63) / 64) * 8;
+    size_t cap = 4096;
+    while (cap >= 1024 && bits + cap * 8 > 60 * 1024) cap >>= 1;
+    if (cap < 1024) return LTG_EINVAL;
+    const size_t lds = bits + cap * 8;
+    const bool vec = (cfg->n_items % 4) == 0 && ((uintptr_t)logits % 16) == 0;
+    auto kern = vec ? k_topk<true> : k_topk<false>;
+    hipLaunchKernelGGL(kern, dim3(n_rows), dim3(TK_NT), lds, (hipStream_t)stream, cfg->n_items, cfg->item_lo, logits,
+                       tr ? tr->indptr : (const int32_t*)nullptr, tr ? tr->indices : (const int32_t*)nullptr, k, (int)cap, score_out, id_out);
+    return check_launch();
+}
+
+int ltg_topk_merge(int32_t n_parts, int32_t n_rows, int32_t k_in, const float* score_in, const int32_t* id_in, int32_t k, float* score_out,
+                   int32_t* id_out, ltg_stream stream) {
+    clear_errors();
+    if (!score_in || !id_in || !score_out || !id_out || n_parts < 1 || n_rows < 0 || k_in < 1 || k_in > 1024 || k < 1 || k > 1024)
+        return LTG_EINVAL;
+    if (n_rows == 0) return LTG_OK;
+    hipLaunchKernelGGL(k_topk_merge, dim3(n_rows), dim3(NT), 0, (hipStream_t)stream, n_parts, n_rows, k_in, score_in, id_in, k, score_out,
+                       id_out);
     return check_launch();
 }
 

@@ -731,6 +731,26 @@ class Engine:
     def rank_finish(self, te, counts, out, k_ndcg=100, k_r1=20, k_r2=50):
         cabi.check(self.lib.ltg_rank_finish(C.byref(te.c), _ptr(counts), k_ndcg, k_r1, k_r2, _ptr(out), self.stream()), "ltg_rank_finish")
 
+    # ------------------------------------------------------------------ top-K recommendations
+    def topk(self, logits_or_acts, tr, k, score_out, id_out):
+        """the k best items of each of the score_out.shape[0] rows of this slab's logits (an Acts or a [rows, I] float32 tensor),
+        fold-in items of `tr` (a CsrRows with LOCAL ids, or None) excluded: score_out [rows, k] float32, id_out [rows, k] int32 GLOBAL
+        ids (ltg_topk: score descending, ties lower id first, padding id -1 / score -inf)."""
+        logits = logits_or_acts.logits if isinstance(logits_or_acts, Acts) else logits_or_acts
+        n = int(score_out.shape[0])
+        assert logits.dtype == torch.float32 and logits.numel() >= n * self.I and tuple(id_out.shape) == tuple(score_out.shape) == (n, k)
+        assert score_out.is_contiguous() and id_out.is_contiguous() and id_out.dtype == torch.int32
+        cabi.check(self.lib.ltg_topk(C.byref(self.cfg), _ptr(logits), C.byref(tr.c) if tr is not None else None, n, int(k),
+                                     _ptr(score_out), _ptr(id_out), self.stream()), "ltg_topk")
+
+    def topk_merge(self, score_in, id_in, k, score_out, id_out):
+        """top-k of the union of the per-slab lists score_in / id_in [parts, rows, k_in] (each as topk writes it) -> [rows, k]"""
+        parts, n, k_in = (int(x) for x in score_in.shape)
+        assert tuple(id_in.shape) == (parts, n, k_in) and tuple(score_out.shape) == tuple(id_out.shape) == (n, k)
+        assert score_in.is_contiguous() and id_in.is_contiguous() and score_out.is_contiguous() and id_out.is_contiguous()
+        cabi.check(self.lib.ltg_topk_merge(parts, n, k_in, _ptr(score_in), _ptr(id_in), int(k), _ptr(score_out), _ptr(id_out),
+                                           self.stream()), "ltg_topk_merge")
+
     # ------------------------------------------------------------------ views in the reference's shapes
     def generator_params_tf(self):
         """The 8 tensors in the reference's order and TF shapes (MultiVAE.py:129-141); W_p1 is a

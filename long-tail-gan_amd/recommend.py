@@ -1,0 +1,134 @@
+#!/usr/bin/env python3
+"""Recommendation CLI with test.py's surface:
+
+    cd <dir holding config.ini> && python <repo>/long-tail-gan_amd/recommend.py <dataset_dir> <checkpoint>
+        [--k 100] [--split test|validation] [--keep-prob 0.75] [--out recs.tsv] [--npz recs.npz]
+
+restores a checkpoint written by train.py, runs test.py's forward over the users of `<split>_tr.csv` (chunks of 20 000 users,
+dropout on with keep_prob 0.75 by default: Q3, RNG counter 2*10^9 + first row of the chunk) and keeps each user's k best items, the
+fold-in items excluded (ltg_topk; the logits never leave the GPU).  Writes one TSV line per user, `uid<TAB>sid_1,sid_2,...` in rank
+order (uid = the CSV's uid, sid = its item column), and with --npz the arrays uids / ids / scores (logits).  The last stdout line
+summarises the long tail: users, niche share@k (recommended slots that are niche items, load_pop_niche_tags' NICHE_TAGS), coverage@k
+(distinct recommended items / n_items) and Recall@20 against `<split>_te.csv` (averaged over the users with held-out items, as
+test.py averages).  Under `python -m torch.distributed.run --nproc-per-node N` the items are sharded as in test.py; rank 0 writes.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+
+import numpy as np
+
+if __package__ in (None, ""):
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import ltgan  # noqa: F401  (alias of this package directory)
+    from ltgan import data_processing as dp
+else:
+    from . import data_processing as dp
+
+RNG_STEP = 2 * 10 ** 9        # test.py's counter: with the defaults the forward is the one test.py scores
+
+
+def parse_args(argv):
+    ap = argparse.ArgumentParser(prog="recommend.py", description="top-K recommendations from a Long-Tail-GAN checkpoint")
+    ap.add_argument("dataset_dir")
+    ap.add_argument("checkpoint")
+    ap.add_argument("--k", type=int, default=100)
+    ap.add_argument("--split", choices=("test", "validation"), default="test")
+    ap.add_argument("--keep-prob", type=float, default=0.75)
+    ap.add_argument("--out", default="recs.tsv")
+    ap.add_argument("--npz", default=None)
+    a = ap.parse_args(argv)
+    if not 1 <= a.k <= 1024:
+        ap.error("--k must be in [1, 1024]")
+    if not 0.0 < a.keep_prob <= 1.0:
+        ap.error("--keep-prob must be in (0, 1]")
+    return a
+
+
+def write_recs(ids, scores, uid_start, tsv_path=None, npz_path=None):
+    """ids / scores [n_users, k] (padding id -1 dropped from the TSV); row r is uid uid_start + r; the ids are the CSV's sids."""
+    ids = np.asarray(ids)
+    uids = np.arange(ids.shape[0], dtype=np.int64) + int(uid_start)
+    if tsv_path:
+        with open(tsv_path, "w") as f:
+            for u, row in zip(uids.tolist(), ids.tolist()):
+                f.write("%d\t%s\n" % (u, ",".join(str(i) for i in row if i >= 0)))
+    if npz_path:
+        np.savez(npz_path, uids=uids, ids=ids.astype(np.int32), scores=np.asarray(scores, np.float32))
+    return uids
+
+
+def long_tail_summary(ids, niche, n_items, te=None, k_recall=20):
+    """users, niche share@k, coverage@k and Recall@k_recall (te: held-out CSR, rows aligned with ids; None -> nan)"""
+    ids = np.asarray(ids)
+    valid = ids >= 0
+    rec = ids[valid]
+    niche_arr = np.zeros(n_items, bool)
+    niche_arr[np.fromiter((int(x) for x in niche), np.int64, len(niche))] = True
+    out = dict(users=int(ids.shape[0]), niche_share=float(niche_arr[rec].mean()) if rec.size else float("nan"),
+               coverage=float(np.unique(rec).size) / n_items, recall20=float("nan"))
+    if te is not None and ids.shape[1] >= k_recall:
+        te = te.tocsr()
+        rs = []
+        for r in range(ids.shape[0]):
+            held = te.indices[te.indptr[r]:te.indptr[r + 1]]
+            if held.size == 0:
+                continue                                  # test.py drops users without held-out items (IDCG == 0)
+            top = ids[r, :k_recall]
+            rs.append(np.isin(top[top >= 0], held).sum() / min(k_recall, held.size))
+        out["recall20"] = float(np.mean(rs)) if rs else float("nan")
+    return out
+
+
+def summary_line(m, k):
+    return "users: %d\tniche_share@%d: %.6f\tcoverage@%d: %.6f\tRecall@20: %.9f" % (m["users"], k, m["niche_share"], k, m["coverage"], m["recall20"])
+
+
+def recommend(args, h0_size, h1_size, h2_size, h3_size, LEARNING_RATE, precision="bf16", batch_size_test=20000, **_):
+    import builtins
+    import torch
+    from ltgan.dataset import EvalData, count_items
+    from ltgan.generator import generator_VAECF as generator
+    from ltgan.sharded import ShardedRecommender, item_slab
+    from ltgan.train import load_checkpoint
+    from ltgan.trainer import Recommender
+    from ltgan.test import _Counters
+    world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
+    device = "cuda:%d" % (int(os.environ.get("LOCAL_RANK", "0")) % max(1, torch.cuda.device_count()))
+    if world > 1:
+        import torch.distributed as dist
+        if not dist.is_initialized():
+            dist.init_process_group(os.environ.get("LTGAN_DIST_BACKEND", "nccl"))
+    print = builtins.print if rank == 0 else (lambda *a, **k: None)                      # noqa: A001
+    d = args.dataset_dir
+    n_items = count_items(d)
+    tr, te, uid0 = dp.load_tr_te_data(os.path.join(d, "%s_tr.csv" % args.split), os.path.join(d, "%s_te.csv" % args.split), n_items)
+    _, _, niche, _, _ = dp.load_pop_niche_tags(os.path.join(d, "item2id.txt"), os.path.join(d, "item_list.txt"),
+                                               os.path.join(d, "niche_items.txt"), n_items)
+    lo, hi = item_slab(n_items, rank, world) if world > 1 else (0, n_items)
+    gen_net, *_ = generator(d + "/", h_sizes=(h0_size, h1_size, h2_size, h3_size), lr=LEARNING_RATE, precision=precision,
+                            device=device, item_lo=lo, item_hi=hi)
+    eng = gen_net.engine
+    load_checkpoint(args.checkpoint, eng, _Counters())
+    if world > 1:
+        rec = ShardedRecommender(eng, EvalData(tr, te, eng.device, item_lo=lo, item_hi=hi), k=args.k, chunk=batch_size_test)
+    else:
+        rec = Recommender(eng, EvalData(tr, te, eng.device), k=args.k, chunk=batch_size_test)
+    ids, scores = rec.run(rng_step=RNG_STEP, keep_prob=args.keep_prob)
+    m = long_tail_summary(ids, niche, n_items, te)
+    if rank == 0:
+        write_recs(ids, scores, uid0, args.out, args.npz)
+    print(summary_line(m, args.k))
+    if world > 1:
+        import torch.distributed as dist
+        dist.barrier()
+        dist.destroy_process_group()
+    return ids, scores, m
+
+
+if __name__ == "__main__":
+    a = parse_args(sys.argv[1:])
+    from ltgan.train import read_config
+    recommend(a, **read_config())

@@ -314,3 +314,44 @@ class ShardedEvaluator:
         n = int(ok.sum())
         return dict(ndcg=float(o[ok, 0].mean()) if n else float("nan"), recall20=float(o[ok, 1].mean()) if n else float("nan"),
                     recall50=float(o[ok, 2].mean()) if n else float("nan"), n_users=n)
+
+
+class ShardedRecommender:
+    """Top-K recommendations over item shards: per chunk of users the sharded forward of ShardedEvaluator, ltg_topk on this
+    rank's slab (global ids), ONE all-gather of the [R][rows][k] candidate lists (scores and ids; a list all-gather works over
+    gloo as well as nccl), then ltg_topk_merge.  Every rank ends with the identical table."""
+
+    def __init__(self, engine, ev, k=100, group=None, chunk=20000):
+        self.eng, self.ev, self.group, self.k = engine, ev, group, int(k)
+        self.R = dist.get_world_size(group)
+        self.chunk = int(min(chunk, max(1, ev.n), eval_chunk_rows(engine.I)))
+        self.acts = engine.new_acts(self.chunk)
+        dev = engine.device
+        self.rowpart = torch.zeros(self.chunk * 5, dtype=torch.float32, device=dev)
+        self.part_s = torch.empty(self.R, self.chunk, self.k, dtype=torch.float32, device=dev)
+        self.part_i = torch.empty(self.R, self.chunk, self.k, dtype=torch.int32, device=dev)
+        self.loc_s = torch.empty(self.chunk, self.k, dtype=torch.float32, device=dev)
+        self.loc_i = torch.empty(self.chunk, self.k, dtype=torch.int32, device=dev)
+        self.scores = torch.empty(ev.n, self.k, dtype=torch.float32, device=dev)
+        self.ids = torch.empty(ev.n, self.k, dtype=torch.int32, device=dev)
+
+    def run(self, rng_step=0, keep_prob=0.75):
+        """-> (ids [n_users, k], scores [n_users, k]) host arrays, identical on every rank"""
+        eng, ev, k = self.eng, self.ev, self.k
+        for lo in range(0, ev.n, self.chunk):
+            hi = min(ev.n, lo + self.chunk)
+            n = hi - lo
+            tr, _ = ev.rows(lo, hi)
+            fo = eng.fwd_opts(keep_prob, 0.0, rng_step + lo)
+            eng.g_fwd_enc(tr, self.acts, fo)
+            dist.all_reduce(self.acts.h1[:n], op=dist.ReduceOp.SUM, group=self.group)
+            eng.g_fwd_rest(tr, None, self.acts, fo, self.rowpart)
+            ls, li = self.loc_s[:n], self.loc_i[:n]
+            eng.topk(self.acts, tr, k, ls, li)
+            ps, pi = self.part_s[:, :n], self.part_i[:, :n]
+            if n < self.chunk:                       # (a short last chunk: contiguous [R][n][k] blocks)
+                ps, pi = ps.contiguous(), pi.contiguous()
+            dist.all_gather(list(ps.unbind(0)), ls, group=self.group)
+            dist.all_gather(list(pi.unbind(0)), li, group=self.group)
+            eng.topk_merge(ps, pi, k, self.scores[lo:hi], self.ids[lo:hi])
+        return self.ids.cpu().numpy(), self.scores.cpu().numpy()

@@ -276,3 +276,27 @@ class Evaluator:
         n = int(ok.sum())
         return dict(ndcg=float(o[ok, 0].mean()) if n else float("nan"), recall20=float(o[ok, 1].mean()) if n else float("nan"),
                     recall50=float(o[ok, 2].mean()) if n else float("nan"), n_users=n)
+
+
+class Recommender:
+    """Top-K recommendations per user (the forward of Evaluator, then ltg_topk instead of the metrics): the same chunks of
+    `chunk` users capped by eval_chunk_rows, the same dropout-on forward (Q3) with counter rng_step + lo per chunk, fold-in
+    items excluded.  keep_prob = 1.0 gives dropout-free, deterministic recommendations."""
+
+    def __init__(self, engine: Engine, ev: EvalData, k=100, chunk=20000):
+        self.eng, self.ev, self.k = engine, ev, int(k)
+        self.chunk = int(min(chunk, max(1, ev.n), eval_chunk_rows(engine.I)))
+        self.acts = engine.new_acts(self.chunk)
+        dev = engine.device
+        self.scores = torch.empty(ev.n, self.k, dtype=torch.float32, device=dev)
+        self.ids = torch.empty(ev.n, self.k, dtype=torch.int32, device=dev)
+
+    def run(self, rng_step=0, keep_prob=0.75):
+        """-> (ids [n_users, k] int32 global item ids, scores [n_users, k] float32 logits) as host arrays"""
+        eng, ev = self.eng, self.ev
+        for lo in range(0, ev.n, self.chunk):
+            hi = min(ev.n, lo + self.chunk)
+            tr, _ = ev.rows(lo, hi)
+            eng.forward(tr, self.acts, keep_prob=keep_prob, is_training=0.0, rng_step=rng_step + lo)
+            eng.topk(self.acts, tr, self.k, self.scores[lo:hi], self.ids[lo:hi])
+        return self.ids.cpu().numpy(), self.scores.cpu().numpy()

@@ -56,7 +56,7 @@ typedef struct ltg_config {
     int32_t h_enc;   /* H = p_dims[1] = 600 */
     int32_t z_dim;   /* Z = p_dims[0] = 200 */
     int32_t d_feat;  /* FEATURE_LEN: rows of the frozen embedding table */
-    int32_t d_h0, d_h1, d_h2, d_h3;
+    int32_t d_h0, d_h1, d_h2, d_h3; /* discriminator layer widths, each >= 1 (else LTG_EINVAL) */
     int32_t precision; /* LTG_PREC_* */
     /* kernel selection knob, 0 = auto; every setting computes the same function (ABI v14: was `reserved0`).
      * STABLE bits -- the host layer and the parity tests select code paths with them:

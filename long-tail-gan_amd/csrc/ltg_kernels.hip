@@ -392,6 +392,7 @@ inline bool small_fast(const ltg_config* c, int rows) {
 
 bool cfg_ok(const ltg_config* c) {
     return c && c->n_items > 0 && c->h_enc > 0 && c->h_enc <= 768 && (c->h_enc % 4) == 0 && c->z_dim > 0 &&
+           c->d_h0 >= 1 && c->d_h1 >= 1 && c->d_h2 >= 1 && c->d_h3 >= 1 &&      // (a layer of width 0 has no tile to launch: refused, not computed)
            (c->precision == LTG_PREC_BF16 || c->precision == LTG_PREC_FP32) && c->d_precision >= 0 && c->d_precision <= LTG_PREC_FP8 &&
            c->d_arith >= 0 && (c->d_arith & 3) <= LTG_DARITH_BF16X4 && (c->d_arith & ~0xF3) == 0;
 }

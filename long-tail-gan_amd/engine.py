@@ -217,6 +217,12 @@ class DFork:
 D_ARITH_DEFAULT = "bf16x6"
 
 
+def _check_d_sizes(h_sizes):
+    """the library refuses (LTG_EINVAL, before any launch) a discriminator with a layer of width < 1: say so at construction"""
+    if len(h_sizes) != 4 or min(int(x) for x in h_sizes) < 1:
+        raise ValueError("discriminator layer sizes must be four widths of at least 1, got %r" % (tuple(h_sizes),))
+
+
 class Engine:
     def __init__(self, n_items, h_sizes=(100, 150, 250, 300), lr=1e-4, p_dims=None, feature_len=None,
                  precision="bf16", seed=98765, d_seed=0, device="cuda:0", beta1=0.9, beta2=0.999, eps=1e-8,
@@ -230,6 +236,7 @@ class Engine:
         lazy_q0: lazy Adam clock of W_q0 (include/ltg.h, ltg_gen_state.q0_last; same results as the dense sweep).  None = on
         for item slabs of 8192 items or more.  Rows are brought up to date by every forward that reads them; `g_flush()`
         does it for all rows and runs after every G step unless a trainer holds `q0_defer` for the length of its phase."""
+        _check_d_sizes(h_sizes)
         self.lib = cabi.load()
         import weakref
         self._pipes = weakref.WeakSet()                              # the Pipe objects created for this engine (check_pipes)
@@ -336,6 +343,7 @@ class Engine:
     def resize_discriminator(self, h_sizes, feature_len=None, d_seed=0):
         """Re-create the discriminator part for other layer sizes (discriminator.py:3: the sizes are arguments of the
         factory, not of the generator): fresh truncated-normal variables, zero Adam moments, new workspace."""
+        _check_d_sizes(h_sizes)
         self.h0, self.h1, self.h2, self.h3 = (int(x) for x in h_sizes)
         if feature_len is not None:
             self.feature_len = int(feature_len)

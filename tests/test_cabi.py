@@ -122,6 +122,26 @@ def test_argument_validation_returns_codes_without_gpu():
     assert os_.seq == 0                                                                                            # nothing was issued
 
 
+def test_discriminator_layer_widths_below_one_are_refused_without_gpu():
+    """A layer of width 0 (or less) has nothing to compute: LTG_EINVAL / zero sizes from every entry point before any launch, and a ValueError
+    from Engine before it touches the library.  Width 1 is a valid discriminator (tests/test_gpu_parity.py holds (1, 1, 1, 1) and (4, 1, 3, 4)
+    to the oracle)."""
+    from ltgan import _cabi as cabi
+    from ltgan.engine import Engine
+    lib = cabi.load()
+    mk = lambda hs: cabi.ltg_config(1000, 600, 200, 1000, *hs, 0, 0, 0, 0, 1, 0, 1e-4, 0.9, 0.999, 1e-8, 1)
+    for hs in ((1, 1, 1, 1), (4, 1, 3, 4)):
+        c = mk(hs)
+        assert lib.ltg_workspace_bytes(C.byref(c), 100, 2000) > 0 and lib.ltg_d_grad_floats(C.byref(c)) > 0, hs
+    for hs in ((0, 150, 250, 300), (100, 0, 250, 300), (100, 150, 0, 300), (100, 150, 250, 0), (100, -1, 250, 300)):
+        c = mk(hs)
+        assert lib.ltg_workspace_bytes(C.byref(c), 100, 2000) == 0 and lib.ltg_d_grad_floats(C.byref(c)) == 0, hs
+        assert lib.ltg_d_step(C.byref(c), None, None, None, None, None, None, 0, None) == -1, hs
+        assert lib.ltg_d_apply(C.byref(c), None, None, 1, None, None) == -1, hs
+        with pytest.raises(ValueError, match="at least 1"):
+            Engine(1000, h_sizes=hs, device="cpu")
+
+
 def test_one_call_step_plan_is_a_pure_function_of_its_arguments():
     """ltg_g_step_sharded_plan (ABI v13) tells the host what a call will do -- catch the next batch's rows up ahead, write the second
     shadow buffer -- so that the host's bookkeeping (caught_up, the exchange of the two shadow pointers) never guesses.  Host-only: the

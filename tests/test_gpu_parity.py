@@ -148,6 +148,11 @@ def test_forward_parity_of_the_second_streaming_form(I, B):
     assert Hh.rel_err(lg, lg1) < 1e-5 and np.abs(lse - lse1).max() < 1e-5      # (same K order per logit; other tiles, other lanes)
 
 
+def _d_case_id(v):
+    """test id of a tuple of layer sizes: 100x150x250x300"""
+    return "x".join(str(x) for x in v) if isinstance(v, tuple) else None
+
+
 def _check_adam_move(move_got, move_want, m_want, lr_t, tag):
     """First-step Adam moves are lr_t*0.1g/(0.0316|g|+1e-8): a sign-like function of g, so rounding
     noise on a near-cancelling gradient (|g| << its terms) is amplified without bound.  Elements
@@ -234,21 +239,31 @@ def _check_warm_adam(p_got, p0, p_want, m_got, m_want, v_got, v_want, tol, tag, 
     return worst
 
 
-G_CASES = [(1000, 100, "step"), (333, 17, "step"), (6000, 100, "step"), (6000, 100, "step-config-d"), (8200, 100, "step"),
-           (8200, 150, "step"), (8200, 100, "one-call"), (20000, 100, "step"), (25024, 100, "step"),
-           (25024, 100, "one-call-config-d"), (200000, 100, "step"), (200000, 100, "one-call"),
+G_D = (20, 24, 40, 36)            # the discriminator of the G-step cases; CONFIG_D = config.ini's sizes
+CONFIG_D = (100, 150, 250, 300)
+G_CASES = [(1000, 100, "step", G_D), (333, 17, "step", G_D), (6000, 100, "step", G_D), (6000, 100, "step", CONFIG_D), (8200, 100, "step", G_D),
+           (8200, 150, "step", G_D), (8200, 100, "one-call", G_D), (20000, 100, "step", G_D), (25024, 100, "step", G_D),
+           (25024, 100, "one-call", CONFIG_D), (200000, 100, "step", G_D), (200000, 100, "one-call", G_D),
            # ragged slabs (I % 32 != 0): the last I % 32 item rows go through the streaming kernels' tail path
-           (25032, 100, "one-call"), (200008, 100, "step"),
+           (25032, 100, "one-call", G_D), (200008, 100, "step", G_D),
            # tuning-knob bit 18: the generic (round-1) kernels -- what sizes the latency path does not serve fall back to (z_dim % 4 != 0,
            # more than 256 rows, discriminator layers that are not multiples of 4) -- over the same oracle, small and streaming-sized slabs
-           (1000, 100, "step-generic"), (333, 17, "step-generic"), (8200, 100, "step-generic")]
+           (1000, 100, "step-generic", G_D), (333, 17, "step-generic", G_D), (8200, 100, "step-generic", G_D),
+           # the fake tower at unaligned sizes (generic kernels) and past the one-kernel tower's h0 / h3 limits (fks_d_*)
+           (1000, 100, "step", (99, 151, 250, 301)), (1000, 100, "step", (132, 150, 250, 324)),
+           # either side of small_fast / mid_fast (rows <= 256), and 300 rows: generic middle layers beside the streaming decoder
+           (1000, 256, "step", G_D), (1000, 257, "step", G_D), (8200, 300, "step", G_D)]
 
 
-def _g_step_case(precision, I, B, path, warm):
+def _g_case_ids(cases):
+    """(I, B, path) as before the discriminator sizes were a field of their own: "-config-d" for config.ini's, "-d<h0>x..." for others"""
+    return ["%d-%d-%s%s" % (I, B, path, "" if hs == G_D else ("-config-d" if hs == CONFIG_D else "-d" + _d_case_id(hs))) for I, B, path, hs in cases]
+
+
+def _g_step_case(precision, I, B, path, warm, hs=G_D):
     import torch
     from ltgan.engine import Pairs, Pipe
     rng, X, P = _problem(I, B, seed=11 * I + B)
-    hs = (100, 150, 250, 300) if path.endswith("config-d") else (20, 24, 40, 36)
     D = O.init_discriminator(I, *hs, seed=5)
     rows, gen, pop = _fake_pairs(rng, X, I)
     valid = (gen >= 0) & (pop >= 0)
@@ -345,14 +360,14 @@ def _g_step_case(precision, I, B, path, warm):
 
 
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])
-@pytest.mark.parametrize("I,B,path", G_CASES)
-def test_g_step_parity(precision, I, B, path):
+@pytest.mark.parametrize("I,B,path,hs", G_CASES, ids=_g_case_ids(G_CASES))
+def test_g_step_parity(precision, I, B, path, hs):
     """path "step": ltg_g_step.  "one-call": ltg_g_step_sharded without a communicator (the G step of every large item slab:
     bias + tanh and the tanh derivative folded into operand loaders, weight update and clock slice forked) -- same oracle, same
     tolerances.  I = 6 000: the middle-layer fast path without the streaming decoder kernels (4 096 < I < 8 192); I = 25 024: the
-    slab one of eight ranks owns at 200 000 items.  "-config-d": config.ini's discriminator sizes inside the G step.  fp32: the one-call
+    slab one of eight ranks owns at 200 000 items.  hs: the discriminator inside the G step (CONFIG_D: config.ini's).  fp32: the one-call
     step refuses the engine and ltg_g_step is checked instead; at I >= 20 000 the fp32 decoder (BASELINE configs 3 / 4 run bf16) is checked too."""
-    _g_step_case(precision, I, B, path, warm=False)
+    _g_step_case(precision, I, B, path, warm=False, hs=hs)
 
 
 @pytest.mark.parametrize("precision,I,B,path", [("fp32", 1000, 100, "step"), ("bf16", 1000, 100, "step"), ("fp32", 6000, 100, "step"),
@@ -368,13 +383,37 @@ def test_g_step_adam_quotient_from_warm_moments(precision, I, B, path):
     _g_step_case(precision, I, B, path, warm=True)
 
 
+# Discriminator layer sizes (config.ini h0_size..h3_size) against the routes the library picks from them alone (csrc/ltg_kernels.hip:
+# d_fast, d_wide, d_tile; the bwd1 tile promotion above 1 024 32 x 32 tiles).  witness "generic": the step equals its tuning-bit-18 twin
+# (the generic kernels forced) bit for bit, and d_arith, which only reaches the latency-path kernels, changes no bit; "fast": the fk_d_*
+# kernels run, so the twin differs somewhere; None: too small for either statement.
+D_SIZES = [((99, 150, 250, 300), "generic"),     # generic; l1 / bwd2 scalar 32, l2 / bwd1 -32 (64 above 1 024 tiles)
+           ((100, 151, 250, 300), "generic"),    # generic; l1 / bwd2 -33, l2 / bwd1 scalar 32
+           ((100, 150, 250, 301), "generic"),    # generic; -33 / scalar 32
+           ((100, 150, 250, 516), "generic"),    # h3 > 512, not wide: generic; -33 / -32
+           ((100, 150, 250, 324), "fast"),       # fk_d, h3 in (320, 512]
+           ((132, 150, 250, 300), "fast"),       # fk_d, h0 > 128
+           ((508, 256, 256, 128), "fast"),       # fk_d, just below d_wide
+           ((512, 256, 256, 128), "generic"),    # d_wide: l1 / bwd1 64, l2 -32, bwd2 128 tiles
+           ((520, 300, 260, 132), "generic"),    # d_wide, 64 / 128 tiles with ragged edges
+           ((514, 300, 250, 130), "generic"),    # d_wide but not all multiples of 4: scalar 32 everywhere
+           ((4, 1, 3, 4), None),                 # fk_d with one-wide layers
+           ((1, 1, 1, 1), "generic")]            # generic scalar
+D_STEP_CASES = [(900, 950, None), (33, 7, None), (1, 0, None), (0, 5, None), (260, 250, None)] + \
+    [(nr, nf, hs) for hs, _ in D_SIZES for nr, nf in ((700, 650), (33, 7))]     # 1 350 rows: six 256-row slabs
+
+
+def _d_case_ids(cases):
+    return ["%d-%d" % (nr, nf) + ("" if hs is None else "-" + _d_case_id(hs)) for nr, nf, hs in cases]
+
+
 @pytest.mark.parametrize("d_arith", ["fp32", "bf16x6"])
-@pytest.mark.parametrize("nr,nf", [(900, 950), (33, 7), (1, 0), (0, 5), (260, 250)])
-def test_d_step_parity(nr, nf, d_arith):
+@pytest.mark.parametrize("nr,nf,hs", D_STEP_CASES, ids=_d_case_ids(D_STEP_CASES))
+def test_d_step_parity(nr, nf, hs, d_arith):
     """d_arith (ltg_config.d_arith): the exact fp32 MFMA and the six-term bf16 split of the same fp32 operands -- SAME bounds (the split leaves
     out 2^-26 per product, below fp32's own rounding); the wide sizes (260, 250) do not take the latency-path kernels: one arithmetic, so
-    either setting must meet the fp32 bounds there"""
-    _d_step_case(nr, nf, warm=False, d_arith=d_arith)
+    either setting must meet the fp32 bounds there.  hs: the layer sizes of D_SIZES, each with its route witness."""
+    _d_step_case(nr, nf, warm=False, d_arith=d_arith, hs=hs, witness=dict(D_SIZES).get(hs))
 
 
 @pytest.mark.parametrize("nr,nf", [(900, 950), (33, 7)])
@@ -390,21 +429,26 @@ def test_d_step_parity_of_the_generic_kernels(nr, nf):
     _d_step_case(nr, nf, warm=False, knob=1 << 18)
 
 
+D_WARM_CASES = [(900, 950, None), (33, 7, None), (260, 250, None),
+                (700, 650, (99, 150, 250, 300))]      # generic kernels, 160 601 parameters (P % 4 = 1): the per-tensor k_d_adam at a non-wide size
+
+
 @pytest.mark.parametrize("d_arith", ["fp32", "bf16x6"])
-@pytest.mark.parametrize("nr,nf", [(900, 950), (33, 7), (260, 250)])
-def test_d_step_adam_quotient_from_warm_moments(nr, nf, d_arith):
+@pytest.mark.parametrize("nr,nf,hs", D_WARM_CASES, ids=_d_case_ids(D_WARM_CASES))
+def test_d_step_adam_quotient_from_warm_moments(nr, nf, hs, d_arith):
     """The D step from injected non-zero Adam moments at shared step t = 212 (train.py:160-163): the flat Adam sweep's theta move,
     m and v element-wise against oracle.SharedAdam (config-5 sizes: the LDS-staged kernels whatever d_arith says)."""
-    _d_step_case(nr, nf, warm=True, d_arith=d_arith)
+    _d_step_case(nr, nf, warm=True, d_arith=d_arith, hs=hs, witness=dict(D_SIZES).get(hs))
 
 
-def _d_step_case(nr, nf, warm, knob=0, d_arith=None, loosen=1.0):
+def _d_step_case(nr, nf, warm, knob=0, d_arith=None, loosen=1.0, hs=None, witness=None):
     import torch
     from ltgan.engine import Pairs
     I = 500
-    hs = (100, 150, 250, 300) if nr > 300 else (12, 20, 28, 16)
-    if nr == 260:
-        hs = (2048, 1024, 512, 256)          # BASELINE config 5: the wide discriminator (3 540 993 parameters), fp32
+    if hs is None:
+        hs = (100, 150, 250, 300) if nr > 300 else (12, 20, 28, 16)
+        if nr == 260:
+            hs = (2048, 1024, 512, 256)          # BASELINE config 5: the wide discriminator (3 540 993 parameters), fp32
     rng = np.random.default_rng(nr * 7 + nf)
     D = O.init_discriminator(I, *hs, seed=3)
     D["b1"] = rng.normal(0, 0.05, D["b1"].shape).astype(np.float32)
@@ -443,49 +487,69 @@ def _d_step_case(nr, nf, warm, knob=0, d_arith=None, loosen=1.0):
             ad.m[k], ad.v[k] = m0[k].astype(np.float64), v0[k].astype(np.float64)
     D64 = {k: np.asarray(v, np.float64) for k, v in D.items()}
     ad.apply(D64, g, O.D_KEYS)
-    # device
-    eng = _engine(I, "fp32", hs=hs, lr=1e-3, d_arith=d_arith)
-    eng.cfg.tuning = knob
-    emb, darr = Hh.disc_to_engine(D)
-    if warm:
-        eng.set_discriminator(emb, darr, m=[m0[k] for k in O.D_KEYS], v=[v0[k] for k in O.D_KEYS])
-    else:
-        eng.set_discriminator(emb, darr)
-    dev = eng.device
-    real = Pairs(torch.from_numpy(rp).to(dev), torch.from_numpy(rn).to(dev)) if nr else Pairs(torch.zeros(1, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int32, device=dev), n=0)
-    fake = Pairs(torch.from_numpy(fp).to(dev), torch.from_numpy(fn).to(dev)) if nf else Pairs(torch.zeros(1, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int32, device=dev), n=0)
-    eng.adam_t = t0
-    loss = eng.d_step(real, fake, keep, rng_step=step)
-    torch.cuda.synchronize()
-    loss = float(loss.cpu().numpy()[0])
+
+    def device_step(knob, d_arith):
+        eng = _engine(I, "fp32", hs=hs, lr=1e-3, d_arith=d_arith)
+        eng.cfg.tuning = knob
+        emb, darr = Hh.disc_to_engine(D)
+        if warm:
+            eng.set_discriminator(emb, darr, m=[m0[k] for k in O.D_KEYS], v=[v0[k] for k in O.D_KEYS])
+        else:
+            eng.set_discriminator(emb, darr)
+        dev = eng.device
+        real = Pairs(torch.from_numpy(rp).to(dev), torch.from_numpy(rn).to(dev)) if nr else Pairs(torch.zeros(1, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int32, device=dev), n=0)
+        fake = Pairs(torch.from_numpy(fp).to(dev), torch.from_numpy(fn).to(dev)) if nf else Pairs(torch.zeros(1, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int32, device=dev), n=0)
+        eng.adam_t = t0
+        loss = eng.d_step(real, fake, keep, rng_step=step)
+        torch.cuda.synchronize()
+        return eng, loss.cpu().numpy()[:1].copy(), [[t.cpu().numpy().copy() for t in ts] for ts in (eng.d_p, eng.d_m, eng.d_v)]
+
+    eng, loss_bits, state = device_step(knob, d_arith)
+    if witness is not None:
+        # the route this size is meant to test, witnessed by the step's bits
+        def same(a, b):
+            return np.array_equal(a[0].view(np.uint32), b[0].view(np.uint32)) and all(
+                np.array_equal(x.view(np.uint32), y.view(np.uint32)) for sa, sb in zip(a[1], b[1]) for x, y in zip(sa, sb))
+        twin = device_step(1 << 18, d_arith)[1:]
+        if witness == "generic":
+            assert same((loss_bits, state), twin), (hs, "not the generic kernels: the bit-18 twin differs")
+            other = "fp32" if eng.d_arith != "fp32" else "bf16x6"
+            assert same((loss_bits, state), device_step(knob, other)[1:]), (hs, "d_arith reached a generic-route kernel")
+        else:
+            assert not same((loss_bits, state), twin), (hs, "the latency-path kernels did not run: the step equals its bit-18 twin")
+    loss = float(loss_bits[0])
     assert abs(loss - want_loss) < 1e-4 * max(1.0, abs(want_loss))
+    d_p, d_m, d_v = state
     if warm:
         worst = 0.0
         for i, k in enumerate(O.D_KEYS):
             sh = np.asarray(D[k]).shape
-            worst = max(worst, _check_warm_adam(eng.d_p[i].cpu().numpy().reshape(sh), np.asarray(D[k]), D64[k], eng.d_m[i].cpu().numpy().reshape(sh), ad.m[k],
-                                                eng.d_v[i].cpu().numpy().reshape(sh), ad.v[k], 1e-4, ("d tensor", k), t0 + 1))
-        print("D step (%d, %d): worst relative error of a theta move from warm moments %.2e" % (nr, nf, worst))
+            worst = max(worst, _check_warm_adam(d_p[i].reshape(sh), np.asarray(D[k]), D64[k], d_m[i].reshape(sh), ad.m[k],
+                                                d_v[i].reshape(sh), ad.v[k], 1e-4, ("d tensor", k), t0 + 1))
+        print("D step (%d, %d) %s: worst relative error of a theta move from warm moments %.2e" % (nr, nf, hs, worst))
         return
     worst_m = worst_v = 0.0
     for i, k in enumerate(O.D_KEYS):
-        m_got = eng.d_m[i].cpu().numpy().reshape(-1)
+        m_got = d_m[i].reshape(-1)
         worst_m = max(worst_m, Hh.rel_err(m_got, ad.m[k].reshape(-1)))
         assert Hh.rel_err(m_got, ad.m[k].reshape(-1)) < 5e-4 * loosen, ("m", k)
-        v_got = eng.d_v[i].cpu().numpy().reshape(-1)
+        v_got = d_v[i].reshape(-1)
         worst_v = max(worst_v, Hh.rel_err(v_got, ad.v[k].reshape(-1)))
         assert Hh.rel_err(v_got, ad.v[k].reshape(-1)) < 1e-3 * loosen, ("v", k)
-    print("D step (%d, %d) d_arith %s: loss rel err %.2e, worst first / second moment rel err %.2e / %.2e" %
-          (nr, nf, eng.d_arith, abs(loss - want_loss) / max(1.0, abs(want_loss)), worst_m, worst_v))
+    print("D step (%d, %d) %s d_arith %s: loss rel err %.2e, worst first / second moment rel err %.2e / %.2e" %
+          (nr, nf, hs, eng.d_arith, abs(loss - want_loss) / max(1.0, abs(want_loss)), worst_m, worst_v))
     for i, k in enumerate(O.D_KEYS):
-        move_got = eng.d_p[i].cpu().numpy().reshape(-1) - np.asarray(D[k], np.float64).reshape(-1)
+        move_got = d_p[i].reshape(-1) - np.asarray(D[k], np.float64).reshape(-1)
         move_want = D64[k].reshape(-1) - np.asarray(D[k], np.float64).reshape(-1)
         _check_adam_move(move_got, move_want, ad.m[k].reshape(-1), ad.lr_t(3), ("theta", k))
 
 
 @pytest.mark.parametrize("d_arith,tol", [("bf16x6", 2e-6), ("bf16x4", 2e-5), ("fp32", 2e-6)])
 @pytest.mark.parametrize("hs,segs", [((100, 150, 250, 300), (1, 63, 64, 65, 700, 1311)), ((12, 20, 28, 16), (5, 130)), ((64, 96, 200, 320), (257,)),
-                                     ((8, 5, 9, 3), (70,)), ((128, 33, 17, 7), (129,))])
+                                     ((8, 5, 9, 3), (70,)), ((128, 33, 17, 7), (129,)),
+                                     # just past the tower's h0 / h3 limits (fks_d_*); fk_d_* (h0 < 32) against fks_d_* at fp32; wide generic; unaligned
+                                     ((132, 150, 250, 300), (1, 257)), ((100, 150, 250, 324), (1, 257)), ((28, 20, 12, 16), (5, 130)), ((32, 16, 16, 16), (5, 130)),
+                                     ((512, 256, 256, 128), (257,)), ((99, 151, 250, 301), (1, 257))])
 def test_forward_only_tower_matches_oracle(hs, segs, d_arith, tol):
     """ltg_fake_tower_batched (discriminator.py:51-55 for many pair batches in one pass; consumed at train.py:155): y of every slot against the
     oracle's tower, segment by segment with the segment's own dropout counter -- through the ONE-kernel tower (csrc/ltg_tower.h: d_arith bf16x6 /
@@ -498,10 +562,6 @@ def test_forward_only_tower_matches_oracle(hs, segs, d_arith, tol):
     D = O.init_discriminator(I, *hs, seed=11)
     for k in ("b1", "b2", "b3", "b4"):
         D[k] = rng.normal(0, 0.05, D[k].shape).astype(np.float32)
-    eng = _engine(I, "fp32", hs=hs, lr=1e-3, d_arith=d_arith)
-    emb, darr = Hh.disc_to_engine(D)
-    eng.set_discriminator(emb, darr)
-    dev = eng.device
     n = sum(segs)
     pop, nic = rng.integers(0, I, n).astype(np.int32), rng.integers(0, I, n).astype(np.int32)
     hole = rng.random(n) < 0.04
@@ -510,11 +570,25 @@ def test_forward_only_tower_matches_oracle(hs, segs, d_arith, tol):
     row0 = np.concatenate([[0], np.cumsum(segs)[:-1]]).astype(np.int32)
     seg_of = np.repeat(np.arange(len(segs), dtype=np.int32), segs)
     steps = (1000 + 7 * np.arange(len(segs))).astype(np.int64)
-    t = lambda a: torch.from_numpy(a).to(dev)
-    y = torch.full((n,), -1.0, dtype=torch.float32, device=dev)
-    eng.fake_tower_batched(Pairs(t(pop), t(nic)), t(seg_of), t(row0), t(steps), y, keep)
-    torch.cuda.synchronize()
-    got = y.cpu().numpy().astype(np.float64)
+
+    def tower(d_arith):
+        eng = _engine(I, "fp32", hs=hs, lr=1e-3, d_arith=d_arith)
+        emb, darr = Hh.disc_to_engine(D)
+        eng.set_discriminator(emb, darr)
+        t = lambda a: torch.from_numpy(a).to(eng.device)
+        y = torch.full((n,), -1.0, dtype=torch.float32, device=eng.device)
+        eng.fake_tower_batched(Pairs(t(pop), t(nic)), t(seg_of), t(row0), t(steps), y, keep)
+        torch.cuda.synchronize()
+        return y.cpu().numpy()
+
+    y32 = tower(d_arith)
+    h0, h12, h3 = hs[0], hs[1] + hs[2], hs[3]
+    one_kernel = 4 <= h0 <= 128 and h0 % 4 == 0 and h3 <= 320 and h12 <= 512     # ft_wsp_capable at these sizes (none of them d_wide)
+    if not one_kernel and d_arith == "fp32":
+        # fks_d_* and the generic kernels have one arithmetic: d_arith must not change a bit of y
+        for other in ("bf16x6", "bf16x4"):
+            assert np.array_equal(tower(other).view(np.uint32), y32.view(np.uint32)), (hs, other)
+    got = y32.astype(np.float64)
     worst = 0.0
     for sidx, (r0, ns) in enumerate(zip(row0, segs)):
         sl = slice(r0, r0 + ns)
@@ -528,13 +602,15 @@ def test_forward_only_tower_matches_oracle(hs, segs, d_arith, tol):
     assert worst < tol, worst
 
 
-def test_d_step_with_its_backward_jobs_on_the_aux_stream_is_bit_identical():
+@pytest.mark.parametrize("hs", [(100, 150, 250, 300), (100, 150, 250, 324), (4, 1, 3, 4)], ids=_d_case_id)
+def test_d_step_with_its_backward_jobs_on_the_aux_stream_is_bit_identical(hs):
     """ltg_d_opts.aux_stream / sync (Engine.d_fork): jobs B / C of the backward's first stage (dw3, db3, dw4, db4, d_loss) beside the
     critical chain job A -> stage 2, handed over through device words -- the same kernels writing the same slab entries, so six steps
-    from equal states must leave the same bits as the one-stream step: losses, every weight, every moment."""
+    from equal states must leave the same bits as the one-stream step: losses, every weight, every moment.  Wherever d_fast holds:
+    config.ini's sizes, h3 in (320, 512] (eleven output tiles), one-wide layers."""
     import torch
     from ltgan.engine import Pairs
-    I, hs = 500, (100, 150, 250, 300)
+    I = 500
     rng = np.random.default_rng(17)
     D = O.init_discriminator(I, *hs, seed=3)
     emb, darr = Hh.disc_to_engine(D)
@@ -572,7 +648,11 @@ def test_d_step_with_its_backward_jobs_on_the_aux_stream_is_bit_identical():
 
 @pytest.mark.parametrize("hs,nr,nf,cuts,dq", [((100, 150, 250, 300), 900, 950, (0, 463, 925, 1388, 1850), "fp32"), ((12, 20, 28, 16), 33, 7, (0, 1, 1, 35, 40), "fp32"),
                                               ((2048, 1024, 512, 256), 260, 250, (0, 255, 510), "fp32"), ((2048, 1024, 512, 256), 260, 250, (0, 255, 510), "fp8"),
-                                              ((512, 256, 256, 128), 700, 650, (0, 600, 1350), "fp8")])
+                                              ((512, 256, 256, 128), 700, 650, (0, 600, 1350), "fp8"),
+                                              ((192, 64, 128, 128), 700, 650, (0, 300, 1000, 1350), "fp8"), ((256, 128, 128, 64), 700, 650, (0, 600, 1350), "fp8"),
+                                              # (the wide h3 = 640 case cuts at a slab boundary: misaligned, b4's one cancelling sum over 580 rows moved by 3.3e-5 with the order)
+                                              ((512, 256, 256, 640), 300, 280, (0, 256, 580), "fp8"), ((256, 128, 128, 100), 700, 650, (0, 600, 1350), "fp8"),
+                                              ((99, 151, 250, 301), 700, 650, (0, 257, 700, 1350), "bf16")])
 def test_d_step_cut_at_the_gradient_exchange_equals_the_step(hs, nr, nf, cuts, dq):
     """ltg_d_grad over disjoint row ranges of the real | fake pair batch (what each rank of a pair-split run computes: the
     ranges straddle the real / fake boundary, one is empty), the gradient vectors summed (the all-reduce), ltg_d_apply ==
@@ -1004,7 +1084,12 @@ def test_fp8_rounding_model_matches_hardware():
 # (wide) in the energy norm, because every value near an e4m3 rounding boundary flips by a 6 % step.
 @pytest.mark.parametrize("dq,hs,tol", [("bf16", (100, 150, 250, 300), 2e-3), ("fp8", (100, 150, 250, 300), 2e-2),
                                        ("bf16", (2048, 1024, 512, 256), 2e-3), ("fp8", (2048, 1024, 512, 256), 6e-2),
-                                       ("fp32", (2048, 1024, 512, 256), 5e-4)])
+                                       ("fp32", (2048, 1024, 512, 256), 5e-4),
+                                       # fp8 routes: the non-staged fk8_d_* forward (h0 % 128 = 64) with the generic mode-2 backward; the staged
+                                       # forward without operand format (h3 % 128 != 0; and h3 > 512, wide); no e4m3 shadows at all (h3 % 64 != 0:
+                                       # generic mode-2 kernels converting on the fly) -- and bf16 operands at unaligned sizes (scalar loaders)
+                                       ("fp8", (192, 64, 128, 128), 2e-2), ("fp8", (256, 128, 128, 64), 2e-2), ("fp8", (512, 256, 256, 640), 6e-2),
+                                       ("fp8", (256, 128, 128, 100), 2e-2), ("bf16", (99, 151, 250, 301), 2e-3)])
 def test_d_step_precision_modes(dq, hs, tol):
     """D step with quantised GEMM operands == oracle fed the SAME quantised operands (d6: compare against the oracle
     fed rounded operands); and close to the fp32 discriminator within the format's own error."""

@@ -20,6 +20,73 @@ def random_history(rng, n_rows, n_items, mean_nnz=18, min_nnz=1):
     return X
 
 
+# Rows the long-tail builder always holds (when they fit in n_items): either side of the kernels' row thresholds -- NT = 256 entries (the
+# strided row loops' second pass), ENC_NT = 1 024 (fk_enc0_fwd's second chunk) -- and one of ~2 500 entries (three chunks)
+LONG_TAIL_ROWS = (1, 255, 256, 257, 1023, 1024, 1025, 2500)
+
+
+def skewed_history(rng, n_rows, n_items, values=False):
+    """A sorted CSR batch shaped like the data the model is for: item popularity Zipf(s = 1) (item 0 the most popular, and in EVERY row),
+    row lengths max(1, round(LogNormal(2.2, 0.9))) clipped to n_items, plus rows of exactly LONG_TAIL_ROWS entries where they fit (a
+    longer one is dropped), at random positions.  The items of a row are drawn by popularity without replacement (Gumbel top-k).
+    values=True: entries from {0.5, 1, 2, 3, 5} instead of 1 (the product uploads `values` for any non-binary history)."""
+    L = np.minimum(np.maximum(1, np.rint(rng.lognormal(2.2, 0.9, n_rows))).astype(np.int64), n_items)
+    forced = [k for k in LONG_TAIL_ROWS if k <= n_items][:n_rows]
+    L[rng.permutation(n_rows)[:len(forced)]] = forced
+    logw = -np.log(np.arange(2, n_items + 1, dtype=np.float64))      # items 1 .. n_items - 1
+    indptr, cols = [0], []
+    for k in L.tolist():
+        it = np.zeros(0, np.int64)
+        if k > 1:
+            g = logw - np.log(-np.log(rng.random(n_items - 1)))
+            it = (np.arange(n_items - 1) if k - 1 == n_items - 1 else np.argpartition(-g, k - 1)[:k - 1]) + 1
+        cols.append(np.sort(np.concatenate([[0], it])))
+        indptr.append(indptr[-1] + k)
+    cols = np.concatenate(cols).astype(np.int32)
+    data = (rng.choice(np.array([0.5, 1.0, 2.0, 3.0, 5.0], np.float32), size=len(cols)) if values else np.ones(len(cols), np.float32))
+    X = sp.csr_matrix((data, cols, np.array(indptr, np.int64)), shape=(n_rows, n_items))
+    assert X.has_sorted_indices
+    return X
+
+
+def skewed_fake_pairs(rng, X, n_items):
+    """(row, gen, pop) triples sorted by row whose per-user count follows the history: a user of n entries gets n .. n + n/4 + 1 pairs
+    (capped at n_items), users of fewer than 256 entries none with probability 0.1; gen distinct within a row, ~5 % holes (-1)."""
+    rows, gen, pop = [], [], []
+    for b, n in enumerate(np.diff(X.indptr).tolist()):
+        if n < 256 and rng.random() < 0.1:
+            continue
+        k = min(n_items, n + int(rng.integers(0, n // 4 + 2)))
+        g = np.sort(rng.choice(n_items, size=k, replace=False))
+        p = rng.integers(0, n_items, k)
+        hole = rng.random(k) < 0.05
+        rows.append(np.full(k, b))
+        gen.append(np.where(hole, -1, g))
+        pop.append(np.where(hole, -1, p))
+    cat = lambda a: np.concatenate(a).astype(np.int32) if a else np.zeros(0, np.int32)
+    return cat(rows), cat(gen), cat(pop)
+
+
+def long_tail_batch(n_items, B, values=False):
+    """Batch 1 of a two-batch skewed history, seeded by the shape, as the parity tests feed it: (X_all [2 B, n_items], X = rows [B, 2 B)
+    -- the batch --, fake pairs of the batch with LOCAL rows).  Batch 0 is skewed too, so that batch 1's rows, entries and distinct items
+    start at non-zero offsets of every device array."""
+    rng = np.random.default_rng(13 * n_items + B + (1 if values else 0))
+    X_all = sp.vstack([skewed_history(rng, B, n_items, values), skewed_history(rng, B, n_items, values)]).tocsr()
+    X_all.sort_indices()
+    X = X_all[B:2 * B].tocsr()
+    return X_all, X, skewed_fake_pairs(rng, X, n_items)
+
+
+def device_batch(X_all, B, device, b=1):
+    """view(b)["batch"] of DeviceData over an IndexData of X_all (no sampler lists): the batch exactly as training hands it to the kernels --
+    uitem, row_norm2, values when not binary, non-zero row / entry / uptr offsets.  Returns (DeviceData, CsrRows); keep the first alive."""
+    from ltgan.dataset import DeviceData, IndexData
+    idx = IndexData(X_all.shape[1], X_all, 0, {}, {}, {}, {}, {}, range(X_all.shape[1]))
+    dd = DeviceData(idx, B, device)
+    return dd, dd.view(b)["batch"]
+
+
 def csc_view(X):
     """(slot, uptr, rowidx, csr_pos, n_unique) of a CSR matrix: the transposed view ltg_g_step needs."""
     from ltgan.dataset import batch_csc

@@ -43,16 +43,37 @@ def _upload_batch(eng, X, with_csc=False):
     return CsrRows(indptr, indices, 0, X.shape[0])
 
 
-@pytest.mark.parametrize("precision,tol", [("fp32", 2e-4), ("bf16", 1e-3)])
-@pytest.mark.parametrize("I,B", [(1000, 100), (777, 37), (64, 1), (2500, 130), (8200, 100), (8200, 150),
-                                 (20000, 100), (200000, 100)])     # the last two: BASELINE configs 3 and 4 (item counts, BATCH_SIZE)
-def test_forward_parity(precision, tol, I, B):
+FWD_CASES = [(I, B, precision, tol, "uniform") for I, B in [(1000, 100), (777, 37), (64, 1), (2500, 130), (8200, 100), (8200, 150),
+                                                              (20000, 100), (200000, 100)]     # the last two: BASELINE configs 3 and 4 (item counts, BATCH_SIZE)
+             for precision, tol in [("fp32", 2e-4), ("bf16", 1e-3)]] + \
+    [(I, B, precision, tol, "skewed") for I, B in [(1000, 100), (4096, 100), (25024, 128)] for precision, tol in [("fp32", 2e-4), ("bf16", 1e-3)]] + \
+    [(4096, 100, "fp32", 2e-4, "skewed-values"), (25024, 128, "bf16", 1e-3, "skewed-values")]
+
+
+def _history_id(history):
+    return "" if history == "uniform" else "-" + history
+
+
+def _long_tail(eng, I, B, history):
+    """batch 1 of Hh.long_tail_batch through DeviceData (the product's batch layout): (DeviceData -- keep it alive --, CsrRows, X, fake pairs)"""
+    X_all, X, pairs = Hh.long_tail_batch(I, B, values=history.endswith("-values"))
+    dd, batch = Hh.device_batch(X_all, B, eng.device)
+    return dd, batch, X, pairs
+
+
+@pytest.mark.parametrize("I,B,precision,tol,history", FWD_CASES, ids=["%d-%d-%s-%s%s" % (I, B, p, t, _history_id(h)) for I, B, p, t, h in FWD_CASES])
+def test_forward_parity(precision, tol, I, B, history):
+    """history "skewed": Hh.long_tail_batch -- rows past NT and ENC_NT entries (fk_enc0_fwd's second and third chunks), Zipf items, the
+    batch through DeviceData (row_norm2, non-zero offsets); "-values": non-binary entries (ltg_batch.values)"""
     import torch
     rng, X, P = _problem(I, B, seed=I + B)
     eng = _engine(I, precision)
     eng.set_generator(Hh.gen_to_engine(P))
     acts = eng.new_acts(B)
-    batch = _upload_batch(eng, X)
+    if history == "uniform":
+        batch = _upload_batch(eng, X)
+    else:
+        dd, batch, X, _ = _long_tail(eng, I, B, history)
     probs = torch.empty(B, I, dtype=torch.float32, device=eng.device)
     step, keep = 7, 0.75
     eng.forward(batch, acts, keep_prob=keep, is_training=1.0, rng_step=step, probs_out=probs)
@@ -260,12 +281,17 @@ def _g_case_ids(cases):
     return ["%d-%d-%s%s" % (I, B, path, "" if hs == G_D else ("-config-d" if hs == CONFIG_D else "-d" + _d_case_id(hs))) for I, B, path, hs in cases]
 
 
-def _g_step_case(precision, I, B, path, warm, hs=G_D):
+def _g_step_case(precision, I, B, path, warm, hs=G_D, history="uniform"):
+    """history "uniform": Hh.random_history, a hand-built batch 0.  "skewed" / "skewed-values": batch 1 of Hh.long_tail_batch through
+    DeviceData (uitem, row_norm2, non-zero offsets, `values` for the second) with Hh.skewed_fake_pairs (> FU * NT pairs, a user past NT)."""
     import torch
     from ltgan.engine import Pairs, Pipe
     rng, X, P = _problem(I, B, seed=11 * I + B)
     D = O.init_discriminator(I, *hs, seed=5)
-    rows, gen, pop = _fake_pairs(rng, X, I)
+    if history == "uniform":
+        rows, gen, pop = _fake_pairs(rng, X, I)
+    else:
+        X_all, X, (rows, gen, pop) = Hh.long_tail_batch(I, B, values=history.endswith("-values"))
     valid = (gen >= 0) & (pop >= 0)
     cnt = int(valid.sum())
     step, dstep, keep, dkeep, anneal, lam = 3, 9, 0.75, 0.7, 0.13, 1.0
@@ -296,6 +322,8 @@ def _g_step_case(precision, I, B, path, warm, hs=G_D):
     assert eng.Z == 200
     if path.endswith("-generic"):
         eng.cfg.tuning = 1 << 18
+    if path.endswith("-wide-grad"):
+        eng.cfg.tuning = 1 << 14             # the column-blocked fk_enc0_grad (its own heavy-row branch) instead of fk_enc0_grad_rows
     if warm:
         eng.set_generator(Hh.gen_to_engine(P), m=Hh.gen_to_engine(m0), v=Hh.gen_to_engine(v0))
     else:
@@ -305,7 +333,10 @@ def _g_step_case(precision, I, B, path, warm, hs=G_D):
     dev = eng.device
     fake = Pairs(torch.from_numpy(pop).to(dev), torch.from_numpy(gen).to(dev), torch.from_numpy(rows).to(dev))
     cnt_t = torch.tensor([cnt], dtype=torch.int32, device=dev)
-    batch = _upload_batch(eng, X, with_csc=True)
+    if history == "uniform":
+        batch = _upload_batch(eng, X, with_csc=True)
+    else:
+        dd, batch = Hh.device_batch(X_all, B, dev)
     acts = eng.new_acts(B)
     eng.adam_t = t0  # exercise the shared counter
     if path.startswith("one-call") and not q:
@@ -359,28 +390,43 @@ def _g_step_case(precision, I, B, path, warm, hs=G_D):
         print("I=%d %s %s: worst relative error of a theta move from warm moments %.2e" % (I, precision, path, worst))
 
 
-@pytest.mark.parametrize("precision", ["fp32", "bf16"])
-@pytest.mark.parametrize("I,B,path,hs", G_CASES, ids=_g_case_ids(G_CASES))
-def test_g_step_parity(precision, I, B, path, hs):
+# Long-tail batches (Hh.long_tail_batch): (precision, I, B, path, history).  I = 1 000: small slab (fk_row_dlogits, dense enc-0 gradient), also
+# at 256 rows, the most the latency path takes; 4 096: the largest small slab, rows past ENC_NT; 6 000: middle-layer fast path without streaming;
+# 25 024: streaming (k_row_stats_merge, k_dlogits_combine in the one-call step, fk_enc0_grad_rows; "-wide-grad": tuning bit 14, fk_enc0_grad)
+G_SKEWED = [(p, I, B, "step", "skewed") for I, B in ((1000, 100), (1000, 256), (4096, 100), (6000, 100), (25024, 128)) for p in ("fp32", "bf16")] + \
+    [("bf16", 25024, 128, "one-call", "skewed"), ("bf16", 25024, 128, "step-wide-grad", "skewed")] + \
+    [(p, I, 100, "step-generic", "skewed") for I in (1000, 8200) for p in ("fp32", "bf16")] + \
+    [("fp32", 1000, 100, "step", "skewed-values"), ("bf16", 25024, 128, "one-call", "skewed-values")]
+G_ALL = [(p, I, B, path, hs, "uniform") for I, B, path, hs in G_CASES for p in ("fp32", "bf16")] + [(p, I, B, path, G_D, h) for p, I, B, path, h in G_SKEWED]
+
+
+@pytest.mark.parametrize("precision,I,B,path,hs,history", G_ALL,
+                         ids=[i + "-" + c[0] + _history_id(c[5]) for i, c in zip(_g_case_ids([c[1:5] for c in G_ALL]), G_ALL)])
+def test_g_step_parity(precision, I, B, path, hs, history):
     """path "step": ltg_g_step.  "one-call": ltg_g_step_sharded without a communicator (the G step of every large item slab:
     bias + tanh and the tanh derivative folded into operand loaders, weight update and clock slice forked) -- same oracle, same
     tolerances.  I = 6 000: the middle-layer fast path without the streaming decoder kernels (4 096 < I < 8 192); I = 25 024: the
     slab one of eight ranks owns at 200 000 items.  hs: the discriminator inside the G step (CONFIG_D: config.ini's).  fp32: the one-call
     step refuses the engine and ltg_g_step is checked instead; at I >= 20 000 the fp32 decoder (BASELINE configs 3 / 4 run bf16) is checked too."""
-    _g_step_case(precision, I, B, path, warm=False, hs=hs)
+    _g_step_case(precision, I, B, path, warm=False, hs=hs, history=history)
 
 
-@pytest.mark.parametrize("precision,I,B,path", [("fp32", 1000, 100, "step"), ("bf16", 1000, 100, "step"), ("fp32", 6000, 100, "step"),
-                                                ("bf16", 8200, 100, "step"), ("bf16", 20000, 100, "step"), ("bf16", 25024, 100, "one-call"),
-                                                ("bf16", 25032, 100, "one-call"),
-                                                # BASELINE config 4's item count: the combination the driver's C4 bench leg runs (one call, warm
-                                                # moments, 200 000 items), and the ragged slab through the five-launch step
-                                                ("bf16", 200000, 100, "one-call"), ("bf16", 200008, 100, "step")])
-def test_g_step_adam_quotient_from_warm_moments(precision, I, B, path):
+WARM_CASES = [(p, I, B, path, "uniform") for p, I, B, path in [
+    ("fp32", 1000, 100, "step"), ("bf16", 1000, 100, "step"), ("fp32", 6000, 100, "step"), ("bf16", 8200, 100, "step"), ("bf16", 20000, 100, "step"),
+    ("bf16", 25024, 100, "one-call"), ("bf16", 25032, 100, "one-call"),
+    # BASELINE config 4's item count: the combination the driver's C4 bench leg runs (one call, warm moments, 200 000 items), and the ragged
+    # slab through the five-launch step
+    ("bf16", 200000, 100, "one-call"), ("bf16", 200008, 100, "step")]] + \
+    [("fp32", 1000, 100, "step", "skewed"), ("bf16", 1000, 100, "step", "skewed"),      # long-tail batches: small slab, streaming one-call step
+     ("bf16", 25024, 128, "one-call", "skewed")]
+
+
+@pytest.mark.parametrize("precision,I,B,path,history", WARM_CASES, ids=["%s-%d-%d-%s%s" % (p, I, B, path, _history_id(h)) for p, I, B, path, h in WARM_CASES])
+def test_g_step_adam_quotient_from_warm_moments(precision, I, B, path, history):
     """The G step from injected NON-ZERO Adam moments at shared step t = 138 against oracle.SharedAdam (train.py:160-164): every
     theta move, m and v element-wise -- dense tile epilogues, the streaming weight update, the lazy clock's kernels (rows of W_q0
     the batch does not touch take a zero-gradient step) all go through the library's one adam_move."""
-    _g_step_case(precision, I, B, path, warm=True)
+    _g_step_case(precision, I, B, path, warm=True, history=history)
 
 
 # Discriminator layer sizes (config.ini h0_size..h3_size) against the routes the library picks from them alone (csrc/ltg_kernels.hip:
@@ -1290,20 +1336,30 @@ def cabi_flags(*names):
     return v
 
 
-@pytest.mark.parametrize("precision,period", [("fp32", 3), ("bf16", 5)])
-def test_lazy_adam_clock_of_the_first_encoder_layer_is_bit_identical_to_the_dense_sweep(precision, period):
+CLOCK_CASES = [("fp32", 3, "uniform"), ("bf16", 5, "uniform"), ("fp32", 3, "skewed"), ("bf16", 5, "skewed")]
+
+
+@pytest.mark.parametrize("precision,period,history", CLOCK_CASES, ids=["%s-%d%s" % (p, n, _history_id(h)) for p, n, h in CLOCK_CASES])
+def test_lazy_adam_clock_of_the_first_encoder_layer_is_bit_identical_to_the_dense_sweep(precision, period, history):
     """ltg_gen_state.q0_last: TF's Adam (train.py:160-164) moves every row of W_q0 every step; the lazy clock applies a row's
     zero-gradient steps later, with the same arithmetic.  Several G steps over DIFFERENT batches (rows go in and out of the
     batches, the rotating slice has a short period), a forward over other users in the middle of the phase, one flush at
-    the end: every parameter, moment and output bit equals the dense sweep's."""
+    the end: every parameter, moment and output bit equals the dense sweep's.  history "skewed": every batch (the forward-only one too) from
+    Hh.skewed_history with Hh.skewed_fake_pairs -- item 0 in every row, rows past NT and ENC_NT entries: the heavy-row branches of both
+    shapes of the sparse gradient and many workgroups of k_q0_touch_rows claiming the same rows."""
     import torch
     from ltgan.engine import CsrRows, Pairs
     I, B, n_batches = 9000, 48, 7
     rng = np.random.default_rng(4242)
     P = O.init_generator(I, seed=3)
-    Xs = [Hh.random_history(rng, B, I, mean_nnz=14) for _ in range(n_batches)]
-    Xf = Hh.random_history(rng, 40, I, mean_nnz=30)                       # forward-only batch (no distinct-item list)
-    fakes = [_fake_pairs(rng, X, I) for X in Xs]
+    if history == "uniform":
+        Xs = [Hh.random_history(rng, B, I, mean_nnz=14) for _ in range(n_batches)]
+        Xf = Hh.random_history(rng, 40, I, mean_nnz=30)                   # forward-only batch (no distinct-item list)
+        fakes = [_fake_pairs(rng, X, I) for X in Xs]
+    else:
+        Xs = [Hh.skewed_history(rng, B, I) for _ in range(n_batches)]
+        Xf = Hh.skewed_history(rng, 40, I)
+        fakes = [Hh.skewed_fake_pairs(rng, X, I) for X in Xs]
     outs = []
     # "one-call": the lazy clock inside ltg_g_step_sharded -- the decoder weight update runs beside the next step's encoder half, the slice
     # of step t on the side stream between the catch-ups of steps t + 1 and t + 2, everything handed over through device words (bf16

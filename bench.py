@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """bench.py -- train users/sec at BATCH_SIZE=100 of the Long-Tail-GAN adversarial training path.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload askubuntu|ml20m|c4]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload askubuntu|ml20m|c4] [--full]
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs if asked and prints the result line.  --full adds what
+takes runs of its own: the CPU baseline, the bounded C3 / C4-shaped legs and the per-rank proxy of an 8-GPU run (Askubuntu_Sample
+at N = 1), the one-GPU reference of the same workload (N > 1) and the device-to-device copy ceiling.
 
 N > 1 without a launcher: bench.py starts the N rank processes itself (torch.distributed.run as a child of a parent that never
 touches the GPU) and relays rank 0's JSON line; under `python -m torch.distributed.run --nproc-per-node N` it is a rank.
@@ -56,9 +60,11 @@ def parse():
     ap.add_argument("--cold-moments", action="store_true", help="leave the moments of W_q0 at zero (a bounded sample touches a fraction of the items: "
                     "rows no batch has touched then cost the lazy clock nothing -- NOT the state of the named configurations)")
     ap.add_argument("--no-probe", action="store_true", help="skip the HIP-event kernel probes (use under rocprofv3 --pmc)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-workloads", action="store_true", help="skip the bounded C3 / C4-shaped 1-GPU measurements reported beside the headline")
-    ap.add_argument("--cpu-seconds", type=float, default=20.0)
+    ap.add_argument("--full", action="store_true", help="also measure what takes runs of its own: the CPU baseline, the C3 / C4-shaped legs and the per-rank proxy "
+                    "(Askubuntu_Sample at N = 1), the one-GPU reference of the workload (N > 1) and the copy ceiling")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-other-workloads", action="store_true", help="--full: skip the bounded C3 / C4-shaped 1-GPU measurements reported beside the headline")
+    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="--full: time budget of the CPU baseline")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32; rank 0's slab when item-sharded): "
                          "the per-sub-epoch D and G losses, phase C's fake pairs and the model's tensors after the step; an array above "
@@ -749,7 +755,7 @@ def main():
     if mode == "item-shard":
         from ltgan.dataset import DeviceData
         from ltgan.sharded import ShardedTrainer, item_slab
-        if world > 1 and rank == 0:
+        if a.full and world > 1 and rank == 0:
             # same workload on ONE GPU, measured in this very job (the other ranks wait): the strong-scaling reference
             e1 = Engine(idx.n_items, h_sizes=a.h_sizes, precision=a.precision, d_precision=a.d_precision, d_arith=a.d_arith, device=device)
             if a.warm:
@@ -788,7 +794,8 @@ def main():
     try:
         for _ in range(a.warmup):
             tr.epoch()
-        # ---- live per-kernel timing (HIP events recorded by the library around ONE kernel per call)
+        # ---- live per-kernel timing (HIP events recorded by the library around ONE kernel per call).  It stays in a plain run: the
+        # calibration's D / G steps leave the state the timed steps start from, and the kernel it picks is probed inside them.
         prof = KernelProfiler(eng, tr, data, a)
         if a.no_probe:
             calib, dominant = None, None
@@ -872,8 +879,8 @@ def main():
             res["sharded_step"]["exchanges_us"] = {k: round(v["avg_us"], 2) for k, v in ex.items()}
             res["sharded_step"]["exchanges_note"] = ("HIP events on the step's stream around each in-stream collective call (every 32nd G step, rank 0): "
                                                      "time the step's critical path spends in the exchange, queueing behind slower ranks included")
-        cc = copy_ceiling(device)
-        prof.copy_gbs = cc["value"]
+        cc = copy_ceiling(device) if a.full else None
+        prof.copy_gbs = cc["value"] if cc else None
         res["roofline"] = prof.roofline(dominant, calib) if dominant else None
         if res["roofline"] is None:
             res["roofline"] = {"kernel": None, "note": "kernel probes disabled (--no-probe)" if a.no_probe else "no probed launch fell into the timed region"}
@@ -881,8 +888,9 @@ def main():
         res["roofline"].update(step_fracs(idx, data, eng, a.sub_epochs, tr.active, dt / a.steps, 1 if replicas else world))
         if eng.lazy_q0:
             res["roofline"]["lazy_q0"] = {"period": eng.q0_period, "warm_moments": bool(a.warm)}
-        res["roofline"]["copy_ceiling_this_box"] = cc
-        res["roofline"]["step_frac_of_copy_ceiling"] = res["roofline"]["step_frac"] * PEAK["hbm"] / 1e9 / cc["value"]
+        if cc:
+            res["roofline"]["copy_ceiling_this_box"] = cc
+            res["roofline"]["step_frac_of_copy_ceiling"] = res["roofline"]["step_frac"] * PEAK["hbm"] / 1e9 / cc["value"]
         if calib:
             res["kernels_us"] = {k: round(v["avg_ms"] * 1e3, 2) for k, v in calib.items()}
             # every probed kernel against ITS roofline (calibration pass: HIP events around one kernel per call, same brackets as `roofline`):
@@ -891,7 +899,7 @@ def main():
         if n1_ref:
             res["n1_same_workload"] = {"value": n1_ref, "unit": "users/s", "note": "same workload, unsharded, on rank 0's GPU in this job"}
             res["strong_scaling_vs_1gpu"] = value / n1_ref
-        if world == 1 and workload == "askubuntu" and not a.no_other_workloads:
+        if a.full and world == 1 and workload == "askubuntu" and not a.no_other_workloads:
             del tr, prof, eng, data
             torch.cuda.empty_cache()
             res["other_workloads"] = other_workloads(a, device, copy_gbs=cc["value"])
@@ -915,7 +923,7 @@ def main():
         if c4v is not None:
             res["c4_same_workload"] = {"value": c4v, "unit": "users/s", "n_gpus": world, "workload": "c4 (200000 items; %d users)" %
                                        (data_users if workload == "c4" else 6400)}
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             from oracle.cpu_port import time_cpu_baseline   # oracle/ is only ever the baseline / checker
             res["cpu_baseline"] = time_cpu_baseline(idx, budget_s=a.cpu_seconds, S=a.sub_epochs, batch_size=a.batch_size)
         sys.stdout.flush()

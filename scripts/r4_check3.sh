@@ -5,7 +5,7 @@ mkdir -p $O
 cd $R
 timeout 3000 python -m pytest tests -m gpu -q --timeout 1500 2>&1 | tail -6
 for i in 1 2; do
-python bench.py --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_default.json
+python bench.py --full --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_default.json
 python - <<'PY'
 import json
 d = json.load(open("gpurun_out/r4/bench_default.json"))

@@ -130,11 +130,29 @@ def test_bench_dump_outputs_of_the_timed_step(tmp_path):
     assert files["gen_W_q0.npy"].shape[1] == 600 and np.all(np.isfinite(files["gen_W_q0.npy"]))
 
 
+def test_bench_plain_run_measures_the_headline_alone():
+    """Without --full bench.py runs nothing of its own beside the timed steps: the line carries the headline keys and the roofline of the
+    kernels probed inside the run, and none of the CPU baseline, the other workloads, the per-rank proxy or the copy ceiling."""
+    import json
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--sub-epochs", "2"],
+                         capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-3000:]
+    d = json.loads(out.stdout.strip().splitlines()[-1])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config", "roofline"):
+        assert k in d, k
+    assert d["unit"] == "users/s" and d["higher_is_better"] is True and d["dtype"] == "bf16" and d["config"]["workload"] == "askubuntu"
+    assert abs(d["ms_per_step"] * 1e-3 * d["value"] - d["config"]["users"]) < 1e-3 * d["config"]["users"]
+    for k in ("cpu_baseline", "other_workloads", "projected_strong_scaling_8gpu_upper_bound", "c4_same_workload"):
+        assert k not in d, k
+    r = d["roofline"]
+    assert r["bound"] in ("hbm", "mfma") and "copy_ceiling_this_box" not in r and r["frac_of_copy_ceiling"] is None
+
+
 def test_bench_contract_one_json_line():
-    """bench.py prints ONE JSON line (the last line of stdout) carrying the driver's keys plus roofline and cpu_baseline."""
+    """bench.py --full prints ONE JSON line (the last line of stdout) carrying the driver's keys plus roofline and cpu_baseline."""
     import json
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--sub-epochs", "2",
-                          "--cpu-seconds", "3"], capture_output=True, text=True, timeout=1200, cwd=ROOT)
+                          "--cpu-seconds", "3", "--full"], capture_output=True, text=True, timeout=1200, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     line = out.stdout.strip().splitlines()[-1]
     d = json.loads(line)
@@ -173,12 +191,12 @@ def test_bench_contract_one_json_line():
 
 
 def test_bench_two_ranks_item_sharded():
-    """`python bench.py --gpus 2` with no launcher around it: the parent starts two fresh rank processes itself (before it
+    """`python bench.py --gpus 2 --full` with no launcher around it: the parent starts two fresh rank processes itself (before it
     touches the GPU), the ranks run the N > 1 branch (rank-0 reference run, item-sharded loop, max over ranks) and the
     parent relays rank 0's ONE JSON line.  The test box has one GPU, so the parent picks gloo and the ranks share it."""
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LTGAN_DIST_BACKEND")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--users", "400", "--sub-epochs", "2"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--users", "400", "--sub-epochs", "2", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     lines = [l for l in out.stdout.strip().splitlines() if l.startswith("{")]

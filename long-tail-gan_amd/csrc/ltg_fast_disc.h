@@ -14,9 +14,6 @@ __global__ __launch_bounds__(NT) void fk_d_l1(PairView pv, int h0, int h1, int h
                                               const float* __restrict__ w1, const float* __restrict__ b1, const float* __restrict__ w2,
                                               const float* __restrict__ b2, DropView dA, DropView dB, float keep, uint64_t seed,
                                               uint64_t step, float* __restrict__ A1) {
-#ifdef LTG_D_EMPTY   // MEASUREMENT BUILD ONLY (results wrong): the grid, registers and LDS of this launch, no work -- the D step's launch structure
-    if (pv.nr >= 0) return;
-#endif
     LTG_STAMP_AT(1, 0);
     __shared__ __attribute__((aligned(16))) float lds[Rg32::LDS_FLOATS];
     const int n = pv.nr + pv.nf, h12 = h1 + h2;
@@ -54,9 +51,6 @@ __global__ __launch_bounds__(DL2_NT) void fk_d_l2(int n, int h12, int h3, const 
                                               const float* __restrict__ b3, const float* __restrict__ w4, DropView dC, float keep,
                                               uint64_t seed, uint64_t step, float* __restrict__ A3, float* __restrict__ G3,
                                               float* __restrict__ spart) {
-#ifdef LTG_D_EMPTY   // MEASUREMENT BUILD ONLY (results wrong): the grid, registers and LDS of this launch, no work -- the D step's launch structure
-    if (n >= 0) return;
-#endif
     LTG_STAMP_AT(2, 0);
     __shared__ __attribute__((aligned(16))) float lds[Rg32k8::LDS_FLOATS];
     const int tn = (h3 + 31) / 32;
@@ -133,9 +127,6 @@ __global__ __launch_bounds__(NT) void fk_d_bwd1(PairView pv, int h12, int h3, in
     // started (the step's jobs B / C on the caller's aux stream, ltg_d_opts.aux_stream): opened when this launch -- job A alone then --
     // runs: the forward in front of it is complete, which is all jobs B / C wait for
     if (blockIdx.x == 0 && threadIdx.x == 0) ltg_gate_set(started);
-#ifdef LTG_D_EMPTY   // MEASUREMENT BUILD ONLY (results wrong): the grid, registers and LDS of this launch, no work -- the D step's launch structure
-    if (pv.nr >= 0) return;
-#endif
     LTG_STAMP_AT(3, 0);
     LTG_STAMP_AT(4, 0);
     __shared__ __attribute__((aligned(16))) float lds[Rg32k::LDS_FLOATS];
@@ -286,9 +277,6 @@ __global__ __launch_bounds__(DB2_NT) void fk_d_bwd2(PairView pv, int h0, int h1,
         if (threadIdx.x == 0) ltg_gate_wait_tail(end_wait);
         return;
     }
-#ifdef LTG_D_EMPTY   // MEASUREMENT BUILD ONLY (results wrong): the grid, registers and LDS of this launch, no work -- the D step's launch structure
-    if (pv.nr >= 0) return;
-#endif
     LTG_STAMP_AT(5, 0);
     __shared__ __attribute__((aligned(16))) float lds[Rg16x32k8b::LDS_FLOATS];
     const int n = pv.nr + pv.nf, h12 = h1 + h2;
@@ -359,9 +347,6 @@ __global__ __launch_bounds__(NT) void fk_d_adam(int ks, int P, int SP, const flo
     // front of the first store: as the guard of an early return it was a round trip of its own in front of every other request of a launch
     // that is nothing but round trips)
     const unsigned dead = ltg_poison_word(poison);
-#ifdef LTG_D_EMPTY   // MEASUREMENT BUILD ONLY (results wrong): the grid, registers and LDS of this launch, no work -- the D step's launch structure
-    if (ks >= 0) return;
-#endif
     const int P4 = P >> 2;
     constexpr int DA_U = 8;
     // Workgroup 0 (dispatched first) does the ragged tail and d_loss and nothing else; the sweep belongs to workgroups 1 .. gridDim.x - 1.

@@ -368,7 +368,7 @@ __global__ __launch_bounds__(NT) void fks_d_l2(int n, int h12, int h3, const flo
 // Round 4: TWO K blocks of global loads in flight per workgroup (two register sets of 16-byte pieces; LDS stays double-buffered): a
 // workgroup's stage used to last one L2 / HBM round trip (~1.2 us against 0.1 us of MFMA), 16 of them per 2048-deep tile.  The loop is
 // unrolled by two with static set names, fetches are clamped instead of guarded and a block past the end is stashed as zeros (adds
-// nothing), so the loop has no branch and every s_waitcnt is an exact count.  -DLTG_SG8_SHALLOW builds the one-block-ahead loop.
+// nothing), so the loop has no branch and every s_waitcnt is an exact count.
 // (Round 5, measured and removed: THREE blocks in flight -- three register sets, the loop unrolled by six -- D step of config 5
 // 128.1-128.5 against 115.2-115.5 us: more loads in flight make it slower, as larger tiles did; the block is not short of bytes in flight.)
 constexpr int SG8_LDK = 128;   // bytes per LDS row of the staged e4m3 block (s8[2 * (BM + BN) * SG8_LDK] per workgroup)
@@ -452,16 +452,6 @@ __device__ __forceinline__ void ltg_sgemm8_core(int K, ARow a_row, BRow b_row, l
     SG8_FETCH(0, ra, rb)
     SG8_STASH(0, ra, rb, 0)
     __syncthreads();
-#ifdef LTG_SG8_SHALLOW
-    int buf = 0;
-    for (int k0 = 0; k0 < K; k0 += BK) {
-        SG8_FETCH(k0 + BK, ra, rb)       // the next block's loads fly under this block's MFMAs
-        SG8_MFMA(buf)
-        SG8_STASH(buf ^ 1, ra, rb, k0 + BK)     // the other buffer: its readers finished before the previous barrier
-        __syncthreads();
-        buf ^= 1;
-    }
-#else
     ltg_u32x4 ra2[RA], rb2[RB];
     SG8_FETCH(BK, ra, rb)                // block 1 in flight; block 2 follows inside the loop
     for (int k0 = 0; k0 < K; k0 += 2 * BK) {
@@ -474,7 +464,6 @@ __device__ __forceinline__ void ltg_sgemm8_core(int K, ARow a_row, BRow b_row, l
         SG8_STASH(0, ra2, rb2, k0 + 2 * BK)
         __syncthreads();
     }
-#endif
 #undef SG8_FETCH
 #undef SG8_STASH
 #undef SG8_MFMA

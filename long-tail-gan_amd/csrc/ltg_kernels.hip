@@ -181,7 +181,7 @@ inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 // the streaming decoder kernels: bf16, large item slab, a training batch (<= 128 rows), H <= 608, 16-B aligned rows
 inline bool stream_ok(const ltg_config* cfg, const ltg_gen_state* gen, int rows) {
     return gen->wp1t_bf16 && cfg->precision == LTG_PREC_BF16 && cfg->n_items >= 8192 && (cfg->n_items % 8) == 0 && rows <= 128 && cfg->h_enc <= ST_KP &&
-           (cfg->h_enc % 4) == 0 && (cfg->tuning & 15) != 9;
+           (cfg->h_enc % 4) == 0;
 }
 // k_dec1_bwd_adam_stream walks the 4 H/4 float4 a wave owns per tile as exactly ten 64-lane accesses
 inline bool dw_stream_ok(int H) { return (H % 4) == 0 && H > 576 && H <= 640; }
@@ -357,12 +357,12 @@ namespace {
 inline bool fast_on(const ltg_config* c) { return (c->tuning & 262144) == 0; }
 inline bool mid_fast(const ltg_config* c, int rows) { return fast_on(c) && (c->z_dim % 4) == 0 && rows <= 256; }
 inline bool d_wide(const ltg_config* c) { return c->d_h0 >= 512 && c->d_h1 + c->d_h2 >= 512 && c->d_h3 >= 128; }
-// fp8 discriminator with EVERY GEMM operand in operand format (ltg_fp8bwd.h).  Tuning-knob bit 24 (register-resident forward
-// tiles) and bit 19 (backward converts on the fly, the round-2 path) switch it off.
+// fp8 discriminator with EVERY GEMM operand in operand format (ltg_fp8bwd.h).  Tuning-knob bit 19 (backward converts on the fly, the
+// round-2 path) switches it off.
 inline bool d_fp8_opfmt(const ltg_config* c, const ltg_disc_state* d) {
     return fast_on(c) && c->d_precision == LTG_PREC_FP8 && d->emb_fp8 && d->w1t_fp8 && d->w2t_fp8 && d->w3t_fp8 && d->w3_fp8 && (c->d_h0 % 128) == 0 &&
            ((c->d_h1 + c->d_h2) % 128) == 0 && (c->d_h3 % 128) == 0 && (c->d_h1 % 64) == 0 && (c->d_h2 % 64) == 0 && c->d_h3 <= 64 * D8_OUT_CM &&
-           (c->tuning & ((1 << 24) | (1 << 19))) == 0;
+           (c->tuning & (1 << 19)) == 0;
 }
 inline bool d_fast(const ltg_config* c) {
     return fast_on(c) && c->d_precision == LTG_PREC_FP32 && !d_wide(c) && c->d_h3 <= 512 && (c->d_h0 % 4) == 0 && ((c->d_h1 + c->d_h2) % 4) == 0 && (c->d_h3 % 4) == 0;
@@ -390,11 +390,13 @@ inline bool small_fast(const ltg_config* c, int rows) {
     return fast_on(c) && unsharded(c) && c->n_items <= RD_MAXI && (c->n_items % 4) == 0 && (c->z_dim % 4) == 0 && rows <= 256;
 }
 
+// ltg_config.tuning: the selection bits include/ltg.h lists; a configuration with any other bit is refused
+constexpr int32_t TUNING_BITS = (1 << 14) | (1 << 17) | (1 << 18) | (1 << 19) | (1 << 20) | (1 << 21) | (1 << 22) | (1 << 26);
 bool cfg_ok(const ltg_config* c) {
     return c && c->n_items > 0 && c->h_enc > 0 && c->h_enc <= 768 && (c->h_enc % 4) == 0 && c->z_dim > 0 &&
            c->d_h0 >= 1 && c->d_h1 >= 1 && c->d_h2 >= 1 && c->d_h3 >= 1 &&      // (a layer of width 0 has no tile to launch: refused, not computed)
            (c->precision == LTG_PREC_BF16 || c->precision == LTG_PREC_FP32) && c->d_precision >= 0 && c->d_precision <= LTG_PREC_FP8 &&
-           c->d_arith >= 0 && (c->d_arith & 3) <= LTG_DARITH_BF16X4 && (c->d_arith & ~0xF3) == 0;
+           c->d_arith >= 0 && (c->d_arith & 3) <= LTG_DARITH_BF16X4 && (c->d_arith & ~0xF3) == 0 && (c->tuning & ~TUNING_BITS) == 0;
 }
 
 inline int Ig_of(const ltg_config* cfg) { return cfg->n_items_global > 0 ? cfg->n_items_global : cfg->n_items; }
@@ -478,7 +480,7 @@ int fwd_stage_rest(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_ba
     int stat_groups = 0;
     const int R = bt->n_rows, I = cfg->n_items, H = cfg->h_enc, Z = cfg->z_dim;
     const Probe pr{o->probe, st};
-    const bool vz = (Z % 4) == 0 && (cfg->tuning & 8192) == 0;   // 16-B loaders of the middle layers (H % 4 == 0 always)
+    const bool vz = (Z % 4) == 0;   // 16-B loaders of the middle layers (H % 4 == 0 always)
     if (apply_bias_tanh) {
         const int n = R * H;
         hipLaunchKernelGGL(k_bias_tanh, dim3((n + NT - 1) / NT < 1024 ? (n + NT - 1) / NT : 1024), dim3(NT), 0, st, n, H, gen->p[4], acts->h1);
@@ -512,8 +514,7 @@ int fwd_stage_rest(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_ba
             else
                 launch_dec1_fwd_stream(cfg, gen, R, acts, nullptr, st);
         } else if (bf && big) hipLaunchKernelGGL((k_dec1_fwd<true, true>), grid2(I, R, 64, 128), dim3(NT), 0, st, R, I, H, acts->h2, gen->p[3], gen->p[7], acts->logits);
-        else if (bf && (cfg->tuning & 65536) == 0) hipLaunchKernelGGL((k_dec1_fwd<true, false, true>), grid2(I, R, 32, 32), dim3(NT), 0, st, R, I, H, acts->h2, gen->p[3], gen->p[7], acts->logits);
-        else if (bf) hipLaunchKernelGGL((k_dec1_fwd<true, false>), grid2(I, R, 32, 32), dim3(NT), 0, st, R, I, H, acts->h2, gen->p[3], gen->p[7], acts->logits);
+        else if (bf) hipLaunchKernelGGL((k_dec1_fwd<true, false, true>), grid2(I, R, 32, 32), dim3(NT), 0, st, R, I, H, acts->h2, gen->p[3], gen->p[7], acts->logits);
         else if (big) hipLaunchKernelGGL((k_dec1_fwd<false, true>), grid2(I, R, 64, 128), dim3(NT), 0, st, R, I, H, acts->h2, gen->p[3], gen->p[7], acts->logits);
         else hipLaunchKernelGGL((k_dec1_fwd<false, false>), grid2(I, R, 32, 32), dim3(NT), 0, st, R, I, H, acts->h2, gen->p[3], gen->p[7], acts->logits);
         pr.after(LTG_K_DEC1_FWD);
@@ -561,17 +562,13 @@ inline int d_mode(const ltg_config* cfg) { return cfg->d_precision == LTG_PREC_B
 inline int d_tile(const ltg_config* cfg, int which) {
     const bool wide = cfg->d_h0 >= 512 && cfg->d_h1 + cfg->d_h2 >= 512 && cfg->d_h3 >= 128;
     const bool vec = (cfg->d_h0 % 4) == 0 && (cfg->d_h1 % 4) == 0 && (cfg->d_h2 % 4) == 0 && (cfg->d_h3 % 4) == 0;
-    const int knob = (cfg->tuning >> 10) & 7;        // tuning: 1 scalar, 2 all 64, 3 all 128
-    if (knob == 1) return 32;
     if (!(wide && vec)) {
         // default sizes (100/150/250/300): l2 and backward stage 1 only touch h12 = 400 and h3 = 300 wide rows -> 16-B
         // loaders on the 32 x 32 tiles; l1 / stage 2 index columns of width h1 = 150 (8-B aligned only) -> scalar
         const bool v12 = ((cfg->d_h1 + cfg->d_h2) % 4) == 0 && (cfg->d_h3 % 4) == 0;
         if (which == 1 || which == 2) return v12 ? -32 : 32;
-        return ((cfg->d_h0 % 4) == 0 && (cfg->tuning & 32768) == 0) ? -33 : 32;   // embedding rows (operand A) in 16-B pieces
+        return (cfg->d_h0 % 4) == 0 ? -33 : 32;   // embedding rows (operand A) in 16-B pieces
     }
-    if (knob == 2) return 64;
-    if (knob == 3) return 128;
     if (which == 1) return d_mode(cfg) == 2 ? 64 : -32;   // l2 (N = h3 = 256): too few 64-tiles to fill the chip unless the loads are the bottleneck
     return which == 3 ? 128 : 64;
 }
@@ -640,7 +637,7 @@ void disc_forward(const ltg_config* cfg, const ltg_disc_state* d, PairView pv, D
     const int md = d_mode(cfg), ts = d_tile(cfg, 0), ts2 = d_tile(cfg, 1), t1 = ts < 0 ? 32 : ts, t2 = ts2 < 0 ? 32 : ts2;
     if (md == 2 && fast_on(cfg) && d->emb_fp8 && d->w1t_fp8 && d->w2t_fp8 && d->w3t_fp8 && (h0 % 64) == 0 && (h12 % 64) == 0) {
         // operand-format storage: both forward layers read e4m3 bytes (embedding table, transposed weight shadows, A1 in e4m3)
-        const bool staged = (h0 % 128) == 0 && (h12 % 128) == 0 && (cfg->tuning & (1 << 24)) == 0;   // LDS-staged tiles (knob bit 24: register-resident)
+        const bool staged = (h0 % 128) == 0 && (h12 % 128) == 0;   // LDS-staged tiles (64- but not 128-multiples: the register-resident block)
         if (with_bwd && d_fp8_opfmt(cfg, d)) {
             // the step's own forward: the same products, and every activation the backward multiplies is left behind in e4m3 in the
             // orientation its GEMM contracts over (ltg_fp8bwd.h)
@@ -795,8 +792,7 @@ static int d_step_impl(const ltg_config* cfg, const ltg_disc_state* disc, PairVi
         // the fork's two gate kernels and its poll cost more than they hide -- and not steadily: D step 32.6-38.9 us with the fork against 34.1 +- 0.1
         // without at 20 000 items, 34.1-38.2 against 32.4 at 200 000 -- profiles/r6_ab_d_fork_small.txt.  Either way the same kernels write the same slab
         // entries: same bits.)
-        const bool fork = o->aux_stream && o->sync && !grad_out && (cfg->tuning & 64) == 0 &&      // (tuning-knob bit 6: no fork)
-                          n >= LTG_D_FORK_MIN_ROWS && d_adam_flat(cfg, disc, L, SP, w.slab, nullptr);
+        const bool fork = o->aux_stream && o->sync && !grad_out && n >= LTG_D_FORK_MIN_ROWS && d_adam_flat(cfg, disc, L, SP, w.slab, nullptr);
         const unsigned* poison = fork ? o->sync + 2 : nullptr;
         const int spl1 = d_spl(cfg, 2), spl2 = d_spl(cfg, 3);
         LTG_PROBED(pr, LTG_K_D_BWD1, LTG_D_SPL_LAUNCH(spl1, fk_d_bwd1, dim3(fork ? nA : nA + nB + nC), dim3(NT), 0, st, pv, h12, h3, nA, nB, ntile, L, SP, w.A1, w.A3, w.G3,
@@ -834,7 +830,7 @@ static int d_step_impl(const ltg_config* cfg, const ltg_disc_state* disc, PairVi
     int ts = d_tile(cfg, 2);
     {   // backward stage 1 with > 1024 32 x 32 tiles is throughput-bound, not latency-bound: 64 x 64 tiles (measured -5 %)
         const long t32 = (long)((n + 31) / 32) * ((h12 + 31) / 32) + (long)ks * ((h12 + 32) / 32) * ((h3 + 31) / 32);
-        if (ts == -32 && t32 > 1024 && (cfg->tuning & 4096) == 0) ts = 64;
+        if (ts == -32 && t32 > 1024) ts = 64;
     }
     const int md = d_mode(cfg), tsb = d_tile(cfg, 3), ta = ts < 0 ? 32 : ts, tb = tsb < 0 ? 32 : tsb;
     auto tiles = [ta](int x) { return (x + ta - 1) / ta; };
@@ -936,7 +932,7 @@ static void g_row_partial(const ltg_config* cfg, const ltg_batch* bt, const ltg_
 
 // dlog as bf16: when BOTH its consumers are the streaming kernels (k_dh2_stream, k_dec1_bwd_adam_stream + ragged tail)
 static bool dlog16_ok(const ltg_config* cfg, const ltg_gen_state* gen, int B) {
-    return fast_on(cfg) && stream_ok(cfg, gen, B) && dw_stream_ok(cfg->h_enc) && (cfg->tuning & 15) == 0 && (cfg->tuning & (1 << 22)) == 0;
+    return fast_on(cfg) && stream_ok(cfg, gen, B) && dw_stream_ok(cfg->h_enc) && (cfg->tuning & (1 << 22)) == 0;
 }
 
 static int g_stage_bwd_dec(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_disc_state* disc, const ltg_batch* bt,
@@ -975,7 +971,7 @@ static int g_stage_bwd_dec(const ltg_config* cfg, const ltg_gen_state* gen, cons
     if (stream && d16) hipLaunchKernelGGL((k_dh2_stream<true, DH2_NH>), dim3(nsplit, DH2_NH), dim3(ST_NT), (size_t)2 * ST_BN * ST_LDW * 2, st, B, I, H, kchunk, w.dlog, gen->wp1t_bf16, w.part);
     else if (stream) hipLaunchKernelGGL((k_dh2_stream<false, DH2_NH>), dim3(nsplit, DH2_NH), dim3(ST_NT), (size_t)2 * ST_BN * ST_LDW * 2, st, B, I, H, kchunk, w.dlog, gen->wp1t_bf16, w.part);
     else if (bf && big) hipLaunchKernelGGL((k_dh2_partial<true, true>), grid2(H, B, 64, 128, nsplit), dim3(NT), 0, st, B, I, H, kchunk, w.dlog, gen->p[3], w.part);
-    else if (bf && (I % 4) == 0 && (cfg->tuning & 65536) == 0) hipLaunchKernelGGL((k_dh2_partial<true, false, true>), grid2(H, B, 32, 32, nsplit), dim3(NT), 0, st, B, I, H, kchunk, w.dlog, gen->p[3], w.part);
+    else if (bf && (I % 4) == 0) hipLaunchKernelGGL((k_dh2_partial<true, false, true>), grid2(H, B, 32, 32, nsplit), dim3(NT), 0, st, B, I, H, kchunk, w.dlog, gen->p[3], w.part);
     else if (bf) hipLaunchKernelGGL((k_dh2_partial<true, false>), grid2(H, B, 32, 32, nsplit), dim3(NT), 0, st, B, I, H, kchunk, w.dlog, gen->p[3], w.part);
     else if (big) hipLaunchKernelGGL((k_dh2_partial<false, true>), grid2(H, B, 64, 128, nsplit), dim3(NT), 0, st, B, I, H, kchunk, w.dlog, gen->p[3], w.part);
     else hipLaunchKernelGGL((k_dh2_partial<false, false>), grid2(H, B, 32, 32, nsplit), dim3(NT), 0, st, B, I, H, kchunk, w.dlog, gen->p[3], w.part);
@@ -1100,7 +1096,7 @@ static void g_chain(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_b
     LTG_PROBED(pr, LTG_K_DZ, hipLaunchKernelGGL(fk_dz, grid2(Z, B, 16, 16), dim3(NT), 0, st, B, Z, H, w.da2, gen->p[2], acts->mulv, o->fwd.eps,
                                                 o->fwd.is_training, o->anneal, cfg->seed, o->fwd.rng_step, w.dmlv));
     LTG_PROBED(pr, LTG_K_DH1, hipLaunchKernelGGL(fk_dh1, grid2(H, B, 16, 16), dim3(NT), 0, st, B, H, 2 * Z, w.dmlv, gen->p[1], acts->h1, w.da1));
-    const bool fused = lazy && fast_on(cfg) && (cfg->tuning & (1 << 25)) == 0;   // Adam on the batch's rows inside the gradient kernel
+    const bool fused = lazy && fast_on(cfg);   // Adam on the batch's rows inside the gradient kernel
     const bool row_waves = (cfg->tuning & (1 << 14)) == 0;   // tuning-knob bit 14: the column-blocked shape of the sparse gradient
     if (fused) g_enc0_grad(cfg, bt, o, acts, w, st, gen, &ad, row_waves);
     else if (slot || lazy) g_enc0_grad(cfg, bt, o, acts, w, st, nullptr, nullptr, row_waves);
@@ -1120,12 +1116,12 @@ static void g_chain(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_b
 
 static int g_stage_bwd_rest(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_batch* bt, const ltg_g_opts* o,
                             const ltg_gen_acts* acts, const float* dh2, const Workspace& w, hipStream_t st, bool da2_ready = false,
-                            bool only_dec1 = false, int dw_groups = 0, LtgH2Done hd = LtgH2Done{nullptr, nullptr, 0u, nullptr}) {
+                            bool only_dec1 = false, LtgH2Done hd = LtgH2Done{nullptr, nullptr, 0u, nullptr}) {
     const int B = bt->n_rows, I = cfg->n_items, H = cfg->h_enc, Z = cfg->z_dim;
     const AdamC ad = make_adam(cfg, o->adam_t);
     const bool bf = cfg->precision == LTG_PREC_BF16;
     const bool big = I >= 8192;
-    const bool vz = (Z % 4) == 0 && (cfg->tuning & 8192) == 0;   // 16-B loaders of the middle layers (H % 4 == 0 always)
+    const bool vz = (Z % 4) == 0;   // 16-B loaders of the middle layers (H % 4 == 0 always)
     // Everything on `st` unless the lazy clock's chain runs beside the weight update (below).  (Measured and removed: small item slabs,
     // the three weight-gradient + Adam kernels on the aux stream beside da2 -> dz -> dh1 -> sweep -- the event pairs cost more than the
     // overlap saves once the chain's kernels take 6-18 us; I = 200 000, the two HBM sweeps side by side: they only contend.)
@@ -1145,18 +1141,15 @@ static int g_stage_bwd_rest(const ltg_config* cfg, const ltg_gen_state* gen, con
     auto launch_dw = [&]() {
         const Probe prs{o->probe, s_dw};
         prs.before(LTG_K_DEC1_BWD_ADAM);
-        const int var = (cfg->tuning & 15) > 0 ? (cfg->tuning & 15) - 1 : (big ? 2 : 0);   // tuning: tuning knob (0 = auto)
-        if (stream_ok(cfg, gen, B) && dw_stream_ok(H) && (cfg->tuning & 15) == 0) {
+        if (stream_ok(cfg, gen, B) && dw_stream_ok(H)) {
             const int ntl = I / 32;
             if (dlog16_ok(cfg, gen, B)) {   // (the producer, g_stage_bwd_dec, stored dlog as bf16 under the same predicate)
                 // persistent workgroups: 224 = 28 per XCD (measured 657 us at 200 000 items; 256: 678, 240: 669, 192: 671) -- and 32 CUs
-                // stay free for whatever runs beside it.  Tuning-knob bits 27-30 = k: 256 - 8 k instead.
-                const int gk = (cfg->tuning >> 27) & 15;
-                int gmax = gk ? 256 - 8 * gk : dw_gmax;
+                // stay free for whatever runs beside it ...
+                int gmax = dw_gmax;
                 // ... and no more workgroups than the same number of rounds needs (782 tiles of a 25 024-item slab: 4 rounds with
                 // 224 or with 196 workgroups -- 60 CUs left to the chain and the collective running beside it)
-                if (!gk && ntl > gmax) gmax = (ntl + (ntl + gmax - 1) / gmax - 1) / ((ntl + gmax - 1) / gmax);
-                if (dw_groups > 0) gmax = dw_groups;
+                if (ntl > gmax) gmax = (ntl + (ntl + gmax - 1) / gmax - 1) / ((ntl + gmax - 1) / gmax);
                 hipLaunchKernelGGL(k_dec1_bwd_adam_stream<true>, dim3(ntl < gmax ? ntl : gmax), dim3(ST_NT), 0, s_dw, B, I, H, w.dlog, acts->h2, *gen, ad, hd);
                 if (I % 32)   // ragged tail: the generic tile kernel on the last I % 32 item rows
                     hipLaunchKernelGGL((k_dec1_bwd_adam<true, 2, false, true>), grid2(H + 1, I - ntl * 32, 64, 64), dim3(NT), 0, s_dw, B, I, H, w.dlog, acts->h2, *gen, ad, ntl * 32,
@@ -1167,13 +1160,11 @@ static int g_stage_bwd_rest(const ltg_config* cfg, const ltg_gen_state* gen, con
                     hipLaunchKernelGGL((k_dec1_bwd_adam<true, 2>), grid2(H + 1, I - ntl * 32, 64, 64), dim3(NT), 0, s_dw, B, I, H, w.dlog, acts->h2, *gen, ad, ntl * 32);
             }
         } else if (!bf) {
-            if (var == 0) hipLaunchKernelGGL((k_dec1_bwd_adam<false, 0>), grid2(H + 1, I, 32, 32), dim3(NT), 0, s_dw, B, I, H, w.dlog, acts->h2, *gen, ad, 0);
-            else hipLaunchKernelGGL((k_dec1_bwd_adam<false, 2>), grid2(H + 1, I, 64, 64), dim3(NT), 0, s_dw, B, I, H, w.dlog, acts->h2, *gen, ad, 0);
-        } else if (var == 0 && (I % 4) == 0 && (cfg->tuning & 65536) == 0) hipLaunchKernelGGL((k_dec1_bwd_adam<true, 0, true>), grid2(H + 1, I, 32, 32), dim3(NT), 0, s_dw, B, I, H, w.dlog, acts->h2, *gen, ad, 0);
-        else if (var == 0) hipLaunchKernelGGL((k_dec1_bwd_adam<true, 0>), grid2(H + 1, I, 32, 32), dim3(NT), 0, s_dw, B, I, H, w.dlog, acts->h2, *gen, ad, 0);
-        else if (var == 1) hipLaunchKernelGGL((k_dec1_bwd_adam<true, 1>), grid2(H + 1, I, 128, 64), dim3(NT), 0, s_dw, B, I, H, w.dlog, acts->h2, *gen, ad, 0);
-        else if (var == 2) hipLaunchKernelGGL((k_dec1_bwd_adam<true, 2>), grid2(H + 1, I, 64, 64), dim3(NT), 0, s_dw, B, I, H, w.dlog, acts->h2, *gen, ad, 0);
-        else hipLaunchKernelGGL((k_dec1_bwd_adam<true, 3>), grid2(H + 1, I, 128, 32), dim3(NT), 0, s_dw, B, I, H, w.dlog, acts->h2, *gen, ad, 0);
+            if (big) hipLaunchKernelGGL((k_dec1_bwd_adam<false, 2>), grid2(H + 1, I, 64, 64), dim3(NT), 0, s_dw, B, I, H, w.dlog, acts->h2, *gen, ad, 0);
+            else hipLaunchKernelGGL((k_dec1_bwd_adam<false, 0>), grid2(H + 1, I, 32, 32), dim3(NT), 0, s_dw, B, I, H, w.dlog, acts->h2, *gen, ad, 0);
+        } else if (big) hipLaunchKernelGGL((k_dec1_bwd_adam<true, 2>), grid2(H + 1, I, 64, 64), dim3(NT), 0, s_dw, B, I, H, w.dlog, acts->h2, *gen, ad, 0);
+        else if ((I % 4) == 0) hipLaunchKernelGGL((k_dec1_bwd_adam<true, 0, true>), grid2(H + 1, I, 32, 32), dim3(NT), 0, s_dw, B, I, H, w.dlog, acts->h2, *gen, ad, 0);
+        else hipLaunchKernelGGL((k_dec1_bwd_adam<true, 0>), grid2(H + 1, I, 32, 32), dim3(NT), 0, s_dw, B, I, H, w.dlog, acts->h2, *gen, ad, 0);
         prs.after(LTG_K_DEC1_BWD_ADAM);
     };
     if ((o->fake_done & G_AUX_SWEEP) && q0_lazy(cfg, gen) && mid_fast(cfg, B) && !only_dec1) {
@@ -1277,9 +1268,9 @@ int ltg_g_step(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_disc_s
     // lazy Adam clock of W_q0: the batch's rows up to date first; its rotating slice (rows NOT of this batch: arithmetic-bound,
     // 48 registers -- it fits beside the 2 x 232-register waves of the HBM-bound decoder kernels) then runs on the aux stream
     q0_touch(cfg, gen, bt, st);
-    const bool aux_sweep = q0_lazy(cfg, gen) && o->aux_stream && o->ev_fork && o->ev_sweep && (cfg->tuning & 512) == 0;
+    const bool aux_sweep = q0_lazy(cfg, gen) && o->aux_stream && o->ev_fork && o->ev_sweep;
     // fork: the fake tower (independent of the generator forward) runs on the caller's aux stream
-    const bool fork = o->aux_stream && o->ev_fork && o->ev_join && nf > 0 && (cfg->tuning & 512) == 0 && !have_y;
+    const bool fork = o->aux_stream && o->ev_fork && o->ev_join && nf > 0 && !have_y;
     if (fork || aux_sweep) {
         hipStream_t aux = (hipStream_t)o->aux_stream;
         if (hipEventRecord((hipEvent_t)o->ev_fork, st) != hipSuccess || hipStreamWaitEvent(aux, (hipEvent_t)o->ev_fork, 0) != hipSuccess)
@@ -1474,6 +1465,8 @@ static bool q0_ahead_capable(const ltg_config* cfg, const ltg_gen_state* gen, co
     if (fl & (LTG_PIPE_NO_DEC1_FORK | LTG_PIPE_NO_SLICE_FORK | LTG_PIPE_EVENTS | LTG_PIPE_SLICE_IN_TOUCH)) return false;
     return q0_lazy(cfg, gen) && (cfg->h_enc >> 2) <= Q0_NT;
 }
+// ltg_pipe.flags: the LTG_PIPE_* switches of include/ltg.h; a pipe with any other bit is refused
+constexpr int32_t PIPE_FLAGS = LTG_PIPE_NO_DEC1_FORK | LTG_PIPE_NO_SLICE_FORK | LTG_PIPE_WIDE_GRAD | LTG_PIPE_EVENTS | LTG_PIPE_SLICE_IN_TOUCH | LTG_PIPE_TAIL_OWN;
 // the pipe's hand-overs are device words (not events, not program order)
 static bool pipe_gates(const ltg_pipe* pp) { return pp->sync && (pp->flags & (LTG_PIPE_NO_DEC1_FORK | LTG_PIPE_EVENTS)) == 0; }
 // the weight update writes the pipe's second shadow buffer
@@ -1481,7 +1474,7 @@ static bool shadow_pingpong(const ltg_gen_state* gen, const ltg_pipe* pp) {
     return pipe_gates(pp) && pp->shadow_out && gen->wp1t_bf16 && pp->shadow_out != gen->wp1t_bf16;
 }
 int ltg_g_step_sharded_plan(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_batch* bt, const ltg_pipe* pp) {
-    if (!cfg_ok(cfg) || !gen || !bt || !pp || !ltg_g_step_sharded_ok(cfg, gen, bt->n_rows)) return 0;
+    if (!cfg_ok(cfg) || !gen || !bt || !pp || (pp->flags & ~PIPE_FLAGS) != 0 || !ltg_g_step_sharded_ok(cfg, gen, bt->n_rows)) return 0;
     return (q0_ahead_capable(cfg, gen, bt, pp) ? LTG_PLAN_AHEAD : 0) | (shadow_pingpong(gen, pp) ? LTG_PLAN_SHADOW : 0);
 }
 
@@ -1534,7 +1527,7 @@ int ltg_g_step_sharded(const ltg_config* cfg, const ltg_gen_state* gen, const lt
     if (!bt->uptr || !bt->rowidx || !bt->csr_pos || !o->cnt || !fake->row || fake->n < 0) return LTG_EINVAL;
     if (bt->n_unique < 0 || (size_t)bt->n_unique > gq0_rows(cfg, bt->n_rows)) return LTG_EINVAL;
     if (!ltg_g_step_sharded_ok(cfg, gen, bt->n_rows)) return LTG_EINVAL;
-    if (!pp->side_stream || !pp->ev_fork || !pp->ev_dec1 || !pp->h1pre || !pp->rowpart_all || !pp->dh2) return LTG_EINVAL;
+    if (!pp->side_stream || !pp->ev_fork || !pp->ev_dec1 || !pp->h1pre || !pp->rowpart_all || !pp->dh2 || (pp->flags & ~PIPE_FLAGS) != 0) return LTG_EINVAL;
     const int R = comm ? comm->n_ranks : 1, rank = comm ? comm->rank : 0;
     if (R < 1 || rank < 0 || rank >= R || (comm && (!comm->all_reduce || !comm->all_gather))) return LTG_EINVAL;
     const int B = bt->n_rows, I = cfg->n_items, H = cfg->h_enc, Z = cfg->z_dim, nf = fake->n;
@@ -1644,14 +1637,7 @@ int ltg_g_step_sharded(const ltg_config* cfg, const ltg_gen_state* gen, const lt
     // 290 us instead of 44 and the update 30 us longer: the step is HBM-bound, overlapping two bandwidth-bound kernels moves no byte
     // less.  profiles/r4_ab_c4_two_launch_split.txt, r4_c4_timeline_two_launch_split.txt.)
     LTG_PROBED(pr, LTG_K_DEC0, hipLaunchKernelGGL(fk_dec0, grid2(H, B, 16, 16), dim3(NT), 0, st, B, H, Z, acts->z, acts->mulv, gen->p[2], gen->p[6], acts->kl_rows,
-                                                  acts->h2,
-#ifdef LTG_X_NO_W7   // MEASUREMENT BUILD ONLY (results wrong): the streaming forward does not wait for the end of the previous weight update -- the
-                     // upper bound of what ANY earlier hand-over of the shadow (tile by tile, word 7 sooner) could gain
-                                                  LTG_NO_GATE,
-#else
-                                                  gates ? LtgGate{pp->sync + 7, pp->seq - 1u, pp->sync + 2, 0} : LTG_NO_GATE,
-#endif
-                                                  poison));
+                                                  acts->h2, gates ? LtgGate{pp->sync + 7, pp->seq - 1u, pp->sync + 2, 0} : LTG_NO_GATE, poison));
     // (Round 5, measured and removed: with ONE rank no exchange sits between the row statistics and dlogits, so k_row_stats_merge was folded
     // into k_dlogits_combine -- every (segment, row) workgroup re-folding the 256 (max, sum exp) pairs and the sparse terms of its row, the
     // step's scalars from the last of B tickets; bit-identical.  The fused kernel took 16.9 us against 10.0 + 5.6 for the two launches:
@@ -1687,7 +1673,6 @@ int ltg_g_step_sharded(const ltg_config* cfg, const ltg_gen_state* gen, const lt
         ltg_g_opts od = *o;
         od.fake_done = 0;
         od.dec1_done = 0;
-        const int dw_groups = (pp->flags >> 8) & 0x1FF;   // measurement: persistent workgroups of the weight update (0 = the library's choice)
         hipStream_t sdw = st;
         const int n_da2 = B * H;
         if (gates)   // the slab sum first: it is the next kernel of the critical stream, the side stream's launches take the host ~30 us
@@ -1711,7 +1696,7 @@ int ltg_g_step_sharded(const ltg_config* cfg, const ltg_gen_state* gen, const lt
         const LtgH2Done hd_last = h2_early ? LtgH2Done{pp->sync + 8, pp->sync + 1, pp->seq, poison} : LtgH2Done{nullptr, nullptr, 0u, poison};
         ltg_gen_state gen_dw = *gen;
         if (pingpong) gen_dw.wp1t_bf16 = pp->shadow_out;   // (the caller exchanges the two pointers after the call)
-        const int rc = g_stage_bwd_rest(cfg, &gen_dw, bt, &od, acts, nullptr, w, sdw, true, true, dw_groups, hd_last);
+        const int rc = g_stage_bwd_rest(cfg, &gen_dw, bt, &od, acts, nullptr, w, sdw, true, true, hd_last);
         if (rc != LTG_OK) return rc;
         // (Round 4, measured and removed: word 7 stored by the NEXT call's first waiter on the side stream when it starts, instead of by one
         // wave behind the update: 149.8 against 146.8 us per step at 20 000 items, 165.7 against 161.5 at 25 024 -- slower; and a host that is

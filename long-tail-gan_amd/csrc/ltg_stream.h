@@ -567,21 +567,6 @@ __global__ __launch_bounds__(ST_NT) void k_dec1_bwd_adam_stream(int B, int I, in
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, lr = lane & 15, lq = lane >> 4;
     if (ltg_poisoned(hd.poison)) return;
     float4 *W4 = reinterpret_cast<float4*>(st.p[3]), *M4 = reinterpret_cast<float4*>(st.m[3]), *V4 = reinterpret_cast<float4*>(st.v[3]);
-#if defined(LTG_X_SPIN)
-    // MEASUREMENT BUILD ONLY (results wrong): the kernel's footprint (registers, LDS, one workgroup per CU) for LTG_X_SPIN us, no memory traffic
-    {
-        Dl[0][tid] = 0;
-        Cs[tid] = 0.f;
-        asm volatile("v_mov_b32 v220, 0" ::: "v220");
-        const unsigned long long t0 = wall_clock64();
-        while (wall_clock64() - t0 < (unsigned long long)(LTG_X_SPIN) * 100ull) __builtin_amdgcn_s_sleep(16);
-        if (Dl[0][tid] == 1) W4[0].x = Cs[tid];
-        return;
-    }
-#elif defined(LTG_X_NOUPDATE)
-    // MEASUREMENT BUILD ONLY (weights do not move): no update at all -- what the chain costs with nothing beside it
-    if (B >= 0) return;
-#endif
     float *bb = st.p[7], *mb = st.m[7], *vb = st.v[7];
     unsigned short* Wb = st.wp1t_bf16;
     // stationary B fragments: B[k = b][n] = h2[b][n] (n < H), 1 (n == H), 0 beyond.  Built through LDS in four
@@ -682,14 +667,9 @@ __global__ __launch_bounds__(ST_NT) void k_dec1_bwd_adam_stream(int B, int I, in
     // theta / m / v as NON-TEMPORAL accesses (the nt bit of global_load / global_store): each element is touched exactly once per step, by
     // this kernel only (the forward reads the bf16 shadow) -- 360 MB per step at 25 024 items that would otherwise push everything else
     // out of the L2s and the memory-side cache.  Measured (same box, interleaved): per-rank proxy 197-204 -> 194 us per G step, C4-shaped
-    // phase G 272-274 -> 256-262 ms, C3-shaped 117.6 -> 114.7 ms.  -DLTG_DW_TEMPORAL builds the plain accesses.
-#ifndef LTG_DW_TEMPORAL
+    // phase G 272-274 -> 256-262 ms, C3-shaped 117.6 -> 114.7 ms.
 #define DW_LDG(P) __builtin_nontemporal_load(P)
 #define DW_STG(V, P) __builtin_nontemporal_store(V, P)
-#else
-#define DW_LDG(P) (*(P))
-#define DW_STG(V, P) (*(P) = (V))
-#endif
 #define DW_LD(S, tt, NJ, J0, LOFF)                                                      \
     _Pragma("unroll") for (int jj = 0; jj < NJ; ++jj) {                                 \
         const size_t u = (size_t)((tt) * 32 + 4 * w) * rowB + 1024u * ((J0) + jj);      \

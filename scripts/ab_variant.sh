@@ -1,6 +1,7 @@
 # same library, two settings of the tuning knob (cfg.tuning) on ONE box: A/B of a schedule or kernel variant
 # usage: ab_variant.sh <workload> <variantA> <variantB> [kernel names...]
-W=${1:-c4}; A=${2:-0}; B=${3:-512}; shift 3 2>/dev/null
+# (default arms: the library's choice against bit 18, the generic kernels)
+W=${1:-c4}; A=${2:-0}; B=${3:-262144}; shift 3 2>/dev/null
 KS=${@:-dec1_bwd_adam enc0_bwd_adam dz dh1}
 for v in $A $B $A $B; do
     python bench.py --workload $W --users 3200 --steps 2 --warmup 1 --no-cpu-baseline --variant $v 2>/dev/null | tail -1 > gpurun_out/ab.json

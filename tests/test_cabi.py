@@ -105,6 +105,18 @@ def test_argument_validation_returns_codes_without_gpu():
     for code, ok in ((0, True), (1, True), (2, True), (1 | (0xE << 4), True), (3, False), (1 | (1 << 8), False), (-1, False)):
         c = cabi.ltg_config(1000, 600, 200, 1000, 100, 150, 250, 300, 0, 0, 0, 0, 1, code, 1e-4, 0.9, 0.999, 1e-8, 1)
         assert (lib.ltg_workspace_bytes(C.byref(c), 100, 2000) > 0) == ok, code
+    # ltg_config.tuning: the selection bits 14, 17-22 and 26; a retired measurement bit (0-3, 9, 12, 24, 27) or one never assigned (7) is refused
+    kept = [1 << b for b in (14, 17, 18, 19, 20, 21, 22, 26)] + [(1 << 18) | (1 << 20)]
+    for bits, ok in [(0, True)] + [(b, True) for b in kept] + [(b, False) for b in (1, 9, 1 << 7, 1 << 9, 1 << 12, 1 << 24, 1 << 27, -1)]:
+        c = cabi.ltg_config(1000, 600, 200, 1000, 100, 150, 250, 300, 0, bits, 0, 0, 1, 0, 1e-4, 0.9, 0.999, 1e-8, 1)
+        assert (lib.ltg_workspace_bytes(C.byref(c), 100, 2000) > 0) == ok, bits
+    # ltg_pipe.flags: the LTG_PIPE_* switches only (the plan of a call that would be refused is 0); host-side checks, no pointer is read
+    sh = cabi.ltg_config(8192, 600, 200, 1000, 100, 150, 250, 300, 0, 0, 0, 0, 1, 0, 1e-4, 0.9, 0.999, 1e-8, 1)
+    gen = cabi.ltg_gen_state(wp1t_bf16=0x1000, q0_last=0x2000, q0_lr_hist=0x3000, q0_ord=0, q0_period=1)
+    bt = cabi.ltg_batch(n_rows=16)
+    for flags, ok in ((0, True), (cabi.LTG_PIPE_TAIL_OWN | cabi.LTG_PIPE_WIDE_GRAD | cabi.LTG_PIPE_SLICE_IN_TOUCH, True), (1 << 8, False), (64, False)):
+        pp = cabi.ltg_pipe(sync=0x4000, shadow_out=0x5000, flags=flags)
+        assert (lib.ltg_g_step_sharded_plan(C.byref(sh), C.byref(gen), C.byref(bt), C.byref(pp)) == cabi.LTG_PLAN_SHADOW) == ok, flags
     # the forward-only tower's split weights live in the workspace only where that kernel serves the sizes (h0 <= 128, h3 <= 320, fp32 discriminator)
     wide = cabi.ltg_config(1000, 600, 200, 1000, 2048, 1024, 512, 256, 0, 0, 0, 0, 1, 1, 1e-4, 0.9, 0.999, 1e-8, 1)
     assert lib.ltg_workspace_bytes(C.byref(good), 1, 64) - lib.ltg_workspace_bytes(C.byref(cabi.ltg_config(1000, 600, 200, 1000, 100, 150, 250, 324, 0, 0, 0, 0, 1, 0, 1e-4, 0.9, 0.999, 1e-8, 1)), 1, 64) > 900000

@@ -581,6 +581,23 @@ int ltg_topk(const ltg_config* cfg, const float* logits, const ltg_batch* tr, in
 int ltg_topk_merge(int32_t n_parts, int32_t n_rows, int32_t k_in, const float* score_in, const int32_t* id_in, int32_t k,
                    float* score_out, int32_t* id_out, ltg_stream stream);
 
+/* Long-tail report from top-K lists (additive in ABI v14): per user and item group NDCG@k_ndcg / Recall@k_r1 / Recall@k_r2, and
+ * the exposure counts, without another scan of the logits.  id_in [n_rows][k_in] as ltg_topk / ltg_topk_merge write it (GLOBAL
+ * ids in rank order, distinct, padding -1); te = held-out rows, GLOBAL ids ascending per row, te->n_rows == n_rows; item_group
+ * [n_items_global] uint8 labels, a label >= n_groups belongs to no group; 1 <= n_groups <= 8; every cutoff in [1, k_in],
+ * 1 <= k_in <= 1024.  out [n_rows][n_groups + 1][4] = {ndcg, recall@k_r1, recall@k_r2, valid} per slot: slot g < n_groups counts
+ * the held-out items with label g (valid = the user has one), slot n_groups every held-out item.  With rank(h) = position of h
+ * in the list: ndcg = sum_{rank(h) < k_ndcg} 1/log2(rank(h)+2) / sum_{r < min(|H|, k_ndcg)} 1/log2(r+2), recall@k =
+ * #{rank(h) < k} / min(k, |H|) (eval_functions.py:11-62 on the held-out matrix restricted to the group's columns).
+ * item_hits [n_items_global] int32 (may be NULL) is ADDED to: +1 for every item among a user's first k_exp list entries; the
+ * caller zeroes it once per split.  Ids outside [0, n_items_global) are never used as an index.
+ * For rows with finite logits and disjoint fold-in / held-out sets, slot n_groups equals ltg_rank_metrics bit for bit and slot g
+ * equals ltg_rank_metrics on the held-out CSR filtered to group g; otherwise (a held-out fold-in item, -inf logits inside the
+ * first k_in) they may differ.  Inherits ltg_topk's limits (n_items per slab <= 360 448, k <= 1024).  No floating-point atomics. */
+int ltg_topk_metrics(const int32_t* id_in, int32_t n_rows, int32_t k_in, const ltg_batch* te, const uint8_t* item_group,
+                     int32_t n_items_global, int32_t n_groups, int32_t k_ndcg, int32_t k_r1, int32_t k_r2, int32_t k_exp,
+                     float* out, int32_t* item_hits, ltg_stream stream);
+
 /* Verification helper of the LTG_PREC_FP8 mode: out[i] = the value the fp8 GEMM operands carry for in[i]
  * (clamp to +-448, round to nearest-even OCP e4m3) -- lets a test pin its CPU model of the rounding to the hardware. */
 int ltg_fp8_roundtrip(const float* in, float* out, int32_t n, ltg_stream stream);

@@ -172,6 +172,7 @@ __global__ __launch_bounds__(64) void k_gate_set(LtgGate g, LtgGate g2 = LTG_NO_
 #include "ltg_clock.h"
 #include "ltg_sampler.h"
 #include "ltg_topk.h"
+#include "ltg_longtail.h"
 
 // ---------------------------------------------------------------------------------------------
 // host side
@@ -1808,6 +1809,22 @@ int ltg_topk_merge(int32_t n_parts, int32_t n_rows, int32_t k_in, const float* s
     if (n_rows == 0) return LTG_OK;
     hipLaunchKernelGGL(k_topk_merge, dim3(n_rows), dim3(NT), 0, (hipStream_t)stream, n_parts, n_rows, k_in, score_in, id_in, k, score_out,
                        id_out);
+    return check_launch();
+}
+
+int ltg_topk_metrics(const int32_t* id_in, int32_t n_rows, int32_t k_in, const ltg_batch* te, const uint8_t* item_group,
+                     int32_t n_items_global, int32_t n_groups, int32_t k_ndcg, int32_t k_r1, int32_t k_r2, int32_t k_exp, float* out,
+                     int32_t* item_hits, ltg_stream stream) {
+    if (!id_in || !te || !item_group || !out || n_rows < 0 || k_in < 1 || k_in > 1024 || n_groups < 1 || n_groups > LT_MAXG ||
+        n_items_global <= 0 || te->n_rows != n_rows)
+        return LTG_EINVAL;
+    for (const int32_t k : {k_ndcg, k_r1, k_r2, k_exp})
+        if (k < 1 || k > k_in) return LTG_EINVAL;
+    if (n_rows == 0) return LTG_OK;
+    if (!te->indptr || !te->indices) return LTG_EINVAL;
+    clear_errors();
+    hipLaunchKernelGGL(k_topk_metrics, dim3(n_rows), dim3(NT), 0, (hipStream_t)stream, k_in, id_in, te->indptr, te->indices, item_group,
+                       n_items_global, n_groups, k_ndcg, k_r1, k_r2, k_exp, out, item_hits);
     return check_launch();
 }
 

@@ -138,13 +138,16 @@ __device__ __forceinline__ void rank_finish_row(const int* cnt, int np, int k_nd
         if (r < k_r2) acc[2] += 1.0;
     }
 }
-__device__ __forceinline__ void rank_write_row(float* out, const double* acc, int nte, int k_ndcg, int k_r1, int k_r2) {
-    double idcg = 0.0;
-    for (int r = 0; r < min(nte, k_ndcg); ++r) idcg += 1.0 / log2((double)r + 2.0);
+__device__ __forceinline__ void rank_write_row_idcg(float* out, const double* acc, double idcg, int nte, int k_r1, int k_r2) {
     out[0] = idcg != 0.0 ? (float)(acc[0] / idcg) : 0.f;
     out[1] = nte > 0 ? (float)(acc[1] / (double)min(k_r1, nte)) : 0.f;
     out[2] = nte > 0 ? (float)(acc[2] / (double)min(k_r2, nte)) : 0.f;
     out[3] = idcg != 0.0 ? 1.f : 0.f;
+}
+__device__ __forceinline__ void rank_write_row(float* out, const double* acc, int nte, int k_ndcg, int k_r1, int k_r2) {
+    double idcg = 0.0;
+    for (int r = 0; r < min(nte, k_ndcg); ++r) idcg += 1.0 / log2((double)r + 2.0);
+    rank_write_row_idcg(out, acc, idcg, nte, k_r1, k_r2);
 }
 
 __global__ __launch_bounds__(NT) void k_rank_metrics(int I, int item_lo, const float* __restrict__ logits, const int32_t* __restrict__ tr_ptr,

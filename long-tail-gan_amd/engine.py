@@ -759,6 +759,20 @@ class Engine:
         cabi.check(self.lib.ltg_topk_merge(parts, n, k_in, _ptr(score_in), _ptr(id_in), int(k), _ptr(score_out), _ptr(id_out),
                                            self.stream()), "ltg_topk_merge")
 
+    def topk_metrics(self, ids, te, labels, n_groups, out, item_hits, k_ndcg=100, k_r1=20, k_r2=50, k_exp=100):
+        """the long-tail report of ids [rows, k_in] int32 (as topk / topk_merge write them) against the held-out rows `te` (a CsrRows,
+        GLOBAL ids): out [rows, n_groups + 1, 4] float32 = {ndcg, recall@k_r1, recall@k_r2, valid} per item group and for all items
+        (labels: uint8 per GLOBAL item id, a label >= n_groups is in no group); item_hits (int32 per GLOBAL item id, or None) gets +1
+        for every item among a row's first k_exp ids (ltg_topk_metrics)."""
+        n, k_in = (int(x) for x in ids.shape)
+        assert ids.dtype == torch.int32 and ids.is_contiguous() and labels.dtype == torch.uint8 and labels.is_contiguous()
+        assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= n * (int(n_groups) + 1) * 4
+        n_glob = int(labels.numel())
+        assert item_hits is None or (item_hits.dtype == torch.int32 and item_hits.is_contiguous() and item_hits.numel() == n_glob)
+        cabi.check(self.lib.ltg_topk_metrics(_ptr(ids), n, k_in, C.byref(te.c), _ptr(labels), n_glob, int(n_groups), int(k_ndcg),
+                                             int(k_r1), int(k_r2), int(k_exp), _ptr(out), _ptr(item_hits), self.stream()),
+                   "ltg_topk_metrics")
+
     # ------------------------------------------------------------------ views in the reference's shapes
     def generator_params_tf(self):
         """The 8 tensors in the reference's order and TF shapes (MultiVAE.py:129-141); W_p1 is a

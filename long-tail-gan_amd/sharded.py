@@ -319,10 +319,13 @@ class ShardedEvaluator:
 class ShardedRecommender:
     """Top-K recommendations over item shards: per chunk of users the sharded forward of ShardedEvaluator, ltg_topk on this
     rank's slab (global ids), ONE all-gather of the [R][rows][k] candidate lists (scores and ids; a list all-gather works over
-    gloo as well as nccl), then ltg_topk_merge.  Every rank ends with the identical table."""
+    gloo as well as nccl), then ltg_topk_merge.  Every rank ends with the identical table.  report: a LongTailReport to fill from
+    each chunk's merged lists; they are identical on every rank, so the report (item_hits included) needs no exchange."""
 
-    def __init__(self, engine, ev, k=100, group=None, chunk=20000):
-        self.eng, self.ev, self.group, self.k = engine, ev, group, int(k)
+    def __init__(self, engine, ev, k=100, group=None, chunk=20000, report=None):
+        self.eng, self.ev, self.group, self.k, self.report = engine, ev, group, int(k), report
+        if report is not None:
+            report.bind(engine, ev.n, self.k)
         self.R = dist.get_world_size(group)
         self.chunk = int(min(chunk, max(1, ev.n), eval_chunk_rows(engine.I)))
         self.acts = engine.new_acts(self.chunk)
@@ -338,10 +341,12 @@ class ShardedRecommender:
     def run(self, rng_step=0, keep_prob=0.75):
         """-> (ids [n_users, k], scores [n_users, k]) host arrays, identical on every rank"""
         eng, ev, k = self.eng, self.ev, self.k
+        if self.report is not None:
+            self.report.item_hits.zero_()
         for lo in range(0, ev.n, self.chunk):
             hi = min(ev.n, lo + self.chunk)
             n = hi - lo
-            tr, _ = ev.rows(lo, hi)
+            tr, te = ev.rows(lo, hi)
             fo = eng.fwd_opts(keep_prob, 0.0, rng_step + lo)
             eng.g_fwd_enc(tr, self.acts, fo)
             dist.all_reduce(self.acts.h1[:n], op=dist.ReduceOp.SUM, group=self.group)
@@ -354,4 +359,6 @@ class ShardedRecommender:
             dist.all_gather(list(ps.unbind(0)), ls, group=self.group)
             dist.all_gather(list(pi.unbind(0)), li, group=self.group)
             eng.topk_merge(ps, pi, k, self.scores[lo:hi], self.ids[lo:hi])
+            if self.report is not None:
+                self.report.add(eng, self.ids[lo:hi], te, lo)
         return self.ids.cpu().numpy(), self.scores.cpu().numpy()

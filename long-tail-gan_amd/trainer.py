@@ -278,13 +278,52 @@ class Evaluator:
                     recall50=float(o[ok, 2].mean()) if n else float("nan"), n_users=n)
 
 
+class LongTailReport:
+    """The long-tail report a Recommender / ShardedRecommender fills when it is passed as `report=`: per user and item group
+    NDCG@k_ndcg / Recall@k_r1 / Recall@k_r2 (plus the all-items slot, which is Evaluator's table) and the exposure counts at k_exp,
+    read off the chunk's top-K lists by ltg_topk_metrics -- one forward per chunk serves the lists and the report.
+    labels: one uint8 per GLOBAL item id, a label >= n_groups is in no group.  After run(): `out` [n_users, n_groups + 1, 4] and
+    `item_hits` [n_items] on the device; table() brings both to the host."""
+
+    def __init__(self, labels, n_groups, k_ndcg=100, k_r1=20, k_r2=50, k_exp=100):
+        self.labels_host = np.ascontiguousarray(np.asarray(labels), dtype=np.uint8)
+        self.n_groups = int(n_groups)
+        self.cut = dict(k_ndcg=int(k_ndcg), k_r1=int(k_r1), k_r2=int(k_r2), k_exp=int(k_exp))
+        if not 1 <= self.n_groups <= 8:
+            raise ValueError("n_groups must be in [1, 8]")
+        if min(self.cut.values()) < 1 or max(self.cut.values()) > 1024:
+            raise ValueError("every cutoff must be in [1, 1024]")
+        self.k = max(self.cut.values())                  # the list length the report needs
+        self.out = self.item_hits = self.labels = None
+
+    def bind(self, engine, n_users, k):
+        if k < self.k:
+            raise ValueError("top-K lists of %d entries are shorter than the report's largest cutoff %d" % (k, self.k))
+        if self.labels_host.size != engine.I_global:
+            raise ValueError("labels hold %d items, the catalogue %d" % (self.labels_host.size, engine.I_global))
+        dev = engine.device
+        self.labels = torch.from_numpy(self.labels_host).to(dev)
+        self.out = torch.zeros(n_users, self.n_groups + 1, 4, dtype=torch.float32, device=dev)
+        self.item_hits = torch.zeros(self.labels_host.size, dtype=torch.int32, device=dev)
+
+    def add(self, engine, ids, te, lo):
+        engine.topk_metrics(ids, te, self.labels, self.n_groups, self.out[lo:], self.item_hits, **self.cut)
+
+    def table(self):
+        """-> (out [n_users, n_groups + 1, 4] float32, item_hits [n_items] int32) host arrays"""
+        return self.out.cpu().numpy(), self.item_hits.cpu().numpy()
+
+
 class Recommender:
     """Top-K recommendations per user (the forward of Evaluator, then ltg_topk instead of the metrics): the same chunks of
     `chunk` users capped by eval_chunk_rows, the same dropout-on forward (Q3) with counter rng_step + lo per chunk, fold-in
-    items excluded.  keep_prob = 1.0 gives dropout-free, deterministic recommendations."""
+    items excluded.  keep_prob = 1.0 gives dropout-free, deterministic recommendations.  report: a LongTailReport to fill from
+    each chunk's lists (k >= its largest cutoff); absent, nothing else runs."""
 
-    def __init__(self, engine: Engine, ev: EvalData, k=100, chunk=20000):
-        self.eng, self.ev, self.k = engine, ev, int(k)
+    def __init__(self, engine: Engine, ev: EvalData, k=100, chunk=20000, report=None):
+        self.eng, self.ev, self.k, self.report = engine, ev, int(k), report
+        if report is not None:
+            report.bind(engine, ev.n, self.k)
         self.chunk = int(min(chunk, max(1, ev.n), eval_chunk_rows(engine.I)))
         self.acts = engine.new_acts(self.chunk)
         dev = engine.device
@@ -294,9 +333,13 @@ class Recommender:
     def run(self, rng_step=0, keep_prob=0.75):
         """-> (ids [n_users, k] int32 global item ids, scores [n_users, k] float32 logits) as host arrays"""
         eng, ev = self.eng, self.ev
+        if self.report is not None:
+            self.report.item_hits.zero_()
         for lo in range(0, ev.n, self.chunk):
             hi = min(ev.n, lo + self.chunk)
-            tr, _ = ev.rows(lo, hi)
+            tr, te = ev.rows(lo, hi)
             eng.forward(tr, self.acts, keep_prob=keep_prob, is_training=0.0, rng_step=rng_step + lo)
             eng.topk(self.acts, tr, self.k, self.scores[lo:hi], self.ids[lo:hi])
+            if self.report is not None:
+                self.report.add(eng, self.ids[lo:hi], te, lo)
         return self.ids.cpu().numpy(), self.scores.cpu().numpy()

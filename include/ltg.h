@@ -581,6 +581,31 @@ int ltg_topk(const ltg_config* cfg, const float* logits, const ltg_batch* tr, in
 int ltg_topk_merge(int32_t n_parts, int32_t n_rows, int32_t k_in, const float* score_in, const int32_t* id_in, int32_t k,
                    float* score_out, int32_t* id_out, ltg_stream stream);
 
+/* Minimum slots per item group at serve time (additive in ABI v14).
+ * ltg_topk_groups: ltg_topk with one more condition of eligibility.  item_group [n_items_global] uint8 = the report's labels, one per
+ * GLOBAL item id (the label of column c is item_group[cfg->item_lo + c]); bit g of group_mask (g = 0..7) admits label g, bit 8
+ * every label >= 8.  An item is eligible iff it is not a fold-in item of tr and its label's bit is set.  Everything else is ltg_topk's
+ * contract: the order, the padding (a row with fewer than k eligible items, down to none), 1 <= k <= 1024, n_items <= 360 448,
+ * bit-identical from run to run; group_mask = 0x1FF gives ltg_topk's lists bit for bit.  LTG_EINVAL before any HIP call: item_group
+ * NULL, group_mask 0 or > 0x1FF, item_lo < 0 or item_lo + n_items > n_items_global, and whatever ltg_topk refuses.
+ * ltg_topk_quota: the list with at least quota[j] entries of reserved list j, composed from lists alone.  score_all / id_all
+ * [n_rows][k_in] = the plain lists (ltg_topk / ltg_topk_merge); score_grp / id_grp [n_lists][n_rows][m_in] = one reserved list per
+ * group (ltg_topk_groups with a single-bit mask, so pairwise disjoint per row), all sorted and padded as ltg_topk writes them;
+ * quota [n_lists] is a HOST array, read before the call returns.  Per row, with U = the first quota[j] entries of every list j
+ * (padding ignored): out [n_rows][k] = U + the first (k - |U|) entries of the plain list that are not in U, in ltg_topk's order,
+ * padded with id -1 / score -inf.  With 0 <= quota[j] <= m_in and sum quota <= k <= k_in this is, walking the row's full ranking
+ * from the top, "take an item if its group still owes slots, or if a slot is left that no group's outstanding minimum claims"
+ * (a group with fewer eligible items than its quota hands the rest to the free slots); quota all 0 = the first k of the plain
+ * list, quota[j] = k = list j.  Scores are copied, never recomputed; ids are never used as an index.  1 <= n_lists <= 8,
+ * 1 <= m_in <= 1024, 1 <= k <= k_in <= 1024; anything else, and a NULL pointer, is LTG_EINVAL before any HIP call; n_rows = 0
+ * returns 0.  score_out / id_out must not alias any input.  No workspace, no global atomics, run-to-run identical. */
+int ltg_topk_groups(const ltg_config* cfg, const float* logits, const ltg_batch* tr, int32_t n_rows, int32_t k,
+                    const uint8_t* item_group, int32_t n_items_global, uint32_t group_mask, float* score_out, int32_t* id_out,
+                    ltg_stream stream);
+int ltg_topk_quota(int32_t n_rows, int32_t k_in, const float* score_all, const int32_t* id_all, int32_t n_lists, int32_t m_in,
+                   const float* score_grp, const int32_t* id_grp, const int32_t* quota, int32_t k, float* score_out,
+                   int32_t* id_out, ltg_stream stream);
+
 /* Long-tail report from top-K lists (additive in ABI v14): per user and item group NDCG@k_ndcg / Recall@k_r1 / Recall@k_r2, and
  * the exposure counts, without another scan of the logits.  id_in [n_rows][k_in] as ltg_topk / ltg_topk_merge write it (GLOBAL
  * ids in rank order, distinct, padding -1); te = held-out rows, GLOBAL ids ascending per row, te->n_rows == n_rows; item_group

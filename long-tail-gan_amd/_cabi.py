@@ -167,6 +167,8 @@ SYMBOLS = {
     "ltg_rank_finish": (C.c_int, [C.POINTER(ltg_batch), vp, C.c_int32, C.c_int32, C.c_int32, vp, vp]),
     "ltg_topk": (C.c_int, [C.POINTER(ltg_config), vp, C.POINTER(ltg_batch), C.c_int32, C.c_int32, vp, vp, vp]),
     "ltg_topk_merge": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, vp, vp, C.c_int32, vp, vp, vp]),
+    "ltg_topk_groups": (C.c_int, [C.POINTER(ltg_config), vp, C.POINTER(ltg_batch), C.c_int32, C.c_int32, vp, C.c_int32, C.c_uint32, vp, vp, vp]),
+    "ltg_topk_quota": (C.c_int, [C.c_int32, C.c_int32, vp, vp, C.c_int32, C.c_int32, vp, vp, C.POINTER(C.c_int32), C.c_int32, vp, vp, vp]),
     "ltg_topk_metrics": (C.c_int, [vp, C.c_int32, C.c_int32, C.POINTER(ltg_batch), vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                    C.c_int32, vp, vp, vp]),
     "ltg_fp8_roundtrip": (C.c_int, [vp, vp, C.c_int32, vp]),

@@ -1782,9 +1782,10 @@ int ltg_rank_metrics(const ltg_config* cfg, const float* logits, const ltg_batch
     return check_launch();
 }
 
-int ltg_topk(const ltg_config* cfg, const float* logits, const ltg_batch* tr, int32_t n_rows, int32_t k, float* score_out, int32_t* id_out,
-             ltg_stream stream) {
-    clear_errors();
+// ltg_topk and ltg_topk_groups: one launch of k_topk; labels == nullptr is the plain instantiation, which never reads the last two arguments.
+// Every refusal comes before the first HIP call.
+static int topk_launch(const ltg_config* cfg, const float* logits, const ltg_batch* tr, int32_t n_rows, int32_t k, const uint8_t* labels,
+                       uint32_t group_mask, float* score_out, int32_t* id_out, ltg_stream stream) {
     if (!cfg || !logits || !score_out || !id_out || cfg->n_items <= 0 || n_rows < 0 || k < 1 || k > 1024) return LTG_EINVAL;
     if (tr && (!tr->indptr || !tr->indices || tr->n_rows != n_rows)) return LTG_EINVAL;
     if (n_rows == 0) return LTG_OK;
@@ -1794,11 +1795,26 @@ int ltg_topk(const ltg_config* cfg, const float* logits, const ltg_batch* tr, in
     while (cap >= 1024 && bits + cap * 8 > 60 * 1024) cap >>= 1;
     if (cap < 1024) return LTG_EINVAL;
     const size_t lds = bits + cap * 8;
+    clear_errors();
     const bool vec = (cfg->n_items % 4) == 0 && ((uintptr_t)logits % 16) == 0;
-    auto kern = vec ? k_topk<true> : k_topk<false>;
+    auto kern = labels ? (vec ? k_topk<true, true> : k_topk<false, true>) : (vec ? k_topk<true, false> : k_topk<false, false>);
     hipLaunchKernelGGL(kern, dim3(n_rows), dim3(TK_NT), lds, (hipStream_t)stream, cfg->n_items, cfg->item_lo, logits,
-                       tr ? tr->indptr : (const int32_t*)nullptr, tr ? tr->indices : (const int32_t*)nullptr, k, (int)cap, score_out, id_out);
+                       tr ? tr->indptr : (const int32_t*)nullptr, tr ? tr->indices : (const int32_t*)nullptr, k, (int)cap, score_out, id_out,
+                       labels, group_mask);
     return check_launch();
+}
+
+int ltg_topk(const ltg_config* cfg, const float* logits, const ltg_batch* tr, int32_t n_rows, int32_t k, float* score_out, int32_t* id_out,
+             ltg_stream stream) {
+    return topk_launch(cfg, logits, tr, n_rows, k, nullptr, 0u, score_out, id_out, stream);
+}
+
+int ltg_topk_groups(const ltg_config* cfg, const float* logits, const ltg_batch* tr, int32_t n_rows, int32_t k, const uint8_t* item_group,
+                    int32_t n_items_global, uint32_t group_mask, float* score_out, int32_t* id_out, ltg_stream stream) {
+    if (!cfg || !item_group || group_mask == 0u || group_mask > 0x1FFu || cfg->item_lo < 0 || cfg->n_items <= 0 ||
+        (int64_t)cfg->item_lo + cfg->n_items > (int64_t)n_items_global)
+        return LTG_EINVAL;
+    return topk_launch(cfg, logits, tr, n_rows, k, item_group + cfg->item_lo, group_mask, score_out, id_out, stream);
 }
 
 int ltg_topk_merge(int32_t n_parts, int32_t n_rows, int32_t k_in, const float* score_in, const int32_t* id_in, int32_t k, float* score_out,
@@ -1809,6 +1825,27 @@ int ltg_topk_merge(int32_t n_parts, int32_t n_rows, int32_t k_in, const float* s
     if (n_rows == 0) return LTG_OK;
     hipLaunchKernelGGL(k_topk_merge, dim3(n_rows), dim3(NT), 0, (hipStream_t)stream, n_parts, n_rows, k_in, score_in, id_in, k, score_out,
                        id_out);
+    return check_launch();
+}
+
+int ltg_topk_quota(int32_t n_rows, int32_t k_in, const float* score_all, const int32_t* id_all, int32_t n_lists, int32_t m_in,
+                   const float* score_grp, const int32_t* id_grp, const int32_t* quota, int32_t k, float* score_out, int32_t* id_out,
+                   ltg_stream stream) {
+    if (!score_all || !id_all || !score_grp || !id_grp || !quota || !score_out || !id_out || n_rows < 0 || n_lists < 1 || n_lists > 8 ||
+        m_in < 1 || m_in > 1024 || k < 1 || k > k_in || k_in > 1024)
+        return LTG_EINVAL;
+    tk_quota q = {};
+    int64_t sum = 0;
+    for (int j = 0; j < n_lists; ++j) {
+        if (quota[j] < 0 || quota[j] > m_in) return LTG_EINVAL;
+        q.q[j] = quota[j];
+        sum += quota[j];
+    }
+    if (sum > k) return LTG_EINVAL;
+    if (n_rows == 0) return LTG_OK;
+    clear_errors();
+    hipLaunchKernelGGL(k_topk_quota, dim3(n_rows), dim3((k_in + 63) / 64 * 64), 0, (hipStream_t)stream, n_rows, k_in, score_all, id_all, n_lists, m_in,
+                       score_grp, id_grp, q, k, score_out, id_out);
     return check_launch();
 }
 

@@ -1,5 +1,6 @@
 // Part of csrc/ltg_kernels.hip (one translation unit, one anonymous namespace; included there after ltg_sampler.h): exact masked top-K
-// per row of the logits (ltg_topk) and the merge of per-slab top-K lists (ltg_topk_merge).
+// per row of the logits (ltg_topk; restricted to admitted item groups: ltg_topk_groups), the merge of per-slab top-K lists (ltg_topk_merge)
+// and the composition of a list with a minimum of slots per group from such lists (ltg_topk_quota).
 //
 // Order: score descending, equal scores lower GLOBAL id first -- the rule k_rank_metrics ranks by, so Recall@k computed from the ids
 // equals ltg_rank_metrics'.  -0.0 == +0.0 (the key canonicalises -0.0).  Fold-in items never appear; every other item is eligible,
@@ -53,17 +54,21 @@ __device__ __forceinline__ void tk_load4(const float* row, int I, const unsigned
         if (i0 + t >= I) fold |= 1u << t;       // past the end: treated like a fold-in item
 }
 
-// One workgroup per row.  LDS: fold-in bitset (ceil(I/32) words) | buf (cap 64-bit words).
+// One workgroup per row.  LDS: bitset of the items that are not eligible (ceil(I/32) words) | buf (cap 64-bit words).
+// GRP (ltg_topk_groups): an item whose label's bit is not in group_mask is not eligible either.  labels = the slab's part of the uint8 array
+// (label of column i at labels[i]); bit min(label, 8) of group_mask admits it.  Every row's workgroup reads the labels itself (I bytes,
+// from the L2 after the first rows): no workspace, no second launch, and the passes below do not know about groups (n_elig falls out
+// of the popcount).  Without GRP the two arguments are not read.
 //   pass 1  per-thread maximum key of the eligible items; T0 = the k-th largest of the TK_NT maxima (bitonic sort of TK_NT words):
 //           at least k eligible items have key >= T0, so the k-th largest key of the row is >= T0
 //   pass 2  every eligible item with key >= T0 into buf (LDS counter); if they fit (<= cap): sort them, write the first k
 //   else    (many equal keys or a flat row, large k) exact radix select of the k-th key Tk over 4 digits of 8 bits (one row pass each),
 //           then one pass that keeps every key > Tk (< k of them) and the first (k - #above) items with key == Tk in id order (a block
 //           scan per tile), sort, write.
-template <bool VEC>
+template <bool VEC, bool GRP>
 __global__ __launch_bounds__(TK_NT) void k_topk(int I, int item_lo, const float* __restrict__ logits, const int32_t* __restrict__ tr_ptr,
                                                  const int32_t* __restrict__ tr_idx, int k, int cap, float* __restrict__ score_out,
-                                                 int32_t* __restrict__ id_out) {
+                                                 int32_t* __restrict__ id_out, const uint8_t* __restrict__ labels, uint32_t group_mask) {
     extern __shared__ __attribute__((aligned(16))) unsigned s_dyn[];
     __shared__ int s_hist[256];
     __shared__ int s_wsum[TK_NT / 64];
@@ -83,7 +88,41 @@ __global__ __launch_bounds__(TK_NT) void k_topk(int I, int item_lo, const float*
         }
     }
     __syncthreads();
-    int nf = 0;                                          // fold-in items of the row (duplicates counted once)
+    if (GRP) {
+        if ((reinterpret_cast<uintptr_t>(labels) & 15) == 0) {      // (item_lo = 0, or a slab cut at a multiple of 16)
+            const int n_full = I >> 5;                   // bitset words whose 32 labels all exist: two 16-byte loads per thread and word
+            for (int i = tid; i < n_full; i += TK_NT) {
+                const uint4 a = reinterpret_cast<const uint4*>(labels)[2 * i], c = reinterpret_cast<const uint4*>(labels)[2 * i + 1];
+                const unsigned wd[8] = {a.x, a.y, a.z, a.w, c.x, c.y, c.z, c.w};
+                unsigned out = 0u;
+#pragma unroll
+                for (int t = 0; t < 32; ++t) out |= (((group_mask >> min((wd[t >> 2] >> ((t & 3) * 8)) & 255u, 8u)) & 1u) ^ 1u) << t;
+                s_bits[i] |= out;
+            }
+            if (tid < (I & 31) && !((group_mask >> min((unsigned)labels[32 * n_full + tid], 8u)) & 1u)) atomicOr(&s_bits[n_full], 1u << tid);
+        } else {                                         // any alignment: one byte per lane, a wave's ballot is the word pair 2q, 2q + 1
+            const int n64 = (I + 63) >> 6;
+            for (int q0 = w; q0 < n64; q0 += 4 * (TK_NT / 64)) {   // four byte loads in flight per lane
+                unsigned lab[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int it = (q0 + u * (TK_NT / 64)) * 64 + lane;
+                    lab[u] = it < I ? labels[it] : 0xFFFFFFFFu;    // past the end: no bit here (tk_load4 treats those columns)
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int q = q0 + u * (TK_NT / 64);
+                    const unsigned long long out = __ballot(lab[u] != 0xFFFFFFFFu && !((group_mask >> min(lab[u], 8u)) & 1u));
+                    if (lane == 0 && q < n64) {                    // (the pair belongs to this wave alone: plain read-modify-write)
+                        s_bits[2 * q] |= (unsigned)out;
+                        if (2 * q + 1 < nw) s_bits[2 * q + 1] |= (unsigned)(out >> 32);
+                    }
+                }
+            }
+        }
+        __syncthreads();
+    }
+    int nf = 0;                                          // items of the row that are not eligible (fold-in duplicates counted once)
     for (int i = tid; i < nw; i += TK_NT) nf += __popc(s_bits[i]);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) nf += __shfl_xor(nf, o);
@@ -281,6 +320,15 @@ __device__ __forceinline__ uint64_t tk_comp_at(const float* s, const int32_t* id
     const int g = id[i];
     return g < 0 ? 0ull : tk_comp(tk_key(s[i]), g);
 }
+// #{i < n : entry i > c} of a list sorted as k_topk writes it (descending words, padding == 0 at the end)
+__device__ __forceinline__ int tk_count_above(const float* s, const int32_t* id, int n, uint64_t c) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (tk_comp_at(s, id, mid) > c) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
 __global__ __launch_bounds__(NT) void k_topk_merge(int n_parts, int n_rows, int k_in, const float* __restrict__ score_in,
                                                    const int32_t* __restrict__ id_in, int k, float* __restrict__ score_out,
                                                    int32_t* __restrict__ id_out) {
@@ -325,5 +373,99 @@ __global__ __launch_bounds__(NT) void k_topk_merge(int n_parts, int n_rows, int 
             io[rank] = ip[j];
             so[rank] = sp[j];
         }
+    }
+}
+
+// Minimum slots per group, composed from lists (ltg_topk_quota).  Per row: all = the plain list [k_in]; grp = n_lists reserved
+// lists [m_in], pairwise disjoint, all sorted and padded as k_topk writes them; u_j = the entries of list j among its first quota[j] that
+// are not padding.  U = those entries; S = U + the first (k - |U|) entries of `all` that are not in U.  No sort: the rank of an entry in S is
+// its position in its own sequence plus the entries of every other sequence that precede it, each a binary search -- a plain entry's
+// searches of the reserved lists also say whether it is a member of U (the entry found equals it).  The kept non-members are a prefix of the
+// non-members of `all`, so "kept non-members before c" = min(non-members among the first lo entries of `all`, k - |U|) with the exclusive
+// scan s_nm of the non-member flags.  One thread per plain entry (k_in <= TK_NT; the block is k_in rounded up to whole waves).  Scores and
+// ids are copied, ids never index anything.
+struct tk_quota { int32_t q[8]; };
+__global__ __launch_bounds__(TK_NT) void k_topk_quota(int n_rows, int k_in, const float* __restrict__ score_all, const int32_t* __restrict__ id_all,
+                                                       int n_lists, int m_in, const float* __restrict__ score_grp,
+                                                       const int32_t* __restrict__ id_grp, tk_quota quota, int k, float* __restrict__ score_out,
+                                                       int32_t* __restrict__ id_out) {
+    __shared__ int s_nm[TK_NT + 1];
+    __shared__ int s_wsum[TK_NT / 64];
+    __shared__ int s_u[8];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int nt = blockDim.x;                           // k_in rounded up to whole waves (the host's choice): a thread per plain entry
+    const float* sa = score_all + (size_t)b * k_in;
+    const int32_t* ia = id_all + (size_t)b * k_in;
+    const size_t part = (size_t)n_rows * m_in, row = (size_t)b * m_in;
+    if (tid < n_lists) {                                 // padding is at the end of a list: u_j by bisection
+        int q = 0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) q = j == tid ? quota.q[j] : q;
+        const int32_t* ig = id_grp + tid * part + row;
+        int lo = 0, hi = q;
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (ig[mid] >= 0) lo = mid + 1; else hi = mid;
+        }
+        s_u[tid] = lo;
+    }
+    __syncthreads();
+    int n_u = 0;
+    for (int j = 0; j < n_lists; ++j) n_u += s_u[j];
+    const int n_free = k - n_u;
+    // ---- the plain entry of this thread: entries of U before it, and is it one of them
+    const uint64_t c = tid < k_in ? tk_comp_at(sa, ia, tid) : 0ull;
+    int ahead = 0;
+    bool member = false;
+    if (c != 0ull) {
+        for (int j = 0; j < n_lists; ++j) {
+            const float* sg = score_grp + j * part + row;
+            const int32_t* ig = id_grp + j * part + row;
+            const int uj = s_u[j], lo = tk_count_above(sg, ig, uj, c);
+            ahead += lo;
+            member = member || (lo < uj && tk_comp_at(sg, ig, lo) == c);
+        }
+    }
+    const int flag = c != 0ull && !member ? 1 : 0;
+    int incl = flag;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int y = __shfl_up(incl, o);
+        if (lane >= o) incl += y;
+    }
+    if (lane == 63) s_wsum[w] = incl;
+    __syncthreads();
+    int p = incl - flag, n_nm = 0;
+    for (int q = 0; q < (nt >> 6); ++q) {
+        p += q < w ? s_wsum[q] : 0;
+        n_nm += s_wsum[q];
+    }
+    s_nm[tid] = p;
+    if (tid == 0) s_nm[nt] = n_nm;
+    __syncthreads();
+    float* so = score_out + (size_t)b * k;
+    int32_t* io = id_out + (size_t)b * k;
+    if (flag && p < n_free && p + ahead < k) {
+        io[p + ahead] = ia[tid];
+        so[p + ahead] = sa[tid];
+    }
+    // ---- the entries of U: entry tid of every list (u_j <= quota[j] <= k <= k_in <= the block)
+    for (int j = 0; j < n_lists; ++j) {
+        const int t = tid;
+        if (t >= s_u[j]) continue;
+        const float* sg = score_grp + j * part + row;
+        const int32_t* ig = id_grp + j * part + row;
+        const uint64_t cu = tk_comp_at(sg, ig, t);
+        int rank = t + min(s_nm[tk_count_above(sa, ia, k_in, cu)], n_free);
+        for (int q = 0; q < n_lists; ++q)
+            if (q != j) rank += tk_count_above(score_grp + q * part + row, id_grp + q * part + row, s_u[q], cu);
+        if (rank < k) {
+            io[rank] = ig[t];
+            so[rank] = sg[t];
+        }
+    }
+    for (int i = n_u + min(n_free, n_nm) + tid; i < k; i += nt) {
+        io[i] = -1;
+        so[i] = -INFINITY;
     }
 }

@@ -759,6 +759,35 @@ class Engine:
         cabi.check(self.lib.ltg_topk_merge(parts, n, k_in, _ptr(score_in), _ptr(id_in), int(k), _ptr(score_out), _ptr(id_out),
                                            self.stream()), "ltg_topk_merge")
 
+    def topk_groups(self, logits_or_acts, tr, k, labels, group_mask, score_out, id_out):
+        """topk over the items whose label is admitted: labels uint8 per GLOBAL item id, bit g of group_mask admits label g (g < 8),
+        bit 8 every label >= 8 (ltg_topk_groups); everything else as topk"""
+        logits = logits_or_acts.logits if isinstance(logits_or_acts, Acts) else logits_or_acts
+        n = int(score_out.shape[0])
+        assert logits.dtype == torch.float32 and logits.numel() >= n * self.I and tuple(id_out.shape) == tuple(score_out.shape) == (n, k)
+        assert score_out.is_contiguous() and id_out.is_contiguous() and id_out.dtype == torch.int32
+        assert labels.dtype == torch.uint8 and labels.is_contiguous()
+        cabi.check(self.lib.ltg_topk_groups(C.byref(self.cfg), _ptr(logits), C.byref(tr.c) if tr is not None else None, n, int(k),
+                                            _ptr(labels), int(labels.numel()), int(group_mask), _ptr(score_out), _ptr(id_out),
+                                            self.stream()), "ltg_topk_groups")
+
+    def topk_quota(self, score_all, id_all, score_grp, id_grp, quota, score_out, id_out):
+        """the lists with at least quota[j] entries of reserved list j: score_all / id_all [rows, k_in] plain lists, score_grp / id_grp
+        [lists, rows, m_in] reserved lists (topk_groups with one bit each), quota a host sequence of `lists` counts -> [rows, k]
+        (ltg_topk_quota; the outputs must not alias an input)"""
+        n, k_in = (int(x) for x in score_all.shape)
+        lists, n_g, m_in = (int(x) for x in score_grp.shape)
+        k = int(score_out.shape[1])
+        assert n_g == n and tuple(id_all.shape) == (n, k_in) and tuple(id_grp.shape) == (lists, n, m_in) and len(quota) == lists
+        assert tuple(score_out.shape) == tuple(id_out.shape) == (n, k)
+        for t in (score_all, score_grp, score_out):
+            assert t.dtype == torch.float32 and t.is_contiguous()
+        for t in (id_all, id_grp, id_out):
+            assert t.dtype == torch.int32 and t.is_contiguous()
+        q = (C.c_int32 * lists)(*[int(x) for x in quota])
+        cabi.check(self.lib.ltg_topk_quota(n, k_in, _ptr(score_all), _ptr(id_all), lists, m_in, _ptr(score_grp), _ptr(id_grp), q, k,
+                                           _ptr(score_out), _ptr(id_out), self.stream()), "ltg_topk_quota")
+
     def topk_metrics(self, ids, te, labels, n_groups, out, item_hits, k_ndcg=100, k_r1=20, k_r2=50, k_exp=100):
         """the long-tail report of ids [rows, k_in] int32 (as topk / topk_merge write them) against the held-out rows `te` (a CsrRows,
         GLOBAL ids): out [rows, n_groups + 1, 4] float32 = {ndcg, recall@k_r1, recall@k_r2, valid} per item group and for all items

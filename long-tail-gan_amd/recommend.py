@@ -3,6 +3,7 @@
 
     cd <dir holding config.ini> && python <repo>/long-tail-gan_amd/recommend.py <dataset_dir> <checkpoint>
         [--k 100] [--split test|validation] [--keep-prob 0.75] [--out recs.tsv] [--npz recs.npz]
+        [--groups niche|pop:N] [--min-slots NAME:M[,NAME:M...]]
 
 restores a checkpoint written by train.py, runs test.py's forward over the users of `<split>_tr.csv` (chunks of 20 000 users,
 dropout on with keep_prob 0.75 by default: Q3, RNG counter 2*10^9 + first row of the chunk) and keeps each user's k best items, the
@@ -11,6 +12,11 @@ order (uid = the CSV's uid, sid = its item column), and with --npz the arrays ui
 summarises the long tail: users, niche share@k (recommended slots that are niche items, load_pop_niche_tags' NICHE_TAGS), coverage@k
 (distinct recommended items / n_items) and Recall@20 against `<split>_te.csv` (averaged over the users with held-out items, as
 test.py averages).  Under `python -m torch.distributed.run --nproc-per-node N` the items are sharded as in test.py; rank 0 writes.
+
+--min-slots NAME:M[,NAME:M...] guarantees every user at least M of the k slots for item group NAME of --groups (longtail.py's groups:
+`niche` = popular / niche, `pop:N` = pop0 .. pop<N-1>, pop0 = head), applied on the GPU (trainer.MinSlots: ltg_topk_groups + ltg_topk_quota):
+walking the user's ranking from the top, an item is taken if its group still owes slots or a slot is left that no group's outstanding
+minimum claims.  `--min-slots niche:100` with --k 100 is a shelf of niche items only.  The M may not sum to more than --k.
 """
 from __future__ import annotations
 
@@ -24,8 +30,10 @@ if __package__ in (None, ""):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import ltgan  # noqa: F401  (alias of this package directory)
     from ltgan import data_processing as dp
+    from ltgan import longtail as lt
 else:
     from . import data_processing as dp
+    from . import longtail as lt
 
 RNG_STEP = 2 * 10 ** 9        # test.py's counter: with the defaults the forward is the one test.py scores
 
@@ -39,11 +47,20 @@ def parse_args(argv):
     ap.add_argument("--keep-prob", type=float, default=0.75)
     ap.add_argument("--out", default="recs.tsv")
     ap.add_argument("--npz", default=None)
+    ap.add_argument("--groups", default="niche")
+    ap.add_argument("--min-slots", default=None)
     a = ap.parse_args(argv)
     if not 1 <= a.k <= 1024:
         ap.error("--k must be in [1, 1024]")
     if not 0.0 < a.keep_prob <= 1.0:
         ap.error("--keep-prob must be in (0, 1]")
+    a.slots = None
+    try:
+        a.group_kind, a.n_groups = lt.parse_groups(a.groups)
+        if a.min_slots is not None:
+            a.slots = lt.parse_min_slots(a.min_slots, lt.group_names(a.group_kind, a.n_groups), a.k)
+    except ValueError as e:
+        ap.error(str(e))
     return a
 
 
@@ -93,7 +110,7 @@ def recommend(args, h0_size, h1_size, h2_size, h3_size, LEARNING_RATE, precision
     from ltgan.generator import generator_VAECF as generator
     from ltgan.sharded import ShardedRecommender, item_slab
     from ltgan.train import load_checkpoint
-    from ltgan.trainer import Recommender
+    from ltgan.trainer import MinSlots, Recommender
     from ltgan.test import _Counters
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     device = "cuda:%d" % (int(os.environ.get("LOCAL_RANK", "0")) % max(1, torch.cuda.device_count()))
@@ -112,10 +129,14 @@ def recommend(args, h0_size, h1_size, h2_size, h3_size, LEARNING_RATE, precision
                             device=device, item_lo=lo, item_hi=hi)
     eng = gen_net.engine
     load_checkpoint(args.checkpoint, eng, _Counters())
+    rule = None
+    if getattr(args, "slots", None):
+        labels, names = lt.build_groups(d, args.group_kind, args.n_groups, n_items)
+        rule = MinSlots(labels, len(names), args.slots)
     if world > 1:
-        rec = ShardedRecommender(eng, EvalData(tr, te, eng.device, item_lo=lo, item_hi=hi), k=args.k, chunk=batch_size_test)
+        rec = ShardedRecommender(eng, EvalData(tr, te, eng.device, item_lo=lo, item_hi=hi), k=args.k, chunk=batch_size_test, rule=rule)
     else:
-        rec = Recommender(eng, EvalData(tr, te, eng.device), k=args.k, chunk=batch_size_test)
+        rec = Recommender(eng, EvalData(tr, te, eng.device), k=args.k, chunk=batch_size_test, rule=rule)
     ids, scores = rec.run(rng_step=RNG_STEP, keep_prob=args.keep_prob)
     m = long_tail_summary(ids, niche, n_items, te)
     if rank == 0:

@@ -320,14 +320,18 @@ class ShardedRecommender:
     """Top-K recommendations over item shards: per chunk of users the sharded forward of ShardedEvaluator, ltg_topk on this
     rank's slab (global ids), ONE all-gather of the [R][rows][k] candidate lists (scores and ids; a list all-gather works over
     gloo as well as nccl), then ltg_topk_merge.  Every rank ends with the identical table.  report: a LongTailReport to fill from
-    each chunk's merged lists; they are identical on every rank, so the report (item_hits included) needs no exchange."""
+    each chunk's merged lists; they are identical on every rank, so the report (item_hits included) needs no exchange.  rule: a
+    MinSlots; its reserved lists (ltg_topk_groups on the slab) are all-gathered and merged exactly like the plain list, then every rank
+    composes the same ruled lists (ltg_topk_quota) -- still no exchange of logits."""
 
-    def __init__(self, engine, ev, k=100, group=None, chunk=20000, report=None):
-        self.eng, self.ev, self.group, self.k, self.report = engine, ev, group, int(k), report
+    def __init__(self, engine, ev, k=100, group=None, chunk=20000, report=None, rule=None):
+        self.eng, self.ev, self.group, self.k, self.report, self.rule = engine, ev, group, int(k), report, rule
         if report is not None:
             report.bind(engine, ev.n, self.k)
         self.R = dist.get_world_size(group)
         self.chunk = int(min(chunk, max(1, ev.n), eval_chunk_rows(engine.I)))
+        if rule is not None:
+            rule.bind(engine, self.chunk, self.k, parts=self.R)
         self.acts = engine.new_acts(self.chunk)
         dev = engine.device
         self.rowpart = torch.zeros(self.chunk * 5, dtype=torch.float32, device=dev)
@@ -358,7 +362,26 @@ class ShardedRecommender:
                 ps, pi = ps.contiguous(), pi.contiguous()
             dist.all_gather(list(ps.unbind(0)), ls, group=self.group)
             dist.all_gather(list(pi.unbind(0)), li, group=self.group)
-            eng.topk_merge(ps, pi, k, self.scores[lo:hi], self.ids[lo:hi])
+            if self.rule is None:
+                eng.topk_merge(ps, pi, k, self.scores[lo:hi], self.ids[lo:hi])
+            else:
+                self._ruled(tr, n, ps, pi, self.scores[lo:hi], self.ids[lo:hi])
             if self.report is not None:
                 self.report.add(eng, self.ids[lo:hi], te, lo)
         return self.ids.cpu().numpy(), self.scores.cpu().numpy()
+
+    def _ruled(self, tr, n, ps, pi, score_out, id_out):
+        """the gathered plain lists ps / pi, and the slab logits still in self.acts -> the ruled lists of the chunk's n rows"""
+        eng, rule, k, R = self.eng, self.rule, self.k, self.R
+        eng.topk_merge(ps, pi, k, *rule.plain(n, k))
+        if rule.groups:
+            m = rule.m
+            g_s, g_i = rule.reserved(n)
+            ls, li = rule.loc_s[: n * m].view(n, m), rule.loc_i[: n * m].view(n, m)
+            qs, qi = rule.part_s[: R * n * m].view(R, n, m), rule.part_i[: R * n * m].view(R, n, m)
+            for j, g in enumerate(rule.groups):
+                eng.topk_groups(self.acts, tr, m, rule.labels, 1 << g, ls, li)
+                dist.all_gather(list(qs.unbind(0)), ls, group=self.group)
+                dist.all_gather(list(qi.unbind(0)), li, group=self.group)
+                eng.topk_merge(qs, qi, m, g_s[j], g_i[j])
+        rule.compose(eng, n, k, score_out, id_out)

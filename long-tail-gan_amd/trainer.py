@@ -314,17 +314,92 @@ class LongTailReport:
         return self.out.cpu().numpy(), self.item_hits.cpu().numpy()
 
 
+class MinSlots:
+    """A serve-time rule, passed as `rule=` to a Recommender / ShardedRecommender: at least slots[g] of every user's k list entries come
+    from item group g (labels: one uint8 per GLOBAL item id, a label >= n_groups is in no group; the labels a LongTailReport takes).  Walking
+    a user's ranking from the top, an item is taken if its group still owes slots, or if a slot is left that no group's outstanding minimum
+    claims; a group with fewer eligible items than its minimum hands the rest to the free slots.  slots all 0 is the plain list; slots[g] = k
+    is the k best items of group g.  Per chunk: the plain list, one reserved list per group with slots[g] > 0 (ltg_topk_groups with that
+    group's bit, every one max(slots) entries long so that they share one array), composed by ltg_topk_quota."""
+
+    def __init__(self, labels, n_groups, slots):
+        self.labels_host = np.ascontiguousarray(np.asarray(labels), dtype=np.uint8)
+        self.n_groups = int(n_groups)
+        if not 1 <= self.n_groups <= 8:
+            raise ValueError("n_groups must be in [1, 8]")
+        self.slots = [int(x) for x in slots]
+        if len(self.slots) != self.n_groups:
+            raise ValueError("slots holds %d counts for %d groups" % (len(self.slots), self.n_groups))
+        if min(self.slots) < 0:
+            raise ValueError("a group's minimum must be >= 0")
+        self.groups = [g for g, m in enumerate(self.slots) if m > 0]        # the groups with a reserved list
+        self.quota = [self.slots[g] for g in self.groups]
+        self.m = max(self.slots)
+        self.labels = None
+
+    def bind(self, engine, rows, k, parts=0):
+        """buffers for chunks of up to `rows` users and lists of k entries; parts > 0: also the all-gather buffers of that many ranks"""
+        if sum(self.slots) > k:
+            raise ValueError("the minimum slots sum to %d, more than the %d entries of a list" % (sum(self.slots), k))
+        if self.labels_host.size != engine.I_global:
+            raise ValueError("labels hold %d items, the catalogue %d" % (self.labels_host.size, engine.I_global))
+        dev = engine.device
+        self.labels = torch.from_numpy(self.labels_host).to(dev)
+        n_l, m = max(1, len(self.groups)), max(1, self.m)
+        self.all_s = torch.empty(rows * k, dtype=torch.float32, device=dev)
+        self.all_i = torch.empty(rows * k, dtype=torch.int32, device=dev)
+        self.grp_s = torch.empty(n_l * rows * m, dtype=torch.float32, device=dev)
+        self.grp_i = torch.empty(n_l * rows * m, dtype=torch.int32, device=dev)
+        if parts:
+            self.loc_s = torch.empty(rows * m, dtype=torch.float32, device=dev)
+            self.loc_i = torch.empty(rows * m, dtype=torch.int32, device=dev)
+            self.part_s = torch.empty(parts * rows * m, dtype=torch.float32, device=dev)
+            self.part_i = torch.empty(parts * rows * m, dtype=torch.int32, device=dev)
+
+    def plain(self, n, k):
+        """where the chunk's plain lists go: ([n, k] scores, [n, k] ids)"""
+        return self.all_s[: n * k].view(n, k), self.all_i[: n * k].view(n, k)
+
+    def reserved(self, n):
+        """where the chunk's reserved lists go: ([groups, n, m] scores, ids), list j for group self.groups[j]"""
+        n_l = len(self.groups)
+        return self.grp_s[: n_l * n * self.m].view(n_l, n, self.m), self.grp_i[: n_l * n * self.m].view(n_l, n, self.m)
+
+    def compose(self, engine, n, k, score_out, id_out):
+        """plain(n, k) and reserved(n) -> the ruled lists"""
+        a_s, a_i = self.plain(n, k)
+        if not self.groups:                              # nothing reserved: the plain list
+            score_out.copy_(a_s)
+            id_out.copy_(a_i)
+            return
+        g_s, g_i = self.reserved(n)
+        engine.topk_quota(a_s, a_i, g_s, g_i, self.quota, score_out, id_out)
+
+    def apply(self, engine, acts, tr, n, k, score_out, id_out):
+        """the ruled lists of the n rows whose logits `acts` holds (unsharded)"""
+        a_s, a_i = self.plain(n, k)
+        engine.topk(acts, tr, k, a_s, a_i)
+        if self.groups:
+            g_s, g_i = self.reserved(n)
+            for j, g in enumerate(self.groups):
+                engine.topk_groups(acts, tr, self.m, self.labels, 1 << g, g_s[j], g_i[j])
+        self.compose(engine, n, k, score_out, id_out)
+
+
 class Recommender:
     """Top-K recommendations per user (the forward of Evaluator, then ltg_topk instead of the metrics): the same chunks of
     `chunk` users capped by eval_chunk_rows, the same dropout-on forward (Q3) with counter rng_step + lo per chunk, fold-in
     items excluded.  keep_prob = 1.0 gives dropout-free, deterministic recommendations.  report: a LongTailReport to fill from
-    each chunk's lists (k >= its largest cutoff); absent, nothing else runs."""
+    each chunk's lists (k >= its largest cutoff); absent, nothing else runs.  rule: a MinSlots the lists are to satisfy (the report then
+    reads the ruled lists); absent, the plain top-K."""
 
-    def __init__(self, engine: Engine, ev: EvalData, k=100, chunk=20000, report=None):
-        self.eng, self.ev, self.k, self.report = engine, ev, int(k), report
+    def __init__(self, engine: Engine, ev: EvalData, k=100, chunk=20000, report=None, rule=None):
+        self.eng, self.ev, self.k, self.report, self.rule = engine, ev, int(k), report, rule
         if report is not None:
             report.bind(engine, ev.n, self.k)
         self.chunk = int(min(chunk, max(1, ev.n), eval_chunk_rows(engine.I)))
+        if rule is not None:
+            rule.bind(engine, self.chunk, self.k)
         self.acts = engine.new_acts(self.chunk)
         dev = engine.device
         self.scores = torch.empty(ev.n, self.k, dtype=torch.float32, device=dev)
@@ -339,7 +414,10 @@ class Recommender:
             hi = min(ev.n, lo + self.chunk)
             tr, te = ev.rows(lo, hi)
             eng.forward(tr, self.acts, keep_prob=keep_prob, is_training=0.0, rng_step=rng_step + lo)
-            eng.topk(self.acts, tr, self.k, self.scores[lo:hi], self.ids[lo:hi])
+            if self.rule is None:
+                eng.topk(self.acts, tr, self.k, self.scores[lo:hi], self.ids[lo:hi])
+            else:
+                self.rule.apply(eng, self.acts, tr, hi - lo, self.k, self.scores[lo:hi], self.ids[lo:hi])
             if self.report is not None:
                 self.report.add(eng, self.ids[lo:hi], te, lo)
         return self.ids.cpu().numpy(), self.scores.cpu().numpy()

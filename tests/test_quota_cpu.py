@@ -1,0 +1,237 @@
+"""CPU-side checks of the minimum-slots rule: ltg_topk_groups / ltg_topk_quota are exported and bound with the header's argument types,
+every documented refusal returns LTG_EINVAL without a GPU, MinSlots validates, both CLIs handle --min-slots (usage errors through the
+scripts themselves), and the two statements of the rule -- the greedy walk over the full ranking, and the composition from lists that
+ltg_topk_quota computes -- agree in numpy (the reference the GPU tests lean on)."""
+import ctypes as C
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import quota_ref as Q
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _cfg(cabi, n_items=1000, item_lo=0):
+    return cabi.ltg_config(n_items, 600, 200, n_items, 100, 150, 250, 300, 0, 0, item_lo, 0, 1, 0, 1e-4, 0.9, 0.999, 1e-8, 1)
+
+
+def test_entry_points_are_exported_and_bound_with_the_headers_types():
+    from ltgan import _cabi as cabi
+    lib = cabi.load()
+    vp, i32 = C.c_void_p, C.c_int32
+    want = {"ltg_topk_groups": [C.POINTER(cabi.ltg_config), vp, C.POINTER(cabi.ltg_batch), i32, i32, vp, i32, C.c_uint32, vp, vp, vp],
+            "ltg_topk_quota": [i32, i32, vp, vp, i32, i32, vp, vp, C.POINTER(i32), i32, vp, vp, vp]}
+    for name, args in want.items():
+        assert cabi.SYMBOLS[name] == (C.c_int, args)
+        assert getattr(lib, name).argtypes == args and getattr(lib, name).restype == C.c_int
+    assert lib.ltg_abi_version() == 14 == cabi.LTG_ABI_VERSION
+    header = open(os.path.join(ROOT, "include", "ltg.h")).read()
+    assert "int ltg_topk_groups(const ltg_config* cfg, const float* logits, const ltg_batch* tr, int32_t n_rows, int32_t k," in header
+    assert "int ltg_topk_quota(int32_t n_rows, int32_t k_in, const float* score_all, const int32_t* id_all, int32_t n_lists, int32_t m_in," in header
+
+
+def test_topk_groups_refusals_without_gpu():
+    from ltgan import _cabi as cabi
+    lib = cabi.load()
+    cfg = _cfg(cabi)
+    buf = (C.c_float * 16)()
+    ib = (C.c_int32 * 16)()
+    lab = (C.c_uint8 * 1000)()
+
+    def call(cfg=cfg, logits=buf, tr=None, n=2, k=4, labels=lab, n_glob=1000, mask=0x1FF, so=buf, io=ib):
+        return lib.ltg_topk_groups(C.byref(cfg) if cfg is not None else None, logits, tr, n, k, labels, n_glob, mask, so, io, None)
+
+    assert call(labels=None) == -1                                      # NULL labels
+    for mask in (0, 0x200, 0xFFFFFFFF):
+        assert call(mask=mask) == -1, mask
+    assert call(n_glob=999) == -1                                       # item_lo + n_items > n_items_global
+    assert call(cfg=_cfg(cabi, 1000, 1), n_glob=1000) == -1
+    assert call(cfg=_cfg(cabi, 1000, -1), n_glob=2000) == -1
+    assert call(n_glob=0) == -1
+    # everything ltg_topk refuses
+    for k in (0, -1, 1025):
+        assert call(k=k) == -1, k
+    assert call(cfg=None) == -1 and call(logits=None) == -1 and call(so=None) == -1 and call(io=None) == -1
+    assert call(n=-1) == -1
+    tr = cabi.ltg_batch(3, 0, C.cast(ib, C.c_void_p), C.cast(ib, C.c_void_p))
+    assert call(tr=C.byref(tr)) == -1                                   # a fold-in batch whose row count disagrees
+    tr = cabi.ltg_batch(2, 0, None, C.cast(ib, C.c_void_p))
+    assert call(tr=C.byref(tr)) == -1                                   # ... or without its arrays
+    big = (C.c_uint8 * 600000)()
+    assert call(cfg=_cfg(cabi, 600000), labels=big, n_glob=600000) == -1  # a slab too large for the kernel's LDS
+    assert call(n=0) == 0                                               # zero rows: nothing to launch
+    assert call(n=0, mask=1) == 0
+
+
+def test_topk_quota_refusals_without_gpu():
+    from ltgan import _cabi as cabi
+    lib = cabi.load()
+    buf = (C.c_float * 64)()
+    ib = (C.c_int32 * 64)()
+
+    def call(n=2, k_in=8, sa=buf, ia=ib, n_lists=2, m_in=4, sg=buf, ig=ib, quota=(2, 3), k=6, so=buf, io=ib):
+        q = (C.c_int32 * 8)(*quota) if quota is not None else None
+        return lib.ltg_topk_quota(n, k_in, sa, ia, n_lists, m_in, sg, ig, q, k, so, io, None)
+
+    for name in ("sa", "ia", "sg", "ig", "quota", "so", "io"):
+        assert call(**{name: None}) == -1, name
+    assert call(n=-1) == -1
+    assert call(n_lists=0) == -1 and call(n_lists=9, quota=(0,) * 8) == -1
+    assert call(m_in=0, quota=(0, 0)) == -1 and call(m_in=1025) == -1
+    assert call(k=0, quota=(0, 0)) == -1 and call(k=9) == -1            # 1 <= k <= k_in
+    assert call(k_in=1025, k=1025) == -1 and call(k_in=0, k=0, quota=(0, 0)) == -1
+    assert call(quota=(-1, 3)) == -1 and call(quota=(5, 0)) == -1       # 0 <= quota[j] <= m_in
+    assert call(quota=(3, 4)) == -1                                     # sum quota > k
+    assert call(n=0) == 0                                               # zero rows: nothing to launch
+    assert call(n=0, quota=(3, 3)) == 0 and call(n=0, k_in=1024, k=1024, m_in=1024, n_lists=8, quota=(128,) * 8) == 0
+    assert call(n=0, quota=(3, 4)) == -1                                # ... but the arguments are still checked
+
+
+class _FakeEngine:
+    I_global, device = 50, "cpu"
+
+
+def test_minslots_validation():
+    from ltgan.trainer import MinSlots
+    labels = np.arange(50, dtype=np.int64) % 3
+    r = MinSlots(labels, 3, [0, 5, 2])
+    assert (r.groups, r.quota, r.m, r.slots) == ([1, 2], [5, 2], 5, [0, 5, 2]) and r.labels_host.dtype == np.uint8
+    for n_groups, slots in ((0, []), (9, [0] * 9), (3, [1, 2]), (3, [1, -1, 0])):
+        with pytest.raises(ValueError):
+            MinSlots(labels, n_groups, slots)
+    with pytest.raises(ValueError):
+        r.bind(_FakeEngine(), 10, 6)                                    # 5 + 2 slots do not fit a list of 6
+    with pytest.raises(ValueError):
+        MinSlots(labels[:49], 3, [0, 5, 2]).bind(_FakeEngine(), 10, 100)    # labels of another catalogue
+    r.bind(_FakeEngine(), 10, 7)
+    assert r.labels.dtype.is_floating_point is False and tuple(r.labels.shape) == (50,)
+    assert tuple(r.plain(4, 7)[1].shape) == (4, 7) and tuple(r.reserved(4)[0].shape) == (2, 4, 5)
+    z = MinSlots(labels, 3, [0, 0, 0])
+    z.bind(_FakeEngine(), 10, 7)
+    assert z.groups == [] and z.m == 0
+
+
+def test_parse_min_slots():
+    from ltgan import longtail as lt
+    assert lt.group_names(*lt.parse_groups("niche")) == ["popular", "niche"]
+    assert lt.group_names(*lt.parse_groups("pop:4")) == ["pop0", "pop1", "pop2", "pop3"]
+    assert lt.niche_groups([1, 2], 5)[1] == lt.group_names("niche", 2) and lt.pop_groups_from_counts([3, 1, 2], 3)[1] == lt.group_names("pop", 3)
+    names = lt.group_names("pop", 4)
+    assert lt.parse_min_slots("pop3:30", names, 100) == [0, 0, 0, 30]
+    assert lt.parse_min_slots("pop3:30,pop0:70", names, 100) == [70, 0, 0, 30]
+    assert lt.parse_min_slots("pop1:0", names, 100) == [0, 0, 0, 0]
+    for bad in ("pop4:1", "niche:1", "pop3:30,pop3:1", "pop3:-1", "pop3", "pop3:x", "", "pop3:60,pop0:41"):
+        with pytest.raises(ValueError):
+            lt.parse_min_slots(bad, names, 100)
+
+
+def test_cli_arguments():
+    from ltgan import longtail as lt
+    from ltgan import recommend as rc
+    a = rc.parse_args(["ds", "model.pt"])                                # today's defaults for today's options, no rule
+    assert (a.dataset_dir, a.checkpoint, a.k, a.split, a.keep_prob, a.out, a.npz) == ("ds", "model.pt", 100, "test", 0.75, "recs.tsv", None)
+    assert (a.groups, a.min_slots, a.slots) == ("niche", None, None)
+    a = rc.parse_args(["ds", "m.pt", "--min-slots", "niche:20"])
+    assert (a.group_kind, a.n_groups, a.slots) == ("niche", 2, [0, 20])
+    a = rc.parse_args(["ds", "m.pt", "--k", "50", "--groups", "pop:4", "--min-slots", "pop3:30,pop2:20"])
+    assert (a.group_kind, a.n_groups, a.slots) == ("pop", 4, [0, 0, 20, 30])
+    b = lt.parse_args(["ds", "model.pt"])
+    assert (b.split, b.groups, b.k, b.keep_prob, b.json, b.group_kind, b.n_groups) == ("test", "niche", 100, 0.75, None, "niche", 2)
+    assert (b.min_slots, b.slots) == (None, None)
+    b = lt.parse_args(["ds", "m.pt", "--groups", "pop:4", "--min-slots", "pop3:30", "--k", "200"])
+    assert b.slots == [0, 0, 0, 30]
+    bad_r = (["--min-slots", "pop3:30"], ["--groups", "pop:4", "--min-slots", "pop4:1"], ["--min-slots", "niche:5,niche:6"],
+             ["--min-slots", "niche:-1"], ["--min-slots", "niche:60,popular:41"], ["--k", "20", "--min-slots", "niche:21"],
+             ["--groups", "pop:9"])
+    for bad in bad_r:
+        with pytest.raises(SystemExit) as e:
+            rc.parse_args(["ds", "m.pt"] + bad)
+        assert e.value.code == 2, bad
+    for bad in bad_r[:5] + (["--k", "20", "--min-slots", "niche:5"], ["--k", "99", "--min-slots", "niche:5"]):
+        with pytest.raises(SystemExit) as e:
+            lt.parse_args(["ds", "m.pt"] + bad)
+        assert e.value.code == 2, bad
+
+
+@pytest.mark.parametrize("script,args,msg", [
+    ("recommend.py", ["--groups", "pop:4", "--min-slots", "pop7:1"], "unknown group"),
+    ("recommend.py", ["--min-slots", "niche:5,niche:5"], "twice"),
+    ("recommend.py", ["--min-slots", "niche:-3"], "M >= 0"),
+    ("recommend.py", ["--k", "50", "--min-slots", "niche:30,popular:21"], "asks for 51 slots"),
+    ("longtail.py", ["--min-slots", "pop0:1"], "unknown group"),
+    ("longtail.py", ["--groups", "pop:4", "--min-slots", "pop3:30,pop3:30"], "twice"),
+    ("longtail.py", ["--min-slots", "niche:-1"], "M >= 0"),
+    ("longtail.py", ["--min-slots", "niche:60,popular:41"], "asks for 101 slots"),
+    ("longtail.py", ["--k", "20", "--min-slots", "niche:5"], "--k >= 100"),
+])
+def test_usage_errors_through_the_scripts(script, args, msg):
+    """exit status 2 before any GPU work: the dataset and the checkpoint named here do not exist"""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "long-tail-gan_amd", script), "ds", "m.pt"] + args, capture_output=True, text=True,
+                         timeout=300)
+    assert out.returncode == 2 and msg in out.stderr, out.stderr[-2000:]
+
+
+def _random_case(rng, trial):
+    I = int(rng.integers(5, 400))
+    G = int(rng.integers(1, 9))
+    kind = trial % 4
+    row = (rng.standard_normal(I) if kind == 0 else rng.integers(0, 3, I) * 0.5 if kind == 1 else np.full(I, 1.5) if kind == 2
+           else rng.choice([0.0, -0.0, -np.inf, 2.0], I)).astype(np.float32)
+    labels = rng.integers(0, G + 1, I).astype(np.uint8)                 # label G: in no group
+    fold = rng.choice(I, int(rng.integers(0, I)), replace=False)        # up to all but one item folded in: |E| < k happens
+    k = int(rng.integers(1, 60))
+    k_in = k + int(rng.integers(0, 5))
+    quota = rng.integers(0, k + 1, G)
+    while quota.sum() > k:
+        quota[rng.integers(G)] //= 2
+    return row, fold, labels, quota, k, k_in
+
+
+def test_greedy_walk_and_composition_from_lists_agree():
+    rng = np.random.default_rng(0)
+    seen = dict(short_group=0, short_row=0, zero=0, shelf=0)
+    for trial in range(3000):
+        row, fold, labels, quota, k, k_in = _random_case(rng, trial)
+        if trial % 50 == 7:
+            quota[:] = 0                                                # the plain list
+        if trial % 50 == 9:
+            quota[:] = 0
+            quota[0] = k                                                # the shelf of group 0
+        a = Q.greedy(row, fold, labels, quota, k)
+        b = Q.composed(row, fold, labels, quota, k, k_in)
+        assert np.array_equal(a, b), trial
+        order = Q.ranked(row, fold)
+        n_g = np.array([(labels[order] == g).sum() for g in range(len(quota))])
+        assert all((labels[b] == g).sum() >= min(quota[g], n_g[g]) for g in range(len(quota)))
+        assert len(b) == min(k, order.size) == len(set(b.tolist()))
+        assert np.array_equal(b, order[np.isin(order, b)])              # still in the ranking's order
+        if quota.sum() == 0:
+            assert np.array_equal(b, order[:k])
+            seen["zero"] += 1
+        if quota[0] == k:
+            own = order[labels[order] == 0]                             # enough of them: nothing else; else all of them
+            assert np.array_equal(b, own[:k]) if n_g[0] >= k else np.isin(own, b).all()
+            seen["shelf"] += int(n_g[0] >= k)
+        seen["short_group"] += int((n_g < quota).any())
+        seen["short_row"] += int(order.size < k)
+    assert min(seen.values()) >= 10, seen
+
+
+def test_masked_lists_reference_is_the_plain_reference_under_the_full_mask():
+    from test_gpu_topk import _eq, _reference, _rows
+    rng = np.random.default_rng(3)
+    L, folds = _rows(rng, 300, 40)
+    labels = rng.integers(0, 12, 300 + 17).astype(np.uint8)
+    for k in (1, 40):
+        S, ID = Q.masked_lists(L, folds, labels, 0x1FF, k, item_lo=17)
+        wS, wID = _reference(L, folds, k, item_lo=17)
+        assert np.array_equal(ID, wID) and _eq(S, wS)
+        S, ID = Q.greedy_lists(L, folds, labels, [0, 0, 0], k, item_lo=17)
+        assert np.array_equal(ID, wID) and _eq(S, wS)
+        S8, ID8 = Q.masked_lists(L, folds, labels, 0x100, k, item_lo=17)      # bit 8: every label >= 8
+        ok = ID8 >= 0
+        assert (labels[ID8[ok]] >= 8).all() and ok.any()

@@ -623,6 +623,38 @@ int ltg_topk_metrics(const int32_t* id_in, int32_t n_rows, int32_t k_in, const l
                      int32_t n_items_global, int32_t n_groups, int32_t k_ndcg, int32_t k_r1, int32_t k_r2, int32_t k_exp,
                      float* out, int32_t* item_hits, ltg_stream stream);
 
+/* Item-to-item neighbours: fused cosine / dot top-K over an item table (additive in ABI v14).
+ * Space: LTG_SPACE_DECODER = the rows of W_p1t (gen->p[3]), LTG_SPACE_ENCODER = the rows of W_q0 (gen->p[0]; the caller runs ltg_g_flush
+ * first when the lazy clock is in use).  Metric: LTG_METRIC_COSINE or LTG_METRIC_DOT.
+ * ltg_item_pack: the slab's table -> the operand image image_out [n_items][608] bf16 in the layout of gen->wp1t_bf16 (row = item, K
+ * zero-padded to 608).  dot: element = bf16 round-to-nearest-even of the fp32 value (decoder / dot == ltg_refresh_shadow bit for bit).
+ * cosine: the row's squared norm summed in fp64, inv = (float)(1.0 / sqrt(norm2)), element = bf16 RNE of the single fp32 product
+ * x * inv; a row of norm 0 gives a row of zeros (score 0, never NaN).  Queries are items: the same call packs them, and a query image is
+ * rows of a table image.  LTG_EINVAL: NULL pointer, unknown space / metric, h_enc > 608.
+ * ltg_item_neighbors: per query row r of q_image [n_q][608] the k best items of this rank's slab (table_image [n_items][608], global id =
+ * cfg->item_lo + row).  Score of (r, j) = the fp32 accumulator of the bf16 MFMA product of the two image rows over the 19 K blocks in
+ * ascending order; it does not depend on where j sits in the slab, so an item-sharded run produces the unsharded scores bit for bit.
+ * Item j is eligible for row r iff j != q_gid[r] (GLOBAL id; -1 excludes nothing) and, when item_group != NULL ([n_items_global] uint8,
+ * one label per GLOBAL id), bit min(label, 8) of group_mask is set -- ltg_topk_groups' rule.  score_out / id_out [n_q][k] exactly as
+ * ltg_topk writes them: scores descending, equal scores lower GLOBAL id first, padding id -1 / score -inf, bit-identical from run to
+ * run, NaN outside the contract -- per-slab lists go straight into ltg_topk_merge.  1 <= k <= LTG_NBR_MAX_K; the slab is streamed, so
+ * ltg_topk's 360 448 items per slab do not apply (the image of a slab must stay below 2^32 bytes: 3 532 110 items).
+ * The workspace (ltg_item_neighbors_ws_bytes; 0 for arguments the call refuses) holds one list per (item segment, query row) -- segments x
+ * n_q x k (score, id) pairs, at most 64 segments -- never a block of the score matrix.
+ * Before any HIP call: LTG_EINVAL for a NULL pointer (item_group may be NULL), n_q < 0, k out of range, group_mask 0 or > 0x1FF when
+ * item_group is given, item_lo < 0 or item_lo + n_items > n_items_global, h_enc > 608; LTG_EWORKSPACE for ws_bytes too small; n_q = 0
+ * returns LTG_OK and touches nothing. */
+#define LTG_SPACE_DECODER 0
+#define LTG_SPACE_ENCODER 1
+#define LTG_METRIC_COSINE 0
+#define LTG_METRIC_DOT 1
+#define LTG_NBR_MAX_K 256
+int ltg_item_pack(const ltg_config* cfg, const ltg_gen_state* gen, int32_t space, int32_t metric, uint16_t* image_out, ltg_stream stream);
+size_t ltg_item_neighbors_ws_bytes(const ltg_config* cfg, int32_t n_q, int32_t k);
+int ltg_item_neighbors(const ltg_config* cfg, const uint16_t* table_image, const uint16_t* q_image, const int32_t* q_gid, int32_t n_q,
+                       const uint8_t* item_group, uint32_t group_mask, int32_t k, float* score_out, int32_t* id_out, void* workspace,
+                       size_t ws_bytes, ltg_stream stream);
+
 /* Verification helper of the LTG_PREC_FP8 mode: out[i] = the value the fp8 GEMM operands carry for in[i]
  * (clamp to +-448, round to nearest-even OCP e4m3) -- lets a test pin its CPU model of the rounding to the hardware. */
 int ltg_fp8_roundtrip(const float* in, float* out, int32_t n, ltg_stream stream);

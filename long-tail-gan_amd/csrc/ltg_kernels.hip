@@ -173,6 +173,7 @@ __global__ __launch_bounds__(64) void k_gate_set(LtgGate g, LtgGate g2 = LTG_NO_
 #include "ltg_sampler.h"
 #include "ltg_topk.h"
 #include "ltg_longtail.h"
+#include "ltg_neighbors.h"
 
 // ---------------------------------------------------------------------------------------------
 // host side
@@ -1862,6 +1863,71 @@ int ltg_topk_metrics(const int32_t* id_in, int32_t n_rows, int32_t k_in, const l
     clear_errors();
     hipLaunchKernelGGL(k_topk_metrics, dim3(n_rows), dim3(NT), 0, (hipStream_t)stream, k_in, id_in, te->indptr, te->indices, item_group,
                        n_items_global, n_groups, k_ndcg, k_r1, k_r2, k_exp, out, item_hits);
+    return check_launch();
+}
+
+// Item-to-item neighbours.  The segmentation is a function of (n_items, n_q, k) alone, so ltg_item_neighbors_ws_bytes and the
+// call agree: enough (query block x segment) workgroups for two per CU, a segment at least 1 024 items, at most 64 segments.
+static int nbr_plan(int I, int n_q, int k, int* seg_len) {
+    const int rows = k <= 128 ? 32 : 16;
+    const int nqb = (n_q + rows - 1) / rows;
+    int want = (512 + nqb - 1) / nqb;
+    const int most = (I + 1023) / 1024 < 64 ? (I + 1023) / 1024 : 64;
+    want = want > most ? most : want;
+    const int len = ((I + want - 1) / want + NB_STEP - 1) / NB_STEP * NB_STEP;
+    *seg_len = len;
+    return (I + len - 1) / len;
+}
+static bool nbr_cfg_ok(const ltg_config* cfg) {
+    return cfg && cfg->n_items > 0 && cfg->h_enc >= 1 && cfg->h_enc <= ST_KP && cfg->item_lo >= 0 &&
+           (int64_t)cfg->item_lo + cfg->n_items <= (int64_t)(cfg->n_items_global ? cfg->n_items_global : cfg->n_items) &&
+           (size_t)cfg->n_items * (size_t)(ST_KP * 2) < ((size_t)1 << 32);
+}
+
+int ltg_item_pack(const ltg_config* cfg, const ltg_gen_state* gen, int32_t space, int32_t metric, uint16_t* image_out, ltg_stream stream) {
+    if (!cfg || !gen || !image_out || cfg->n_items <= 0 || cfg->h_enc < 1 || cfg->h_enc > ST_KP ||
+        (space != LTG_SPACE_DECODER && space != LTG_SPACE_ENCODER) || (metric != LTG_METRIC_COSINE && metric != LTG_METRIC_DOT))
+        return LTG_EINVAL;
+    const float* W = gen->p[space == LTG_SPACE_DECODER ? 3 : 0];
+    if (!W) return LTG_EINVAL;
+    clear_errors();
+    const int gx = (cfg->n_items + NT / 64 - 1) / (NT / 64);
+    auto kern = metric == LTG_METRIC_COSINE ? k_item_pack<true> : k_item_pack<false>;
+    hipLaunchKernelGGL(kern, dim3(gx < 65536 ? gx : 65536), dim3(NT), 0, (hipStream_t)stream, cfg->n_items, cfg->h_enc, W, image_out);
+    return check_launch();
+}
+
+size_t ltg_item_neighbors_ws_bytes(const ltg_config* cfg, int32_t n_q, int32_t k) {
+    if (!nbr_cfg_ok(cfg) || n_q <= 0 || k < 1 || k > LTG_NBR_MAX_K) return 0;
+    int seg_len;
+    const int nseg = nbr_plan(cfg->n_items, n_q, k, &seg_len);
+    return align_up((size_t)nseg * (size_t)n_q * (size_t)k * (sizeof(float) + sizeof(int32_t)));
+}
+
+int ltg_item_neighbors(const ltg_config* cfg, const uint16_t* table_image, const uint16_t* q_image, const int32_t* q_gid,
+                       int32_t n_q, const uint8_t* item_group, uint32_t group_mask, int32_t k, float* score_out, int32_t* id_out,
+                       void* workspace, size_t ws_bytes, ltg_stream stream) {
+    if (!nbr_cfg_ok(cfg) || !table_image || !q_image || !q_gid || !score_out || !id_out || n_q < 0 || k < 1 || k > LTG_NBR_MAX_K)
+        return LTG_EINVAL;
+    if (item_group && (group_mask == 0u || group_mask > 0x1FFu)) return LTG_EINVAL;
+    if (n_q == 0) return LTG_OK;
+    if (!workspace) return LTG_EINVAL;
+    if (ws_bytes < ltg_item_neighbors_ws_bytes(cfg, n_q, k)) return LTG_EWORKSPACE;
+    int seg_len;
+    const int nseg = nbr_plan(cfg->n_items, n_q, k, &seg_len);
+    float* ws_score = (float*)workspace;
+    int32_t* ws_id = (int32_t*)(ws_score + (size_t)nseg * n_q * k);
+    const uint8_t* labels = item_group ? item_group + cfg->item_lo : nullptr;
+    clear_errors();
+#define LTG_NBR(NTB, GRP)                                                                                                                  \
+    hipLaunchKernelGGL((k_item_neighbors<NTB, GRP>), dim3((n_q + 16 * NTB - 1) / (16 * NTB), nseg), dim3(NB_NT),                             \
+                       (size_t)ST_KS * NTB * 64 * 16 + (size_t)NB_ENT * 8, (hipStream_t)stream, cfg->n_items, cfg->item_lo, n_q, seg_len, k, \
+                       table_image, q_image, q_gid, labels, group_mask, ws_score, ws_id)
+    if (k <= 128) { if (labels) LTG_NBR(2, true); else LTG_NBR(2, false); }
+    else { if (labels) LTG_NBR(1, true); else LTG_NBR(1, false); }
+#undef LTG_NBR
+    if (hipGetLastError() != hipSuccess) return LTG_ELAUNCH;
+    hipLaunchKernelGGL(k_topk_merge, dim3(n_q), dim3(NT), 0, (hipStream_t)stream, nseg, n_q, k, ws_score, ws_id, k, score_out, id_out);
     return check_launch();
 }
 

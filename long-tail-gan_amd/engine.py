@@ -802,6 +802,41 @@ class Engine:
                                              int(k_r1), int(k_r2), int(k_exp), _ptr(out), _ptr(item_hits), self.stream()),
                    "ltg_topk_metrics")
 
+    # ------------------------------------------------------------------ item-to-item neighbours
+    def item_pack(self, space="decoder", metric="cosine", out=None):
+        """this slab's item table (`decoder`: the rows of W_p1t, `encoder`: the rows of W_q0) as the bf16 operand image [I, 608] int16 of
+        ltg_item_neighbors (`cosine`: unit rows, `dot`: the rows as they are).  A query image is rows of such an image."""
+        if out is None:
+            out = torch.empty(self.I, 608, dtype=torch.int16, device=self.device)
+        assert out.dtype == torch.int16 and out.is_contiguous() and tuple(out.shape) == (self.I, 608)
+        if space == "encoder":
+            self.g_flush()               # the lazy clock of W_q0: every row at the current step before it is read
+        cabi.check(self.lib.ltg_item_pack(C.byref(self.cfg), C.byref(self.gen_c), cabi.LTG_SPACE[space], cabi.LTG_METRIC[metric], _ptr(out),
+                                          self.stream()), "ltg_item_pack")
+        return out
+
+    def item_neighbors_ws_bytes(self, n_q, k):
+        return int(self.lib.ltg_item_neighbors_ws_bytes(C.byref(self.cfg), int(n_q), int(k)))
+
+    def item_neighbors(self, table_image, q_image, q_gid, k, score_out, id_out, labels=None, group_mask=0x1FF, ws=None):
+        """the k nearest items of this slab for every row of q_image [n_q, 608] int16: table_image [I, 608] int16 (item_pack), q_gid [n_q]
+        int32 = the GLOBAL id each query must not return (-1: none), labels (uint8 per GLOBAL item id, or None) / group_mask as in
+        topk_groups -> score_out [n_q, k] float32, id_out [n_q, k] int32 GLOBAL ids, ordered and padded as topk writes them
+        (ltg_item_neighbors).  ws: a uint8 tensor of item_neighbors_ws_bytes(n_q, k) bytes (allocated when absent)."""
+        n = int(q_image.shape[0])
+        assert table_image.dtype == q_image.dtype == torch.int16 and table_image.is_contiguous() and q_image.is_contiguous()
+        assert tuple(table_image.shape) == (self.I, 608) and tuple(q_image.shape) == (n, 608)
+        assert q_gid.dtype == torch.int32 and q_gid.is_contiguous() and q_gid.numel() == n
+        assert tuple(score_out.shape) == tuple(id_out.shape) == (n, k) and score_out.is_contiguous() and id_out.is_contiguous()
+        assert score_out.dtype == torch.float32 and id_out.dtype == torch.int32
+        assert labels is None or (labels.dtype == torch.uint8 and labels.is_contiguous() and labels.numel() == (self.cfg.n_items_global or self.I))
+        need = self.item_neighbors_ws_bytes(n, k) if n else 0
+        if ws is None:
+            ws = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
+        cabi.check(self.lib.ltg_item_neighbors(C.byref(self.cfg), _ptr(table_image), _ptr(q_image), _ptr(q_gid), n, _ptr(labels),
+                                               int(group_mask), int(k), _ptr(score_out), _ptr(id_out), _ptr(ws), ws.numel(), self.stream()),
+                   "ltg_item_neighbors")
+
     # ------------------------------------------------------------------ views in the reference's shapes
     def generator_params_tf(self):
         """The 8 tensors in the reference's order and TF shapes (MultiVAE.py:129-141); W_p1 is a

@@ -30,7 +30,7 @@ import torch
 import torch.distributed as dist
 
 from .engine import Pipe, _ptr
-from .trainer import Trainer, eval_chunk_rows
+from .trainer import ItemNeighbors, Trainer, eval_chunk_rows, neighbors_ws_bytes
 
 D_SPLIT_MIN_PARAMS = 1_000_000
 
@@ -385,3 +385,48 @@ class ShardedRecommender:
                 dist.all_gather(list(qi.unbind(0)), li, group=self.group)
                 eng.topk_merge(qs, qi, m, g_s[j], g_i[j])
         rule.compose(eng, n, k, score_out, id_out)
+
+
+class ShardedItemNeighbors(ItemNeighbors):
+    """ItemNeighbors over item shards.  Every rank packs its slab.  Per chunk of queries every rank copies the image rows of the queries it
+    owns into a zeroed [n][608] buffer, which is all-reduced viewed as int32 (exactly one rank contributes a row, so the sum is that row:
+    works over gloo and nccl); every rank searches its slab (global ids), the lists are all-gathered and merged with ltg_topk_merge as
+    ShardedRecommender does.  A pair's score does not depend on the slab that holds the item, so every rank ends with the identical
+    table, bit-identical to ItemNeighbors on the whole catalogue."""
+
+    def __init__(self, engine, k=20, space="decoder", metric="cosine", labels=None, n_groups=None, only=None, chunk=4096, group=None):
+        super().__init__(engine, k=k, space=space, metric=metric, labels=labels, n_groups=n_groups, only=only, chunk=chunk)
+        self.group = group
+        self.R = dist.get_world_size(group)
+
+    def run(self, query_ids=None):
+        eng, k, R = self.eng, self.k, self.R
+        dev = eng.device
+        lo_i, hi_i = eng.item_lo, eng.item_hi
+        q = self._queries(query_ids)
+        self.pack()
+        ids = torch.empty(len(q), k, dtype=torch.int32, device=dev)
+        scores = torch.empty(len(q), k, dtype=torch.float32, device=dev)
+        qd = torch.from_numpy(q).to(dev)
+        c = min(self.chunk, max(1, len(q)))
+        ws = torch.empty(neighbors_ws_bytes(eng.item_neighbors_ws_bytes, len(q), c, k), dtype=torch.uint8, device=dev)
+        qimg = torch.empty(c, 608, dtype=torch.int16, device=dev)
+        loc_s = torch.empty(c, k, dtype=torch.float32, device=dev)
+        loc_i = torch.empty(c, k, dtype=torch.int32, device=dev)
+        for lo in range(0, len(q), c):
+            hi = min(len(q), lo + c)
+            n = hi - lo
+            g = qd[lo:hi].long()
+            qi = qimg[:n]
+            qi.zero_()
+            own = (g >= lo_i) & (g < hi_i)
+            qi[own] = self.image.index_select(0, g[own] - lo_i)
+            dist.all_reduce(qi.view(torch.int32), op=dist.ReduceOp.SUM, group=self.group)
+            ls, li = loc_s[:n], loc_i[:n]
+            eng.item_neighbors(self.image, qi, qd[lo:hi], k, ls, li, self.labels, self.mask, ws=ws)
+            ps = torch.empty(R, n, k, dtype=torch.float32, device=dev)
+            pi = torch.empty(R, n, k, dtype=torch.int32, device=dev)
+            dist.all_gather(list(ps.unbind(0)), ls, group=self.group)
+            dist.all_gather(list(pi.unbind(0)), li, group=self.group)
+            eng.topk_merge(ps, pi, k, scores[lo:hi], ids[lo:hi])
+        return ids.cpu().numpy(), scores.cpu().numpy()

@@ -421,3 +421,76 @@ class Recommender:
             if self.report is not None:
                 self.report.add(eng, self.ids[lo:hi], te, lo)
         return self.ids.cpu().numpy(), self.scores.cpu().numpy()
+
+
+def group_mask_of(only, n_groups):
+    """the group_mask of ltg_topk_groups / ltg_item_neighbors that admits the group indices `only` (None: every group)"""
+    if only is None:
+        return 0x1FF
+    mask = 0
+    for g in only:
+        if not 0 <= int(g) < int(n_groups):
+            raise ValueError("group index %r outside [0, %d)" % (g, n_groups))
+        mask |= 1 << min(int(g), 8)
+    if mask == 0:
+        raise ValueError("`only` admits no group")
+    return mask
+
+
+def neighbors_ws_bytes(ws_bytes, n_q, chunk, k):
+    """the workspace for walking n_q queries in chunks of `chunk`: the largest need over the chunk lengths that occur.  ws_bytes(n, k) =
+    ltg_item_neighbors_ws_bytes.  It is NOT monotone in n: fewer query blocks get more item segments (the grid is sized to fill the chip),
+    so a shorter last chunk can need more than a full one -- 3 392 queries more than 4 096 at 200 000 items."""
+    n_q, chunk = int(n_q), max(1, int(chunk))
+    sizes = {min(chunk, n_q)} | ({n_q % chunk} if n_q > chunk else set())
+    return max([int(ws_bytes(n, k)) for n in sizes if n > 0] + [1])
+
+
+class ItemNeighbors:
+    """The k nearest items of items (ltg_item_neighbors): space `decoder` (rows of W_p1t) or `encoder` (rows of W_q0), metric `cosine` or
+    `dot`; a query never returns itself.  labels (uint8 per global item id, longtail.build_groups) + only (group indices) restrict the
+    NEIGHBOURS to those groups -- `only=[niche]` over the popular items is the niche shelf of every head item.  The table is packed once
+    into the bf16 operand image; the queries are walked in chunks of `chunk`, their rows taken out of the image by index.  The scores
+    stay on the chip: the workspace is lists."""
+
+    def __init__(self, engine: Engine, k=20, space="decoder", metric="cosine", labels=None, n_groups=None, only=None, chunk=4096):
+        self.eng, self.k, self.space, self.metric, self.chunk = engine, int(k), space, metric, max(1, int(chunk))
+        dev = engine.device
+        self.labels = None
+        self.mask = 0x1FF
+        if labels is not None:
+            self.labels = torch.as_tensor(np.ascontiguousarray(labels, dtype=np.uint8)).to(dev)
+            self.mask = group_mask_of(only, n_groups if n_groups is not None else int(self.labels.max().item()) + 1)
+        elif only is not None:
+            raise ValueError("`only` needs labels")
+        self.image = None
+
+    def pack(self):
+        self.image = self.eng.item_pack(self.space, self.metric, out=self.image)
+        return self.image
+
+    def _queries(self, query_ids):
+        n_glob = self.eng.cfg.n_items_global or self.eng.I
+        q = np.arange(n_glob, dtype=np.int32) if query_ids is None else np.ascontiguousarray(query_ids, dtype=np.int32).reshape(-1)
+        if q.size and (q.min() < 0 or q.max() >= n_glob):
+            raise ValueError("query ids outside [0, %d)" % n_glob)
+        return q
+
+    def query_rows(self, gid):
+        """the image rows of the global ids gid (a device int32 tensor)"""
+        return self.image.index_select(0, gid.long())
+
+    def run(self, query_ids=None):
+        """-> (ids [n_q, k] int32 global item ids, scores [n_q, k] float32) as host arrays; query_ids None = every item"""
+        eng, k = self.eng, self.k
+        dev = eng.device
+        q = self._queries(query_ids)
+        self.pack()
+        ids = torch.empty(len(q), k, dtype=torch.int32, device=dev)
+        scores = torch.empty(len(q), k, dtype=torch.float32, device=dev)
+        qd = torch.from_numpy(q).to(dev)
+        ws = torch.empty(neighbors_ws_bytes(eng.item_neighbors_ws_bytes, len(q), self.chunk, k), dtype=torch.uint8, device=dev)
+        for lo in range(0, len(q), self.chunk):
+            hi = min(len(q), lo + self.chunk)
+            eng.item_neighbors(self.image, self.query_rows(qd[lo:hi]), qd[lo:hi], k, scores[lo:hi], ids[lo:hi], self.labels, self.mask, ws=ws)
+        return ids.cpu().numpy(), scores.cpu().numpy()

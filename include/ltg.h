@@ -655,6 +655,29 @@ int ltg_item_neighbors(const ltg_config* cfg, const uint16_t* table_image, const
                        const uint8_t* item_group, uint32_t group_mask, int32_t k, float* score_out, int32_t* id_out, void* workspace,
                        size_t ws_bytes, ltg_stream stream);
 
+/* Diversified top-K lists: greedy maximal marginal relevance over a row's candidate list (additive in ABI v14).
+ * image [image_rows][608] bf16 as ltg_item_pack writes it, row r = GLOBAL id image_lo + r (16-byte aligned); score_in / id_in
+ * [n_rows][c_in] sorted and padded as ltg_topk writes them; 1 <= k <= c_in <= LTG_DIV_MAX_C.  An entry whose id lies outside
+ * [image_lo, image_lo + image_rows) is padding, and so is everything behind it: the image is never indexed with an unchecked id.  A
+ * non-padding entry with a non-finite score is outside the contract.
+ * Per row, n = the candidates in front of the padding, s their scores, S[i][j] = the fp32 accumulator of the 19-step
+ * v_mfma_f32_16x16x32_bf16 chain over the image rows of candidates i and j (a score of ltg_item_neighbors, never rounded):
+ *   rel_i = (s_i - s_{n-1}) / (s_0 - s_{n-1}) in fp32 (one subtraction pair, one IEEE division); all 0 when s_0 == s_{n-1};
+ *   the first pick is position 0; after a pick p, m_i = S[i][p] (first pick) or max(m_i, S[i][p]);
+ *   the next pick is the position not yet picked with the largest obj_i = lambda * rel_i - (1 - lambda) * m_i -- two fp32 products and
+ *   one subtraction, no contraction, 1 - lambda computed once in fp32 -- equal objectives to the lowest position.
+ * score_out / id_out [n_rows][k] = the picks in pick order, min(k, n) of them, each with its ORIGINAL score bit for bit (so the list is
+ * generally not descending in score), then padding id -1 / score -inf.  lambda = 1 gives the first k candidates bit for bit.
+ * stat_out (may be NULL) [n_rows][2] = the mean of S over the unordered pairs among the first min(k, n) candidates, and over the
+ * pairs of the output list; 0 with fewer than two entries; fp32 sums.
+ * One launch, one workgroup per row, S stays in LDS; no workspace, no atomics outside LDS, bit-identical from run to run.
+ * LTG_EINVAL before any HIP call: image / score_in / id_in / score_out / id_out NULL, c_in outside [1, 256], k outside [1, c_in],
+ * lambda outside [0, 1] or NaN, image_rows < 1, image_lo < 0, n_rows < 0, image not 16-byte aligned; n_rows = 0 returns LTG_OK. */
+#define LTG_DIV_MAX_C 256
+int ltg_topk_diversify(const uint16_t* image, int32_t image_lo, int32_t image_rows, int32_t n_rows, int32_t c_in,
+                       const float* score_in, const int32_t* id_in, float lambda, int32_t k, float* score_out, int32_t* id_out,
+                       float* stat_out /* may be NULL */, ltg_stream stream);
+
 /* Verification helper of the LTG_PREC_FP8 mode: out[i] = the value the fp8 GEMM operands carry for in[i]
  * (clamp to +-448, round to nearest-even OCP e4m3) -- lets a test pin its CPU model of the rounding to the hardware. */
 int ltg_fp8_roundtrip(const float* in, float* out, int32_t n, ltg_stream stream);

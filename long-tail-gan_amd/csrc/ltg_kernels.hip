@@ -174,6 +174,7 @@ __global__ __launch_bounds__(64) void k_gate_set(LtgGate g, LtgGate g2 = LTG_NO_
 #include "ltg_topk.h"
 #include "ltg_longtail.h"
 #include "ltg_neighbors.h"
+#include "ltg_diversify.h"
 
 // ---------------------------------------------------------------------------------------------
 // host side
@@ -1928,6 +1929,24 @@ int ltg_item_neighbors(const ltg_config* cfg, const uint16_t* table_image, const
 #undef LTG_NBR
     if (hipGetLastError() != hipSuccess) return LTG_ELAUNCH;
     hipLaunchKernelGGL(k_topk_merge, dim3(n_q), dim3(NT), 0, (hipStream_t)stream, nseg, n_q, k, ws_score, ws_id, k, score_out, id_out);
+    return check_launch();
+}
+
+// Diversified top-K lists: one launch, no workspace.  Every refusal comes before the first HIP call.
+int ltg_topk_diversify(const uint16_t* image, int32_t image_lo, int32_t image_rows, int32_t n_rows, int32_t c_in, const float* score_in,
+                       const int32_t* id_in, float lambda, int32_t k, float* score_out, int32_t* id_out, float* stat_out, ltg_stream stream) {
+    if (!image || !score_in || !id_in || !score_out || !id_out || c_in < 1 || c_in > LTG_DIV_MAX_C || k < 1 || k > c_in ||
+        !(lambda >= 0.f && lambda <= 1.f) || image_rows < 1 || image_lo < 0 || n_rows < 0 || ((uintptr_t)image % 16) != 0)
+        return LTG_EINVAL;
+    if (n_rows == 0) return LTG_OK;
+    clear_errors();
+#define LTG_DIV(CT)                                                                                                                      \
+    hipLaunchKernelGGL((k_topk_diversify<CT>), dim3(n_rows), dim3(CT * 16), (size_t)(CT + CT * (CT + 1) / 2) * 1024, (hipStream_t)stream, \
+                       image, image_lo, image_rows, c_in, score_in, id_in, lambda, k, score_out, id_out, stat_out)
+    if (c_in <= 64) LTG_DIV(4);
+    else if (c_in <= 128) LTG_DIV(8);
+    else LTG_DIV(16);
+#undef LTG_DIV
     return check_launch();
 }
 

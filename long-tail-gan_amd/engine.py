@@ -788,6 +788,23 @@ class Engine:
         cabi.check(self.lib.ltg_topk_quota(n, k_in, _ptr(score_all), _ptr(id_all), lists, m_in, _ptr(score_grp), _ptr(id_grp), q, k,
                                            _ptr(score_out), _ptr(id_out), self.stream()), "ltg_topk_quota")
 
+    def topk_diversify(self, image, image_lo, score_in, id_in, lam, k, score_out, id_out, stat_out=None):
+        """greedy MMR over candidate lists: image [rows, 608] int16 (item_pack; row r = GLOBAL id image_lo + r), score_in / id_in
+        [n, c_in] as topk / topk_merge write them, lam in [0, 1] the weight of relevance -> score_out / id_out [n, k] = the picks in
+        pick order with their original scores, padded with id -1 / score -inf; stat_out (None, or [n, 2] float32) = the mean pair
+        similarity of the first k candidates and of the picks (ltg_topk_diversify; the outputs must not alias an input)"""
+        n, c_in = (int(x) for x in score_in.shape)
+        assert image.dtype == torch.int16 and image.is_contiguous() and image.dim() == 2 and int(image.shape[1]) == 608
+        assert tuple(id_in.shape) == (n, c_in) and tuple(score_out.shape) == tuple(id_out.shape) == (n, int(k))
+        for t in (score_in, score_out):
+            assert t.dtype == torch.float32 and t.is_contiguous()
+        for t in (id_in, id_out):
+            assert t.dtype == torch.int32 and t.is_contiguous()
+        assert stat_out is None or (stat_out.dtype == torch.float32 and stat_out.is_contiguous() and tuple(stat_out.shape) == (n, 2))
+        cabi.check(self.lib.ltg_topk_diversify(_ptr(image), int(image_lo), int(image.shape[0]), n, c_in, _ptr(score_in), _ptr(id_in),
+                                               float(lam), int(k), _ptr(score_out), _ptr(id_out), _ptr(stat_out), self.stream()),
+                   "ltg_topk_diversify")
+
     def topk_metrics(self, ids, te, labels, n_groups, out, item_hits, k_ndcg=100, k_r1=20, k_r2=50, k_exp=100):
         """the long-tail report of ids [rows, k_in] int32 (as topk / topk_merge write them) against the held-out rows `te` (a CsrRows,
         GLOBAL ids): out [rows, n_groups + 1, 4] float32 = {ndcg, recall@k_r1, recall@k_r2, valid} per item group and for all items

@@ -3,6 +3,7 @@
 
     cd <dir holding config.ini> && python <repo>/long-tail-gan_amd/longtail.py <dataset_dir> <checkpoint>
         [--split test|validation] [--groups niche|pop:N] [--min-slots NAME:M[,NAME:M...]] [--k 100] [--keep-prob 0.75] [--json report.json]
+        [--diversify LAMBDA] [--candidates N] [--div-space decoder|encoder]
 
 restores a checkpoint written by train.py, runs test.py's forward over the users of `<split>_tr.csv` ONCE (chunks of 20 000 users,
 dropout on with keep_prob 0.75 by default: Q3, RNG counter 2*10^9 + first row of the chunk), keeps each user's top-K list on the GPU
@@ -24,6 +25,12 @@ reads it, so that at least M of its entries come from group NAME (trainer.MinSlo
 the accuracy / exposure trade-off of that rule.  The lines keep their form, but the first line is the re-ranked lists' NDCG@100 /
 Recall@20 / Recall@50 and no longer test.py's.  The rule is stated over the whole list of max(100, --k) entries, so it needs --k >= 100,
 and the M may not sum to more than --k.
+
+--diversify LAMBDA (0 <= LAMBDA <= 1; not together with --min-slots) re-ranks every list by greedy maximal marginal relevance before the
+report reads it (trainer.Diversify; ltg_topk at --candidates N, then ltg_topk_diversify): the next entry is the candidate with the largest
+LAMBDA * relevance - (1 - LAMBDA) * (largest cosine similarity to the entries already chosen), similarity between the rows of the decoder
+table (--div-space encoder: W_q0's).  N defaults to min(256, 2 K) and must lie in [K, 256], K = max(100, --k) the length of the lists.
+One more line follows the report: `ils@K: <before> -> <after>`, the mean pair similarity inside the plain and the diversified lists.
 """
 from __future__ import annotations
 
@@ -88,6 +95,38 @@ def parse_min_slots(spec, names, k):
     return slots
 
 
+def add_diversify_args(ap):
+    """the options of the MMR re-ranking (trainer.Diversify), shared with recommend.py"""
+    ap.add_argument("--diversify", type=float, default=None, metavar="LAMBDA")
+    ap.add_argument("--candidates", type=int, default=None, metavar="N")
+    ap.add_argument("--div-space", choices=("decoder", "encoder"), default="decoder")
+
+
+def check_diversify_args(ap, a, k):
+    """refuses (ap.error) what trainer.Diversify would refuse for lists of k entries, and the combination with --min-slots"""
+    if a.diversify is None:
+        if a.candidates is not None:
+            ap.error("--candidates needs --diversify")
+        return
+    if a.min_slots is not None:
+        ap.error("--diversify cannot be combined with --min-slots")
+    if not 0.0 <= a.diversify <= 1.0:
+        ap.error("--diversify takes LAMBDA in [0, 1]")
+    if k > 256:
+        ap.error("--diversify re-ranks at most 256 candidates: lists of %d entries are too long" % k)
+    if a.candidates is not None and not k <= a.candidates <= 256:
+        ap.error("--candidates must be in [k, 256] = [%d, 256], got %d" % (k, a.candidates))
+
+
+def ils_line(stats, ids, k):
+    """the line --diversify adds: the mean pair similarity of the plain top-k lists -> of the diversified ones (Diversify.stats()
+    [n_users, 2]), averaged in float64 over the users whose list holds at least two entries (ids [n_users, k], padding -1)"""
+    st = np.asarray(stats).astype(np.float64)
+    ok = (np.asarray(ids) >= 0).sum(axis=1) >= 2
+    b, a = (float(st[ok, 0].mean()), float(st[ok, 1].mean())) if ok.any() else (float("nan"), float("nan"))
+    return "ils@%d: %.6f -> %.6f" % (k, b, a)
+
+
 def parse_args(argv):
     ap = argparse.ArgumentParser(prog="longtail.py", description="per-group accuracy and exposure of a Long-Tail-GAN checkpoint")
     ap.add_argument("dataset_dir")
@@ -98,6 +137,7 @@ def parse_args(argv):
     ap.add_argument("--k", type=int, default=100)
     ap.add_argument("--keep-prob", type=float, default=0.75)
     ap.add_argument("--json", default=None)
+    add_diversify_args(ap)
     a = ap.parse_args(argv)
     try:
         a.group_kind, a.n_groups = parse_groups(a.groups)
@@ -115,6 +155,7 @@ def parse_args(argv):
             a.slots = parse_min_slots(a.min_slots, group_names(a.group_kind, a.n_groups), a.k)
         except ValueError as e:
             ap.error(str(e))
+    check_diversify_args(ap, a, max(K_NDCG, K_R1, K_R2, a.k))       # (the length of the lists: LongTailReport.k)
     return a
 
 
@@ -215,7 +256,7 @@ def longtail(args, h0_size, h1_size, h2_size, h3_size, LEARNING_RATE, precision=
     from ltgan.generator import generator_VAECF as generator
     from ltgan.sharded import ShardedRecommender, item_slab
     from ltgan.train import load_checkpoint
-    from ltgan.trainer import LongTailReport, MinSlots, Recommender
+    from ltgan.trainer import Diversify, LongTailReport, MinSlots, Recommender
     from ltgan.test import _Counters
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     device = "cuda:%d" % (int(os.environ.get("LOCAL_RANK", "0")) % max(1, torch.cuda.device_count()))
@@ -235,16 +276,21 @@ def longtail(args, h0_size, h1_size, h2_size, h3_size, LEARNING_RATE, precision=
     load_checkpoint(args.checkpoint, eng, _Counters())
     report = LongTailReport(labels, len(names), k_ndcg=K_NDCG, k_r1=K_R1, k_r2=K_R2, k_exp=args.k)
     rule = MinSlots(labels, len(names), args.slots) if getattr(args, "slots", None) else None
+    div = None
+    if getattr(args, "diversify", None) is not None:
+        div = Diversify(args.diversify, candidates=args.candidates, space=args.div_space)
     if world > 1:
         rec = ShardedRecommender(eng, EvalData(tr, te, eng.device, item_lo=lo, item_hi=hi), k=report.k, chunk=batch_size_test, report=report,
-                                 rule=rule)
+                                 rule=rule, diversify=div)
     else:
-        rec = Recommender(eng, EvalData(tr, te, eng.device), k=report.k, chunk=batch_size_test, report=report, rule=rule)
-    rec.run(rng_step=RNG_STEP, keep_prob=args.keep_prob)
+        rec = Recommender(eng, EvalData(tr, te, eng.device), k=report.k, chunk=batch_size_test, report=report, rule=rule, diversify=div)
+    ids, _ = rec.run(rng_step=RNG_STEP, keep_prob=args.keep_prob)
     rep = aggregate(*report.table(), labels, names, args.k)
     rep.update(split=args.split, groups_spec=args.groups)
     for line in report_lines(rep):
         print(line)
+    if div is not None:
+        print(ils_line(div.stats(), ids, report.k))
     if args.json and rank == 0:
         write_json(rep, args.json)
     if world > 1:

@@ -3,7 +3,7 @@
 
     cd <dir holding config.ini> && python <repo>/long-tail-gan_amd/recommend.py <dataset_dir> <checkpoint>
         [--k 100] [--split test|validation] [--keep-prob 0.75] [--out recs.tsv] [--npz recs.npz]
-        [--groups niche|pop:N] [--min-slots NAME:M[,NAME:M...]]
+        [--groups niche|pop:N] [--min-slots NAME:M[,NAME:M...]] [--diversify LAMBDA] [--candidates N] [--div-space decoder|encoder]
 
 restores a checkpoint written by train.py, runs test.py's forward over the users of `<split>_tr.csv` (chunks of 20 000 users,
 dropout on with keep_prob 0.75 by default: Q3, RNG counter 2*10^9 + first row of the chunk) and keeps each user's k best items, the
@@ -17,6 +17,12 @@ test.py averages).  Under `python -m torch.distributed.run --nproc-per-node N` t
 `niche` = popular / niche, `pop:N` = pop0 .. pop<N-1>, pop0 = head), applied on the GPU (trainer.MinSlots: ltg_topk_groups + ltg_topk_quota):
 walking the user's ranking from the top, an item is taken if its group still owes slots or a slot is left that no group's outstanding
 minimum claims.  `--min-slots niche:100` with --k 100 is a shelf of niche items only.  The M may not sum to more than --k.
+
+--diversify LAMBDA (0 <= LAMBDA <= 1; not together with --min-slots) re-ranks every list by greedy maximal marginal relevance on the GPU
+(trainer.Diversify: ltg_topk at --candidates N, then ltg_topk_diversify): the next entry is the candidate with the largest
+LAMBDA * relevance - (1 - LAMBDA) * (largest cosine similarity to the entries already chosen), similarity between the rows of the decoder
+table (--div-space encoder: W_q0's).  N defaults to min(256, 2 k) and must lie in [k, 256].  The lists are written in pick order, and one
+more line follows the summary: `ils@k: <before> -> <after>`, the mean pair similarity inside the plain and the diversified lists.
 """
 from __future__ import annotations
 
@@ -49,6 +55,7 @@ def parse_args(argv):
     ap.add_argument("--npz", default=None)
     ap.add_argument("--groups", default="niche")
     ap.add_argument("--min-slots", default=None)
+    lt.add_diversify_args(ap)
     a = ap.parse_args(argv)
     if not 1 <= a.k <= 1024:
         ap.error("--k must be in [1, 1024]")
@@ -61,6 +68,7 @@ def parse_args(argv):
             a.slots = lt.parse_min_slots(a.min_slots, lt.group_names(a.group_kind, a.n_groups), a.k)
     except ValueError as e:
         ap.error(str(e))
+    lt.check_diversify_args(ap, a, a.k)
     return a
 
 
@@ -110,7 +118,7 @@ def recommend(args, h0_size, h1_size, h2_size, h3_size, LEARNING_RATE, precision
     from ltgan.generator import generator_VAECF as generator
     from ltgan.sharded import ShardedRecommender, item_slab
     from ltgan.train import load_checkpoint
-    from ltgan.trainer import MinSlots, Recommender
+    from ltgan.trainer import Diversify, MinSlots, Recommender
     from ltgan.test import _Counters
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     device = "cuda:%d" % (int(os.environ.get("LOCAL_RANK", "0")) % max(1, torch.cuda.device_count()))
@@ -133,15 +141,21 @@ def recommend(args, h0_size, h1_size, h2_size, h3_size, LEARNING_RATE, precision
     if getattr(args, "slots", None):
         labels, names = lt.build_groups(d, args.group_kind, args.n_groups, n_items)
         rule = MinSlots(labels, len(names), args.slots)
+    div = None
+    if getattr(args, "diversify", None) is not None:
+        div = Diversify(args.diversify, candidates=args.candidates, space=args.div_space)
     if world > 1:
-        rec = ShardedRecommender(eng, EvalData(tr, te, eng.device, item_lo=lo, item_hi=hi), k=args.k, chunk=batch_size_test, rule=rule)
+        rec = ShardedRecommender(eng, EvalData(tr, te, eng.device, item_lo=lo, item_hi=hi), k=args.k, chunk=batch_size_test, rule=rule,
+                                 diversify=div)
     else:
-        rec = Recommender(eng, EvalData(tr, te, eng.device), k=args.k, chunk=batch_size_test, rule=rule)
+        rec = Recommender(eng, EvalData(tr, te, eng.device), k=args.k, chunk=batch_size_test, rule=rule, diversify=div)
     ids, scores = rec.run(rng_step=RNG_STEP, keep_prob=args.keep_prob)
     m = long_tail_summary(ids, niche, n_items, te)
     if rank == 0:
         write_recs(ids, scores, uid0, args.out, args.npz)
     print(summary_line(m, args.k))
+    if div is not None:
+        print(lt.ils_line(div.stats(), ids, args.k))
     if world > 1:
         import torch.distributed as dist
         dist.barrier()

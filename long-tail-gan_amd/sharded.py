@@ -322,16 +322,23 @@ class ShardedRecommender:
     gloo as well as nccl), then ltg_topk_merge.  Every rank ends with the identical table.  report: a LongTailReport to fill from
     each chunk's merged lists; they are identical on every rank, so the report (item_hits included) needs no exchange.  rule: a
     MinSlots; its reserved lists (ltg_topk_groups on the slab) are all-gathered and merged exactly like the plain list, then every rank
-    composes the same ruled lists (ltg_topk_quota) -- still no exchange of logits."""
+    composes the same ruled lists (ltg_topk_quota) -- still no exchange of logits.  diversify: a Diversify (not together with rule); the
+    per-slab lists are then `candidates` long, gathered and merged at that length, and every rank runs ltg_topk_diversify on the same
+    merged candidates against the image of the whole catalogue (Diversify.pack: one all-reduce per run()), so the table is identical on
+    every rank and bit-identical to the unsharded Recommender's."""
 
-    def __init__(self, engine, ev, k=100, group=None, chunk=20000, report=None, rule=None):
-        self.eng, self.ev, self.group, self.k, self.report, self.rule = engine, ev, group, int(k), report, rule
+    def __init__(self, engine, ev, k=100, group=None, chunk=20000, report=None, rule=None, diversify=None):
+        self.eng, self.ev, self.group, self.k, self.report, self.rule, self.diversify = engine, ev, group, int(k), report, rule, diversify
+        if rule is not None and diversify is not None:
+            raise ValueError("diversify= and rule= cannot be combined")
         if report is not None:
             report.bind(engine, ev.n, self.k)
         self.R = dist.get_world_size(group)
         self.chunk = int(min(chunk, max(1, ev.n), eval_chunk_rows(engine.I)))
         if rule is not None:
             rule.bind(engine, self.chunk, self.k, parts=self.R)
+        if diversify is not None:
+            diversify.bind(engine, self.chunk, self.k, ev.n, parts=self.R)
         self.acts = engine.new_acts(self.chunk)
         dev = engine.device
         self.rowpart = torch.zeros(self.chunk * 5, dtype=torch.float32, device=dev)
@@ -347,6 +354,9 @@ class ShardedRecommender:
         eng, ev, k = self.eng, self.ev, self.k
         if self.report is not None:
             self.report.item_hits.zero_()
+        div = self.diversify
+        if div is not None:
+            div.pack(eng, group=self.group)
         for lo in range(0, ev.n, self.chunk):
             hi = min(ev.n, lo + self.chunk)
             n = hi - lo
@@ -355,6 +365,11 @@ class ShardedRecommender:
             eng.g_fwd_enc(tr, self.acts, fo)
             dist.all_reduce(self.acts.h1[:n], op=dist.ReduceOp.SUM, group=self.group)
             eng.g_fwd_rest(tr, None, self.acts, fo, self.rowpart)
+            if div is not None:
+                self._diversified(tr, n, lo, self.scores[lo:hi], self.ids[lo:hi])
+                if self.report is not None:
+                    self.report.add(eng, self.ids[lo:hi], te, lo)
+                continue
             ls, li = self.loc_s[:n], self.loc_i[:n]
             eng.topk(self.acts, tr, k, ls, li)
             ps, pi = self.part_s[:, :n], self.part_i[:, :n]
@@ -369,6 +384,18 @@ class ShardedRecommender:
             if self.report is not None:
                 self.report.add(eng, self.ids[lo:hi], te, lo)
         return self.ids.cpu().numpy(), self.scores.cpu().numpy()
+
+    def _diversified(self, tr, n, lo, score_out, id_out):
+        """the slab logits in self.acts -> the diversified lists of the chunk's n rows (users lo .. lo + n)"""
+        eng, div, R = self.eng, self.diversify, self.R
+        c = div.c
+        ls, li = div.loc_s[: n * c].view(n, c), div.loc_i[: n * c].view(n, c)
+        ps, pi = div.part_s[: R * n * c].view(R, n, c), div.part_i[: R * n * c].view(R, n, c)
+        eng.topk(self.acts, tr, c, ls, li)
+        dist.all_gather(list(ps.unbind(0)), ls, group=self.group)
+        dist.all_gather(list(pi.unbind(0)), li, group=self.group)
+        eng.topk_merge(ps, pi, c, *div.candidates_of(n))
+        div.rerank(eng, n, self.k, lo, score_out, id_out)
 
     def _ruled(self, tr, n, ps, pi, score_out, id_out):
         """the gathered plain lists ps / pi, and the slab logits still in self.acts -> the ruled lists of the chunk's n rows"""

@@ -16,6 +16,7 @@ import time
 import numpy as np
 import torch
 
+from ._cabi import LTG_METRIC, LTG_SPACE
 from .dataset import DeviceData, EvalData
 from .engine import Engine, Pipe
 
@@ -386,20 +387,96 @@ class MinSlots:
         self.compose(engine, n, k, score_out, id_out)
 
 
+class Diversify:
+    """A serve-time re-ranking, passed as `diversify=` to a Recommender / ShardedRecommender: greedy maximal marginal relevance.  Each
+    user's `candidates` best items (ltg_topk; default min(256, 2 k), k <= candidates <= 256) are re-ranked so that the next entry is the
+    one with the largest  lam * relevance - (1 - lam) * (largest similarity to what the list already holds)  -- relevance = the score
+    scaled to [0, 1] over the candidates, similarity = the product of the items' rows in the bf16 image of the `decoder` (W_p1t) or
+    `encoder` (W_q0) table, `cosine` or `dot` (ltg_item_pack).  lam = 1 is the plain list.  The image is packed once per run(); per chunk
+    ltg_topk at `candidates`, then ONE launch of ltg_topk_diversify: the candidates' similarity matrix never leaves the chip.  The lists
+    keep every pick's original score, so they are generally not descending.  After run(): stats() [n_users, 2] = the mean pair similarity
+    of the plain top-k list and of the diversified one."""
+
+    def __init__(self, lam, candidates=None, space="decoder", metric="cosine"):
+        self.lam = float(lam)
+        if not 0.0 <= self.lam <= 1.0:               # (NaN fails both comparisons)
+            raise ValueError("lam must be in [0, 1], got %r" % (lam,))
+        if space not in LTG_SPACE or metric not in LTG_METRIC:
+            raise ValueError("space must be decoder or encoder, metric cosine or dot")
+        self.candidates = None if candidates is None else int(candidates)
+        self.space, self.metric = space, metric
+        self.c = self.image = self.stat = None
+        self.image_lo = 0
+
+    def bind(self, engine, rows, k, n_users, parts=0):
+        """buffers for chunks of up to `rows` users, lists of k entries and a table of n_users; parts > 0: also the all-gather buffers of
+        that many ranks"""
+        c = min(256, 2 * k) if self.candidates is None else self.candidates
+        if not k <= c <= 256:
+            raise ValueError("candidates must be in [k, 256] = [%d, 256], got %d" % (k, c))
+        self.c = c
+        dev = engine.device
+        self.cand_s = torch.empty(rows * c, dtype=torch.float32, device=dev)
+        self.cand_i = torch.empty(rows * c, dtype=torch.int32, device=dev)
+        self.stat = torch.zeros(n_users, 2, dtype=torch.float32, device=dev)
+        if parts:
+            self.loc_s = torch.empty(rows * c, dtype=torch.float32, device=dev)
+            self.loc_i = torch.empty(rows * c, dtype=torch.int32, device=dev)
+            self.part_s = torch.empty(parts * rows * c, dtype=torch.float32, device=dev)
+            self.part_i = torch.empty(parts * rows * c, dtype=torch.int32, device=dev)
+
+    def pack(self, engine, group=None):
+        """the image of the whole catalogue, once per run().  group given (item shards): every rank packs its slab into a zeroed
+        [I_global, 608] buffer at its item_lo, and the buffer is all-reduced viewed as int32 -- exactly one rank contributes each row."""
+        if group is None and engine.I == engine.I_global:
+            self.image = engine.item_pack(self.space, self.metric, out=self.image)
+            return
+        import torch.distributed as dist
+        if self.image is None:
+            self.image = torch.empty(engine.I_global, 608, dtype=torch.int16, device=engine.device)
+        self.image.zero_()
+        engine.item_pack(self.space, self.metric, out=self.image[engine.item_lo:engine.item_hi])
+        dist.all_reduce(self.image.view(torch.int32), op=dist.ReduceOp.SUM, group=group)
+
+    def candidates_of(self, n):
+        """where the chunk's candidate lists go: ([n, candidates] scores, ids)"""
+        return self.cand_s[: n * self.c].view(n, self.c), self.cand_i[: n * self.c].view(n, self.c)
+
+    def rerank(self, engine, n, k, lo, score_out, id_out):
+        """candidates_of(n) -> the diversified lists of users lo .. lo + n"""
+        c_s, c_i = self.candidates_of(n)
+        engine.topk_diversify(self.image, self.image_lo, c_s, c_i, self.lam, k, score_out, id_out, self.stat[lo:lo + n])
+
+    def apply(self, engine, acts, tr, n, k, lo, score_out, id_out):
+        """the diversified lists of the n rows whose logits `acts` holds (unsharded)"""
+        c_s, c_i = self.candidates_of(n)
+        engine.topk(acts, tr, self.c, c_s, c_i)
+        self.rerank(engine, n, k, lo, score_out, id_out)
+
+    def stats(self):
+        """-> [n_users, 2] float32 host array: mean pair similarity of the first k candidates, and of the list"""
+        return self.stat.cpu().numpy()
+
+
 class Recommender:
     """Top-K recommendations per user (the forward of Evaluator, then ltg_topk instead of the metrics): the same chunks of
     `chunk` users capped by eval_chunk_rows, the same dropout-on forward (Q3) with counter rng_step + lo per chunk, fold-in
     items excluded.  keep_prob = 1.0 gives dropout-free, deterministic recommendations.  report: a LongTailReport to fill from
     each chunk's lists (k >= its largest cutoff); absent, nothing else runs.  rule: a MinSlots the lists are to satisfy (the report then
-    reads the ruled lists); absent, the plain top-K."""
+    reads the ruled lists); absent, the plain top-K.  diversify: a Diversify the lists are re-ranked by (the report then reads the
+    diversified lists); not together with rule."""
 
-    def __init__(self, engine: Engine, ev: EvalData, k=100, chunk=20000, report=None, rule=None):
-        self.eng, self.ev, self.k, self.report, self.rule = engine, ev, int(k), report, rule
+    def __init__(self, engine: Engine, ev: EvalData, k=100, chunk=20000, report=None, rule=None, diversify=None):
+        self.eng, self.ev, self.k, self.report, self.rule, self.diversify = engine, ev, int(k), report, rule, diversify
+        if rule is not None and diversify is not None:
+            raise ValueError("diversify= and rule= cannot be combined")
         if report is not None:
             report.bind(engine, ev.n, self.k)
         self.chunk = int(min(chunk, max(1, ev.n), eval_chunk_rows(engine.I)))
         if rule is not None:
             rule.bind(engine, self.chunk, self.k)
+        if diversify is not None:
+            diversify.bind(engine, self.chunk, self.k, ev.n)
         self.acts = engine.new_acts(self.chunk)
         dev = engine.device
         self.scores = torch.empty(ev.n, self.k, dtype=torch.float32, device=dev)
@@ -410,11 +487,15 @@ class Recommender:
         eng, ev = self.eng, self.ev
         if self.report is not None:
             self.report.item_hits.zero_()
+        if self.diversify is not None:
+            self.diversify.pack(eng)
         for lo in range(0, ev.n, self.chunk):
             hi = min(ev.n, lo + self.chunk)
             tr, te = ev.rows(lo, hi)
             eng.forward(tr, self.acts, keep_prob=keep_prob, is_training=0.0, rng_step=rng_step + lo)
-            if self.rule is None:
+            if self.diversify is not None:
+                self.diversify.apply(eng, self.acts, tr, hi - lo, self.k, lo, self.scores[lo:hi], self.ids[lo:hi])
+            elif self.rule is None:
                 eng.topk(self.acts, tr, self.k, self.scores[lo:hi], self.ids[lo:hi])
             else:
                 self.rule.apply(eng, self.acts, tr, hi - lo, self.k, self.scores[lo:hi], self.ids[lo:hi])

@@ -132,3 +132,189 @@ def rel_err(a, b):
     a = np.asarray(a, np.float64)
     b = np.asarray(b, np.float64)
     return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
+
+
+# ---- hot parameter sets: the dynamic range of a trained model (tests/test_hot_params_cpu.py pins what they give; tests/test_gpu_hot_range.py
+# holds the kernels to the oracle on them).  Xavier logits span +-2 of a row and no tanh passes 0.99: exp(m_old - m_new) is ~1 at every merge.
+HOT_SEED = 1234                       # the engine seed of the GPU tests (dropout / epsilon counters)
+HOT_PROFILES = ("spike-last", "ramp-up", "ramp-down", "dead-tile")
+# W_p1 factor per profile, times sqrt((600 + I) / 1600) (Xavier's limit is sqrt(6 / (600 + I)): the factor keeps the per-row spread of the
+# logits the same at every I).  One factor for all four profiles cannot meet the conditions of test_hot_params_cpu: with sigma the
+# per-row standard deviation of h2 . W_p1 (0.71 per unit of the factor), "spike-last" needs 0.1 % of a row 87 below its maximum from
+# sigma alone (sigma >= 14, and 0.1 % only from 14.5 at 1 000 items), the ramps add 60 to that spread (10 % pass 87 from sigma = 9), and
+# "dead-tile" (170 of range from the bias) must stay inside 250 (sigma <= 13)
+HOT_WP1 = {"spike-last": 21.0, "ramp-up": 10.0, "ramp-down": 10.0, "dead-tile": 17.5}
+DEAD_TILE = (64, 96)                  # bp1[64:96] -= 120: one whole 32-item tile of the streaming kernels
+
+
+def hot_bias(I, profile):
+    """what the profile adds to bp1 (fp64 [I])"""
+    assert profile in HOT_PROFILES and I >= 128
+    i = np.arange(I, dtype=np.float64)
+    b = np.zeros(I)
+    if profile in ("spike-last", "dead-tile"):
+        b[I - 3] += 20.0              # the row maximum in the ragged last tile (I % 32 = 8 at 1 000 / 8 200 / 25 032 / 65 544 items)
+    if profile == "ramp-up":
+        b += 60.0 * i / I             # every tile raises the running maximum
+    if profile == "ramp-down":
+        b += 60.0 * (I - 1 - i) / I   # the first tile fixes the maximum, later tiles underflow against it
+    if profile == "dead-tile":
+        b[DEAD_TILE[0]:DEAD_TILE[1]] -= 120.0     # exp(x - m) = 0 in fp32 for the whole tile
+        b[5] -= 150.0
+    return b
+
+
+def hot_generator(P, profile):
+    """A copy of an O.init_generator set at a trained model's range: W_q0 x 12 r, W_q1 x 2, W_p0 x 2 (r = sqrt(I / 1000)), W_p1 x
+    HOT_WP1[profile] sqrt((600 + I) / 1600), bp1 += hot_bias.  The oracle is finite everywhere with it."""
+    I = P["Wp1"].shape[1]
+    r = np.sqrt(I / 1000.0)
+    Q = {k: np.array(v, dtype=np.float32, copy=True) for k, v in P.items()}
+    Q["Wq0"] *= np.float32(12.0 * r)
+    Q["Wq1"] *= np.float32(2.0)
+    Q["Wp0"] *= np.float32(2.0)
+    Q["Wp1"] *= np.float32(HOT_WP1[profile] * np.sqrt((600.0 + I) / 1600.0))
+    Q["bp1"] = (Q["bp1"].astype(np.float64) + hot_bias(I, profile)).astype(np.float32)
+    return Q
+
+
+def hot_discriminator(D):
+    """A copy of an O.init_discriminator set with emb, w1 .. w4 x 2 (biases stay 0): scores to +-8, a few per cent of the fc layer's tanh
+    above 0.99.  Not x 3: there fp32's own 1 - y costs 8e-2 on a row's -log(1 - y), oracle against oracle."""
+    Q = {k: np.array(v, dtype=np.float32, copy=True) for k, v in D.items()}
+    for k in ("emb", "w1", "w2", "w3", "w4"):
+        Q[k] *= np.float32(2.0)
+    return Q
+
+
+def hot_problem(I, B, profile, seed):
+    """(rng, X, P) as the parity tests' _problem(I, B, seed) builds them, P made hot"""
+    rng = np.random.default_rng(seed)
+    X = random_history(rng, B, I)
+    return rng, X, hot_generator(O.init_generator(I, seed=seed + 1), profile)
+
+
+def hot_fake_pairs(rng, X, I, per_user=5):
+    """(row, gen, pop) sorted by row, gen ascending and distinct within a row, ~5 % holes -- and in every fourth user's list a pair on item I - 3
+    (the spike: a probability near 1), on an item of DEAD_TILE and on item 5 (probabilities that are 0 in fp32 under "dead-tile")"""
+    rows, gen, pop = [], [], []
+    for b in range(X.shape[0]):
+        if b % 4 and rng.random() < 0.1:
+            continue
+        g = set(rng.choice(I, size=int(rng.integers(1, per_user + 1)), replace=False).tolist())
+        if b % 4 == 0:
+            g |= {I - 3, DEAD_TILE[0] + (7 * b) % (DEAD_TILE[1] - DEAD_TILE[0]), 5}
+        for gi in sorted(g):
+            hole = gi not in (I - 3, 5) and rng.random() < 0.05
+            rows.append(b)
+            gen.append(-1 if hole else int(gi))
+            pop.append(-1 if hole else int(rng.integers(0, I)))
+    return np.array(rows, np.int32), np.array(gen, np.int32), np.array(pop, np.int32)
+
+
+# ---- the stage comparators of tests/test_gpu_hot_range.py (each stage is fed what the DEVICE produced in the stage before it: with hot
+# parameters the fp32 oracle itself is 1e-3 off the fp64 oracle on probabilities end to end, so an end-to-end bound says nothing)
+ACC_K = 600                           # products per logit (h_enc)
+
+
+def logits_ratio(got, h2, Wp1, bp1):
+    """stage (b): the worst |got - want| / bound, element-wise, want = the fp64 product of the operands as given plus the bias, bound =
+    (ACC_K + 1) 2^-23 (sum_k |a_k b_k| + |bias|) -- what ACC_K fp32 accumulations of exact products and the bias add can lose (the form of
+    neighbors_ref.score_bound).  Returns (ratio, where)."""
+    a, w = np.asarray(h2, np.float64), np.asarray(Wp1, np.float64)
+    b = np.asarray(bp1, np.float64)
+    want = a @ w + b
+    bound = (ACC_K + 1) * 2.0 ** -23 * (np.abs(a) @ np.abs(w) + np.abs(b))
+    ratio = np.abs(np.asarray(got, np.float64) - want) / bound
+    at = np.unravel_index(int(np.argmax(ratio)), ratio.shape)
+    return float(ratio[at]), at
+
+
+def check_logits(got, h2, Wp1, bp1):
+    ratio, at = logits_ratio(got, h2, Wp1, bp1)
+    assert ratio <= 1.0, ("logits", at, ratio)
+    return ratio
+
+
+def lse64(logits):
+    x = np.asarray(logits, np.float64)
+    m = x.max(1)
+    return m + np.log(np.exp(x - m[:, None]).sum(1))
+
+
+def lse_bound(logits):
+    """stage (c)'s bound per row, from the reference alone: 8 x the worst gap between the oracle's log-sum-exp at float32 and at float64 on
+    THESE logits (the device sums in another order than numpy's pairwise one), never below 2 ulp of the lse.  Returns (lse64, bound, gap)."""
+    want = lse64(logits)
+    x = np.asarray(logits, np.float32)
+    m = x.max(1, keepdims=True)
+    with np.errstate(under="ignore"):
+        l32 = (m + np.log(np.exp(x - m).sum(1, keepdims=True)))[:, 0]
+    assert l32.dtype == np.float32
+    gap = float(np.abs(l32.astype(np.float64) - want).max())
+    return want, np.maximum(8.0 * gap, 2.0 * np.spacing(np.abs(want).astype(np.float32)).astype(np.float64)), gap
+
+
+def lse_ratio(got, logits, extra=0.0):
+    """stage (c): the worst |got - lse64(logits)| / (lse_bound + extra).  Returns (ratio, row, error, bound, the fp32 gap)."""
+    want, bound, gap = lse_bound(logits)
+    g = np.asarray(got, np.float64)
+    err = np.where(np.isfinite(g), np.abs(g - want), np.inf)
+    r = int(np.argmax(err / (bound + extra)))
+    return float(err[r] / (bound[r] + extra)), r, float(err[r]), float(bound[r] + extra), gap
+
+
+def check_lse(got, logits, extra=0.0):
+    ratio, r, err, bound, gap = lse_ratio(got, logits, extra)
+    assert ratio <= 1.0, ("lse row", r, err, bound)
+    return err, bound, gap
+
+
+def probs_ratio(got, logits, lse):
+    """stage (d): p against exp(logit - lse) in fp64.  Where that is >= 2^-100: relative error <= (|logit - lse| + 8) 2^-23 -- the subtraction
+    and the x log2(e) product round once each (|x| 2^-24 relative after the exponential, each), a few ulp for the exponential itself.  Below:
+    0 <= p <= 2^-99.  Returns (the worst error / bound of the first kind, where, whether all of the second kind are in range)."""
+    x = np.asarray(logits, np.float64) - np.asarray(lse, np.float64)[:, None]
+    want = np.exp(x)
+    p = np.asarray(got, np.float64)
+    big = want >= 2.0 ** -100
+    small_ok = bool(np.all(p[~big] >= 0.0) and np.all(p[~big] <= 2.0 ** -99))
+    ratio = np.where(big, np.abs(p - want) / np.where(big, want, 1.0) / ((np.abs(x) + 8.0) * 2.0 ** -23), 0.0)
+    ratio = np.where(np.isfinite(p), ratio, np.inf)
+    at = np.unravel_index(int(np.argmax(ratio)), ratio.shape)
+    return float(ratio[at]), at, small_ok
+
+
+def check_probs(got, logits, lse):
+    ratio, at, small_ok = probs_ratio(got, logits, lse)
+    assert small_ok, "a probability below 2^-100 is negative or above 2^-99"
+    assert ratio <= 1.0, ("probs", at, ratio)
+    return ratio
+
+
+# ---- the cases of tests/test_gpu_hot_range.py, shared with tests/test_hot_params_cpu.py (which pins the oracle's range on every one of them).
+# Forward: (I, B, precision, tuning knob, profiles) -- the smallest item counts that reach each kernel
+_TWO = ("ramp-up", "dead-tile")
+HOT_FWD = [(1000, 100, "fp32", 0, HOT_PROFILES), (1000, 100, "bf16", 0, HOT_PROFILES),      # small slab
+           (1000, 100, "bf16", 1 << 18, HOT_PROFILES),                                        # the generic kernels
+           (4096, 37, "bf16", 0, _TWO),                                                       # the largest small slab
+           (6000, 64, "bf16", 0, _TWO),                                                       # middle-layer fast path without streaming
+           (8200, 100, "fp32", 0, HOT_PROFILES), (8200, 100, "bf16", 0, HOT_PROFILES),        # first streaming form, ragged tail
+           (8200, 150, "bf16", 0, HOT_PROFILES),                                              # more than 112 rows
+           (25032, 128, "bf16", 0, _TWO),                                                     # ragged slab, 7 segments of 4 096
+           (8200, 100, "bf16", 1 << 17, HOT_PROFILES), (25032, 16, "bf16", 1 << 17, _TWO),    # the second streaming form, forced
+           (65544, 16, "bf16", 0, _TWO)]                                                      # ... chosen by the library itself
+HOT_FWD_STEP, HOT_KEEP = 7, 0.75
+HOT_SPAN = (8200, (100, 100, 50), "dead-tile", 21)          # rows_per_step: I, rows of the batches, profile, rng_step
+# G step: (precision, I, B, path, warm); both _TWO profiles each
+HOT_G = [("fp32", 1000, 100, "step", False), ("bf16", 1000, 100, "step", False), ("bf16", 1000, 100, "step-generic", False),
+         ("bf16", 6000, 100, "step", False), ("fp32", 8200, 100, "step", False), ("bf16", 8200, 100, "step", False),
+         ("bf16", 25032, 100, "one-call", False), ("bf16", 8200, 100, "step", True), ("bf16", 25032, 100, "one-call", True)]
+HOT_G_STEP = 3
+
+
+def hot_forward_inputs(I, B, profile, step=HOT_FWD_STEP, is_training=1.0, seed=None):
+    """(X, P, dropout mask, eps) of a forward case: _problem's seed I + B unless given"""
+    _, X, P = hot_problem(I, B, profile, I + B if seed is None else seed)
+    eps = eps_dense(HOT_SEED, step, B, O.Z_DIM) if is_training else np.zeros((B, O.Z_DIM))
+    return X, P, dropout_mask_dense(HOT_SEED, step, B, I, HOT_KEEP), eps

@@ -250,30 +250,13 @@ def write_json(rep, path):
 
 
 def longtail(args, h0_size, h1_size, h2_size, h3_size, LEARNING_RATE, precision="bf16", batch_size_test=20000, **_):
-    import builtins
-    import torch
-    from ltgan.dataset import EvalData, count_items
-    from ltgan.generator import generator_VAECF as generator
-    from ltgan.sharded import ShardedRecommender, item_slab
-    from ltgan.train import load_checkpoint
-    from ltgan.trainer import Diversify, LongTailReport, MinSlots, Recommender
-    from ltgan.test import _Counters
-    world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
-    device = "cuda:%d" % (int(os.environ.get("LOCAL_RANK", "0")) % max(1, torch.cuda.device_count()))
-    if world > 1:
-        import torch.distributed as dist
-        if not dist.is_initialized():
-            dist.init_process_group(os.environ.get("LTGAN_DIST_BACKEND", "nccl"))
-    print = builtins.print if rank == 0 else (lambda *a, **k: None)                      # noqa: A001
+    from ltgan.dataset import EvalData
+    from ltgan.serving import Diversify, LongTailReport, MinSlots, Recommender, ShardedRecommender, close_model, open_model
     d = args.dataset_dir
-    n_items = count_items(d)
+    eng, lo, hi, rank, world, print = open_model(d, args.checkpoint, (h0_size, h1_size, h2_size, h3_size), LEARNING_RATE, precision)  # noqa: A001
+    n_items = eng.I_global
     tr, te, _ = dp.load_tr_te_data(os.path.join(d, "%s_tr.csv" % args.split), os.path.join(d, "%s_te.csv" % args.split), n_items)
     labels, names = build_groups(d, args.group_kind, args.n_groups, n_items)
-    lo, hi = item_slab(n_items, rank, world) if world > 1 else (0, n_items)
-    gen_net, *_ = generator(d + "/", h_sizes=(h0_size, h1_size, h2_size, h3_size), lr=LEARNING_RATE, precision=precision,
-                            device=device, item_lo=lo, item_hi=hi)
-    eng = gen_net.engine
-    load_checkpoint(args.checkpoint, eng, _Counters())
     report = LongTailReport(labels, len(names), k_ndcg=K_NDCG, k_r1=K_R1, k_r2=K_R2, k_exp=args.k)
     rule = MinSlots(labels, len(names), args.slots) if getattr(args, "slots", None) else None
     div = None
@@ -293,10 +276,7 @@ def longtail(args, h0_size, h1_size, h2_size, h3_size, LEARNING_RATE, precision=
         print(ils_line(div.stats(), ids, report.k))
     if args.json and rank == 0:
         write_json(rep, args.json)
-    if world > 1:
-        import torch.distributed as dist
-        dist.barrier()
-        dist.destroy_process_group()
+    close_model(world)
     return rep
 
 

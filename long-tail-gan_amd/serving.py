@@ -1,0 +1,535 @@
+"""Everything that serves a trained model: validation / test scoring, top-K lists (plain, with minimum slots per item group, diversified),
+the long-tail report read off them, similar-item lists, and the set-up the four CLIs (test.py, recommend.py, longtail.py, similar.py) share.
+
+One chunk walk (Recommender.run) serves every kind of list, unsharded and over item shards: the forward sits behind one method that
+ShardedRecommender overrides, and every catalogue-wide list comes from one SlabLists, which alone knows whether the catalogue is cut
+into slabs.  A new kind of list is one branch of that walk and one apply(lists, ...) of its own.
+"""
+from __future__ import annotations
+
+import os
+
+import numpy as np
+import torch
+import torch.distributed as dist
+
+from ._cabi import LTG_METRIC, LTG_SPACE
+
+EVAL_LOGITS_BYTES = 2 << 30
+
+
+def eval_chunk_rows(n_items_local, budget=EVAL_LOGITS_BYTES):
+    """users per scoring chunk so that the [chunk, I] fp32 logits stay within `budget` bytes (test.py:76 scores 20 000
+    users at a time: 16 GB at I = 200 000)."""
+    return max(1, int(budget // (4 * max(1, n_items_local))))
+
+
+def chunk_rows(engine, ev, chunk):
+    """the users per chunk every scorer walks `ev` in: `chunk`, capped by the users there are and by eval_chunk_rows of the slab"""
+    return int(min(chunk, max(1, ev.n), eval_chunk_rows(engine.I)))
+
+
+def metric_means(out):
+    """the metric table [n_users, 4] = {ndcg, recall20, recall50, valid} -> its float64 means over the valid users"""
+    o = out.cpu().numpy().astype(np.float64)
+    ok = o[:, 3] > 0
+    n = int(ok.sum())
+    return dict(ndcg=float(o[ok, 0].mean()) if n else float("nan"), recall20=float(o[ok, 1].mean()) if n else float("nan"),
+                recall50=float(o[ok, 2].mean()) if n else float("nan"), n_users=n)
+
+
+def sharded_forward(engine, tr, n, acts, rowpart, keep_prob, rng_step, group=None):
+    """the scoring forward of the n rows `tr` over item shards: this slab's part of the encoder pre-activation, ONE all-reduce of it,
+    then the replicated middle layers and this slab's logits (dropout on, eps off: Evaluator's forward)"""
+    fo = engine.fwd_opts(keep_prob, 0.0, rng_step)
+    engine.g_fwd_enc(tr, acts, fo)
+    dist.all_reduce(acts.h1[:n], op=dist.ReduceOp.SUM, group=group)
+    engine.g_fwd_rest(tr, None, acts, fo, rowpart)
+
+
+class Evaluator:
+    """Validation / test scoring (train.py:333-348, test.py:138-173): forward with dropout ON (Q3),
+    fold-in items masked to -inf, NDCG@100 / Recall@20 / Recall@50, in chunks of `chunk` users
+    (test.py:76 uses 20000), capped so that a chunk's logits stay within EVAL_LOGITS_BYTES."""
+
+    def __init__(self, engine, ev, chunk=20000):
+        self.eng, self.ev, self.chunk = engine, ev, chunk_rows(engine, ev, chunk)
+        self.acts = engine.new_acts(self.chunk)
+        self.out = torch.zeros(ev.n, 4, dtype=torch.float32, device=engine.device)
+
+    def run(self, rng_step=0, keep_prob=0.75):
+        eng, ev = self.eng, self.ev
+        for lo in range(0, ev.n, self.chunk):
+            hi = min(ev.n, lo + self.chunk)
+            tr, te = ev.rows(lo, hi)
+            eng.forward(tr, self.acts, keep_prob=keep_prob, is_training=0.0, rng_step=rng_step + lo)
+            eng.rank_metrics(self.acts, tr, te, self.out[lo:])
+        return metric_means(self.out)
+
+
+class ShardedEvaluator:
+    """Validation / test scoring over item shards (train.py:333-348, test.py:138-173).  Per chunk of users: the
+    sharded forward (one all-reduce of the encoder pre-activation), then two small exchanges for the ranking:
+      1. all-reduce(sum) of the held-out entries' scores   (float32 per held-out entry; the owner contributes)
+      2. all-reduce(sum) of the per-entry rank counts      (int32 per held-out entry)
+    The softmax is never materialised: ranking by logits equals ranking by probabilities row by row.  Every rank
+    ends with the identical metric table."""
+
+    def __init__(self, engine, ev, group=None, chunk=20000):
+        self.eng, self.ev, self.group = engine, ev, group
+        self.chunk = chunk_rows(engine, ev, chunk)
+        self.acts = engine.new_acts(self.chunk)
+        dev = engine.device
+        n_te = max(1, int(ev.te_indices.numel()))
+        self.score = torch.zeros(n_te, dtype=torch.float32, device=dev)
+        self.count = torch.zeros(n_te, dtype=torch.int32, device=dev)
+        self.out = torch.zeros(ev.n, 4, dtype=torch.float32, device=dev)
+        self.rowpart = torch.zeros(self.chunk * 5, dtype=torch.float32, device=dev)
+
+    def run(self, rng_step=0, keep_prob=0.75):
+        eng, ev = self.eng, self.ev
+        te_ptr = ev.te_host.indptr
+        for lo in range(0, ev.n, self.chunk):
+            hi = min(ev.n, lo + self.chunk)
+            tr, te = ev.rows(lo, hi)
+            sharded_forward(eng, tr, hi - lo, self.acts, self.rowpart, keep_prob, rng_step + lo, self.group)
+            e0, e1 = int(te_ptr[lo]), int(te_ptr[hi])
+            eng.rank_scores(self.acts, tr, te, self.score)
+            if e1 > e0:
+                dist.all_reduce(self.score[e0:e1], op=dist.ReduceOp.SUM, group=self.group)
+            eng.rank_counts(self.acts, tr, te, self.score, self.count)
+            if e1 > e0:
+                dist.all_reduce(self.count[e0:e1], op=dist.ReduceOp.SUM, group=self.group)
+            eng.rank_finish(te, self.count, self.out[lo:])
+        return metric_means(self.out)
+
+
+class SlabLists:
+    """The one source of catalogue-wide lists: the L best items of the logits in `acts` over the WHOLE catalogue, optionally only the
+    items a group mask admits.  parts == 1 (the engine holds every item): ltg_topk / ltg_topk_groups straight into the caller's outputs.
+    parts > 1 (item shards, one rank per slab): the slab's list (global ids), ONE all-gather of the scores and one of the ids (list
+    all-gathers work over gloo as well as nccl), then ltg_topk_merge into the outputs -- every rank ends with the identical lists and no
+    logit is ever exchanged.  One flat pair of local / gathered buffers serves lists of every length up to `longest` for chunks of up to
+    `rows` rows: each call views them as [n, L] / [parts, n, L], so a short last chunk is contiguous like a full one.  Reusing them for
+    the next list of a chunk is safe: the gathers are synchronous collectives on the stream the engine launches on (torch's current
+    stream), so the merge that reads the gathered buffers is enqueued before the next local list overwrites them."""
+
+    def __init__(self, engine, rows, longest, group=None, parts=1):
+        self.eng, self.group, self.parts = engine, group, int(parts)
+        self.loc_s = self.loc_i = self.part_s = self.part_i = None
+        if self.parts > 1:
+            n, dev = int(rows) * int(longest), engine.device
+            self.loc_s = torch.empty(n, dtype=torch.float32, device=dev)
+            self.loc_i = torch.empty(n, dtype=torch.int32, device=dev)
+            self.part_s = torch.empty(self.parts * n, dtype=torch.float32, device=dev)
+            self.part_i = torch.empty(self.parts * n, dtype=torch.int32, device=dev)
+
+    def local(self, n, L, score_out, id_out):
+        """where this rank's own [n, L] lists go: the outputs themselves when there is nothing to gather"""
+        if self.parts == 1:
+            return score_out, id_out
+        return self.loc_s[: n * L].view(n, L), self.loc_i[: n * L].view(n, L)
+
+    def merge(self, loc_s, loc_i, score_out, id_out):
+        """this rank's lists (where local() put them) -> the catalogue-wide ones in score_out / id_out [n, k]"""
+        if self.parts == 1:
+            return
+        R, (n, L) = self.parts, loc_s.shape
+        ps, pi = self.part_s[: R * n * L].view(R, n, L), self.part_i[: R * n * L].view(R, n, L)
+        dist.all_gather(list(ps.unbind(0)), loc_s, group=self.group)
+        dist.all_gather(list(pi.unbind(0)), loc_i, group=self.group)
+        self.eng.topk_merge(ps, pi, int(score_out.shape[1]), score_out, id_out)
+
+    def topk(self, acts, tr, n, L, score_out, id_out, labels=None, mask=None):
+        """score_out / id_out [n, L] <- the L best items of the n rows of logits in `acts`, fold-in items of `tr` excluded; mask given:
+        only items whose label (labels: uint8 per GLOBAL item id) the group mask admits"""
+        ls, li = self.local(n, L, score_out, id_out)
+        if mask is None:
+            self.eng.topk(acts, tr, L, ls, li)
+        else:
+            self.eng.topk_groups(acts, tr, L, labels, mask, ls, li)
+        self.merge(ls, li, score_out, id_out)
+
+
+class LongTailReport:
+    """The long-tail report a Recommender / ShardedRecommender fills when it is passed as `report=`: per user and item group
+    NDCG@k_ndcg / Recall@k_r1 / Recall@k_r2 (plus the all-items slot, which is Evaluator's table) and the exposure counts at k_exp,
+    read off the chunk's top-K lists by ltg_topk_metrics -- one forward per chunk serves the lists and the report.
+    labels: one uint8 per GLOBAL item id, a label >= n_groups is in no group.  After run(): `out` [n_users, n_groups + 1, 4] and
+    `item_hits` [n_items] on the device; table() brings both to the host."""
+
+    def __init__(self, labels, n_groups, k_ndcg=100, k_r1=20, k_r2=50, k_exp=100):
+        self.labels_host = np.ascontiguousarray(np.asarray(labels), dtype=np.uint8)
+        self.n_groups = int(n_groups)
+        self.cut = dict(k_ndcg=int(k_ndcg), k_r1=int(k_r1), k_r2=int(k_r2), k_exp=int(k_exp))
+        if not 1 <= self.n_groups <= 8:
+            raise ValueError("n_groups must be in [1, 8]")
+        if min(self.cut.values()) < 1 or max(self.cut.values()) > 1024:
+            raise ValueError("every cutoff must be in [1, 1024]")
+        self.k = max(self.cut.values())                  # the list length the report needs
+        self.out = self.item_hits = self.labels = None
+
+    def bind(self, engine, n_users, k):
+        if k < self.k:
+            raise ValueError("top-K lists of %d entries are shorter than the report's largest cutoff %d" % (k, self.k))
+        if self.labels_host.size != engine.I_global:
+            raise ValueError("labels hold %d items, the catalogue %d" % (self.labels_host.size, engine.I_global))
+        dev = engine.device
+        self.labels = torch.from_numpy(self.labels_host).to(dev)
+        self.out = torch.zeros(n_users, self.n_groups + 1, 4, dtype=torch.float32, device=dev)
+        self.item_hits = torch.zeros(self.labels_host.size, dtype=torch.int32, device=dev)
+
+    def add(self, engine, ids, te, lo):
+        engine.topk_metrics(ids, te, self.labels, self.n_groups, self.out[lo:], self.item_hits, **self.cut)
+
+    def table(self):
+        """-> (out [n_users, n_groups + 1, 4] float32, item_hits [n_items] int32) host arrays"""
+        return self.out.cpu().numpy(), self.item_hits.cpu().numpy()
+
+
+class MinSlots:
+    """A serve-time rule, passed as `rule=` to a Recommender / ShardedRecommender: at least slots[g] of every user's k list entries come
+    from item group g (labels: one uint8 per GLOBAL item id, a label >= n_groups is in no group; the labels a LongTailReport takes).  Walking
+    a user's ranking from the top, an item is taken if its group still owes slots, or if a slot is left that no group's outstanding minimum
+    claims; a group with fewer eligible items than its minimum hands the rest to the free slots.  slots all 0 is the plain list; slots[g] = k
+    is the k best items of group g.  Per chunk: the plain list, one reserved list per group with slots[g] > 0 (ltg_topk_groups with that
+    group's bit, every one max(slots) entries long so that they share one array), composed by ltg_topk_quota.  Over item shards every one
+    of those lists is gathered and merged by the SlabLists, and every rank composes the same ruled lists."""
+
+    def __init__(self, labels, n_groups, slots):
+        self.labels_host = np.ascontiguousarray(np.asarray(labels), dtype=np.uint8)
+        self.n_groups = int(n_groups)
+        if not 1 <= self.n_groups <= 8:
+            raise ValueError("n_groups must be in [1, 8]")
+        self.slots = [int(x) for x in slots]
+        if len(self.slots) != self.n_groups:
+            raise ValueError("slots holds %d counts for %d groups" % (len(self.slots), self.n_groups))
+        if min(self.slots) < 0:
+            raise ValueError("a group's minimum must be >= 0")
+        self.groups = [g for g, m in enumerate(self.slots) if m > 0]        # the groups with a reserved list
+        self.quota = [self.slots[g] for g in self.groups]
+        self.m = max(self.slots)
+        self.labels = None
+
+    def bind(self, engine, rows, k):
+        """buffers for chunks of up to `rows` users and lists of k entries"""
+        if sum(self.slots) > k:
+            raise ValueError("the minimum slots sum to %d, more than the %d entries of a list" % (sum(self.slots), k))
+        if self.labels_host.size != engine.I_global:
+            raise ValueError("labels hold %d items, the catalogue %d" % (self.labels_host.size, engine.I_global))
+        dev = engine.device
+        self.labels = torch.from_numpy(self.labels_host).to(dev)
+        n_l, m = max(1, len(self.groups)), max(1, self.m)
+        self.all_s = torch.empty(rows * k, dtype=torch.float32, device=dev)
+        self.all_i = torch.empty(rows * k, dtype=torch.int32, device=dev)
+        self.grp_s = torch.empty(n_l * rows * m, dtype=torch.float32, device=dev)
+        self.grp_i = torch.empty(n_l * rows * m, dtype=torch.int32, device=dev)
+
+    def plain(self, n, k):
+        """where the chunk's plain lists go: ([n, k] scores, [n, k] ids)"""
+        return self.all_s[: n * k].view(n, k), self.all_i[: n * k].view(n, k)
+
+    def reserved(self, n):
+        """where the chunk's reserved lists go: ([groups, n, m] scores, ids), list j for group self.groups[j]"""
+        n_l = len(self.groups)
+        return self.grp_s[: n_l * n * self.m].view(n_l, n, self.m), self.grp_i[: n_l * n * self.m].view(n_l, n, self.m)
+
+    def apply(self, lists, acts, tr, n, k, score_out, id_out):
+        """the ruled lists of the n rows whose logits `acts` holds; lists: the SlabLists the plain and the reserved lists come from"""
+        a_s, a_i = self.plain(n, k)
+        lists.topk(acts, tr, n, k, a_s, a_i)
+        if not self.groups:                              # nothing reserved: the plain list
+            score_out.copy_(a_s)
+            id_out.copy_(a_i)
+            return
+        g_s, g_i = self.reserved(n)
+        for j, g in enumerate(self.groups):
+            lists.topk(acts, tr, n, self.m, g_s[j], g_i[j], self.labels, 1 << g)
+        lists.eng.topk_quota(a_s, a_i, g_s, g_i, self.quota, score_out, id_out)
+
+
+class Diversify:
+    """A serve-time re-ranking, passed as `diversify=` to a Recommender / ShardedRecommender: greedy maximal marginal relevance.  Each
+    user's `candidates` best items (ltg_topk; default min(256, 2 k), k <= candidates <= 256) are re-ranked so that the next entry is the
+    one with the largest  lam * relevance - (1 - lam) * (largest similarity to what the list already holds)  -- relevance = the score
+    scaled to [0, 1] over the candidates, similarity = the product of the items' rows in the bf16 image of the `decoder` (W_p1t) or
+    `encoder` (W_q0) table, `cosine` or `dot` (ltg_item_pack).  lam = 1 is the plain list.  The image is packed once per run(); per chunk
+    ltg_topk at `candidates`, then ONE launch of ltg_topk_diversify: the candidates' similarity matrix never leaves the chip.  The lists
+    keep every pick's original score, so they are generally not descending.  After run(): stats() [n_users, 2] = the mean pair similarity
+    of the plain top-k list and of the diversified one.  Over item shards the candidates are gathered and merged at their own length by
+    the SlabLists and every rank re-ranks the same candidates against the image of the whole catalogue."""
+
+    def __init__(self, lam, candidates=None, space="decoder", metric="cosine"):
+        self.lam = float(lam)
+        if not 0.0 <= self.lam <= 1.0:               # (NaN fails both comparisons)
+            raise ValueError("lam must be in [0, 1], got %r" % (lam,))
+        if space not in LTG_SPACE or metric not in LTG_METRIC:
+            raise ValueError("space must be decoder or encoder, metric cosine or dot")
+        self.candidates = None if candidates is None else int(candidates)
+        self.space, self.metric = space, metric
+        self.c = self.image = self.stat = None
+        self.image_lo = 0
+
+    def bind(self, engine, rows, k, n_users):
+        """buffers for chunks of up to `rows` users, lists of k entries and a table of n_users"""
+        c = min(256, 2 * k) if self.candidates is None else self.candidates
+        if not k <= c <= 256:
+            raise ValueError("candidates must be in [k, 256] = [%d, 256], got %d" % (k, c))
+        self.c = c
+        dev = engine.device
+        self.cand_s = torch.empty(rows * c, dtype=torch.float32, device=dev)
+        self.cand_i = torch.empty(rows * c, dtype=torch.int32, device=dev)
+        self.stat = torch.zeros(n_users, 2, dtype=torch.float32, device=dev)
+
+    def pack(self, engine, group=None):
+        """the image of the whole catalogue, once per run().  group given (item shards): every rank packs its slab into a zeroed
+        [I_global, 608] buffer at its item_lo, and the buffer is all-reduced viewed as int32 -- exactly one rank contributes each row."""
+        if group is None and engine.I == engine.I_global:
+            self.image = engine.item_pack(self.space, self.metric, out=self.image)
+            return
+        if self.image is None:
+            self.image = torch.empty(engine.I_global, 608, dtype=torch.int16, device=engine.device)
+        self.image.zero_()
+        engine.item_pack(self.space, self.metric, out=self.image[engine.item_lo:engine.item_hi])
+        dist.all_reduce(self.image.view(torch.int32), op=dist.ReduceOp.SUM, group=group)
+
+    def candidates_of(self, n):
+        """where the chunk's candidate lists go: ([n, candidates] scores, ids)"""
+        return self.cand_s[: n * self.c].view(n, self.c), self.cand_i[: n * self.c].view(n, self.c)
+
+    def apply(self, lists, acts, tr, n, k, lo, score_out, id_out):
+        """the diversified lists of users lo .. lo + n, whose logits `acts` holds; lists: the SlabLists the candidates come from"""
+        c_s, c_i = self.candidates_of(n)
+        lists.topk(acts, tr, n, self.c, c_s, c_i)
+        lists.eng.topk_diversify(self.image, self.image_lo, c_s, c_i, self.lam, k, score_out, id_out, self.stat[lo:lo + n])
+
+    def stats(self):
+        """-> [n_users, 2] float32 host array: mean pair similarity of the first k candidates, and of the list"""
+        return self.stat.cpu().numpy()
+
+
+class Recommender:
+    """Top-K recommendations per user (the forward of Evaluator, then ltg_topk instead of the metrics): the same chunks of
+    `chunk` users capped by eval_chunk_rows, the same dropout-on forward (Q3) with counter rng_step + lo per chunk, fold-in
+    items excluded.  keep_prob = 1.0 gives dropout-free, deterministic recommendations.  report: a LongTailReport to fill from
+    each chunk's lists (k >= its largest cutoff); absent, nothing else runs.  rule: a MinSlots the lists are to satisfy (the report then
+    reads the ruled lists); absent, the plain top-K.  diversify: a Diversify the lists are re-ranked by (the report then reads the
+    diversified lists); not together with rule.  Every list comes out of one SlabLists (self.lists)."""
+
+    sharded = False                                  # ShardedRecommender: one rank of `group` per item slab
+
+    def __init__(self, engine, ev, k=100, chunk=20000, report=None, rule=None, diversify=None, group=None):
+        if rule is not None and diversify is not None:
+            raise ValueError("diversify= and rule= cannot be combined")
+        self.eng, self.ev, self.k, self.report, self.rule, self.diversify, self.group = engine, ev, int(k), report, rule, diversify, group
+        if report is not None:
+            report.bind(engine, ev.n, self.k)
+        self.chunk = chunk_rows(engine, ev, chunk)
+        longest = self.k
+        if rule is not None:
+            rule.bind(engine, self.chunk, self.k)
+            longest = max(longest, rule.m)
+        if diversify is not None:
+            diversify.bind(engine, self.chunk, self.k, ev.n)
+            longest = max(longest, diversify.c)
+        self.lists = SlabLists(engine, self.chunk, longest, group, dist.get_world_size(group) if self.sharded else 1)
+        self.acts = engine.new_acts(self.chunk)
+        dev = engine.device
+        self.scores = torch.empty(ev.n, self.k, dtype=torch.float32, device=dev)
+        self.ids = torch.empty(ev.n, self.k, dtype=torch.int32, device=dev)
+
+    def _forward(self, tr, n, keep_prob, rng_step):
+        """the logits of the n rows `tr` into self.acts"""
+        self.eng.forward(tr, self.acts, keep_prob=keep_prob, is_training=0.0, rng_step=rng_step)
+
+    def run(self, rng_step=0, keep_prob=0.75):
+        """-> (ids [n_users, k] int32 global item ids, scores [n_users, k] float32 logits) as host arrays (over item shards: identical
+        on every rank)"""
+        eng, ev, k = self.eng, self.ev, self.k
+        if self.report is not None:
+            self.report.item_hits.zero_()
+        if self.diversify is not None:
+            self.diversify.pack(eng, group=self.group)
+        for lo in range(0, ev.n, self.chunk):
+            hi = min(ev.n, lo + self.chunk)
+            n = hi - lo
+            tr, te = ev.rows(lo, hi)
+            self._forward(tr, n, keep_prob, rng_step + lo)
+            if self.diversify is not None:
+                self.diversify.apply(self.lists, self.acts, tr, n, k, lo, self.scores[lo:hi], self.ids[lo:hi])
+            elif self.rule is not None:
+                self.rule.apply(self.lists, self.acts, tr, n, k, self.scores[lo:hi], self.ids[lo:hi])
+            else:
+                self.lists.topk(self.acts, tr, n, k, self.scores[lo:hi], self.ids[lo:hi])
+            if self.report is not None:
+                self.report.add(eng, self.ids[lo:hi], te, lo)
+        return self.ids.cpu().numpy(), self.scores.cpu().numpy()
+
+
+class ShardedRecommender(Recommender):
+    """Recommender over item shards: per chunk of users the sharded forward of ShardedEvaluator, and a SlabLists over the ranks of
+    `group`, so that every list -- plain, reserved, candidates -- is this slab's list, gathered and merged (ltg_topk_merge).  Every rank
+    ends with the identical table, bit-identical to the unsharded Recommender's; the lists a report reads are identical on every rank, so
+    the report (item_hits included) needs no exchange, and neither do ltg_topk_quota and ltg_topk_diversify (against the image of the
+    whole catalogue, Diversify.pack: one all-reduce per run())."""
+
+    sharded = True
+
+    def __init__(self, engine, ev, k=100, group=None, chunk=20000, report=None, rule=None, diversify=None):
+        super().__init__(engine, ev, k=k, chunk=chunk, report=report, rule=rule, diversify=diversify, group=group)
+        self.rowpart = torch.zeros(self.chunk * 5, dtype=torch.float32, device=engine.device)
+
+    def _forward(self, tr, n, keep_prob, rng_step):
+        sharded_forward(self.eng, tr, n, self.acts, self.rowpart, keep_prob, rng_step, self.group)
+
+
+def group_mask_of(only, n_groups):
+    """the group_mask of ltg_topk_groups / ltg_item_neighbors that admits the group indices `only` (None: every group)"""
+    if only is None:
+        return 0x1FF
+    mask = 0
+    for g in only:
+        if not 0 <= int(g) < int(n_groups):
+            raise ValueError("group index %r outside [0, %d)" % (g, n_groups))
+        mask |= 1 << min(int(g), 8)
+    if mask == 0:
+        raise ValueError("`only` admits no group")
+    return mask
+
+
+def neighbors_ws_bytes(ws_bytes, n_q, chunk, k):
+    """the workspace for walking n_q queries in chunks of `chunk`: the largest need over the chunk lengths that occur.  ws_bytes(n, k) =
+    ltg_item_neighbors_ws_bytes.  It is NOT monotone in n: fewer query blocks get more item segments (the grid is sized to fill the chip),
+    so a shorter last chunk can need more than a full one -- 3 392 queries more than 4 096 at 200 000 items."""
+    n_q, chunk = int(n_q), max(1, int(chunk))
+    sizes = {min(chunk, n_q)} | ({n_q % chunk} if n_q > chunk else set())
+    return max([int(ws_bytes(n, k)) for n in sizes if n > 0] + [1])
+
+
+class ItemNeighbors:
+    """The k nearest items of items (ltg_item_neighbors): space `decoder` (rows of W_p1t) or `encoder` (rows of W_q0), metric `cosine` or
+    `dot`; a query never returns itself.  labels (uint8 per global item id, longtail.build_groups) + only (group indices) restrict the
+    NEIGHBOURS to those groups -- `only=[niche]` over the popular items is the niche shelf of every head item.  The table is packed once
+    into the bf16 operand image; the queries are walked in chunks of `chunk`, their rows taken out of the image by index.  The scores
+    stay on the chip: the workspace is lists."""
+
+    def __init__(self, engine, k=20, space="decoder", metric="cosine", labels=None, n_groups=None, only=None, chunk=4096):
+        self.eng, self.k, self.space, self.metric, self.chunk = engine, int(k), space, metric, max(1, int(chunk))
+        dev = engine.device
+        self.labels = None
+        self.mask = 0x1FF
+        if labels is not None:
+            self.labels = torch.as_tensor(np.ascontiguousarray(labels, dtype=np.uint8)).to(dev)
+            self.mask = group_mask_of(only, n_groups if n_groups is not None else int(self.labels.max().item()) + 1)
+        elif only is not None:
+            raise ValueError("`only` needs labels")
+        self.image = None
+
+    def pack(self):
+        self.image = self.eng.item_pack(self.space, self.metric, out=self.image)
+        return self.image
+
+    def _queries(self, query_ids):
+        n_glob = self.eng.cfg.n_items_global or self.eng.I
+        q = np.arange(n_glob, dtype=np.int32) if query_ids is None else np.ascontiguousarray(query_ids, dtype=np.int32).reshape(-1)
+        if q.size and (q.min() < 0 or q.max() >= n_glob):
+            raise ValueError("query ids outside [0, %d)" % n_glob)
+        return q
+
+    def query_rows(self, gid):
+        """the image rows of the global ids gid (a device int32 tensor)"""
+        return self.image.index_select(0, gid.long())
+
+    def run(self, query_ids=None):
+        """-> (ids [n_q, k] int32 global item ids, scores [n_q, k] float32) as host arrays; query_ids None = every item"""
+        eng, k = self.eng, self.k
+        dev = eng.device
+        q = self._queries(query_ids)
+        self.pack()
+        ids = torch.empty(len(q), k, dtype=torch.int32, device=dev)
+        scores = torch.empty(len(q), k, dtype=torch.float32, device=dev)
+        qd = torch.from_numpy(q).to(dev)
+        ws = torch.empty(neighbors_ws_bytes(eng.item_neighbors_ws_bytes, len(q), self.chunk, k), dtype=torch.uint8, device=dev)
+        for lo in range(0, len(q), self.chunk):
+            hi = min(len(q), lo + self.chunk)
+            eng.item_neighbors(self.image, self.query_rows(qd[lo:hi]), qd[lo:hi], k, scores[lo:hi], ids[lo:hi], self.labels, self.mask, ws=ws)
+        return ids.cpu().numpy(), scores.cpu().numpy()
+
+
+class ShardedItemNeighbors(ItemNeighbors):
+    """ItemNeighbors over item shards.  Every rank packs its slab.  Per chunk of queries every rank copies the image rows of the queries it
+    owns into a zeroed [n][608] buffer, which is all-reduced viewed as int32 (exactly one rank contributes a row, so the sum is that row:
+    works over gloo and nccl); every rank searches its slab (global ids), and a SlabLists gathers and merges the lists as it does for
+    ShardedRecommender.  A pair's score does not depend on the slab that holds the item, so every rank ends with the identical
+    table, bit-identical to ItemNeighbors on the whole catalogue."""
+
+    def __init__(self, engine, k=20, space="decoder", metric="cosine", labels=None, n_groups=None, only=None, chunk=4096, group=None):
+        super().__init__(engine, k=k, space=space, metric=metric, labels=labels, n_groups=n_groups, only=only, chunk=chunk)
+        self.group = group
+        self.R = dist.get_world_size(group)
+
+    def run(self, query_ids=None):
+        eng, k = self.eng, self.k
+        dev = eng.device
+        lo_i, hi_i = eng.item_lo, eng.item_hi
+        q = self._queries(query_ids)
+        self.pack()
+        ids = torch.empty(len(q), k, dtype=torch.int32, device=dev)
+        scores = torch.empty(len(q), k, dtype=torch.float32, device=dev)
+        qd = torch.from_numpy(q).to(dev)
+        c = min(self.chunk, max(1, len(q)))
+        ws = torch.empty(neighbors_ws_bytes(eng.item_neighbors_ws_bytes, len(q), c, k), dtype=torch.uint8, device=dev)
+        qimg = torch.empty(c, 608, dtype=torch.int16, device=dev)
+        lists = SlabLists(eng, c, k, self.group, self.R)
+        for lo in range(0, len(q), c):
+            hi = min(len(q), lo + c)
+            n = hi - lo
+            g = qd[lo:hi].long()
+            qi = qimg[:n]
+            qi.zero_()
+            own = (g >= lo_i) & (g < hi_i)
+            qi[own] = self.image.index_select(0, g[own] - lo_i)
+            dist.all_reduce(qi.view(torch.int32), op=dist.ReduceOp.SUM, group=self.group)
+            ls, li = lists.local(n, k, scores[lo:hi], ids[lo:hi])
+            eng.item_neighbors(self.image, qi, qd[lo:hi], k, ls, li, self.labels, self.mask, ws=ws)
+            lists.merge(ls, li, scores[lo:hi], ids[lo:hi])
+        return ids.cpu().numpy(), scores.cpu().numpy()
+
+
+# ---------------------------------------------------------------- what the four CLIs share (test.py, recommend.py, longtail.py, similar.py)
+class _Counters:
+    """load_checkpoint also restores the trainer's counters; the serving flows have no trainer."""
+    update_count = 0.0
+    rng_step = 0
+
+    def __init__(self):
+        self.np_rng = np.random.RandomState(0)
+
+
+def open_model(dataset_dir, checkpoint, h_sizes, lr, precision="bf16", device=None):
+    """The set-up of a serving CLI: under `python -m torch.distributed.run` (WORLD_SIZE > 1) the process group (LTGAN_DIST_BACKEND,
+    default nccl) and this rank's item slab, else the whole catalogue; the device (LOCAL_RANK's, unless given); the generator's engine
+    on that slab with the checkpoint restored.  -> (engine, item_lo, item_hi, rank, world, print): print is silent on every rank but 0.
+    close_model(world) is its counterpart."""
+    import builtins
+    from .dataset import count_items
+    from .generator import generator_VAECF
+    from .sharded import item_slab
+    from .train import load_checkpoint
+    world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
+    if device is None:
+        device = "cuda:%d" % (int(os.environ.get("LOCAL_RANK", "0")) % max(1, torch.cuda.device_count()))
+    if world > 1 and not dist.is_initialized():
+        dist.init_process_group(os.environ.get("LTGAN_DIST_BACKEND", "nccl"))
+    n_items = count_items(dataset_dir)
+    lo, hi = item_slab(n_items, rank, world) if world > 1 else (0, n_items)
+    gen_net, *_ = generator_VAECF(dataset_dir + "/", h_sizes=tuple(h_sizes), lr=lr, precision=precision, device=device, item_lo=lo, item_hi=hi)
+    load_checkpoint(checkpoint, gen_net.engine, _Counters())
+    return gen_net.engine, lo, hi, rank, world, builtins.print if rank == 0 else (lambda *a, **k: None)
+
+
+def close_model(world):
+    """every rank has finished: the barrier, then the process group goes"""
+    if world > 1:
+        dist.barrier()
+        dist.destroy_process_group()

@@ -30,7 +30,8 @@ import torch
 import torch.distributed as dist
 
 from .engine import Pipe, _ptr
-from .trainer import ItemNeighbors, Trainer, eval_chunk_rows, neighbors_ws_bytes
+from .serving import ShardedEvaluator, ShardedItemNeighbors, ShardedRecommender  # noqa: F401
+from .trainer import Trainer
 
 D_SPLIT_MIN_PARAMS = 1_000_000
 
@@ -270,190 +271,3 @@ class ShardedTrainer(Trainer):
             eng.g_bwd_dec1(v["batch"], v["fake"], self.acts, go)
             work.wait()
             eng.g_bwd_rest(v["batch"], v["fake"], self.acts, go, self.dh2)
-
-
-class ShardedEvaluator:
-    """Validation / test scoring over item shards (train.py:333-348, test.py:138-173).  Per chunk of users: the
-    sharded forward (one all-reduce of the encoder pre-activation), then two small exchanges for the ranking:
-      1. all-reduce(sum) of the held-out entries' scores   (float32 per held-out entry; the owner contributes)
-      2. all-reduce(sum) of the per-entry rank counts      (int32 per held-out entry)
-    The softmax is never materialised: ranking by logits equals ranking by probabilities row by row.  Every rank
-    ends with the identical metric table."""
-
-    def __init__(self, engine, ev, group=None, chunk=20000):
-        self.eng, self.ev, self.group = engine, ev, group
-        self.chunk = int(min(chunk, max(1, ev.n), eval_chunk_rows(engine.I)))
-        self.acts = engine.new_acts(self.chunk)
-        dev = engine.device
-        n_te = max(1, int(ev.te_indices.numel()))
-        self.score = torch.zeros(n_te, dtype=torch.float32, device=dev)
-        self.count = torch.zeros(n_te, dtype=torch.int32, device=dev)
-        self.out = torch.zeros(ev.n, 4, dtype=torch.float32, device=dev)
-        self.rowpart = torch.zeros(self.chunk * 5, dtype=torch.float32, device=dev)
-
-    def run(self, rng_step=0, keep_prob=0.75):
-        eng, ev = self.eng, self.ev
-        te_ptr = ev.te_host.indptr
-        for lo in range(0, ev.n, self.chunk):
-            hi = min(ev.n, lo + self.chunk)
-            tr, te = ev.rows(lo, hi)
-            fo = eng.fwd_opts(keep_prob, 0.0, rng_step + lo)
-            eng.g_fwd_enc(tr, self.acts, fo)
-            dist.all_reduce(self.acts.h1[: hi - lo], op=dist.ReduceOp.SUM, group=self.group)
-            eng.g_fwd_rest(tr, None, self.acts, fo, self.rowpart)
-            e0, e1 = int(te_ptr[lo]), int(te_ptr[hi])
-            eng.rank_scores(self.acts, tr, te, self.score)
-            if e1 > e0:
-                dist.all_reduce(self.score[e0:e1], op=dist.ReduceOp.SUM, group=self.group)
-            eng.rank_counts(self.acts, tr, te, self.score, self.count)
-            if e1 > e0:
-                dist.all_reduce(self.count[e0:e1], op=dist.ReduceOp.SUM, group=self.group)
-            eng.rank_finish(te, self.count, self.out[lo:])
-        o = self.out.cpu().numpy().astype(np.float64)
-        ok = o[:, 3] > 0
-        n = int(ok.sum())
-        return dict(ndcg=float(o[ok, 0].mean()) if n else float("nan"), recall20=float(o[ok, 1].mean()) if n else float("nan"),
-                    recall50=float(o[ok, 2].mean()) if n else float("nan"), n_users=n)
-
-
-class ShardedRecommender:
-    """Top-K recommendations over item shards: per chunk of users the sharded forward of ShardedEvaluator, ltg_topk on this
-    rank's slab (global ids), ONE all-gather of the [R][rows][k] candidate lists (scores and ids; a list all-gather works over
-    gloo as well as nccl), then ltg_topk_merge.  Every rank ends with the identical table.  report: a LongTailReport to fill from
-    each chunk's merged lists; they are identical on every rank, so the report (item_hits included) needs no exchange.  rule: a
-    MinSlots; its reserved lists (ltg_topk_groups on the slab) are all-gathered and merged exactly like the plain list, then every rank
-    composes the same ruled lists (ltg_topk_quota) -- still no exchange of logits.  diversify: a Diversify (not together with rule); the
-    per-slab lists are then `candidates` long, gathered and merged at that length, and every rank runs ltg_topk_diversify on the same
-    merged candidates against the image of the whole catalogue (Diversify.pack: one all-reduce per run()), so the table is identical on
-    every rank and bit-identical to the unsharded Recommender's."""
-
-    def __init__(self, engine, ev, k=100, group=None, chunk=20000, report=None, rule=None, diversify=None):
-        self.eng, self.ev, self.group, self.k, self.report, self.rule, self.diversify = engine, ev, group, int(k), report, rule, diversify
-        if rule is not None and diversify is not None:
-            raise ValueError("diversify= and rule= cannot be combined")
-        if report is not None:
-            report.bind(engine, ev.n, self.k)
-        self.R = dist.get_world_size(group)
-        self.chunk = int(min(chunk, max(1, ev.n), eval_chunk_rows(engine.I)))
-        if rule is not None:
-            rule.bind(engine, self.chunk, self.k, parts=self.R)
-        if diversify is not None:
-            diversify.bind(engine, self.chunk, self.k, ev.n, parts=self.R)
-        self.acts = engine.new_acts(self.chunk)
-        dev = engine.device
-        self.rowpart = torch.zeros(self.chunk * 5, dtype=torch.float32, device=dev)
-        self.part_s = torch.empty(self.R, self.chunk, self.k, dtype=torch.float32, device=dev)
-        self.part_i = torch.empty(self.R, self.chunk, self.k, dtype=torch.int32, device=dev)
-        self.loc_s = torch.empty(self.chunk, self.k, dtype=torch.float32, device=dev)
-        self.loc_i = torch.empty(self.chunk, self.k, dtype=torch.int32, device=dev)
-        self.scores = torch.empty(ev.n, self.k, dtype=torch.float32, device=dev)
-        self.ids = torch.empty(ev.n, self.k, dtype=torch.int32, device=dev)
-
-    def run(self, rng_step=0, keep_prob=0.75):
-        """-> (ids [n_users, k], scores [n_users, k]) host arrays, identical on every rank"""
-        eng, ev, k = self.eng, self.ev, self.k
-        if self.report is not None:
-            self.report.item_hits.zero_()
-        div = self.diversify
-        if div is not None:
-            div.pack(eng, group=self.group)
-        for lo in range(0, ev.n, self.chunk):
-            hi = min(ev.n, lo + self.chunk)
-            n = hi - lo
-            tr, te = ev.rows(lo, hi)
-            fo = eng.fwd_opts(keep_prob, 0.0, rng_step + lo)
-            eng.g_fwd_enc(tr, self.acts, fo)
-            dist.all_reduce(self.acts.h1[:n], op=dist.ReduceOp.SUM, group=self.group)
-            eng.g_fwd_rest(tr, None, self.acts, fo, self.rowpart)
-            if div is not None:
-                self._diversified(tr, n, lo, self.scores[lo:hi], self.ids[lo:hi])
-                if self.report is not None:
-                    self.report.add(eng, self.ids[lo:hi], te, lo)
-                continue
-            ls, li = self.loc_s[:n], self.loc_i[:n]
-            eng.topk(self.acts, tr, k, ls, li)
-            ps, pi = self.part_s[:, :n], self.part_i[:, :n]
-            if n < self.chunk:                       # (a short last chunk: contiguous [R][n][k] blocks)
-                ps, pi = ps.contiguous(), pi.contiguous()
-            dist.all_gather(list(ps.unbind(0)), ls, group=self.group)
-            dist.all_gather(list(pi.unbind(0)), li, group=self.group)
-            if self.rule is None:
-                eng.topk_merge(ps, pi, k, self.scores[lo:hi], self.ids[lo:hi])
-            else:
-                self._ruled(tr, n, ps, pi, self.scores[lo:hi], self.ids[lo:hi])
-            if self.report is not None:
-                self.report.add(eng, self.ids[lo:hi], te, lo)
-        return self.ids.cpu().numpy(), self.scores.cpu().numpy()
-
-    def _diversified(self, tr, n, lo, score_out, id_out):
-        """the slab logits in self.acts -> the diversified lists of the chunk's n rows (users lo .. lo + n)"""
-        eng, div, R = self.eng, self.diversify, self.R
-        c = div.c
-        ls, li = div.loc_s[: n * c].view(n, c), div.loc_i[: n * c].view(n, c)
-        ps, pi = div.part_s[: R * n * c].view(R, n, c), div.part_i[: R * n * c].view(R, n, c)
-        eng.topk(self.acts, tr, c, ls, li)
-        dist.all_gather(list(ps.unbind(0)), ls, group=self.group)
-        dist.all_gather(list(pi.unbind(0)), li, group=self.group)
-        eng.topk_merge(ps, pi, c, *div.candidates_of(n))
-        div.rerank(eng, n, self.k, lo, score_out, id_out)
-
-    def _ruled(self, tr, n, ps, pi, score_out, id_out):
-        """the gathered plain lists ps / pi, and the slab logits still in self.acts -> the ruled lists of the chunk's n rows"""
-        eng, rule, k, R = self.eng, self.rule, self.k, self.R
-        eng.topk_merge(ps, pi, k, *rule.plain(n, k))
-        if rule.groups:
-            m = rule.m
-            g_s, g_i = rule.reserved(n)
-            ls, li = rule.loc_s[: n * m].view(n, m), rule.loc_i[: n * m].view(n, m)
-            qs, qi = rule.part_s[: R * n * m].view(R, n, m), rule.part_i[: R * n * m].view(R, n, m)
-            for j, g in enumerate(rule.groups):
-                eng.topk_groups(self.acts, tr, m, rule.labels, 1 << g, ls, li)
-                dist.all_gather(list(qs.unbind(0)), ls, group=self.group)
-                dist.all_gather(list(qi.unbind(0)), li, group=self.group)
-                eng.topk_merge(qs, qi, m, g_s[j], g_i[j])
-        rule.compose(eng, n, k, score_out, id_out)
-
-
-class ShardedItemNeighbors(ItemNeighbors):
-    """ItemNeighbors over item shards.  Every rank packs its slab.  Per chunk of queries every rank copies the image rows of the queries it
-    owns into a zeroed [n][608] buffer, which is all-reduced viewed as int32 (exactly one rank contributes a row, so the sum is that row:
-    works over gloo and nccl); every rank searches its slab (global ids), the lists are all-gathered and merged with ltg_topk_merge as
-    ShardedRecommender does.  A pair's score does not depend on the slab that holds the item, so every rank ends with the identical
-    table, bit-identical to ItemNeighbors on the whole catalogue."""
-
-    def __init__(self, engine, k=20, space="decoder", metric="cosine", labels=None, n_groups=None, only=None, chunk=4096, group=None):
-        super().__init__(engine, k=k, space=space, metric=metric, labels=labels, n_groups=n_groups, only=only, chunk=chunk)
-        self.group = group
-        self.R = dist.get_world_size(group)
-
-    def run(self, query_ids=None):
-        eng, k, R = self.eng, self.k, self.R
-        dev = eng.device
-        lo_i, hi_i = eng.item_lo, eng.item_hi
-        q = self._queries(query_ids)
-        self.pack()
-        ids = torch.empty(len(q), k, dtype=torch.int32, device=dev)
-        scores = torch.empty(len(q), k, dtype=torch.float32, device=dev)
-        qd = torch.from_numpy(q).to(dev)
-        c = min(self.chunk, max(1, len(q)))
-        ws = torch.empty(neighbors_ws_bytes(eng.item_neighbors_ws_bytes, len(q), c, k), dtype=torch.uint8, device=dev)
-        qimg = torch.empty(c, 608, dtype=torch.int16, device=dev)
-        loc_s = torch.empty(c, k, dtype=torch.float32, device=dev)
-        loc_i = torch.empty(c, k, dtype=torch.int32, device=dev)
-        for lo in range(0, len(q), c):
-            hi = min(len(q), lo + c)
-            n = hi - lo
-            g = qd[lo:hi].long()
-            qi = qimg[:n]
-            qi.zero_()
-            own = (g >= lo_i) & (g < hi_i)
-            qi[own] = self.image.index_select(0, g[own] - lo_i)
-            dist.all_reduce(qi.view(torch.int32), op=dist.ReduceOp.SUM, group=self.group)
-            ls, li = loc_s[:n], loc_i[:n]
-            eng.item_neighbors(self.image, qi, qd[lo:hi], k, ls, li, self.labels, self.mask, ws=ws)
-            ps = torch.empty(R, n, k, dtype=torch.float32, device=dev)
-            pi = torch.empty(R, n, k, dtype=torch.int32, device=dev)
-            dist.all_gather(list(ps.unbind(0)), ls, group=self.group)
-            dist.all_gather(list(pi.unbind(0)), li, group=self.group)
-            eng.topk_merge(ps, pi, k, scores[lo:hi], ids[lo:hi])
-        return ids.cpu().numpy(), scores.cpu().numpy()

@@ -17,56 +17,28 @@ if __package__ in (None, ""):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import ltgan  # noqa: F401  (alias of this package directory)
     from ltgan import data_processing as dp
-    from ltgan.dataset import EvalData, count_items
+    from ltgan.dataset import EvalData
     from ltgan.discriminator import discriminator
-    from ltgan.generator import generator_VAECF as generator
-    from ltgan.sharded import ShardedEvaluator, item_slab
-    from ltgan.train import load_checkpoint, read_config
-    from ltgan.trainer import Evaluator
+    from ltgan.serving import Evaluator, ShardedEvaluator, _Counters, close_model, open_model  # noqa: F401
+    from ltgan.train import read_config
 else:
     from . import data_processing as dp
-    from .dataset import EvalData, count_items
+    from .dataset import EvalData
     from .discriminator import discriminator
-    from .generator import generator_VAECF as generator
-    from .sharded import ShardedEvaluator, item_slab
-    from .train import load_checkpoint, read_config
-    from .trainer import Evaluator
-
-
-class _Counters:
-    """load_checkpoint also restores the trainer's counters; the test flow has no trainer."""
-    update_count = 0.0
-    rng_step = 0
-
-    def __init__(self):
-        import numpy as np
-        self.np_rng = np.random.RandomState(0)
+    from .serving import Evaluator, ShardedEvaluator, _Counters, close_model, open_model  # noqa: F401
+    from .train import read_config
 
 
 def test_GAN(h0_size, h1_size, h2_size, h3_size, NUM_EPOCH, NUM_SUB_EPOCHS, BATCH_SIZE, DISPLAY_ITER, LEARNING_RATE, to_restore,
              model_name, dataset, GANLAMBDA, output_path, precision="bf16", device=None, batch_size_test=20000):
     """Codes/test.py:30-173 (same argument list)."""
-    import builtins
-    world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
-    if device is None:
-        import torch
-        device = "cuda:%d" % (int(os.environ.get("LOCAL_RANK", "0")) % max(1, torch.cuda.device_count()))
-    if world > 1:
-        import torch.distributed as dist
-        if not dist.is_initialized():
-            dist.init_process_group(os.environ.get("LTGAN_DIST_BACKEND", "nccl"))
-    print = builtins.print if rank == 0 else (lambda *a, **k: None)                      # noqa: A001
+    eng, lo, hi, rank, world, print = open_model(dataset, output_path, (h0_size, h1_size, h2_size, h3_size), LEARNING_RATE, precision, device)  # noqa: A001
     DATA_DIR = dataset + "/"
-    n_items = count_items(DATA_DIR)
+    n_items = eng.I_global
+    discriminator(n_items, n_items, h0_size, h1_size, h2_size, h3_size)   # the reference's six arguments (train.py:136)
     print("Loading Test Matrix...", end="")
     tr, te, _ = dp.load_tr_te_data(os.path.join(DATA_DIR, "test_tr.csv"), os.path.join(DATA_DIR, "test_te.csv"), n_items)
     print("N_test:", tr.shape[0])
-    lo, hi = item_slab(n_items, rank, world) if world > 1 else (0, n_items)
-    gen_net, *_ = generator(DATA_DIR, h_sizes=(h0_size, h1_size, h2_size, h3_size), lr=LEARNING_RATE, precision=precision,
-                            device=device, item_lo=lo, item_hi=hi)
-    eng = gen_net.engine
-    discriminator(n_items, n_items, h0_size, h1_size, h2_size, h3_size)   # the reference's six arguments (train.py:136)
-    load_checkpoint(output_path, eng, _Counters())
     print("Model Loaded")
     if world > 1:
         ev = ShardedEvaluator(eng, EvalData(tr, te, eng.device, item_lo=lo, item_hi=hi), chunk=batch_size_test)
@@ -74,10 +46,7 @@ def test_GAN(h0_size, h1_size, h2_size, h3_size, NUM_EPOCH, NUM_SUB_EPOCHS, BATC
         ev = Evaluator(eng, EvalData(tr, te, eng.device), chunk=batch_size_test)
     m = ev.run(rng_step=2 * 10 ** 9)
     print(str(m["ndcg"]) + "\t" + str(m["recall20"]) + "\t" + str(m["recall50"]))
-    if world > 1:
-        import torch.distributed as dist
-        dist.barrier()
-        dist.destroy_process_group()
+    close_model(world)
     return m
 
 

@@ -16,9 +16,9 @@ import time
 import numpy as np
 import torch
 
-from ._cabi import LTG_METRIC, LTG_SPACE
-from .dataset import DeviceData, EvalData
+from .dataset import DeviceData
 from .engine import Engine, Pipe
+from .serving import EVAL_LOGITS_BYTES, Diversify, Evaluator, ItemNeighbors, LongTailReport, MinSlots, Recommender, eval_chunk_rows, group_mask_of, neighbors_ws_bytes  # noqa: F401
 
 
 CREATE_LOGITS_BYTES = 1 << 30      # logits of one phase-C span (rows x I x 4)
@@ -244,334 +244,3 @@ class Trainer:
         torch.cuda.synchronize()
         t3 = time.perf_counter()
         return dict(user_err_cnt=err, t_create=t1 - t0, t_d=t2 - t1, t_g=t3 - t2, t_total=t3 - t0)
-
-
-EVAL_LOGITS_BYTES = 2 << 30
-
-
-def eval_chunk_rows(n_items_local, budget=EVAL_LOGITS_BYTES):
-    """users per scoring chunk so that the [chunk, I] fp32 logits stay within `budget` bytes (test.py:76 scores 20 000
-    users at a time: 16 GB at I = 200 000)."""
-    return max(1, int(budget // (4 * max(1, n_items_local))))
-
-
-class Evaluator:
-    """Validation / test scoring (train.py:333-348, test.py:138-173): forward with dropout ON (Q3),
-    fold-in items masked to -inf, NDCG@100 / Recall@20 / Recall@50, in chunks of `chunk` users
-    (test.py:76 uses 20000), capped so that a chunk's logits stay within EVAL_LOGITS_BYTES."""
-
-    def __init__(self, engine: Engine, ev: EvalData, chunk=20000):
-        self.eng, self.ev, self.chunk = engine, ev, int(min(chunk, max(1, ev.n), eval_chunk_rows(engine.I)))
-        self.acts = engine.new_acts(self.chunk)
-        self.out = torch.zeros(ev.n, 4, dtype=torch.float32, device=engine.device)
-
-    def run(self, rng_step=0, keep_prob=0.75):
-        eng, ev = self.eng, self.ev
-        for lo in range(0, ev.n, self.chunk):
-            hi = min(ev.n, lo + self.chunk)
-            tr, te = ev.rows(lo, hi)
-            eng.forward(tr, self.acts, keep_prob=keep_prob, is_training=0.0, rng_step=rng_step + lo)
-            eng.rank_metrics(self.acts, tr, te, self.out[lo:])
-        o = self.out.cpu().numpy().astype(np.float64)
-        ok = o[:, 3] > 0
-        n = int(ok.sum())
-        return dict(ndcg=float(o[ok, 0].mean()) if n else float("nan"), recall20=float(o[ok, 1].mean()) if n else float("nan"),
-                    recall50=float(o[ok, 2].mean()) if n else float("nan"), n_users=n)
-
-
-class LongTailReport:
-    """The long-tail report a Recommender / ShardedRecommender fills when it is passed as `report=`: per user and item group
-    NDCG@k_ndcg / Recall@k_r1 / Recall@k_r2 (plus the all-items slot, which is Evaluator's table) and the exposure counts at k_exp,
-    read off the chunk's top-K lists by ltg_topk_metrics -- one forward per chunk serves the lists and the report.
-    labels: one uint8 per GLOBAL item id, a label >= n_groups is in no group.  After run(): `out` [n_users, n_groups + 1, 4] and
-    `item_hits` [n_items] on the device; table() brings both to the host."""
-
-    def __init__(self, labels, n_groups, k_ndcg=100, k_r1=20, k_r2=50, k_exp=100):
-        self.labels_host = np.ascontiguousarray(np.asarray(labels), dtype=np.uint8)
-        self.n_groups = int(n_groups)
-        self.cut = dict(k_ndcg=int(k_ndcg), k_r1=int(k_r1), k_r2=int(k_r2), k_exp=int(k_exp))
-        if not 1 <= self.n_groups <= 8:
-            raise ValueError("n_groups must be in [1, 8]")
-        if min(self.cut.values()) < 1 or max(self.cut.values()) > 1024:
-            raise ValueError("every cutoff must be in [1, 1024]")
-        self.k = max(self.cut.values())                  # the list length the report needs
-        self.out = self.item_hits = self.labels = None
-
-    def bind(self, engine, n_users, k):
-        if k < self.k:
-            raise ValueError("top-K lists of %d entries are shorter than the report's largest cutoff %d" % (k, self.k))
-        if self.labels_host.size != engine.I_global:
-            raise ValueError("labels hold %d items, the catalogue %d" % (self.labels_host.size, engine.I_global))
-        dev = engine.device
-        self.labels = torch.from_numpy(self.labels_host).to(dev)
-        self.out = torch.zeros(n_users, self.n_groups + 1, 4, dtype=torch.float32, device=dev)
-        self.item_hits = torch.zeros(self.labels_host.size, dtype=torch.int32, device=dev)
-
-    def add(self, engine, ids, te, lo):
-        engine.topk_metrics(ids, te, self.labels, self.n_groups, self.out[lo:], self.item_hits, **self.cut)
-
-    def table(self):
-        """-> (out [n_users, n_groups + 1, 4] float32, item_hits [n_items] int32) host arrays"""
-        return self.out.cpu().numpy(), self.item_hits.cpu().numpy()
-
-
-class MinSlots:
-    """A serve-time rule, passed as `rule=` to a Recommender / ShardedRecommender: at least slots[g] of every user's k list entries come
-    from item group g (labels: one uint8 per GLOBAL item id, a label >= n_groups is in no group; the labels a LongTailReport takes).  Walking
-    a user's ranking from the top, an item is taken if its group still owes slots, or if a slot is left that no group's outstanding minimum
-    claims; a group with fewer eligible items than its minimum hands the rest to the free slots.  slots all 0 is the plain list; slots[g] = k
-    is the k best items of group g.  Per chunk: the plain list, one reserved list per group with slots[g] > 0 (ltg_topk_groups with that
-    group's bit, every one max(slots) entries long so that they share one array), composed by ltg_topk_quota."""
-
-    def __init__(self, labels, n_groups, slots):
-        self.labels_host = np.ascontiguousarray(np.asarray(labels), dtype=np.uint8)
-        self.n_groups = int(n_groups)
-        if not 1 <= self.n_groups <= 8:
-            raise ValueError("n_groups must be in [1, 8]")
-        self.slots = [int(x) for x in slots]
-        if len(self.slots) != self.n_groups:
-            raise ValueError("slots holds %d counts for %d groups" % (len(self.slots), self.n_groups))
-        if min(self.slots) < 0:
-            raise ValueError("a group's minimum must be >= 0")
-        self.groups = [g for g, m in enumerate(self.slots) if m > 0]        # the groups with a reserved list
-        self.quota = [self.slots[g] for g in self.groups]
-        self.m = max(self.slots)
-        self.labels = None
-
-    def bind(self, engine, rows, k, parts=0):
-        """buffers for chunks of up to `rows` users and lists of k entries; parts > 0: also the all-gather buffers of that many ranks"""
-        if sum(self.slots) > k:
-            raise ValueError("the minimum slots sum to %d, more than the %d entries of a list" % (sum(self.slots), k))
-        if self.labels_host.size != engine.I_global:
-            raise ValueError("labels hold %d items, the catalogue %d" % (self.labels_host.size, engine.I_global))
-        dev = engine.device
-        self.labels = torch.from_numpy(self.labels_host).to(dev)
-        n_l, m = max(1, len(self.groups)), max(1, self.m)
-        self.all_s = torch.empty(rows * k, dtype=torch.float32, device=dev)
-        self.all_i = torch.empty(rows * k, dtype=torch.int32, device=dev)
-        self.grp_s = torch.empty(n_l * rows * m, dtype=torch.float32, device=dev)
-        self.grp_i = torch.empty(n_l * rows * m, dtype=torch.int32, device=dev)
-        if parts:
-            self.loc_s = torch.empty(rows * m, dtype=torch.float32, device=dev)
-            self.loc_i = torch.empty(rows * m, dtype=torch.int32, device=dev)
-            self.part_s = torch.empty(parts * rows * m, dtype=torch.float32, device=dev)
-            self.part_i = torch.empty(parts * rows * m, dtype=torch.int32, device=dev)
-
-    def plain(self, n, k):
-        """where the chunk's plain lists go: ([n, k] scores, [n, k] ids)"""
-        return self.all_s[: n * k].view(n, k), self.all_i[: n * k].view(n, k)
-
-    def reserved(self, n):
-        """where the chunk's reserved lists go: ([groups, n, m] scores, ids), list j for group self.groups[j]"""
-        n_l = len(self.groups)
-        return self.grp_s[: n_l * n * self.m].view(n_l, n, self.m), self.grp_i[: n_l * n * self.m].view(n_l, n, self.m)
-
-    def compose(self, engine, n, k, score_out, id_out):
-        """plain(n, k) and reserved(n) -> the ruled lists"""
-        a_s, a_i = self.plain(n, k)
-        if not self.groups:                              # nothing reserved: the plain list
-            score_out.copy_(a_s)
-            id_out.copy_(a_i)
-            return
-        g_s, g_i = self.reserved(n)
-        engine.topk_quota(a_s, a_i, g_s, g_i, self.quota, score_out, id_out)
-
-    def apply(self, engine, acts, tr, n, k, score_out, id_out):
-        """the ruled lists of the n rows whose logits `acts` holds (unsharded)"""
-        a_s, a_i = self.plain(n, k)
-        engine.topk(acts, tr, k, a_s, a_i)
-        if self.groups:
-            g_s, g_i = self.reserved(n)
-            for j, g in enumerate(self.groups):
-                engine.topk_groups(acts, tr, self.m, self.labels, 1 << g, g_s[j], g_i[j])
-        self.compose(engine, n, k, score_out, id_out)
-
-
-class Diversify:
-    """A serve-time re-ranking, passed as `diversify=` to a Recommender / ShardedRecommender: greedy maximal marginal relevance.  Each
-    user's `candidates` best items (ltg_topk; default min(256, 2 k), k <= candidates <= 256) are re-ranked so that the next entry is the
-    one with the largest  lam * relevance - (1 - lam) * (largest similarity to what the list already holds)  -- relevance = the score
-    scaled to [0, 1] over the candidates, similarity = the product of the items' rows in the bf16 image of the `decoder` (W_p1t) or
-    `encoder` (W_q0) table, `cosine` or `dot` (ltg_item_pack).  lam = 1 is the plain list.  The image is packed once per run(); per chunk
-    ltg_topk at `candidates`, then ONE launch of ltg_topk_diversify: the candidates' similarity matrix never leaves the chip.  The lists
-    keep every pick's original score, so they are generally not descending.  After run(): stats() [n_users, 2] = the mean pair similarity
-    of the plain top-k list and of the diversified one."""
-
-    def __init__(self, lam, candidates=None, space="decoder", metric="cosine"):
-        self.lam = float(lam)
-        if not 0.0 <= self.lam <= 1.0:               # (NaN fails both comparisons)
-            raise ValueError("lam must be in [0, 1], got %r" % (lam,))
-        if space not in LTG_SPACE or metric not in LTG_METRIC:
-            raise ValueError("space must be decoder or encoder, metric cosine or dot")
-        self.candidates = None if candidates is None else int(candidates)
-        self.space, self.metric = space, metric
-        self.c = self.image = self.stat = None
-        self.image_lo = 0
-
-    def bind(self, engine, rows, k, n_users, parts=0):
-        """buffers for chunks of up to `rows` users, lists of k entries and a table of n_users; parts > 0: also the all-gather buffers of
-        that many ranks"""
-        c = min(256, 2 * k) if self.candidates is None else self.candidates
-        if not k <= c <= 256:
-            raise ValueError("candidates must be in [k, 256] = [%d, 256], got %d" % (k, c))
-        self.c = c
-        dev = engine.device
-        self.cand_s = torch.empty(rows * c, dtype=torch.float32, device=dev)
-        self.cand_i = torch.empty(rows * c, dtype=torch.int32, device=dev)
-        self.stat = torch.zeros(n_users, 2, dtype=torch.float32, device=dev)
-        if parts:
-            self.loc_s = torch.empty(rows * c, dtype=torch.float32, device=dev)
-            self.loc_i = torch.empty(rows * c, dtype=torch.int32, device=dev)
-            self.part_s = torch.empty(parts * rows * c, dtype=torch.float32, device=dev)
-            self.part_i = torch.empty(parts * rows * c, dtype=torch.int32, device=dev)
-
-    def pack(self, engine, group=None):
-        """the image of the whole catalogue, once per run().  group given (item shards): every rank packs its slab into a zeroed
-        [I_global, 608] buffer at its item_lo, and the buffer is all-reduced viewed as int32 -- exactly one rank contributes each row."""
-        if group is None and engine.I == engine.I_global:
-            self.image = engine.item_pack(self.space, self.metric, out=self.image)
-            return
-        import torch.distributed as dist
-        if self.image is None:
-            self.image = torch.empty(engine.I_global, 608, dtype=torch.int16, device=engine.device)
-        self.image.zero_()
-        engine.item_pack(self.space, self.metric, out=self.image[engine.item_lo:engine.item_hi])
-        dist.all_reduce(self.image.view(torch.int32), op=dist.ReduceOp.SUM, group=group)
-
-    def candidates_of(self, n):
-        """where the chunk's candidate lists go: ([n, candidates] scores, ids)"""
-        return self.cand_s[: n * self.c].view(n, self.c), self.cand_i[: n * self.c].view(n, self.c)
-
-    def rerank(self, engine, n, k, lo, score_out, id_out):
-        """candidates_of(n) -> the diversified lists of users lo .. lo + n"""
-        c_s, c_i = self.candidates_of(n)
-        engine.topk_diversify(self.image, self.image_lo, c_s, c_i, self.lam, k, score_out, id_out, self.stat[lo:lo + n])
-
-    def apply(self, engine, acts, tr, n, k, lo, score_out, id_out):
-        """the diversified lists of the n rows whose logits `acts` holds (unsharded)"""
-        c_s, c_i = self.candidates_of(n)
-        engine.topk(acts, tr, self.c, c_s, c_i)
-        self.rerank(engine, n, k, lo, score_out, id_out)
-
-    def stats(self):
-        """-> [n_users, 2] float32 host array: mean pair similarity of the first k candidates, and of the list"""
-        return self.stat.cpu().numpy()
-
-
-class Recommender:
-    """Top-K recommendations per user (the forward of Evaluator, then ltg_topk instead of the metrics): the same chunks of
-    `chunk` users capped by eval_chunk_rows, the same dropout-on forward (Q3) with counter rng_step + lo per chunk, fold-in
-    items excluded.  keep_prob = 1.0 gives dropout-free, deterministic recommendations.  report: a LongTailReport to fill from
-    each chunk's lists (k >= its largest cutoff); absent, nothing else runs.  rule: a MinSlots the lists are to satisfy (the report then
-    reads the ruled lists); absent, the plain top-K.  diversify: a Diversify the lists are re-ranked by (the report then reads the
-    diversified lists); not together with rule."""
-
-    def __init__(self, engine: Engine, ev: EvalData, k=100, chunk=20000, report=None, rule=None, diversify=None):
-        self.eng, self.ev, self.k, self.report, self.rule, self.diversify = engine, ev, int(k), report, rule, diversify
-        if rule is not None and diversify is not None:
-            raise ValueError("diversify= and rule= cannot be combined")
-        if report is not None:
-            report.bind(engine, ev.n, self.k)
-        self.chunk = int(min(chunk, max(1, ev.n), eval_chunk_rows(engine.I)))
-        if rule is not None:
-            rule.bind(engine, self.chunk, self.k)
-        if diversify is not None:
-            diversify.bind(engine, self.chunk, self.k, ev.n)
-        self.acts = engine.new_acts(self.chunk)
-        dev = engine.device
-        self.scores = torch.empty(ev.n, self.k, dtype=torch.float32, device=dev)
-        self.ids = torch.empty(ev.n, self.k, dtype=torch.int32, device=dev)
-
-    def run(self, rng_step=0, keep_prob=0.75):
-        """-> (ids [n_users, k] int32 global item ids, scores [n_users, k] float32 logits) as host arrays"""
-        eng, ev = self.eng, self.ev
-        if self.report is not None:
-            self.report.item_hits.zero_()
-        if self.diversify is not None:
-            self.diversify.pack(eng)
-        for lo in range(0, ev.n, self.chunk):
-            hi = min(ev.n, lo + self.chunk)
-            tr, te = ev.rows(lo, hi)
-            eng.forward(tr, self.acts, keep_prob=keep_prob, is_training=0.0, rng_step=rng_step + lo)
-            if self.diversify is not None:
-                self.diversify.apply(eng, self.acts, tr, hi - lo, self.k, lo, self.scores[lo:hi], self.ids[lo:hi])
-            elif self.rule is None:
-                eng.topk(self.acts, tr, self.k, self.scores[lo:hi], self.ids[lo:hi])
-            else:
-                self.rule.apply(eng, self.acts, tr, hi - lo, self.k, self.scores[lo:hi], self.ids[lo:hi])
-            if self.report is not None:
-                self.report.add(eng, self.ids[lo:hi], te, lo)
-        return self.ids.cpu().numpy(), self.scores.cpu().numpy()
-
-
-def group_mask_of(only, n_groups):
-    """the group_mask of ltg_topk_groups / ltg_item_neighbors that admits the group indices `only` (None: every group)"""
-    if only is None:
-        return 0x1FF
-    mask = 0
-    for g in only:
-        if not 0 <= int(g) < int(n_groups):
-            raise ValueError("group index %r outside [0, %d)" % (g, n_groups))
-        mask |= 1 << min(int(g), 8)
-    if mask == 0:
-        raise ValueError("`only` admits no group")
-    return mask
-
-
-def neighbors_ws_bytes(ws_bytes, n_q, chunk, k):
-    """the workspace for walking n_q queries in chunks of `chunk`: the largest need over the chunk lengths that occur.  ws_bytes(n, k) =
-    ltg_item_neighbors_ws_bytes.  It is NOT monotone in n: fewer query blocks get more item segments (the grid is sized to fill the chip),
-    so a shorter last chunk can need more than a full one -- 3 392 queries more than 4 096 at 200 000 items."""
-    n_q, chunk = int(n_q), max(1, int(chunk))
-    sizes = {min(chunk, n_q)} | ({n_q % chunk} if n_q > chunk else set())
-    return max([int(ws_bytes(n, k)) for n in sizes if n > 0] + [1])
-
-
-class ItemNeighbors:
-    """The k nearest items of items (ltg_item_neighbors): space `decoder` (rows of W_p1t) or `encoder` (rows of W_q0), metric `cosine` or
-    `dot`; a query never returns itself.  labels (uint8 per global item id, longtail.build_groups) + only (group indices) restrict the
-    NEIGHBOURS to those groups -- `only=[niche]` over the popular items is the niche shelf of every head item.  The table is packed once
-    into the bf16 operand image; the queries are walked in chunks of `chunk`, their rows taken out of the image by index.  The scores
-    stay on the chip: the workspace is lists."""
-
-    def __init__(self, engine: Engine, k=20, space="decoder", metric="cosine", labels=None, n_groups=None, only=None, chunk=4096):
-        self.eng, self.k, self.space, self.metric, self.chunk = engine, int(k), space, metric, max(1, int(chunk))
-        dev = engine.device
-        self.labels = None
-        self.mask = 0x1FF
-        if labels is not None:
-            self.labels = torch.as_tensor(np.ascontiguousarray(labels, dtype=np.uint8)).to(dev)
-            self.mask = group_mask_of(only, n_groups if n_groups is not None else int(self.labels.max().item()) + 1)
-        elif only is not None:
-            raise ValueError("`only` needs labels")
-        self.image = None
-
-    def pack(self):
-        self.image = self.eng.item_pack(self.space, self.metric, out=self.image)
-        return self.image
-
-    def _queries(self, query_ids):
-        n_glob = self.eng.cfg.n_items_global or self.eng.I
-        q = np.arange(n_glob, dtype=np.int32) if query_ids is None else np.ascontiguousarray(query_ids, dtype=np.int32).reshape(-1)
-        if q.size and (q.min() < 0 or q.max() >= n_glob):
-            raise ValueError("query ids outside [0, %d)" % n_glob)
-        return q
-
-    def query_rows(self, gid):
-        """the image rows of the global ids gid (a device int32 tensor)"""
-        return self.image.index_select(0, gid.long())
-
-    def run(self, query_ids=None):
-        """-> (ids [n_q, k] int32 global item ids, scores [n_q, k] float32) as host arrays; query_ids None = every item"""
-        eng, k = self.eng, self.k
-        dev = eng.device
-        q = self._queries(query_ids)
-        self.pack()
-        ids = torch.empty(len(q), k, dtype=torch.int32, device=dev)
-        scores = torch.empty(len(q), k, dtype=torch.float32, device=dev)
-        qd = torch.from_numpy(q).to(dev)
-        ws = torch.empty(neighbors_ws_bytes(eng.item_neighbors_ws_bytes, len(q), self.chunk, k), dtype=torch.uint8, device=dev)
-        for lo in range(0, len(q), self.chunk):
-            hi = min(len(q), lo + self.chunk)
-            eng.item_neighbors(self.image, self.query_rows(qd[lo:hi]), qd[lo:hi], k, scores[lo:hi], ids[lo:hi], self.labels, self.mask, ws=ws)
-        return ids.cpu().numpy(), scores.cpu().numpy()

@@ -63,6 +63,7 @@ class _FakeEngine:
 
 
 def test_diversify_validation():
+    from ltgan.serving import SlabLists
     from ltgan.trainer import Diversify, Recommender
     for lam in (-0.1, 1.1, float("nan")):
         with pytest.raises(ValueError):
@@ -77,8 +78,10 @@ def test_diversify_validation():
     d.bind(_FakeEngine(), 10, 200, 33)
     assert d.c == 256                                                   # min(256, 2 k)
     d = Diversify(0.25, candidates=64, space="encoder", metric="dot")
-    d.bind(_FakeEngine(), 10, 64, 5, parts=3)
-    assert d.c == 64 and d.part_s.numel() == 3 * 10 * 64 and (d.space, d.metric) == ("encoder", "dot")
+    d.bind(_FakeEngine(), 10, 64, 5)
+    assert d.c == 64 and (d.space, d.metric) == ("encoder", "dot")
+    lists = SlabLists(_FakeEngine(), rows=10, longest=64, parts=3)          # the all-gather buffers of three ranks: one set for every list
+    assert lists.part_s.numel() == lists.part_i.numel() == 3 * 10 * 64 and lists.loc_s.numel() == lists.loc_i.numel() == 10 * 64
     for k, c in ((65, 64), (10, 257), (257, None)):
         with pytest.raises(ValueError):
             Diversify(0.5, candidates=c).bind(_FakeEngine(), 10, k, 5)

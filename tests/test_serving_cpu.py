@@ -1,0 +1,25 @@
+"""The serving layer's one source of catalogue-wide lists (serving.SlabLists) and its one chunk walk (Recommender.run, shared by
+ShardedRecommender) without a GPU: a fake engine on CPU tensors records every call (tests/serving_cpu_worker.py).  Every gathered and
+merged list must equal torch.topk on the full 150-column logits on both ranks of a world-size-2 gloo run -- slabs of 128 and 22 items, a
+full chunk of 5 rows and a short last one of 3, lists of 7 and of 4 entries alternating on one set of buffers -- and the recorded
+sequence of engine calls and collectives must be the one written out in the worker for plain, ruled (two reserved groups, and none)
+and diversified lists, with and without a report, item-sharded and not."""
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_unsharded_lists_are_written_directly_and_the_calls_are_the_direct_ones():
+    import serving_cpu_worker as W
+    W.unsharded()
+
+
+def test_world_size_two_lists_and_call_sequences():
+    env = dict(os.environ, MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="1")
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
+           "--master-port", "29641", os.path.join(ROOT, "tests", "serving_cpu_worker.py")]
+    out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600)
+    assert out.returncode == 0 and "SERVING_CPU_OK" in out.stdout, out.stdout[-2000:] + out.stderr[-4000:]
+

@@ -678,6 +678,27 @@ int ltg_topk_diversify(const uint16_t* image, int32_t image_lo, int32_t image_ro
                        const float* score_in, const int32_t* id_in, float lambda, int32_t k, float* score_out, int32_t* id_out,
                        float* stat_out /* may be NULL */, ltg_stream stream);
 
+/* Item audiences: the k likeliest users of an item, selected down the columns of the row-major logits (additive in ABI v14).
+ * ltg_item_audience: per query column q_col[q] (LOCAL column of logits [n_rows][cfg->n_items]; q_col is DEVICE memory, need not be sorted
+ * or distinct -- duplicates give identical lists; the caller validates its values) the k best eligible rows of THIS chunk.  Score of
+ * (row, column) = logits[row][column] - lse[row], one fp32 subtraction (the log-probability the row's softmax gives the item); lse NULL:
+ * the raw logit.  Row r is eligible iff the column is not in r's fold-in list of tr (LOCAL ids, ascending per row, as ltg_topk takes
+ * them; tr NULL: every row is eligible); -inf scores are eligible, NaN is outside the contract.  score_out / id_out [n_q][k] exactly as
+ * ltg_topk writes a list with id = row_lo + row: score descending, equal scores lower row first, -0.0 == +0.0, padding id -1 / score
+ * -inf (n_rows < k pads), bit-identical from run to run.  The call is pure per chunk; chunks over disjoint row ranges accumulate with
+ * ltg_topk_merge (n_parts = 2: the running lists and this chunk's; n_rows = n_q; k_in = k).
+ * The logits are read once, every request a run along a row, and are not modified; the [n_rows][n_q] scores are never written anywhere.
+ * The workspace (ltg_item_audience_ws_bytes; 0 for arguments the call refuses, and 0 when the chunk is walked as one row segment: ws may
+ * then be NULL) holds one list per (row segment, query) -- segments x n_q x k (score, id) pairs, at most 32 segments.
+ * 1 <= k <= LTG_AUD_MAX_K.  LTG_EINVAL before any HIP call: cfg / logits / q_col / score_out / id_out NULL, k out of range, n_rows, n_q
+ * or row_lo negative, row_lo + n_rows > INT32_MAX, a tr whose n_rows differs from the call's or that lacks indptr / indices, a workspace
+ * that is NULL or too small when one is needed.  n_rows = 0 or n_q = 0 launches nothing and returns LTG_OK. */
+#define LTG_AUD_MAX_K 256
+size_t ltg_item_audience_ws_bytes(const ltg_config* cfg, int32_t n_rows, int32_t n_q, int32_t k);
+int ltg_item_audience(const ltg_config* cfg, const float* logits, const float* lse /* [n_rows] or NULL */, const ltg_batch* tr /* or NULL */,
+                      int32_t n_rows, int32_t row_lo, const int32_t* q_col, int32_t n_q, int32_t k, float* score_out, int32_t* id_out,
+                      void* ws, size_t ws_bytes, ltg_stream stream);
+
 /* Verification helper of the LTG_PREC_FP8 mode: out[i] = the value the fp8 GEMM operands carry for in[i]
  * (clamp to +-448, round to nearest-even OCP e4m3) -- lets a test pin its CPU model of the rounding to the hardware. */
 int ltg_fp8_roundtrip(const float* in, float* out, int32_t n, ltg_stream stream);

@@ -172,6 +172,7 @@ __global__ __launch_bounds__(64) void k_gate_set(LtgGate g, LtgGate g2 = LTG_NO_
 #include "ltg_clock.h"
 #include "ltg_sampler.h"
 #include "ltg_topk.h"
+#include "ltg_audience.h"
 #include "ltg_longtail.h"
 #include "ltg_neighbors.h"
 #include "ltg_diversify.h"
@@ -1929,6 +1930,60 @@ int ltg_item_neighbors(const ltg_config* cfg, const uint16_t* table_image, const
 #undef LTG_NBR
     if (hipGetLastError() != hipSuccess) return LTG_ELAUNCH;
     hipLaunchKernelGGL(k_topk_merge, dim3(n_q), dim3(NT), 0, (hipStream_t)stream, nseg, n_q, k, ws_score, ws_id, k, score_out, id_out);
+    return check_launch();
+}
+
+// Item audiences.  The segmentation is a function of (n_rows, n_q, k) alone, so ltg_item_audience_ws_bytes and the call agree:
+// enough (column block x row segment) workgroups for four per CU, a segment at least 1 024 rows, at most 32 segments (the merge of a
+// column's segment lists stays short).  One segment needs no workspace: the kernel writes the outputs itself.
+static int aud_blocks(int n_q, int k) {
+    const int cols = k <= 128 ? 16 : 8;
+    return (int)(((int64_t)n_q + cols - 1) / cols);
+}
+static int aud_plan(int n_rows, int n_q, int k, int* seg_len) {
+    const int nqb = aud_blocks(n_q, k);
+    int64_t want = (1024 + (int64_t)nqb - 1) / nqb;
+    const int64_t most = ((int64_t)n_rows + 1023) / 1024 < 32 ? ((int64_t)n_rows + 1023) / 1024 : 32;
+    want = want > most ? most : want;
+    const int64_t len = (((int64_t)n_rows + want - 1) / want + AU_ROWS - 1) / AU_ROWS * AU_ROWS;
+    *seg_len = (int)(len < 0x7FFFFF80 ? len : 0x7FFFFF80);
+    return (int)(((int64_t)n_rows + *seg_len - 1) / *seg_len);
+}
+static bool aud_args_ok(const ltg_config* cfg, int32_t n_rows, int32_t n_q, int32_t k) {
+    return cfg && cfg->n_items > 0 && n_rows >= 0 && n_q >= 0 && k >= 1 && k <= LTG_AUD_MAX_K;
+}
+
+size_t ltg_item_audience_ws_bytes(const ltg_config* cfg, int32_t n_rows, int32_t n_q, int32_t k) {
+    if (!aud_args_ok(cfg, n_rows, n_q, k) || n_rows == 0 || n_q == 0) return 0;
+    int seg_len;
+    const int nseg = aud_plan(n_rows, n_q, k, &seg_len);
+    return nseg > 1 ? align_up((size_t)nseg * (size_t)n_q * (size_t)k * (sizeof(float) + sizeof(int32_t))) : 0;
+}
+
+int ltg_item_audience(const ltg_config* cfg, const float* logits, const float* lse, const ltg_batch* tr, int32_t n_rows, int32_t row_lo,
+                      const int32_t* q_col, int32_t n_q, int32_t k, float* score_out, int32_t* id_out, void* ws, size_t ws_bytes,
+                      ltg_stream stream) {
+    if (!aud_args_ok(cfg, n_rows, n_q, k) || !logits || !q_col || !score_out || !id_out || row_lo < 0 ||
+        (int64_t)row_lo + (int64_t)n_rows > (int64_t)INT32_MAX)
+        return LTG_EINVAL;
+    if (tr && (!tr->indptr || !tr->indices || tr->n_rows != n_rows)) return LTG_EINVAL;
+    const size_t need = ltg_item_audience_ws_bytes(cfg, n_rows, n_q, k);
+    if (need > 0 && (!ws || ws_bytes < need)) return LTG_EINVAL;
+    if (n_rows == 0 || n_q == 0) return LTG_OK;
+    int seg_len;
+    const int nseg = aud_plan(n_rows, n_q, k, &seg_len);
+    float* list_s = nseg > 1 ? (float*)ws : score_out;
+    int32_t* list_i = nseg > 1 ? (int32_t*)((float*)ws + (size_t)nseg * n_q * k) : id_out;
+    clear_errors();
+#define LTG_AUD(COLS, CAP)                                                                                                              \
+    hipLaunchKernelGGL((k_item_audience<COLS, CAP>), dim3(aud_blocks(n_q, k), nseg), dim3(AU_NT), (size_t)COLS * CAP * 8,                     \
+                       (hipStream_t)stream, cfg->n_items, n_rows, row_lo, n_q, seg_len, k, logits, lse,                                   \
+                       tr ? tr->indptr : (const int32_t*)nullptr, tr ? tr->indices : (const int32_t*)nullptr, q_col, list_s, list_i)
+    if (k <= 128) LTG_AUD(16, 256); else LTG_AUD(8, 512);
+#undef LTG_AUD
+    if (nseg == 1) return check_launch();
+    if (hipGetLastError() != hipSuccess) return LTG_ELAUNCH;
+    hipLaunchKernelGGL(k_topk_merge, dim3(n_q), dim3(NT), 0, (hipStream_t)stream, nseg, n_q, k, list_s, list_i, k, score_out, id_out);
     return check_launch();
 }
 

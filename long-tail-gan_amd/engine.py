@@ -854,6 +854,33 @@ class Engine:
                                                int(group_mask), int(k), _ptr(score_out), _ptr(id_out), _ptr(ws), ws.numel(), self.stream()),
                    "ltg_item_neighbors")
 
+    # ------------------------------------------------------------------ item audiences
+    def item_audience_ws_bytes(self, n_rows, n_q, k):
+        return int(self.lib.ltg_item_audience_ws_bytes(C.byref(self.cfg), int(n_rows), int(n_q), int(k)))
+
+    def item_audience(self, logits_or_acts, lse, tr, row_lo, q_col, k, score_out, id_out, ws=None, n_rows=None):
+        """the k likeliest rows of this chunk for every query column: logits (an Acts or a [rows, I] float32 tensor) of tr.n_rows rows
+        (tr: a CsrRows with LOCAL ids whose fold-in items make a row ineligible for that column, or None; the row count is n_rows if
+        given, else tr's, lse's or the logits'), lse [rows] float32 or None (None: the raw logit is the score, else logit - lse), q_col [n_q] int32 LOCAL columns on
+        the device -> score_out [n_q, k] float32, id_out [n_q, k] int32 = row_lo + row, ordered and padded as topk writes them
+        (ltg_item_audience).  ws: a uint8 tensor of item_audience_ws_bytes(rows, n_q, k) bytes (allocated when absent)."""
+        logits = logits_or_acts.logits if isinstance(logits_or_acts, Acts) else logits_or_acts
+        n_q = int(q_col.numel())
+        n = int(n_rows) if n_rows is not None else int(tr.n_rows) if tr is not None else int(lse.numel()) if lse is not None else int(logits.shape[0])
+        assert tr is None or int(tr.n_rows) == n
+        assert logits.dtype == torch.float32 and logits.is_contiguous() and logits.numel() >= n * self.I
+        assert lse is None or (lse.dtype == torch.float32 and lse.is_contiguous() and lse.numel() >= n)
+        assert q_col.dtype == torch.int32 and q_col.is_contiguous() and q_col.dim() == 1
+        assert tuple(score_out.shape) == tuple(id_out.shape) == (n_q, k) and score_out.is_contiguous() and id_out.is_contiguous()
+        assert score_out.dtype == torch.float32 and id_out.dtype == torch.int32
+        need = self.item_audience_ws_bytes(n, n_q, k)
+        if ws is None:
+            ws = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
+        assert ws.dtype == torch.uint8 and ws.numel() >= need
+        cabi.check(self.lib.ltg_item_audience(C.byref(self.cfg), _ptr(logits), _ptr(lse), C.byref(tr.c) if tr is not None else None, n,
+                                              int(row_lo), _ptr(q_col), n_q, int(k), _ptr(score_out), _ptr(id_out), _ptr(ws), ws.numel(),
+                                              self.stream()), "ltg_item_audience")
+
     # ------------------------------------------------------------------ views in the reference's shapes
     def generator_params_tf(self):
         """The 8 tensors in the reference's order and TF shapes (MultiVAE.py:129-141); W_p1 is a

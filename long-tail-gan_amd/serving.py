@@ -1,5 +1,6 @@
 """Everything that serves a trained model: validation / test scoring, top-K lists (plain, with minimum slots per item group, diversified),
-the long-tail report read off them, similar-item lists, and the set-up the four CLIs (test.py, recommend.py, longtail.py, similar.py) share.
+the long-tail report read off them, similar-item lists, item audiences (the k likeliest users of an item, gathered over the same chunk
+walk), and the set-up the CLIs (test.py, recommend.py, longtail.py, similar.py, audience.py) share.
 
 One chunk walk (Recommender.run) serves every kind of list, unsharded and over item shards: the forward sits behind one method that
 ShardedRecommender overrides, and every catalogue-wide list comes from one SlabLists, which alone knows whether the catalogue is cut
@@ -308,20 +309,102 @@ class Diversify:
         return self.stat.cpu().numpy()
 
 
+class Audience:
+    """The item audiences a Recommender / ShardedRecommender gathers when it is passed as `audience=`: for every query item (GLOBAL ids,
+    any order, repeats allowed) the k users of the split with the largest score -- `logprob`: logit - lse, the log-probability the user's
+    softmax gives the item, comparable across users; `logit`: the raw logit -- among the users whose fold-in row does not hold the item.
+    Lists are ltg_topk's with "id" = user row (score descending, ties lower row first, padding -1 / -inf).  Per chunk: ONE
+    ltg_item_audience on the chunk's logits (they stay where the forward left them, and no score matrix is written), then ONE
+    ltg_topk_merge of [running lists, chunk lists].  The kernel is given the columns in ascending order, so that neighbouring lanes read
+    neighbouring columns; table() undoes that.  Over item shards every rank serves the queries whose column it owns, from the full-row lse
+    (ShardedRecommender._forward combines it), and table() all-reduces the lists so that every rank ends with the whole table."""
+
+    MAX_K = 256                                      # LTG_AUD_MAX_K
+
+    def __init__(self, items, k=100, score="logprob"):
+        self.items = np.ascontiguousarray(np.asarray(items), dtype=np.int32).reshape(-1)
+        self.k = int(k)
+        if not 1 <= self.k <= self.MAX_K:
+            raise ValueError("k must be in [1, %d], got %d" % (self.MAX_K, self.k))
+        if score not in ("logprob", "logit"):
+            raise ValueError("score must be logprob or logit")
+        self.score = score
+        self.group, self.sharded = None, False
+        self.q_col = self.where = self.pair_s = self.pair_i = self.out_s = self.out_i = self.ws = None
+
+    @property
+    def needs_lse(self):
+        return self.score == "logprob"
+
+    def bind(self, engine, rows, n_users, group=None, sharded=False):
+        """buffers for chunks of up to `rows` users of a split of n_users; sharded: the engine holds one item slab of the ranks of `group`"""
+        q, k, dev = self.items, self.k, engine.device
+        if q.size and (q.min() < 0 or q.max() >= engine.I_global):
+            raise ValueError("query ids outside [0, %d)" % engine.I_global)
+        self.group, self.sharded = group, bool(sharded)
+        lo = engine.item_lo if self.sharded else 0
+        mine = np.nonzero((q >= lo) & (q < lo + engine.I))[0]
+        mine = mine[np.argsort(q[mine], kind="stable")]          # this rank's queries, columns ascending
+        n = int(mine.size)
+        self.where = torch.from_numpy(mine.astype(np.int64)).to(dev)     # list j of this rank = row where[j] of the table
+        self.q_col = torch.from_numpy((q[mine] - lo).astype(np.int32)).to(dev)
+        self.pair_s = torch.empty(2, n, k, dtype=torch.float32, device=dev)   # [running lists, this chunk's lists]: ltg_topk_merge's parts
+        self.pair_i = torch.empty(2, n, k, dtype=torch.int32, device=dev)
+        self.out_s = torch.empty(n, k, dtype=torch.float32, device=dev)
+        self.out_i = torch.empty(n, k, dtype=torch.int32, device=dev)
+        need = neighbors_ws_bytes(lambda r, kk: engine.item_audience_ws_bytes(r, n, kk), n_users, rows, k)
+        self.ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        self.reset()
+
+    def reset(self):
+        """empty running lists: the start of a run()"""
+        self.pair_s[0].fill_(float("-inf"))
+        self.pair_i[0].fill_(-1)
+
+    def add(self, engine, acts, tr, n, lo):
+        """users lo .. lo + n, whose logits (and lse) `acts` holds, into the running lists"""
+        if self.q_col.numel() == 0:
+            return
+        engine.item_audience(acts, acts.lse if self.needs_lse else None, tr, lo, self.q_col, self.k, self.pair_s[1], self.pair_i[1],
+                             ws=self.ws, n_rows=n)
+        engine.topk_merge(self.pair_s, self.pair_i, self.k, self.out_s, self.out_i)     # (never in place: the merge scatters)
+        self.pair_s[0].copy_(self.out_s)
+        self.pair_i[0].copy_(self.out_i)
+
+    def table(self):
+        """-> (ids [n_q, k] int32 user rows, scores [n_q, k] float32) host arrays, row r = query items[r].  Over item shards: every rank
+        writes its own queries' lists into zeroed buffers, which are all-reduced viewed as int32 -- exactly one rank contributes a row."""
+        n_q, k, dev = int(self.items.size), self.k, self.pair_s.device
+        ids = torch.zeros(n_q, k, dtype=torch.int32, device=dev)
+        scores = torch.zeros(n_q, k, dtype=torch.float32, device=dev)
+        if self.where.numel():
+            ids[self.where] = self.pair_i[0]
+            scores[self.where] = self.pair_s[0]
+        if self.sharded:
+            dist.all_reduce(ids, op=dist.ReduceOp.SUM, group=self.group)
+            dist.all_reduce(scores.view(torch.int32), op=dist.ReduceOp.SUM, group=self.group)
+        return ids.cpu().numpy(), scores.cpu().numpy()
+
+
 class Recommender:
     """Top-K recommendations per user (the forward of Evaluator, then ltg_topk instead of the metrics): the same chunks of
     `chunk` users capped by eval_chunk_rows, the same dropout-on forward (Q3) with counter rng_step + lo per chunk, fold-in
     items excluded.  keep_prob = 1.0 gives dropout-free, deterministic recommendations.  report: a LongTailReport to fill from
     each chunk's lists (k >= its largest cutoff); absent, nothing else runs.  rule: a MinSlots the lists are to satisfy (the report then
     reads the ruled lists); absent, the plain top-K.  diversify: a Diversify the lists are re-ranked by (the report then reads the
-    diversified lists); not together with rule.  Every list comes out of one SlabLists (self.lists)."""
+    diversified lists); not together with rule.  Every list comes out of one SlabLists (self.lists).  audience: an Audience to gather
+    from each chunk's logits, right after the forward (audience.table() after run()); k = 0 then walks the chunks without user lists --
+    run() returns [n_users, 0] arrays and no list kernel is launched."""
 
     sharded = False                                  # ShardedRecommender: one rank of `group` per item slab
 
-    def __init__(self, engine, ev, k=100, chunk=20000, report=None, rule=None, diversify=None, group=None):
+    def __init__(self, engine, ev, k=100, chunk=20000, report=None, rule=None, diversify=None, group=None, audience=None):
         if rule is not None and diversify is not None:
             raise ValueError("diversify= and rule= cannot be combined")
+        if int(k) == 0 and (report is not None or rule is not None or diversify is not None):
+            raise ValueError("k = 0 serves no user lists: report=, rule= and diversify= need k >= 1")
         self.eng, self.ev, self.k, self.report, self.rule, self.diversify, self.group = engine, ev, int(k), report, rule, diversify, group
+        self.audience = audience
         if report is not None:
             report.bind(engine, ev.n, self.k)
         self.chunk = chunk_rows(engine, ev, chunk)
@@ -333,6 +416,8 @@ class Recommender:
             diversify.bind(engine, self.chunk, self.k, ev.n)
             longest = max(longest, diversify.c)
         self.lists = SlabLists(engine, self.chunk, longest, group, dist.get_world_size(group) if self.sharded else 1)
+        if audience is not None:
+            audience.bind(engine, self.chunk, ev.n, group=group, sharded=self.sharded)
         self.acts = engine.new_acts(self.chunk)
         dev = engine.device
         self.scores = torch.empty(ev.n, self.k, dtype=torch.float32, device=dev)
@@ -350,11 +435,17 @@ class Recommender:
             self.report.item_hits.zero_()
         if self.diversify is not None:
             self.diversify.pack(eng, group=self.group)
+        if self.audience is not None:
+            self.audience.reset()
         for lo in range(0, ev.n, self.chunk):
             hi = min(ev.n, lo + self.chunk)
             n = hi - lo
             tr, te = ev.rows(lo, hi)
             self._forward(tr, n, keep_prob, rng_step + lo)
+            if self.audience is not None:
+                self.audience.add(eng, self.acts, tr, n, lo)
+            if k == 0:                                   # no user lists: the walk serves the audience alone
+                continue
             if self.diversify is not None:
                 self.diversify.apply(self.lists, self.acts, tr, n, k, lo, self.scores[lo:hi], self.ids[lo:hi])
             elif self.rule is not None:
@@ -375,12 +466,22 @@ class ShardedRecommender(Recommender):
 
     sharded = True
 
-    def __init__(self, engine, ev, k=100, group=None, chunk=20000, report=None, rule=None, diversify=None):
-        super().__init__(engine, ev, k=k, chunk=chunk, report=report, rule=rule, diversify=diversify, group=group)
+    def __init__(self, engine, ev, k=100, group=None, chunk=20000, report=None, rule=None, diversify=None, audience=None):
+        super().__init__(engine, ev, k=k, chunk=chunk, report=report, rule=rule, diversify=diversify, group=group, audience=audience)
         self.rowpart = torch.zeros(self.chunk * 5, dtype=torch.float32, device=engine.device)
+        self.rowpart_all = None
+        if audience is not None and audience.needs_lse:
+            self.rowpart_all = torch.zeros(dist.get_world_size(group) * self.chunk * 5, dtype=torch.float32, device=engine.device)
 
     def _forward(self, tr, n, keep_prob, rng_step):
+        """the slab's logits; with an audience that ranks by log-probability also the FULL-row lse in acts.lse: the slabs' row partials
+        are all-gathered and combined (ltg_rowstats_combine, as ShardedTrainer.create_phase does) -- one more small collective per chunk"""
         sharded_forward(self.eng, tr, n, self.acts, self.rowpart, keep_prob, rng_step, self.group)
+        if self.rowpart_all is not None:
+            R, m = dist.get_world_size(self.group), n * 5
+            out = self.rowpart_all[: R * m]
+            dist.all_gather([out[r * m:(r + 1) * m] for r in range(R)], self.rowpart[:m], group=self.group)
+            self.eng.rowstats_combine(out, R, n, self.acts.lse)
 
 
 def group_mask_of(only, n_groups):
@@ -496,7 +597,7 @@ class ShardedItemNeighbors(ItemNeighbors):
         return ids.cpu().numpy(), scores.cpu().numpy()
 
 
-# ---------------------------------------------------------------- what the four CLIs share (test.py, recommend.py, longtail.py, similar.py)
+# ---------------------------------------------------------------- what the CLIs share (test.py, recommend.py, longtail.py, similar.py, audience.py)
 class _Counters:
     """load_checkpoint also restores the trainer's counters; the serving flows have no trainer."""
     update_count = 0.0

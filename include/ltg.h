@@ -699,6 +699,29 @@ int ltg_item_audience(const ltg_config* cfg, const float* logits, const float* l
                       int32_t n_rows, int32_t row_lo, const int32_t* q_col, int32_t n_q, int32_t k, float* score_out, int32_t* id_out,
                       void* ws, size_t ws_bytes, ltg_stream stream);
 
+/* Why a user got a list entry: per (user row, entry) the r history items of that user nearest to the entry (additive in ABI v14;
+ * DESIGN 5.14).  image [image_rows][608] bf16 as ltg_item_pack writes it, row i = GLOBAL id image_lo + i (16-byte aligned).  id_in
+ * [n_rows][k_in]: lists as ltg_topk / ltg_topk_merge / ltg_topk_quota / ltg_topk_diversify write them; the first `top` entries of every
+ * row are explained, 1 <= top <= min(k_in, LTG_WHY_MAX_TOP).  tr: the fold-in rows of the same users (tr->n_rows == n_rows, indptr absolute
+ * offsets, ids ascending per row, values ignored); the GLOBAL id of a history item is hist_lo + indices[...] -- on an item-sharded rank
+ * hist_lo = cfg->item_lo and tr holds the slab's part of the history.
+ * Per (row u, entry e < top) with g = id_in[u][e]: the candidates are the history items h of row u whose global id lies inside
+ * [image_lo, image_lo + image_rows) and differs from g; the score of h = the fp32 accumulator of the 19-step v_mfma_f32_16x16x32_bf16
+ * chain over the image rows of g and h, K blocks ascending (a score of ltg_item_neighbors, never rounded; it depends neither on where
+ * a row is staged nor on the slab the history item came from).  score_out / id_out [n_rows][top][r]: entry (u, e) holds the r best
+ * candidates exactly as ltg_item_neighbors writes a list -- score descending, equal scores lower GLOBAL id first, -0.0 == +0.0, padding
+ * id -1 / score -inf.  A g outside the image (padding -1 included) gets r paddings and, unlike ltg_topk_diversify, does not end the row.
+ * No id, of the list or of the history, indexes the image unchecked.  Viewed as [n_rows * top][r] the outputs are ltg_topk-format lists:
+ * per-slab outputs go straight into ltg_topk_merge (n_rows = n_rows * top, k_in = k = r).
+ * One launch, one workgroup per row, the top x history scores stay in LDS; no workspace, no atomics, bit-identical from run to run.
+ * LTG_EINVAL before any HIP call: image / tr / tr->indptr / tr->indices / id_in / score_out / id_out NULL, tr->n_rows != n_rows,
+ * n_rows < 0, k_in outside [1, 1024], top outside [1, min(k_in, 256)], r outside [1, 8], image_rows < 1, image_lo < 0, hist_lo < 0, image
+ * not 16-byte aligned; n_rows = 0 returns LTG_OK and launches nothing. */
+#define LTG_WHY_MAX_TOP 256
+#define LTG_WHY_MAX_R 8
+int ltg_topk_explain(const uint16_t* image, int32_t image_lo, int32_t image_rows, const ltg_batch* tr, int32_t hist_lo, int32_t n_rows,
+                     int32_t k_in, const int32_t* id_in, int32_t top, int32_t r, float* score_out, int32_t* id_out, ltg_stream stream);
+
 /* Verification helper of the LTG_PREC_FP8 mode: out[i] = the value the fp8 GEMM operands carry for in[i]
  * (clamp to +-448, round to nearest-even OCP e4m3) -- lets a test pin its CPU model of the rounding to the hardware. */
 int ltg_fp8_roundtrip(const float* in, float* out, int32_t n, ltg_stream stream);

@@ -176,6 +176,7 @@ __global__ __launch_bounds__(64) void k_gate_set(LtgGate g, LtgGate g2 = LTG_NO_
 #include "ltg_longtail.h"
 #include "ltg_neighbors.h"
 #include "ltg_diversify.h"
+#include "ltg_explain.h"
 
 // ---------------------------------------------------------------------------------------------
 // host side
@@ -2002,6 +2003,26 @@ int ltg_topk_diversify(const uint16_t* image, int32_t image_lo, int32_t image_ro
     else if (c_in <= 128) LTG_DIV(8);
     else LTG_DIV(16);
 #undef LTG_DIV
+    return check_launch();
+}
+
+// Why a user got a list entry: one launch, no workspace.  Every refusal comes before the first HIP call.
+int ltg_topk_explain(const uint16_t* image, int32_t image_lo, int32_t image_rows, const ltg_batch* tr, int32_t hist_lo, int32_t n_rows,
+                     int32_t k_in, const int32_t* id_in, int32_t top, int32_t r, float* score_out, int32_t* id_out, ltg_stream stream) {
+    if (!image || !tr || !tr->indptr || !tr->indices || !id_in || !score_out || !id_out || n_rows < 0 || tr->n_rows != n_rows || k_in < 1 ||
+        k_in > 1024 || top < 1 || top > k_in || top > LTG_WHY_MAX_TOP || r < 1 || r > LTG_WHY_MAX_R || image_rows < 1 || image_lo < 0 ||
+        hist_lo < 0 || ((uintptr_t)image % 16) != 0)
+        return LTG_EINVAL;
+    if (n_rows == 0) return LTG_OK;
+    clear_errors();
+#define LTG_WHY(CT)                                                                                                                        \
+    hipLaunchKernelGGL((k_topk_explain<CT>), dim3(n_rows), dim3(EX_NT), (size_t)(CT + EX_HB / 16) * 1024 + (size_t)EX_HB * (CT * 16 + 4) * 4, \
+                       (hipStream_t)stream, image, image_lo, image_rows, tr->indptr, tr->indices, hist_lo, k_in, id_in, top, r, score_out, \
+                       id_out)
+    if (top <= 64) LTG_WHY(4);
+    else if (top <= 128) LTG_WHY(8);
+    else LTG_WHY(16);
+#undef LTG_WHY
     return check_launch();
 }
 

@@ -805,6 +805,21 @@ class Engine:
                                                float(lam), int(k), _ptr(score_out), _ptr(id_out), _ptr(stat_out), self.stream()),
                    "ltg_topk_diversify")
 
+    def topk_explain(self, image, image_lo, tr, id_in, top, r, score_out, id_out):
+        """why the lists hold their entries: image [rows, 608] int16 (item_pack; row i = GLOBAL id image_lo + i), tr the fold-in rows of
+        the same users (a CsrRows with this slab's LOCAL ids), id_in [n, k_in] int32 lists as topk / topk_merge / topk_quota /
+        topk_diversify write them -> score_out / id_out [n, top, r]: per entry e < top the r history items of its user nearest to it,
+        ordered and padded as item_neighbors writes a list (ltg_topk_explain; an entry outside the image gets r paddings)"""
+        n, k_in = (int(x) for x in id_in.shape)
+        assert image.dtype == torch.int16 and image.is_contiguous() and image.dim() == 2 and int(image.shape[1]) == 608
+        assert tuple(score_out.shape) == tuple(id_out.shape) == (n, int(top), int(r))
+        assert score_out.dtype == torch.float32 and score_out.is_contiguous()
+        for t in (id_in, id_out):
+            assert t.dtype == torch.int32 and t.is_contiguous()
+        cabi.check(self.lib.ltg_topk_explain(_ptr(image), int(image_lo), int(image.shape[0]), C.byref(tr.c), int(self.item_lo), n, k_in,
+                                             _ptr(id_in), int(top), int(r), _ptr(score_out), _ptr(id_out), self.stream()),
+                   "ltg_topk_explain")
+
     def topk_metrics(self, ids, te, labels, n_groups, out, item_hits, k_ndcg=100, k_r1=20, k_r2=50, k_exp=100):
         """the long-tail report of ids [rows, k_in] int32 (as topk / topk_merge write them) against the held-out rows `te` (a CsrRows,
         GLOBAL ids): out [rows, n_groups + 1, 4] float32 = {ndcg, recall@k_r1, recall@k_r2, valid} per item group and for all items

@@ -4,6 +4,7 @@
     cd <dir holding config.ini> && python <repo>/long-tail-gan_amd/recommend.py <dataset_dir> <checkpoint>
         [--k 100] [--split test|validation] [--keep-prob 0.75] [--out recs.tsv] [--npz recs.npz]
         [--groups niche|pop:N] [--min-slots NAME:M[,NAME:M...]] [--diversify LAMBDA] [--candidates N] [--div-space decoder|encoder]
+        [--explain R] [--explain-top N] [--explain-space decoder|encoder] [--explain-metric cosine|dot] [--why why.tsv]
 
 restores a checkpoint written by train.py, runs test.py's forward over the users of `<split>_tr.csv` (chunks of 20 000 users,
 dropout on with keep_prob 0.75 by default: Q3, RNG counter 2*10^9 + first row of the chunk) and keeps each user's k best items, the
@@ -23,6 +24,13 @@ minimum claims.  `--min-slots niche:100` with --k 100 is a shelf of niche items 
 LAMBDA * relevance - (1 - LAMBDA) * (largest cosine similarity to the entries already chosen), similarity between the rows of the decoder
 table (--div-space encoder: W_q0's).  N defaults to min(256, 2 k) and must lie in [k, 256].  The lists are written in pick order, and one
 more line follows the summary: `ils@k: <before> -> <after>`, the mean pair similarity inside the plain and the diversified lists.
+
+--explain R (1 <= R <= 8) explains the first --explain-top N entries (default min(k, 256)) of every list, whichever kind it is, on the GPU
+(trainer.Explain: one ltg_topk_explain per chunk): the R items of the user's fold-in history nearest to the entry, by the cosine (or
+--explain-metric dot) of their rows in the decoder table (--explain-space encoder: W_q0's), as similar.py ranks neighbours.  --why
+(default why.tsv) gets one line per user and explained entry, `uid<TAB>sid<TAB>hsid:score,hsid:score,...`, best first, in recs.tsv's id
+spaces; --npz also stores why_ids / why_scores [users, N, R] (padding id -1 / score -inf).  One more stdout line follows:
+`why@N: <explained entries> entries, <history items named> reasons`.
 """
 from __future__ import annotations
 
@@ -56,6 +64,11 @@ def parse_args(argv):
     ap.add_argument("--groups", default="niche")
     ap.add_argument("--min-slots", default=None)
     lt.add_diversify_args(ap)
+    ap.add_argument("--explain", type=int, default=None, metavar="R")
+    ap.add_argument("--explain-top", type=int, default=None, metavar="N")
+    ap.add_argument("--explain-space", choices=("decoder", "encoder"), default=None)
+    ap.add_argument("--explain-metric", choices=("cosine", "dot"), default=None)
+    ap.add_argument("--why", default=None)
     a = ap.parse_args(argv)
     if not 1 <= a.k <= 1024:
         ap.error("--k must be in [1, 1024]")
@@ -69,11 +82,21 @@ def parse_args(argv):
     except ValueError as e:
         ap.error(str(e))
     lt.check_diversify_args(ap, a, a.k)
+    if a.explain is None:
+        if a.explain_top is not None or a.explain_space is not None or a.explain_metric is not None or a.why is not None:
+            ap.error("--explain-top, --explain-space, --explain-metric and --why need --explain")
+    else:
+        if not 1 <= a.explain <= 8:
+            ap.error("--explain takes R in [1, 8]")
+        if a.explain_top is not None and not 1 <= a.explain_top <= min(a.k, 256):
+            ap.error("--explain-top must be in [1, min(k, 256)] = [1, %d]" % min(a.k, 256))
+        a.why = a.why or "why.tsv"
     return a
 
 
-def write_recs(ids, scores, uid_start, tsv_path=None, npz_path=None):
-    """ids / scores [n_users, k] (padding id -1 dropped from the TSV); row r is uid uid_start + r; the ids are the CSV's sids."""
+def write_recs(ids, scores, uid_start, tsv_path=None, npz_path=None, why=None):
+    """ids / scores [n_users, k] (padding id -1 dropped from the TSV); row r is uid uid_start + r; the ids are the CSV's sids.
+    why: (why_ids, why_scores) of an Explain, stored in the npz as well."""
     ids = np.asarray(ids)
     uids = np.arange(ids.shape[0], dtype=np.int64) + int(uid_start)
     if tsv_path:
@@ -81,8 +104,29 @@ def write_recs(ids, scores, uid_start, tsv_path=None, npz_path=None):
             for u, row in zip(uids.tolist(), ids.tolist()):
                 f.write("%d\t%s\n" % (u, ",".join(str(i) for i in row if i >= 0)))
     if npz_path:
-        np.savez(npz_path, uids=uids, ids=ids.astype(np.int32), scores=np.asarray(scores, np.float32))
+        extra = {} if why is None else dict(why_ids=np.asarray(why[0], np.int32), why_scores=np.asarray(why[1], np.float32))
+        np.savez(npz_path, uids=uids, ids=ids.astype(np.int32), scores=np.asarray(scores, np.float32), **extra)
     return uids
+
+
+def write_why(why_ids, why_scores, ids, uid_start, tsv_path):
+    """why_ids / why_scores [n_users, top, r] (Explain.table()), ids [n_users, k] the lists they explain: one line per user and explained
+    entry, `uid<TAB>sid<TAB>hsid:score,...` best first; padding is left out -- a padding entry has no line, a padding reason no field.
+    -> (lines written, reasons written)"""
+    why_ids, why_scores, ids = np.asarray(why_ids), np.asarray(why_scores), np.asarray(ids)
+    n_lines = n_reasons = 0
+    with open(tsv_path, "w") as f:
+        for u in range(why_ids.shape[0]):
+            for e in range(why_ids.shape[1]):
+                sid = int(ids[u, e])
+                if sid < 0:
+                    continue
+                keep = why_ids[u, e] >= 0
+                f.write("%d\t%d\t%s\n" % (int(uid_start) + u, sid, ",".join(
+                    "%d:%.6g" % (int(h), float(x)) for h, x in zip(why_ids[u, e][keep].tolist(), why_scores[u, e][keep].tolist()))))
+                n_lines += 1
+                n_reasons += int(keep.sum())
+    return n_lines, n_reasons
 
 
 def long_tail_summary(ids, niche, n_items, te=None, k_recall=20):
@@ -113,7 +157,7 @@ def summary_line(m, k):
 
 def recommend(args, h0_size, h1_size, h2_size, h3_size, LEARNING_RATE, precision="bf16", batch_size_test=20000, **_):
     from ltgan.dataset import EvalData
-    from ltgan.serving import Diversify, MinSlots, Recommender, ShardedRecommender, close_model, open_model
+    from ltgan.serving import Diversify, Explain, MinSlots, Recommender, ShardedRecommender, close_model, open_model
     d = args.dataset_dir
     eng, lo, hi, rank, world, print = open_model(d, args.checkpoint, (h0_size, h1_size, h2_size, h3_size), LEARNING_RATE, precision)  # noqa: A001
     n_items = eng.I_global
@@ -127,18 +171,25 @@ def recommend(args, h0_size, h1_size, h2_size, h3_size, LEARNING_RATE, precision
     div = None
     if getattr(args, "diversify", None) is not None:
         div = Diversify(args.diversify, candidates=args.candidates, space=args.div_space)
+    why = None
+    if getattr(args, "explain", None) is not None:
+        why = Explain(args.explain, top=args.explain_top, space=args.explain_space or "decoder", metric=args.explain_metric or "cosine")
     if world > 1:
         rec = ShardedRecommender(eng, EvalData(tr, te, eng.device, item_lo=lo, item_hi=hi), k=args.k, chunk=batch_size_test, rule=rule,
-                                 diversify=div)
+                                 diversify=div, explain=why)
     else:
-        rec = Recommender(eng, EvalData(tr, te, eng.device), k=args.k, chunk=batch_size_test, rule=rule, diversify=div)
+        rec = Recommender(eng, EvalData(tr, te, eng.device), k=args.k, chunk=batch_size_test, rule=rule, diversify=div, explain=why)
     ids, scores = rec.run(rng_step=RNG_STEP, keep_prob=args.keep_prob)
     m = long_tail_summary(ids, niche, n_items, te)
+    why_tab = why.table() if why is not None else None
     if rank == 0:
-        write_recs(ids, scores, uid0, args.out, args.npz)
+        write_recs(ids, scores, uid0, args.out, args.npz, why=why_tab)
     print(summary_line(m, args.k))
     if div is not None:
         print(lt.ils_line(div.stats(), ids, args.k))
+    if why is not None:
+        n_lines, n_reasons = write_why(why_tab[0], why_tab[1], ids, uid0, args.why) if rank == 0 else (0, 0)
+        print("why@%d: %d entries, %d reasons" % (why.top, n_lines, n_reasons))
     close_model(world)
     return ids, scores, m
 

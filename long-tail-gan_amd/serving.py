@@ -1,6 +1,6 @@
 """Everything that serves a trained model: validation / test scoring, top-K lists (plain, with minimum slots per item group, diversified),
-the long-tail report read off them, similar-item lists, item audiences (the k likeliest users of an item, gathered over the same chunk
-walk), and the set-up the CLIs (test.py, recommend.py, longtail.py, similar.py, audience.py) share.
+the long-tail report read off them, the explanation of every list entry (the user's history items nearest to it), similar-item lists,
+item audiences (the k likeliest users of an item, gathered over the same chunk walk), and the set-up the CLIs (test.py, recommend.py, longtail.py, similar.py, audience.py) share.
 
 One chunk walk (Recommender.run) serves every kind of list, unsharded and over item shards: the forward sits behind one method that
 ShardedRecommender overrides, and every catalogue-wide list comes from one SlabLists, which alone knows whether the catalogue is cut
@@ -249,6 +249,20 @@ class MinSlots:
         lists.eng.topk_quota(a_s, a_i, g_s, g_i, self.quota, score_out, id_out)
 
 
+def catalogue_image(engine, space, metric, image=None, group=None):
+    """-> the bf16 operand image [I_global, 608] int16 of the WHOLE catalogue (ltg_item_pack), written into `image` when one is given.
+    Over item shards every rank packs its slab into a zeroed buffer at its item_lo, and the buffer is all-reduced viewed as int32 --
+    exactly one rank contributes each row."""
+    if group is None and engine.I == engine.I_global:
+        return engine.item_pack(space, metric, out=image)
+    if image is None:
+        image = torch.empty(engine.I_global, 608, dtype=torch.int16, device=engine.device)
+    image.zero_()
+    engine.item_pack(space, metric, out=image[engine.item_lo:engine.item_hi])
+    dist.all_reduce(image.view(torch.int32), op=dist.ReduceOp.SUM, group=group)
+    return image
+
+
 class Diversify:
     """A serve-time re-ranking, passed as `diversify=` to a Recommender / ShardedRecommender: greedy maximal marginal relevance.  Each
     user's `candidates` best items (ltg_topk; default min(256, 2 k), k <= candidates <= 256) are re-ranked so that the next entry is the
@@ -285,14 +299,7 @@ class Diversify:
     def pack(self, engine, group=None):
         """the image of the whole catalogue, once per run().  group given (item shards): every rank packs its slab into a zeroed
         [I_global, 608] buffer at its item_lo, and the buffer is all-reduced viewed as int32 -- exactly one rank contributes each row."""
-        if group is None and engine.I == engine.I_global:
-            self.image = engine.item_pack(self.space, self.metric, out=self.image)
-            return
-        if self.image is None:
-            self.image = torch.empty(engine.I_global, 608, dtype=torch.int16, device=engine.device)
-        self.image.zero_()
-        engine.item_pack(self.space, self.metric, out=self.image[engine.item_lo:engine.item_hi])
-        dist.all_reduce(self.image.view(torch.int32), op=dist.ReduceOp.SUM, group=group)
+        self.image = catalogue_image(engine, self.space, self.metric, self.image, group)
 
     def candidates_of(self, n):
         """where the chunk's candidate lists go: ([n, candidates] scores, ids)"""
@@ -307,6 +314,65 @@ class Diversify:
     def stats(self):
         """-> [n_users, 2] float32 host array: mean pair similarity of the first k candidates, and of the list"""
         return self.stat.cpu().numpy()
+
+
+class Explain:
+    """Why a user got each list entry, passed as `explain=` to a Recommender / ShardedRecommender: for the first `top` entries of every
+    user's list (default min(k, 256)) the r items of that user's fold-in history nearest to the entry -- "because you interacted with X
+    and Y".  Nearness is ItemNeighbors': the product of the two items' rows in the bf16 image of the `decoder` (W_p1t) or `encoder` (W_q0)
+    table, `cosine` or `dot`; an entry never explains itself.  The image is packed once per run() (a Diversify of the same space and
+    metric shares its image); per chunk ONE launch of ltg_topk_explain on whatever list is served -- plain, ruled or diversified -- and
+    the top x history scores never leave the chip.  Over item shards every rank explains from its slab's part of the histories, and the
+    SlabLists gathers and merges the [n * top, r] lists: every rank ends with the table of the unsharded run, bit for bit.
+    After run(): why_i / why_s [n_users, top, r] on the device (ids are GLOBAL item ids, ordered and padded as ltg_topk writes a
+    list); table() brings both to the host."""
+
+    MAX_TOP, MAX_R = 256, 8                          # LTG_WHY_MAX_TOP, LTG_WHY_MAX_R
+
+    def __init__(self, r=3, top=None, space="decoder", metric="cosine"):
+        self.r = int(r)
+        if not 1 <= self.r <= self.MAX_R:
+            raise ValueError("r must be in [1, %d], got %r" % (self.MAX_R, r))
+        self.top_arg = None if top is None else int(top)
+        if self.top_arg is not None and not 1 <= self.top_arg <= self.MAX_TOP:
+            raise ValueError("top must be in [1, %d], got %r" % (self.MAX_TOP, top))
+        if space not in LTG_SPACE or metric not in LTG_METRIC:
+            raise ValueError("space must be decoder or encoder, metric cosine or dot")
+        self.space, self.metric = space, metric
+        self.top = self.image = self.why_s = self.why_i = None
+        self.image_lo = 0
+
+    def bind(self, engine, k, n_users):
+        """the device tables for lists of k entries and a split of n_users"""
+        top = min(k, self.MAX_TOP) if self.top_arg is None else self.top_arg
+        if not 1 <= top <= min(k, self.MAX_TOP):
+            raise ValueError("top must be in [1, min(k, %d)] = [1, %d], got %d" % (self.MAX_TOP, min(k, self.MAX_TOP), top))
+        if not 1 <= self.r <= self.MAX_R:
+            raise ValueError("r must be in [1, %d], got %d" % (self.MAX_R, self.r))
+        self.top = top
+        dev = engine.device
+        self.why_s = torch.empty(n_users, top, self.r, dtype=torch.float32, device=dev)
+        self.why_i = torch.empty(n_users, top, self.r, dtype=torch.int32, device=dev)
+
+    def pack(self, engine, group=None, share=None):
+        """the image of the whole catalogue, once per run(); share: a Diversify whose image (already packed for this run) is the same"""
+        if share is not None and (share.space, share.metric) == (self.space, self.metric):
+            self.image = share.image
+        else:
+            self.image = catalogue_image(engine, self.space, self.metric, self.image, group)
+
+    def apply(self, lists, tr, n, lo, ids):
+        """the explanations of users lo .. lo + n, whose final lists are ids [n, k]; lists: the SlabLists whose buffers the per-slab
+        explanations are gathered through"""
+        top, r = self.top, self.r
+        out_s, out_i = self.why_s[lo:lo + n].view(n * top, r), self.why_i[lo:lo + n].view(n * top, r)
+        ls, li = lists.local(n * top, r, out_s, out_i)
+        lists.eng.topk_explain(self.image, self.image_lo, tr, ids, top, r, ls.view(n, top, r), li.view(n, top, r))
+        lists.merge(ls, li, out_s, out_i)
+
+    def table(self):
+        """-> (ids [n_users, top, r] int32 global item ids, scores [n_users, top, r] float32) host arrays"""
+        return self.why_i.cpu().numpy(), self.why_s.cpu().numpy()
 
 
 class Audience:
@@ -394,17 +460,20 @@ class Recommender:
     reads the ruled lists); absent, the plain top-K.  diversify: a Diversify the lists are re-ranked by (the report then reads the
     diversified lists); not together with rule.  Every list comes out of one SlabLists (self.lists).  audience: an Audience to gather
     from each chunk's logits, right after the forward (audience.table() after run()); k = 0 then walks the chunks without user lists --
-    run() returns [n_users, 0] arrays and no list kernel is launched."""
+    run() returns [n_users, 0] arrays and no list kernel is launched.  explain: an Explain filled from each chunk's final lists, whichever
+    kind they are (explain.table() after run()); needs k >= 1."""
 
     sharded = False                                  # ShardedRecommender: one rank of `group` per item slab
 
-    def __init__(self, engine, ev, k=100, chunk=20000, report=None, rule=None, diversify=None, group=None, audience=None):
+    def __init__(self, engine, ev, k=100, chunk=20000, report=None, rule=None, diversify=None, group=None, audience=None, explain=None):
         if rule is not None and diversify is not None:
             raise ValueError("diversify= and rule= cannot be combined")
         if int(k) == 0 and (report is not None or rule is not None or diversify is not None):
             raise ValueError("k = 0 serves no user lists: report=, rule= and diversify= need k >= 1")
+        if int(k) == 0 and explain is not None:
+            raise ValueError("k = 0 serves no user lists: explain= needs k >= 1")
         self.eng, self.ev, self.k, self.report, self.rule, self.diversify, self.group = engine, ev, int(k), report, rule, diversify, group
-        self.audience = audience
+        self.audience, self.explain = audience, explain
         if report is not None:
             report.bind(engine, ev.n, self.k)
         self.chunk = chunk_rows(engine, ev, chunk)
@@ -415,6 +484,9 @@ class Recommender:
         if diversify is not None:
             diversify.bind(engine, self.chunk, self.k, ev.n)
             longest = max(longest, diversify.c)
+        if explain is not None:
+            explain.bind(engine, self.k, ev.n)
+            longest = max(longest, explain.top * explain.r)          # (its per-slab lists are [rows * top, r])
         self.lists = SlabLists(engine, self.chunk, longest, group, dist.get_world_size(group) if self.sharded else 1)
         if audience is not None:
             audience.bind(engine, self.chunk, ev.n, group=group, sharded=self.sharded)
@@ -435,6 +507,8 @@ class Recommender:
             self.report.item_hits.zero_()
         if self.diversify is not None:
             self.diversify.pack(eng, group=self.group)
+        if self.explain is not None:
+            self.explain.pack(eng, group=self.group, share=self.diversify)
         if self.audience is not None:
             self.audience.reset()
         for lo in range(0, ev.n, self.chunk):
@@ -454,6 +528,8 @@ class Recommender:
                 self.lists.topk(self.acts, tr, n, k, self.scores[lo:hi], self.ids[lo:hi])
             if self.report is not None:
                 self.report.add(eng, self.ids[lo:hi], te, lo)
+            if self.explain is not None:
+                self.explain.apply(self.lists, tr, n, lo, self.ids[lo:hi])
         return self.ids.cpu().numpy(), self.scores.cpu().numpy()
 
 
@@ -462,12 +538,14 @@ class ShardedRecommender(Recommender):
     `group`, so that every list -- plain, reserved, candidates -- is this slab's list, gathered and merged (ltg_topk_merge).  Every rank
     ends with the identical table, bit-identical to the unsharded Recommender's; the lists a report reads are identical on every rank, so
     the report (item_hits included) needs no exchange, and neither do ltg_topk_quota and ltg_topk_diversify (against the image of the
-    whole catalogue, Diversify.pack: one all-reduce per run())."""
+    whole catalogue, Diversify.pack: one all-reduce per run()).  An Explain sees this slab's part of every history: its per-slab
+    explanations are one more gathered and merged list per chunk."""
 
     sharded = True
 
-    def __init__(self, engine, ev, k=100, group=None, chunk=20000, report=None, rule=None, diversify=None, audience=None):
-        super().__init__(engine, ev, k=k, chunk=chunk, report=report, rule=rule, diversify=diversify, group=group, audience=audience)
+    def __init__(self, engine, ev, k=100, group=None, chunk=20000, report=None, rule=None, diversify=None, audience=None, explain=None):
+        super().__init__(engine, ev, k=k, chunk=chunk, report=report, rule=rule, diversify=diversify, group=group, audience=audience,
+                         explain=explain)
         self.rowpart = torch.zeros(self.chunk * 5, dtype=torch.float32, device=engine.device)
         self.rowpart_all = None
         if audience is not None and audience.needs_lse:

@@ -722,6 +722,41 @@ int ltg_item_audience(const ltg_config* cfg, const float* logits, const float* l
 int ltg_topk_explain(const uint16_t* image, int32_t image_lo, int32_t image_rows, const ltg_batch* tr, int32_t hist_lo, int32_t n_rows,
                      int32_t k_in, const int32_t* id_in, int32_t top, int32_t r, float* score_out, int32_t* id_out, ltg_stream stream);
 
+/* Calibrated top-K lists: every user's list follows the class mix of that user's fold-in history (additive in ABI v14).
+ * Classes: C = n_groups + 1, the class of an item = min(label, n_groups), the last class is "in no group"; 1 <= n_groups <= 8.
+ *
+ * ltg_hist_groups: count_out[u][c] (int32 [n_rows][C], WRITTEN, not added to) = the history items of row u whose GLOBAL id hist_lo +
+ * indices[..] lies in [0, n_items_global) and whose class is c (item_group: uint8 per GLOBAL id); an id outside that range counts nowhere
+ * and indexes nothing.  tr: the fold-in rows as ltg_topk_explain takes them (tr->n_rows == n_rows, indptr absolute, values ignored); on an
+ * item-sharded rank hist_lo = cfg->item_lo, tr holds the slab's part of the histories and the host adds the counts (one int32 all-reduce).
+ * One wave per row, no atomics, no workspace.  LTG_EINVAL before any HIP call: tr / indptr / indices / item_group / count_out NULL,
+ * tr->n_rows != n_rows, n_rows < 0, hist_lo < 0, n_items_global < 1, n_groups outside [1, 8].
+ *
+ * ltg_topk_calibrate: score_grp / id_grp [n_lists][n_rows][m_in] = one ltg_topk_groups list per class that has one (the layout of
+ * ltg_topk_quota's reserved lists; padding id < 0 ends a list; a non-padding entry with a non-finite score is outside the contract;
+ * lists of different classes hold disjoint ids); list_class (HOST, read before the call returns) = their classes, strictly ascending in
+ * [0, n_groups]; hist [n_rows][C] as ltg_hist_groups writes it (a class without a list has no candidates, its history still counts).
+ * Per row, with h = the row of hist, H = sum h, n = the non-padding entries over all lists, kk = min(k, n):
+ *   plain list = the first kk entries of the merge of the lists in ltg_topk's order; s_hi / s_lo its first / last score;
+ *     rel(s) = (s - s_lo) / (s_hi - s_lo), two fp32 subtractions and one IEEE fp32 division; 0 for every s when s_hi == s_lo;
+ *   tv of a list of m entries with class counts n_c = (float)((double)D / (double)(2 H m)), D = sum_c |h_c m - n_c H| (int64); 0 if H == 0;
+ *   round t = 0 .. kk - 1 picks, among the heads of the lists not used up, the one with the largest
+ *     obj = a * rel(s) - lambda * tv(list so far plus one entry of the head's class, m = t + 1),  a = 1 - lambda in fp32, two fp32 products
+ *     and one subtraction, never contracted; equal objectives: the head that comes first in ltg_topk's order.
+ * score_out / id_out [n_rows][k]: the picks in pick order, every one with its original score bit for bit (generally not descending), padded
+ * with id -1 / score -inf.  stat_out ([n_rows][2], may be NULL) = {tv of the plain list, tv of the output}; both 0 when H == 0 or kk == 0.
+ * lambda = 0 is the plain list.  One launch, no workspace, no atomics, bit-identical from run to run; ids never index anything; the outputs
+ * must not alias the inputs.  LTG_EINVAL before any HIP call: a NULL pointer (stat_out and stream excepted), n_groups outside [1, 8],
+ * n_lists outside [1, n_groups + 1], m_in outside [1, 1024], k outside [1, m_in], lambda outside [0, 1] or NaN, list_class not strictly
+ * ascending or out of range, n_rows < 0.  For both: n_rows = 0 returns LTG_OK and launches nothing (the arguments are still checked). */
+#define LTG_CAL_MAX_CLASSES 9
+int ltg_hist_groups(const ltg_batch* tr, int32_t hist_lo, int32_t n_rows, const uint8_t* item_group, int32_t n_items_global,
+                    int32_t n_groups, int32_t* count_out /* [n_rows][n_groups+1] */, ltg_stream stream);
+int ltg_topk_calibrate(int32_t n_rows, int32_t n_lists, int32_t m_in, const float* score_grp, const int32_t* id_grp,
+                       const int32_t* list_class /* HOST [n_lists] */, int32_t n_groups, const int32_t* hist /* device [n_rows][n_groups+1] */,
+                       float lambda, int32_t k, float* score_out, int32_t* id_out, float* stat_out /* [n_rows][2], may be NULL */,
+                       ltg_stream stream);
+
 /* Verification helper of the LTG_PREC_FP8 mode: out[i] = the value the fp8 GEMM operands carry for in[i]
  * (clamp to +-448, round to nearest-even OCP e4m3) -- lets a test pin its CPU model of the rounding to the hardware. */
 int ltg_fp8_roundtrip(const float* in, float* out, int32_t n, ltg_stream stream);

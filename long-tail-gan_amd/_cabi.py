@@ -24,6 +24,7 @@ LTG_NBR_MAX_K = 256
 LTG_AUD_MAX_K = 256                          # ltg_item_audience: the longest audience list
 LTG_DIV_MAX_C = 256                          # ltg_topk_diversify: the longest candidate list
 LTG_WHY_MAX_TOP, LTG_WHY_MAX_R = 256, 8      # ltg_topk_explain: the entries explained per row, the history items per entry
+LTG_CAL_MAX_CLASSES = 9                      # ltg_hist_groups / ltg_topk_calibrate: n_groups + 1 classes at the most
 
 ERRORS = {0: "LTG_OK", -1: "LTG_EINVAL", -2: "LTG_EWORKSPACE", -3: "LTG_ELAUNCH"}
 
@@ -183,6 +184,9 @@ SYMBOLS = {
     "ltg_topk_diversify": (C.c_int, [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, C.c_float, C.c_int32, vp, vp, vp, vp]),
     "ltg_topk_explain": (C.c_int, [vp, C.c_int32, C.c_int32, C.POINTER(ltg_batch), C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, vp,
                                    vp, vp]),
+    "ltg_hist_groups": (C.c_int, [C.POINTER(ltg_batch), C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, vp, vp]),
+    "ltg_topk_calibrate": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, vp, vp, C.POINTER(C.c_int32), C.c_int32, vp, C.c_float, C.c_int32, vp, vp,
+                                     vp, vp]),
     "ltg_item_audience_ws_bytes": (C.c_size_t, [C.POINTER(ltg_config), C.c_int32, C.c_int32, C.c_int32]),
     "ltg_item_audience": (C.c_int, [C.POINTER(ltg_config), vp, vp, C.POINTER(ltg_batch), C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, vp, vp,
                                     vp, C.c_size_t, vp]),

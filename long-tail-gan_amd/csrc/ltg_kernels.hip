@@ -177,6 +177,7 @@ __global__ __launch_bounds__(64) void k_gate_set(LtgGate g, LtgGate g2 = LTG_NO_
 #include "ltg_neighbors.h"
 #include "ltg_diversify.h"
 #include "ltg_explain.h"
+#include "ltg_calibrate.h"
 
 // ---------------------------------------------------------------------------------------------
 // host side
@@ -2023,6 +2024,44 @@ int ltg_topk_explain(const uint16_t* image, int32_t image_lo, int32_t image_rows
     else if (top <= 128) LTG_WHY(8);
     else LTG_WHY(16);
 #undef LTG_WHY
+    return check_launch();
+}
+
+// Calibrated top-K lists: the class histogram of the histories, and the composition of class lists.  One launch each, no
+// workspace.  Every refusal comes before the first HIP call.
+int ltg_hist_groups(const ltg_batch* tr, int32_t hist_lo, int32_t n_rows, const uint8_t* item_group, int32_t n_items_global, int32_t n_groups,
+                    int32_t* count_out, ltg_stream stream) {
+    if (!tr || !tr->indptr || !tr->indices || !item_group || !count_out || n_rows < 0 || tr->n_rows != n_rows || hist_lo < 0 ||
+        n_items_global < 1 || n_groups < 1 || n_groups > LTG_CAL_MAX_CLASSES - 1)
+        return LTG_EINVAL;
+    if (n_rows == 0) return LTG_OK;
+    clear_errors();
+    hipLaunchKernelGGL(k_hist_groups, dim3((n_rows + NT / 64 - 1) / (NT / 64)), dim3(NT), 0, (hipStream_t)stream, n_rows, tr->indptr, tr->indices,
+                       hist_lo, item_group, n_items_global, n_groups, count_out);
+    return check_launch();
+}
+
+int ltg_topk_calibrate(int32_t n_rows, int32_t n_lists, int32_t m_in, const float* score_grp, const int32_t* id_grp, const int32_t* list_class,
+                       int32_t n_groups, const int32_t* hist, float lambda, int32_t k, float* score_out, int32_t* id_out, float* stat_out,
+                       ltg_stream stream) {
+    if (!score_grp || !id_grp || !list_class || !hist || !score_out || !id_out || n_rows < 0 || n_groups < 1 ||
+        n_groups > LTG_CAL_MAX_CLASSES - 1 || n_lists < 1 || n_lists > n_groups + 1 || m_in < 1 || m_in > 1024 || k < 1 || k > m_in ||
+        !(lambda >= 0.f && lambda <= 1.f))
+        return LTG_EINVAL;
+    cal_map map;
+    for (int c = 0; c < CAL_C; ++c) map.list_of[c] = -1;
+    for (int j = 0; j < n_lists; ++j) {
+        if (list_class[j] < 0 || list_class[j] > n_groups || (j > 0 && list_class[j] <= list_class[j - 1])) return LTG_EINVAL;
+        map.list_of[list_class[j]] = j;
+    }
+    if (n_rows == 0) return LTG_OK;
+    clear_errors();
+    // the lists of a wave's four rows in LDS when they leave room for five workgroups per CU, else the heads come from global memory
+    const size_t lds = (size_t)n_lists * CAL_ROWS * m_in * (sizeof(float) + sizeof(int32_t));
+    const bool stage = lds <= 32 * 1024;
+    hipLaunchKernelGGL(stage ? k_topk_calibrate<true> : k_topk_calibrate<false>, dim3((n_rows + CAL_ROWS - 1) / CAL_ROWS), dim3(64),
+                       stage ? lds : 0, (hipStream_t)stream, n_rows, n_lists, m_in, score_grp, id_grp, map, n_groups, hist, lambda, k, score_out,
+                       id_out, stat_out);
     return check_launch();
 }
 

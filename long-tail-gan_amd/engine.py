@@ -820,6 +820,35 @@ class Engine:
                                              _ptr(id_in), int(top), int(r), _ptr(score_out), _ptr(id_out), self.stream()),
                    "ltg_topk_explain")
 
+    def hist_groups(self, tr, labels, n_groups, count_out, hist_lo=None):
+        """the class histogram of the histories: tr the fold-in rows (a CsrRows with this slab's LOCAL ids; hist_lo, default this slab's
+        item_lo, makes them GLOBAL), labels uint8 per GLOBAL item id -> count_out [rows, n_groups + 1] int32, WRITTEN: the history items
+        of every row per class min(label, n_groups) (ltg_hist_groups; an id outside the catalogue counts nowhere)"""
+        n = int(count_out.shape[0])
+        assert labels.dtype == torch.uint8 and labels.is_contiguous()
+        assert count_out.dtype == torch.int32 and count_out.is_contiguous() and tuple(count_out.shape) == (n, int(n_groups) + 1)
+        cabi.check(self.lib.ltg_hist_groups(C.byref(tr.c), int(self.item_lo if hist_lo is None else hist_lo), n, _ptr(labels),
+                                            int(labels.numel()), int(n_groups), _ptr(count_out), self.stream()), "ltg_hist_groups")
+
+    def topk_calibrate(self, score_grp, id_grp, list_class, n_groups, hist, lam, k, score_out, id_out, stat_out=None):
+        """the lists whose class mix follows the histories: score_grp / id_grp [lists, rows, m_in] one topk_groups list per class that
+        has one, list_class a host sequence of their classes (strictly ascending, in [0, n_groups]), hist [rows, n_groups + 1] int32 as
+        hist_groups writes it, lam in [0, 1] the weight of calibration -> score_out / id_out [rows, k] = the picks in pick order with
+        their original scores, padded with id -1 / score -inf; stat_out (None, or [rows, 2] float32) = the miscalibration of the plain
+        list and of the output (ltg_topk_calibrate; the outputs must not alias an input)"""
+        lists, n, m_in = (int(x) for x in score_grp.shape)
+        assert tuple(id_grp.shape) == (lists, n, m_in) and len(list_class) == lists
+        assert tuple(score_out.shape) == tuple(id_out.shape) == (n, int(k))
+        assert hist.dtype == torch.int32 and hist.is_contiguous() and tuple(hist.shape) == (n, int(n_groups) + 1)
+        for t in (score_grp, score_out):
+            assert t.dtype == torch.float32 and t.is_contiguous()
+        for t in (id_grp, id_out):
+            assert t.dtype == torch.int32 and t.is_contiguous()
+        assert stat_out is None or (stat_out.dtype == torch.float32 and stat_out.is_contiguous() and tuple(stat_out.shape) == (n, 2))
+        lc = (C.c_int32 * lists)(*[int(x) for x in list_class])
+        cabi.check(self.lib.ltg_topk_calibrate(n, lists, m_in, _ptr(score_grp), _ptr(id_grp), lc, int(n_groups), _ptr(hist), float(lam),
+                                               int(k), _ptr(score_out), _ptr(id_out), _ptr(stat_out), self.stream()), "ltg_topk_calibrate")
+
     def topk_metrics(self, ids, te, labels, n_groups, out, item_hits, k_ndcg=100, k_r1=20, k_r2=50, k_exp=100):
         """the long-tail report of ids [rows, k_in] int32 (as topk / topk_merge write them) against the held-out rows `te` (a CsrRows,
         GLOBAL ids): out [rows, n_groups + 1, 4] float32 = {ndcg, recall@k_r1, recall@k_r2, valid} per item group and for all items

@@ -3,7 +3,7 @@
 
     cd <dir holding config.ini> && python <repo>/long-tail-gan_amd/longtail.py <dataset_dir> <checkpoint>
         [--split test|validation] [--groups niche|pop:N] [--min-slots NAME:M[,NAME:M...]] [--k 100] [--keep-prob 0.75] [--json report.json]
-        [--diversify LAMBDA] [--candidates N] [--div-space decoder|encoder]
+        [--diversify LAMBDA] [--candidates N] [--div-space decoder|encoder] [--calibrate LAMBDA]
 
 restores a checkpoint written by train.py, runs test.py's forward over the users of `<split>_tr.csv` ONCE (chunks of 20 000 users,
 dropout on with keep_prob 0.75 by default: Q3, RNG counter 2*10^9 + first row of the chunk), keeps each user's top-K list on the GPU
@@ -31,6 +31,13 @@ report reads it (trainer.Diversify; ltg_topk at --candidates N, then ltg_topk_di
 LAMBDA * relevance - (1 - LAMBDA) * (largest cosine similarity to the entries already chosen), similarity between the rows of the decoder
 table (--div-space encoder: W_q0's).  N defaults to min(256, 2 K) and must lie in [K, 256], K = max(100, --k) the length of the lists.
 One more line follows the report: `ils@K: <before> -> <after>`, the mean pair similarity inside the plain and the diversified lists.
+
+--calibrate LAMBDA (0 <= LAMBDA <= 1; not together with --min-slots or --diversify) composes every list so that its mix of the groups of
+--groups follows the mix of the user's own fold-in history, before the report reads it (trainer.Calibrate; one ltg_topk_groups list per
+group, ltg_hist_groups, then ltg_topk_calibrate): the next entry is the best remaining item of some group with the largest
+(1 - LAMBDA) * relevance - LAMBDA * miscalibration, miscalibration = the total-variation distance between the history's group shares and
+those of the list so far plus that item.  LAMBDA 0 is the plain list.  The last line is then `miscal@K: <before> -> <after>`, the mean
+miscalibration of the plain and of the calibrated lists over the users with a non-empty history.
 """
 from __future__ import annotations
 
@@ -118,6 +125,30 @@ def check_diversify_args(ap, a, k):
         ap.error("--candidates must be in [k, 256] = [%d, 256], got %d" % (k, a.candidates))
 
 
+def add_calibrate_args(ap):
+    """the option of the calibrated lists (trainer.Calibrate), shared with recommend.py"""
+    ap.add_argument("--calibrate", type=float, default=None, metavar="LAMBDA")
+
+
+def check_calibrate_args(ap, a):
+    """refuses (ap.error) what trainer.Calibrate would refuse, and the combination with --min-slots or --diversify"""
+    if a.calibrate is None:
+        return
+    if a.min_slots is not None or a.diversify is not None:
+        ap.error("--calibrate cannot be combined with --min-slots or --diversify")
+    if not 0.0 <= a.calibrate <= 1.0:
+        ap.error("--calibrate takes LAMBDA in [0, 1]")
+
+
+def miscal_line(stats, tr, k):
+    """the line --calibrate adds: the mean miscalibration of the plain top-k lists -> of the calibrated ones (Calibrate.stats()
+    [n_users, 2]), averaged in float64 over the users with a non-empty fold-in history (tr: the fold-in CSR, rows aligned with stats)"""
+    st = np.asarray(stats).astype(np.float64)
+    ok = np.diff(tr.tocsr().indptr) > 0
+    b, a = (float(st[ok, 0].mean()), float(st[ok, 1].mean())) if ok.any() else (float("nan"), float("nan"))
+    return "miscal@%d: %.6f -> %.6f" % (k, b, a)
+
+
 def ils_line(stats, ids, k):
     """the line --diversify adds: the mean pair similarity of the plain top-k lists -> of the diversified ones (Diversify.stats()
     [n_users, 2]), averaged in float64 over the users whose list holds at least two entries (ids [n_users, k], padding -1)"""
@@ -138,6 +169,7 @@ def parse_args(argv):
     ap.add_argument("--keep-prob", type=float, default=0.75)
     ap.add_argument("--json", default=None)
     add_diversify_args(ap)
+    add_calibrate_args(ap)
     a = ap.parse_args(argv)
     try:
         a.group_kind, a.n_groups = parse_groups(a.groups)
@@ -156,6 +188,7 @@ def parse_args(argv):
         except ValueError as e:
             ap.error(str(e))
     check_diversify_args(ap, a, max(K_NDCG, K_R1, K_R2, a.k))       # (the length of the lists: LongTailReport.k)
+    check_calibrate_args(ap, a)
     return a
 
 
@@ -251,7 +284,7 @@ def write_json(rep, path):
 
 def longtail(args, h0_size, h1_size, h2_size, h3_size, LEARNING_RATE, precision="bf16", batch_size_test=20000, **_):
     from ltgan.dataset import EvalData
-    from ltgan.serving import Diversify, LongTailReport, MinSlots, Recommender, ShardedRecommender, close_model, open_model
+    from ltgan.serving import Calibrate, Diversify, LongTailReport, MinSlots, Recommender, ShardedRecommender, close_model, open_model
     d = args.dataset_dir
     eng, lo, hi, rank, world, print = open_model(d, args.checkpoint, (h0_size, h1_size, h2_size, h3_size), LEARNING_RATE, precision)  # noqa: A001
     n_items = eng.I_global
@@ -262,11 +295,13 @@ def longtail(args, h0_size, h1_size, h2_size, h3_size, LEARNING_RATE, precision=
     div = None
     if getattr(args, "diversify", None) is not None:
         div = Diversify(args.diversify, candidates=args.candidates, space=args.div_space)
+    cal = Calibrate(labels, len(names), args.calibrate) if getattr(args, "calibrate", None) is not None else None
     if world > 1:
         rec = ShardedRecommender(eng, EvalData(tr, te, eng.device, item_lo=lo, item_hi=hi), k=report.k, chunk=batch_size_test, report=report,
-                                 rule=rule, diversify=div)
+                                 rule=rule, diversify=div, calibrate=cal)
     else:
-        rec = Recommender(eng, EvalData(tr, te, eng.device), k=report.k, chunk=batch_size_test, report=report, rule=rule, diversify=div)
+        rec = Recommender(eng, EvalData(tr, te, eng.device), k=report.k, chunk=batch_size_test, report=report, rule=rule, diversify=div,
+                          calibrate=cal)
     ids, _ = rec.run(rng_step=RNG_STEP, keep_prob=args.keep_prob)
     rep = aggregate(*report.table(), labels, names, args.k)
     rep.update(split=args.split, groups_spec=args.groups)
@@ -274,6 +309,8 @@ def longtail(args, h0_size, h1_size, h2_size, h3_size, LEARNING_RATE, precision=
         print(line)
     if div is not None:
         print(ils_line(div.stats(), ids, report.k))
+    if cal is not None:
+        print(miscal_line(cal.stats(), tr, report.k))
     if args.json and rank == 0:
         write_json(rep, args.json)
     close_model(world)

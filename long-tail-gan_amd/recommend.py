@@ -5,6 +5,7 @@
         [--k 100] [--split test|validation] [--keep-prob 0.75] [--out recs.tsv] [--npz recs.npz]
         [--groups niche|pop:N] [--min-slots NAME:M[,NAME:M...]] [--diversify LAMBDA] [--candidates N] [--div-space decoder|encoder]
         [--explain R] [--explain-top N] [--explain-space decoder|encoder] [--explain-metric cosine|dot] [--why why.tsv]
+        [--calibrate LAMBDA]
 
 restores a checkpoint written by train.py, runs test.py's forward over the users of `<split>_tr.csv` (chunks of 20 000 users,
 dropout on with keep_prob 0.75 by default: Q3, RNG counter 2*10^9 + first row of the chunk) and keeps each user's k best items, the
@@ -31,6 +32,13 @@ more line follows the summary: `ils@k: <before> -> <after>`, the mean pair simil
 (default why.tsv) gets one line per user and explained entry, `uid<TAB>sid<TAB>hsid:score,hsid:score,...`, best first, in recs.tsv's id
 spaces; --npz also stores why_ids / why_scores [users, N, R] (padding id -1 / score -inf).  One more stdout line follows:
 `why@N: <explained entries> entries, <history items named> reasons`.
+
+--calibrate LAMBDA (0 <= LAMBDA <= 1; not together with --min-slots or --diversify) composes every list on the GPU so that its mix of the
+groups of --groups follows the mix of the user's own fold-in history (trainer.Calibrate: one ltg_topk_groups list per group,
+ltg_hist_groups, then ltg_topk_calibrate): the next entry is the best remaining item of some group with the largest
+(1 - LAMBDA) * relevance - LAMBDA * miscalibration, miscalibration = the total-variation distance between the history's group shares and
+those of the list so far plus that item.  LAMBDA 0 is the plain list.  The lists are written in pick order, and the last stdout line is
+`miscal@k: <before> -> <after>`, the mean miscalibration of the plain and of the calibrated lists over the users with a non-empty history.
 """
 from __future__ import annotations
 
@@ -64,6 +72,7 @@ def parse_args(argv):
     ap.add_argument("--groups", default="niche")
     ap.add_argument("--min-slots", default=None)
     lt.add_diversify_args(ap)
+    lt.add_calibrate_args(ap)
     ap.add_argument("--explain", type=int, default=None, metavar="R")
     ap.add_argument("--explain-top", type=int, default=None, metavar="N")
     ap.add_argument("--explain-space", choices=("decoder", "encoder"), default=None)
@@ -82,6 +91,7 @@ def parse_args(argv):
     except ValueError as e:
         ap.error(str(e))
     lt.check_diversify_args(ap, a, a.k)
+    lt.check_calibrate_args(ap, a)
     if a.explain is None:
         if a.explain_top is not None or a.explain_space is not None or a.explain_metric is not None or a.why is not None:
             ap.error("--explain-top, --explain-space, --explain-metric and --why need --explain")
@@ -157,7 +167,7 @@ def summary_line(m, k):
 
 def recommend(args, h0_size, h1_size, h2_size, h3_size, LEARNING_RATE, precision="bf16", batch_size_test=20000, **_):
     from ltgan.dataset import EvalData
-    from ltgan.serving import Diversify, Explain, MinSlots, Recommender, ShardedRecommender, close_model, open_model
+    from ltgan.serving import Calibrate, Diversify, Explain, MinSlots, Recommender, ShardedRecommender, close_model, open_model
     d = args.dataset_dir
     eng, lo, hi, rank, world, print = open_model(d, args.checkpoint, (h0_size, h1_size, h2_size, h3_size), LEARNING_RATE, precision)  # noqa: A001
     n_items = eng.I_global
@@ -171,14 +181,19 @@ def recommend(args, h0_size, h1_size, h2_size, h3_size, LEARNING_RATE, precision
     div = None
     if getattr(args, "diversify", None) is not None:
         div = Diversify(args.diversify, candidates=args.candidates, space=args.div_space)
+    cal = None
+    if getattr(args, "calibrate", None) is not None:
+        labels, names = lt.build_groups(d, args.group_kind, args.n_groups, n_items)
+        cal = Calibrate(labels, len(names), args.calibrate)
     why = None
     if getattr(args, "explain", None) is not None:
         why = Explain(args.explain, top=args.explain_top, space=args.explain_space or "decoder", metric=args.explain_metric or "cosine")
     if world > 1:
         rec = ShardedRecommender(eng, EvalData(tr, te, eng.device, item_lo=lo, item_hi=hi), k=args.k, chunk=batch_size_test, rule=rule,
-                                 diversify=div, explain=why)
+                                 diversify=div, explain=why, calibrate=cal)
     else:
-        rec = Recommender(eng, EvalData(tr, te, eng.device), k=args.k, chunk=batch_size_test, rule=rule, diversify=div, explain=why)
+        rec = Recommender(eng, EvalData(tr, te, eng.device), k=args.k, chunk=batch_size_test, rule=rule, diversify=div, explain=why,
+                          calibrate=cal)
     ids, scores = rec.run(rng_step=RNG_STEP, keep_prob=args.keep_prob)
     m = long_tail_summary(ids, niche, n_items, te)
     why_tab = why.table() if why is not None else None
@@ -190,6 +205,8 @@ def recommend(args, h0_size, h1_size, h2_size, h3_size, LEARNING_RATE, precision
     if why is not None:
         n_lines, n_reasons = write_why(why_tab[0], why_tab[1], ids, uid0, args.why) if rank == 0 else (0, 0)
         print("why@%d: %d entries, %d reasons" % (why.top, n_lines, n_reasons))
+    if cal is not None:
+        print(lt.miscal_line(cal.stats(), tr, args.k))
     close_model(world)
     return ids, scores, m
 

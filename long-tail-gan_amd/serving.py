@@ -1,4 +1,5 @@
-"""Everything that serves a trained model: validation / test scoring, top-K lists (plain, with minimum slots per item group, diversified),
+"""Everything that serves a trained model: validation / test scoring, top-K lists (plain, with minimum slots per item group, diversified,
+calibrated to each user's history),
 the long-tail report read off them, the explanation of every list entry (the user's history items nearest to it), similar-item lists,
 item audiences (the k likeliest users of an item, gathered over the same chunk walk), and the set-up the CLIs (test.py, recommend.py, longtail.py, similar.py, audience.py) share.
 
@@ -316,6 +317,66 @@ class Diversify:
         return self.stat.cpu().numpy()
 
 
+class Calibrate:
+    """A serve-time re-ranking, passed as `calibrate=` to a Recommender / ShardedRecommender: calibrated recommendation (Steck, RecSys
+    2018) with the total-variation distance in place of the KL divergence.  Every user's list follows the class mix of that user's
+    fold-in history (labels: one uint8 per GLOBAL item id, the class of an item = min(label, n_groups), the last class is "in no group";
+    the labels a LongTailReport takes): greedily, the next entry is the best remaining item of some class with the largest
+    (1 - lam) * relevance - lam * (miscalibration of the list so far plus that item) -- relevance = the score scaled to [0, 1] over the
+    plain top-k list, miscalibration = half the sum over the classes of |history share - list share|.  lam = 0 is the plain list; a user
+    without a history keeps the plain list at every lam.  Per chunk: one ltg_topk_groups list of k entries per class that occurs in the
+    catalogue (so the greedy runs over the whole catalogue, not over a truncated candidate set), ltg_hist_groups on the chunk's histories,
+    then ONE launch of ltg_topk_calibrate.  The lists keep every pick's original score, so they are generally not descending.  After
+    run(): stats() [n_users, 2] = the miscalibration of the plain top-k list and of the calibrated one.  Over item shards every class
+    list is gathered and merged by the SlabLists, every rank counts its slab's part of the histories and the counts are all-reduced: no
+    logit is exchanged and every rank composes the same lists."""
+
+    def __init__(self, labels, n_groups, lam):
+        self.labels_host = np.ascontiguousarray(np.asarray(labels), dtype=np.uint8)
+        self.n_groups = int(n_groups)
+        if not 1 <= self.n_groups <= 8:
+            raise ValueError("n_groups must be in [1, 8]")
+        self.lam = float(lam)
+        if not 0.0 <= self.lam <= 1.0:               # (NaN fails both comparisons)
+            raise ValueError("lam must be in [0, 1], got %r" % (lam,))
+        self.classes = self.masks = self.labels = self.stat = None
+
+    def bind(self, engine, rows, k, n_users):
+        """buffers for chunks of up to `rows` users, lists of k entries and a table of n_users"""
+        if self.labels_host.size != engine.I_global:
+            raise ValueError("labels hold %d items, the catalogue %d" % (self.labels_host.size, engine.I_global))
+        g, dev = self.n_groups, engine.device
+        self.classes = [int(c) for c in np.unique(np.minimum(self.labels_host, g))]      # a class with no item needs no list
+        self.masks = [1 << c if c < g else (0x1FF >> g) << g for c in self.classes]       # the last class: bits n_groups .. 8
+        self.labels = torch.from_numpy(self.labels_host).to(dev)
+        n_l = len(self.classes)
+        self.grp_s = torch.empty(n_l * rows * k, dtype=torch.float32, device=dev)
+        self.grp_i = torch.empty(n_l * rows * k, dtype=torch.int32, device=dev)
+        self.hist = torch.empty(rows * (g + 1), dtype=torch.int32, device=dev)
+        self.stat = torch.zeros(n_users, 2, dtype=torch.float32, device=dev)
+
+    def class_lists(self, n, k):
+        """where the chunk's class lists go: ([classes, n, k] scores, ids), list j for class self.classes[j]"""
+        n_l = len(self.classes)
+        return self.grp_s[: n_l * n * k].view(n_l, n, k), self.grp_i[: n_l * n * k].view(n_l, n, k)
+
+    def apply(self, lists, acts, tr, n, k, lo, score_out, id_out):
+        """the calibrated lists of users lo .. lo + n, whose logits `acts` holds; lists: the SlabLists the class lists come from"""
+        eng = lists.eng
+        g_s, g_i = self.class_lists(n, k)
+        for j, mask in enumerate(self.masks):
+            lists.topk(acts, tr, n, k, g_s[j], g_i[j], self.labels, mask)
+        hist = self.hist[: n * (self.n_groups + 1)].view(n, self.n_groups + 1)
+        eng.hist_groups(tr, self.labels, self.n_groups, hist, hist_lo=eng.item_lo if lists.parts > 1 else 0)
+        if lists.parts > 1:                              # every rank counted its slab's part of the histories
+            dist.all_reduce(hist, op=dist.ReduceOp.SUM, group=lists.group)
+        eng.topk_calibrate(g_s, g_i, self.classes, self.n_groups, hist, self.lam, k, score_out, id_out, self.stat[lo:lo + n])
+
+    def stats(self):
+        """-> [n_users, 2] float32 host array: the miscalibration of the plain top-k list, and of the calibrated list"""
+        return self.stat.cpu().numpy()
+
+
 class Explain:
     """Why a user got each list entry, passed as `explain=` to a Recommender / ShardedRecommender: for the first `top` entries of every
     user's list (default min(k, 256)) the r items of that user's fold-in history nearest to the entry -- "because you interacted with X
@@ -461,19 +522,25 @@ class Recommender:
     diversified lists); not together with rule.  Every list comes out of one SlabLists (self.lists).  audience: an Audience to gather
     from each chunk's logits, right after the forward (audience.table() after run()); k = 0 then walks the chunks without user lists --
     run() returns [n_users, 0] arrays and no list kernel is launched.  explain: an Explain filled from each chunk's final lists, whichever
-    kind they are (explain.table() after run()); needs k >= 1."""
+    kind they are (explain.table() after run()); needs k >= 1.  calibrate: a Calibrate the lists are composed by (the report and the
+    explanations then read the calibrated lists); not together with rule or diversify; needs k >= 1."""
 
     sharded = False                                  # ShardedRecommender: one rank of `group` per item slab
 
-    def __init__(self, engine, ev, k=100, chunk=20000, report=None, rule=None, diversify=None, group=None, audience=None, explain=None):
+    def __init__(self, engine, ev, k=100, chunk=20000, report=None, rule=None, diversify=None, group=None, audience=None, explain=None,
+                 calibrate=None):
         if rule is not None and diversify is not None:
             raise ValueError("diversify= and rule= cannot be combined")
+        if calibrate is not None and (rule is not None or diversify is not None):
+            raise ValueError("calibrate= cannot be combined with rule= or diversify=")
+        if int(k) == 0 and calibrate is not None:
+            raise ValueError("k = 0 serves no user lists: calibrate= needs k >= 1")
         if int(k) == 0 and (report is not None or rule is not None or diversify is not None):
             raise ValueError("k = 0 serves no user lists: report=, rule= and diversify= need k >= 1")
         if int(k) == 0 and explain is not None:
             raise ValueError("k = 0 serves no user lists: explain= needs k >= 1")
         self.eng, self.ev, self.k, self.report, self.rule, self.diversify, self.group = engine, ev, int(k), report, rule, diversify, group
-        self.audience, self.explain = audience, explain
+        self.audience, self.explain, self.calibrate = audience, explain, calibrate
         if report is not None:
             report.bind(engine, ev.n, self.k)
         self.chunk = chunk_rows(engine, ev, chunk)
@@ -484,6 +551,8 @@ class Recommender:
         if diversify is not None:
             diversify.bind(engine, self.chunk, self.k, ev.n)
             longest = max(longest, diversify.c)
+        if calibrate is not None:
+            calibrate.bind(engine, self.chunk, self.k, ev.n)             # (its class lists are k long: `longest` is k already)
         if explain is not None:
             explain.bind(engine, self.k, ev.n)
             longest = max(longest, explain.top * explain.r)          # (its per-slab lists are [rows * top, r])
@@ -524,6 +593,8 @@ class Recommender:
                 self.diversify.apply(self.lists, self.acts, tr, n, k, lo, self.scores[lo:hi], self.ids[lo:hi])
             elif self.rule is not None:
                 self.rule.apply(self.lists, self.acts, tr, n, k, self.scores[lo:hi], self.ids[lo:hi])
+            elif self.calibrate is not None:
+                self.calibrate.apply(self.lists, self.acts, tr, n, k, lo, self.scores[lo:hi], self.ids[lo:hi])
             else:
                 self.lists.topk(self.acts, tr, n, k, self.scores[lo:hi], self.ids[lo:hi])
             if self.report is not None:
@@ -543,9 +614,10 @@ class ShardedRecommender(Recommender):
 
     sharded = True
 
-    def __init__(self, engine, ev, k=100, group=None, chunk=20000, report=None, rule=None, diversify=None, audience=None, explain=None):
+    def __init__(self, engine, ev, k=100, group=None, chunk=20000, report=None, rule=None, diversify=None, audience=None, explain=None,
+                 calibrate=None):
         super().__init__(engine, ev, k=k, chunk=chunk, report=report, rule=rule, diversify=diversify, group=group, audience=audience,
-                         explain=explain)
+                         explain=explain, calibrate=calibrate)
         self.rowpart = torch.zeros(self.chunk * 5, dtype=torch.float32, device=engine.device)
         self.rowpart_all = None
         if audience is not None and audience.needs_lse:

@@ -757,6 +757,42 @@ int ltg_topk_calibrate(int32_t n_rows, int32_t n_lists, int32_t m_in, const floa
                        float lambda, int32_t k, float* score_out, int32_t* id_out, float* stat_out /* [n_rows][2], may be NULL */,
                        ltg_stream stream);
 
+/* Exposure-capped top-K lists: no item appears in more than cap[item] of the served lists (additive in ABI v14).
+ * cand_score / cand_id [n_rows][c_in]: every row's c_in best items as ltg_topk / ltg_topk_merge write them (logits descending, ties lower
+ * id first, ids distinct within a row; the first id < 0 ends the row; an id >= n_items_global is skipped and never used as an index).
+ * cap [n_items_global] int32 >= 0 per GLOBAL item id.  lse [n_rows] or NULL.  1 <= k <= c_in <= 1024, n_rows * c_in < 2^31.
+ * Entry (u, j) carries the word  w = (key(s) << 32) | ((0x7FFFFFFF - u) << 1) | (s is -0.0),  s = fp32 (cand_score - lse[u]), the logit when
+ * lse is NULL, key = ltg_topk's order-preserving key: ltg_item_audience's order -- score descending, equal scores lower row first, -0.0 ==
+ * +0.0; -inf is eligible, NaN is outside the contract.  The result is the user-optimal stable many-to-many matching of user-proposing
+ * deferred acceptance, stated as the least thresholds thr[item] (words, 0 at the start) such that, with active(u) = the first k entries of
+ * row u whose cap[id] > 0 and whose word >= thr[id], no item has more than cap[item] active entries.  A round = propose (the active bytes
+ * from thr) then accept (an item with more than cap active entries raises thr to its cap-th largest active word).  Thresholds only rise, a
+ * round after convergence changes nothing, and the fixed point does not depend on the order or the batching of the rounds: lists are
+ * bit-identical from run to run.  No floating-point atomics, no sort.
+ *
+ * ltg_cap_index   once per candidate table: the per-item index of the entries (global integer atomics for the counts and the cursors only;
+ *                 nothing read from it depends on the order they leave), thr <- 0, state <- 0.
+ * ltg_cap_rounds  enqueues n_rounds rounds (1 .. LTG_CAP_MAX_ROUNDS) back to back.  The matching has converged when a round raised no
+ *                 threshold: state[4] < state[1] after a batch.  k, cap, lse and the candidates must be the same in every call of one matching.
+ * ltg_cap_finish  score_out / id_out [n_rows][k] = the active entries of every row in candidate order, each with its original logit bit for
+ *                 bit, padded with id -1 / score -inf (a row whose candidates run out gets a short list); fills state[2], state[3].
+ * state (device, int32 [LTG_CAP_STATE]): [0] threshold raises so far, [1] rounds run, [2] entries passed over (catalogue entries before a
+ * row's k-th active one -- all of them in a short row -- that are not active), [3] rows with a short list, [4] the last round that raised a
+ * threshold (0: none), [5..7] 0.  ws: ltg_cap_ws_bytes(n_rows, c_in, n_items_global) bytes, 256-byte aligned, the same buffer through
+ * index, rounds and finish.  LTG_EINVAL before any HIP call: a NULL pointer (lse and stream excepted), n_rows < 0, c_in outside [1, 1024],
+ * k outside [1, c_in], n_items_global < 1, n_rows * c_in >= 2^31, n_rounds outside [1, LTG_CAP_MAX_ROUNDS], ws_bytes too small
+ * (ltg_cap_ws_bytes returns 0 for sizes it refuses).  n_rows = 0 returns LTG_OK and launches nothing (the arguments are still checked). */
+#define LTG_CAP_STATE 8
+#define LTG_CAP_MAX_ROUNDS 64
+size_t ltg_cap_ws_bytes(int32_t n_rows, int32_t c_in, int32_t n_items_global);
+int ltg_cap_index(int32_t n_rows, int32_t c_in, const int32_t* cand_id, int32_t n_items_global, int32_t* state /* device [LTG_CAP_STATE] */,
+                  void* ws, size_t ws_bytes, ltg_stream stream);
+int ltg_cap_rounds(int32_t n_rows, int32_t c_in, const float* cand_score, const int32_t* cand_id, const float* lse /* may be NULL */,
+                   const int32_t* cap /* device [n_items_global] */, int32_t n_items_global, int32_t k, int32_t n_rounds, int32_t* state,
+                   void* ws, size_t ws_bytes, ltg_stream stream);
+int ltg_cap_finish(int32_t n_rows, int32_t c_in, const float* cand_score, const int32_t* cand_id, int32_t n_items_global, int32_t k,
+                   float* score_out, int32_t* id_out, int32_t* state, void* ws, size_t ws_bytes, ltg_stream stream);
+
 /* Verification helper of the LTG_PREC_FP8 mode: out[i] = the value the fp8 GEMM operands carry for in[i]
  * (clamp to +-448, round to nearest-even OCP e4m3) -- lets a test pin its CPU model of the rounding to the hardware. */
 int ltg_fp8_roundtrip(const float* in, float* out, int32_t n, ltg_stream stream);

@@ -173,6 +173,7 @@ __global__ __launch_bounds__(64) void k_gate_set(LtgGate g, LtgGate g2 = LTG_NO_
 #include "ltg_sampler.h"
 #include "ltg_topk.h"
 #include "ltg_audience.h"
+#include "ltg_cap.h"
 #include "ltg_longtail.h"
 #include "ltg_neighbors.h"
 #include "ltg_diversify.h"
@@ -1986,6 +1987,92 @@ int ltg_item_audience(const ltg_config* cfg, const float* logits, const float* l
     if (nseg == 1) return check_launch();
     if (hipGetLastError() != hipSuccess) return LTG_ELAUNCH;
     hipLaunchKernelGGL(k_topk_merge, dim3(n_q), dim3(NT), 0, (hipStream_t)stream, nseg, n_q, k, list_s, list_i, k, score_out, id_out);
+    return check_launch();
+}
+
+// Exposure-capped top-K lists.  The workspace holds the thresholds, the per-item index (offsets, cursors, entry numbers), one
+// active byte per candidate entry and one int32 per row; its layout is a function of (n_rows, c_in, n_items_global) alone.  Every refusal
+// comes before the first HIP call.
+struct CapWs {
+    uint64_t* thr;
+    int32_t *off, *cur, *seg, *row_over;
+    uint8_t* active;
+    size_t bytes;
+};
+static bool cap_args_ok(int32_t n_rows, int32_t c_in, int32_t n_items_global) {
+    return n_rows >= 0 && c_in >= 1 && c_in <= 1024 && n_items_global >= 1 && (int64_t)n_rows * (int64_t)c_in < ((int64_t)1 << 31);
+}
+static CapWs cap_carve(int32_t n_rows, int32_t c_in, int32_t n_items_global, char* base) {
+    const size_t I = (size_t)n_items_global, E = (size_t)n_rows * (size_t)c_in;
+    CapWs w;
+    size_t o = 0;
+    auto take = [&](size_t bytes) {                  // (no pointer arithmetic on the null base of the size query)
+        char* p = base ? base + o : nullptr;
+        o += align_up(bytes);
+        return p;
+    };
+    w.thr = (uint64_t*)take(I * sizeof(uint64_t));
+    w.off = (int32_t*)take((I + 1) * sizeof(int32_t));
+    w.cur = (int32_t*)take(I * sizeof(int32_t));
+    w.seg = (int32_t*)take((E > 0 ? E : 1) * sizeof(int32_t));
+    w.row_over = (int32_t*)take(((size_t)n_rows > 0 ? (size_t)n_rows : 1) * sizeof(int32_t));
+    w.active = (uint8_t*)take(E > 0 ? E : 1);
+    w.bytes = o;
+    return w;
+}
+
+size_t ltg_cap_ws_bytes(int32_t n_rows, int32_t c_in, int32_t n_items_global) {
+    return cap_args_ok(n_rows, c_in, n_items_global) ? cap_carve(n_rows, c_in, n_items_global, nullptr).bytes : 0;
+}
+
+int ltg_cap_index(int32_t n_rows, int32_t c_in, const int32_t* cand_id, int32_t n_items_global, int32_t* state, void* ws, size_t ws_bytes,
+                  ltg_stream stream) {
+    if (!cap_args_ok(n_rows, c_in, n_items_global) || !cand_id || !state || !ws ||
+        ws_bytes < cap_carve(n_rows, c_in, n_items_global, nullptr).bytes)
+        return LTG_EINVAL;
+    if (n_rows == 0) return LTG_OK;
+    const CapWs w = cap_carve(n_rows, c_in, n_items_global, (char*)ws);
+    const hipStream_t st = (hipStream_t)stream;
+    const int I = n_items_global, row_blocks = (n_rows + CP_NT / 64 - 1) / (CP_NT / 64);
+    clear_errors();
+    hipLaunchKernelGGL(k_cap_zero, dim3((I + CP_NT - 1) / CP_NT), dim3(CP_NT), 0, st, I, w.cur, state);
+    hipLaunchKernelGGL(k_cap_count<false>, dim3(row_blocks), dim3(CP_NT), 0, st, n_rows, c_in, cand_id, I, w.cur, (const int32_t*)w.off, w.seg);
+    hipLaunchKernelGGL(k_cap_scan, dim3(1), dim3(1024), 0, st, I, w.cur, w.off, w.thr);
+    hipLaunchKernelGGL(k_cap_count<true>, dim3(row_blocks), dim3(CP_NT), 0, st, n_rows, c_in, cand_id, I, w.cur, (const int32_t*)w.off, w.seg);
+    return check_launch();
+}
+
+int ltg_cap_rounds(int32_t n_rows, int32_t c_in, const float* cand_score, const int32_t* cand_id, const float* lse, const int32_t* cap,
+                   int32_t n_items_global, int32_t k, int32_t n_rounds, int32_t* state, void* ws, size_t ws_bytes, ltg_stream stream) {
+    if (!cap_args_ok(n_rows, c_in, n_items_global) || !cand_score || !cand_id || !cap || !state || !ws || k < 1 || k > c_in || n_rounds < 1 ||
+        n_rounds > LTG_CAP_MAX_ROUNDS || ws_bytes < cap_carve(n_rows, c_in, n_items_global, nullptr).bytes)
+        return LTG_EINVAL;
+    if (n_rows == 0) return LTG_OK;
+    const CapWs w = cap_carve(n_rows, c_in, n_items_global, (char*)ws);
+    const hipStream_t st = (hipStream_t)stream;
+    const int row_blocks = (n_rows + CP_NT / 64 - 1) / (CP_NT / 64);
+    clear_errors();
+    for (int r = 0; r < n_rounds; ++r) {
+        hipLaunchKernelGGL(k_cap_propose, dim3(row_blocks), dim3(CP_NT), 0, st, n_rows, c_in, k, cand_score, cand_id, lse, cap, n_items_global,
+                           (const uint64_t*)w.thr, w.active, state);
+        hipLaunchKernelGGL(k_cap_accept, dim3(n_items_global), dim3(CP_NT), 0, st, c_in, cand_score, lse, cap, (const int32_t*)w.off,
+                           (const int32_t*)w.seg, (const uint8_t*)w.active, w.thr, state);
+    }
+    return check_launch();
+}
+
+int ltg_cap_finish(int32_t n_rows, int32_t c_in, const float* cand_score, const int32_t* cand_id, int32_t n_items_global, int32_t k,
+                   float* score_out, int32_t* id_out, int32_t* state, void* ws, size_t ws_bytes, ltg_stream stream) {
+    if (!cap_args_ok(n_rows, c_in, n_items_global) || !cand_score || !cand_id || !score_out || !id_out || !state || !ws || k < 1 || k > c_in ||
+        ws_bytes < cap_carve(n_rows, c_in, n_items_global, nullptr).bytes)
+        return LTG_EINVAL;
+    if (n_rows == 0) return LTG_OK;
+    const CapWs w = cap_carve(n_rows, c_in, n_items_global, (char*)ws);
+    const hipStream_t st = (hipStream_t)stream;
+    clear_errors();
+    hipLaunchKernelGGL(k_cap_finish, dim3((n_rows + CP_NT / 64 - 1) / (CP_NT / 64)), dim3(CP_NT), 0, st, n_rows, c_in, k, cand_score, cand_id,
+                       n_items_global, (const uint8_t*)w.active, score_out, id_out, w.row_over);
+    hipLaunchKernelGGL(k_cap_stats, dim3(1), dim3(1024), 0, st, n_rows, k, (const int32_t*)id_out, (const int32_t*)w.row_over, state);
     return check_launch();
 }
 

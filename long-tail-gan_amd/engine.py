@@ -925,6 +925,43 @@ class Engine:
                                               int(row_lo), _ptr(q_col), n_q, int(k), _ptr(score_out), _ptr(id_out), _ptr(ws), ws.numel(),
                                               self.stream()), "ltg_item_audience")
 
+    def cap_ws_bytes(self, n_rows, c_in, n_items=None):
+        """the workspace of the exposure-capped matching of n_rows x c_in candidates over n_items (default: the catalogue) global ids"""
+        return int(self.lib.ltg_cap_ws_bytes(int(n_rows), int(c_in), int(self.I_global if n_items is None else n_items)))
+
+    def _cap_check(self, cand_s, cand_i, state, ws, n_items):
+        n, c = (int(x) for x in cand_i.shape)
+        assert cand_i.dtype == torch.int32 and cand_i.is_contiguous()
+        assert cand_s is None or (tuple(cand_s.shape) == (n, c) and cand_s.dtype == torch.float32 and cand_s.is_contiguous())
+        assert state.dtype == torch.int32 and state.is_contiguous() and state.numel() >= cabi.LTG_CAP_STATE
+        assert ws.dtype == torch.uint8 and ws.numel() >= self.cap_ws_bytes(n, c, n_items)
+        return n, c
+
+    def cap_index(self, cand_i, n_items, state, ws):
+        """the start of a matching over the candidates cand_i [rows, c] int32 (GLOBAL ids as topk / topk_merge write them): the per-item
+        index into ws, thresholds and state [LTG_CAP_STATE] int32 zeroed (ltg_cap_index)"""
+        n, c = self._cap_check(None, cand_i, state, ws, n_items)
+        cabi.check(self.lib.ltg_cap_index(n, c, _ptr(cand_i), int(n_items), _ptr(state), _ptr(ws), ws.numel(), self.stream()), "ltg_cap_index")
+
+    def cap_rounds(self, cand_s, cand_i, lse, cap, k, n_rounds, state, ws):
+        """n_rounds propose / accept rounds of the matching cap_index started: cand_s [rows, c] float32 logits, lse [rows] float32 or None
+        (None: items rank users by the logit, else by logit - lse), cap [n_items] int32 per GLOBAL id (ltg_cap_rounds).  Converged when
+        state[4] < state[1]: the last round raised no threshold."""
+        n, c = self._cap_check(cand_s, cand_i, state, ws, int(cap.numel()))
+        assert cap.dtype == torch.int32 and cap.is_contiguous()
+        assert lse is None or (lse.dtype == torch.float32 and lse.is_contiguous() and lse.numel() >= n)
+        cabi.check(self.lib.ltg_cap_rounds(n, c, _ptr(cand_s), _ptr(cand_i), _ptr(lse), _ptr(cap), int(cap.numel()), int(k), int(n_rounds),
+                                           _ptr(state), _ptr(ws), ws.numel(), self.stream()), "ltg_cap_rounds")
+
+    def cap_finish(self, cand_s, cand_i, n_items, k, score_out, id_out, state, ws):
+        """the lists of the matching as it stands: score_out / id_out [rows, k] = every row's active entries in candidate order with
+        their original logits, padded with id -1 / score -inf; state[2] / state[3] = entries passed over / short lists (ltg_cap_finish)"""
+        n, c = self._cap_check(cand_s, cand_i, state, ws, n_items)
+        assert tuple(score_out.shape) == tuple(id_out.shape) == (n, int(k)) and score_out.is_contiguous() and id_out.is_contiguous()
+        assert score_out.dtype == torch.float32 and id_out.dtype == torch.int32
+        cabi.check(self.lib.ltg_cap_finish(n, c, _ptr(cand_s), _ptr(cand_i), int(n_items), int(k), _ptr(score_out), _ptr(id_out), _ptr(state),
+                                           _ptr(ws), ws.numel(), self.stream()), "ltg_cap_finish")
+
     # ------------------------------------------------------------------ views in the reference's shapes
     def generator_params_tf(self):
         """The 8 tensors in the reference's order and TF shapes (MultiVAE.py:129-141); W_p1 is a

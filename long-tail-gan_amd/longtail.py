@@ -4,6 +4,7 @@
     cd <dir holding config.ini> && python <repo>/long-tail-gan_amd/longtail.py <dataset_dir> <checkpoint>
         [--split test|validation] [--groups niche|pop:N] [--min-slots NAME:M[,NAME:M...]] [--k 100] [--keep-prob 0.75] [--json report.json]
         [--diversify LAMBDA] [--candidates N] [--div-space decoder|encoder] [--calibrate LAMBDA]
+        [--cap C|NAME:C[,NAME:C...]] [--cap-candidates N] [--cap-score logprob|logit]
 
 restores a checkpoint written by train.py, runs test.py's forward over the users of `<split>_tr.csv` ONCE (chunks of 20 000 users,
 dropout on with keep_prob 0.75 by default: Q3, RNG counter 2*10^9 + first row of the chunk), keeps each user's top-K list on the GPU
@@ -38,6 +39,13 @@ group, ltg_hist_groups, then ltg_topk_calibrate): the next entry is the best rem
 (1 - LAMBDA) * relevance - LAMBDA * miscalibration, miscalibration = the total-variation distance between the history's group shares and
 those of the list so far plus that item.  LAMBDA 0 is the plain list.  The last line is then `miscal@K: <before> -> <after>`, the mean
 miscalibration of the plain and of the calibrated lists over the users with a non-empty history.
+
+--cap C (C >= 0: every item) or --cap NAME:C[,NAME:C...] (only the items of those groups of --groups; not together with --min-slots,
+--diversify or --calibrate) serves lists in which no item appears more than C times, before the report reads them (trainer.ExposureCap;
+ltg_topk at --cap-candidates N, then ltg_cap_index / ltg_cap_rounds / ltg_cap_finish once over the whole split): the stable matching in
+which a user prefers their N best items in order and an item prefers the users by --cap-score (logprob: logit - lse, the default; logit).
+N defaults to min(1024, 4 K) and must lie in [K, 1024], K = max(100, --k).  The last line is then
+`cap@K: max exposure <plain> -> <capped>, <items> items at their cap, <users> short lists, <rounds> rounds`.
 """
 from __future__ import annotations
 
@@ -140,6 +148,76 @@ def check_calibrate_args(ap, a):
         ap.error("--calibrate takes LAMBDA in [0, 1]")
 
 
+def parse_cap(spec, names):
+    """'C' -> C; 'NAME:C[,NAME:C...]' -> {group index: C}; an unknown name, a name twice or C < 0 raises ValueError"""
+    try:
+        c = int(spec)
+    except ValueError:
+        c = None
+    if c is not None:
+        if c < 0:
+            raise ValueError("--cap takes C >= 0, got %r" % (spec,))
+        return c
+    caps = {}
+    for part in spec.split(","):
+        name, sep, m = part.strip().rpartition(":")
+        try:
+            m = int(m) if sep else -1
+        except ValueError:
+            m = -1
+        if not sep or m < 0:
+            raise ValueError("--cap takes C or NAME:C[,NAME:C...] with C >= 0, got %r" % (part,))
+        if name not in names:
+            raise ValueError("--cap: unknown group %r (the groups are %s)" % (name, ", ".join(names)))
+        if names.index(name) in caps:
+            raise ValueError("--cap names group %r twice" % (name,))
+        caps[names.index(name)] = m
+    return caps
+
+
+def add_cap_args(ap):
+    """the options of the exposure-capped lists (trainer.ExposureCap), shared with recommend.py"""
+    ap.add_argument("--cap", default=None, metavar="C|NAME:C[,NAME:C...]")
+    ap.add_argument("--cap-candidates", type=int, default=None, metavar="N")
+    ap.add_argument("--cap-score", choices=("logprob", "logit"), default=None)
+
+
+def check_cap_args(ap, a, k):
+    """refuses (ap.error) what trainer.ExposureCap would refuse for lists of k entries, and the combination with the per-user rules;
+    a.caps = the parsed --cap (None without the option)"""
+    a.caps = None
+    if a.cap is None:
+        if a.cap_candidates is not None or a.cap_score is not None:
+            ap.error("--cap-candidates and --cap-score need --cap")
+        return
+    if a.min_slots is not None or a.diversify is not None or a.calibrate is not None:
+        ap.error("--cap cannot be combined with --min-slots, --diversify or --calibrate")
+    try:
+        a.caps = parse_cap(a.cap, group_names(a.group_kind, a.n_groups))
+    except ValueError as e:
+        ap.error(str(e))
+    if a.cap_candidates is not None and not k <= a.cap_candidates <= 1024:
+        ap.error("--cap-candidates must be in [k, 1024] = [%d, 1024], got %d" % (k, a.cap_candidates))
+
+
+def make_cap(a, labels, n_groups):
+    """the ExposureCap of the parsed options (labels: the --groups labels, needed for NAME:C)"""
+    from ltgan.serving import ExposureCap
+    cap = (labels, n_groups, a.caps) if isinstance(a.caps, dict) else a.caps
+    return ExposureCap(cap, candidates=a.cap_candidates, score=a.cap_score or "logprob")
+
+
+def cap_line(plain_ids, ids, cap_vec, stats, k):
+    """the line --cap adds: the largest number of lists one item appears in, plain top-k -> capped (plain_ids / ids [n_users, k],
+    padding -1; cap_vec: the cap per item), the items that sit exactly at their cap, the short lists and the rounds (ExposureCap.stats())"""
+    n_items = len(cap_vec)
+    before = np.bincount(plain_ids[plain_ids >= 0], minlength=n_items)
+    after = np.bincount(ids[ids >= 0], minlength=n_items)
+    at_cap = int(((after == np.asarray(cap_vec)) & (np.asarray(cap_vec) > 0)).sum())
+    return "cap@%d: max exposure %d -> %d, %d items at their cap, %d short lists, %d rounds" % (
+        k, int(before.max()) if n_items else 0, int(after.max()) if n_items else 0, at_cap, stats["short"], stats["rounds"])
+
+
 def miscal_line(stats, tr, k):
     """the line --calibrate adds: the mean miscalibration of the plain top-k lists -> of the calibrated ones (Calibrate.stats()
     [n_users, 2]), averaged in float64 over the users with a non-empty fold-in history (tr: the fold-in CSR, rows aligned with stats)"""
@@ -170,6 +248,7 @@ def parse_args(argv):
     ap.add_argument("--json", default=None)
     add_diversify_args(ap)
     add_calibrate_args(ap)
+    add_cap_args(ap)
     a = ap.parse_args(argv)
     try:
         a.group_kind, a.n_groups = parse_groups(a.groups)
@@ -189,6 +268,7 @@ def parse_args(argv):
             ap.error(str(e))
     check_diversify_args(ap, a, max(K_NDCG, K_R1, K_R2, a.k))       # (the length of the lists: LongTailReport.k)
     check_calibrate_args(ap, a)
+    check_cap_args(ap, a, max(K_NDCG, K_R1, K_R2, a.k))
     return a
 
 
@@ -296,12 +376,13 @@ def longtail(args, h0_size, h1_size, h2_size, h3_size, LEARNING_RATE, precision=
     if getattr(args, "diversify", None) is not None:
         div = Diversify(args.diversify, candidates=args.candidates, space=args.div_space)
     cal = Calibrate(labels, len(names), args.calibrate) if getattr(args, "calibrate", None) is not None else None
+    cap = make_cap(args, labels, len(names)) if getattr(args, "caps", None) is not None else None
     if world > 1:
         rec = ShardedRecommender(eng, EvalData(tr, te, eng.device, item_lo=lo, item_hi=hi), k=report.k, chunk=batch_size_test, report=report,
-                                 rule=rule, diversify=div, calibrate=cal)
+                                 rule=rule, diversify=div, calibrate=cal, cap=cap)
     else:
         rec = Recommender(eng, EvalData(tr, te, eng.device), k=report.k, chunk=batch_size_test, report=report, rule=rule, diversify=div,
-                          calibrate=cal)
+                          calibrate=cal, cap=cap)
     ids, _ = rec.run(rng_step=RNG_STEP, keep_prob=args.keep_prob)
     rep = aggregate(*report.table(), labels, names, args.k)
     rep.update(split=args.split, groups_spec=args.groups)
@@ -311,6 +392,8 @@ def longtail(args, h0_size, h1_size, h2_size, h3_size, LEARNING_RATE, precision=
         print(ils_line(div.stats(), ids, report.k))
     if cal is not None:
         print(miscal_line(cal.stats(), tr, report.k))
+    if cap is not None:
+        print(cap_line(cap.plain_ids(report.k), ids, cap.cap_vector(), cap.stats(), report.k))
     if args.json and rank == 0:
         write_json(rep, args.json)
     close_model(world)

@@ -5,7 +5,7 @@
         [--k 100] [--split test|validation] [--keep-prob 0.75] [--out recs.tsv] [--npz recs.npz]
         [--groups niche|pop:N] [--min-slots NAME:M[,NAME:M...]] [--diversify LAMBDA] [--candidates N] [--div-space decoder|encoder]
         [--explain R] [--explain-top N] [--explain-space decoder|encoder] [--explain-metric cosine|dot] [--why why.tsv]
-        [--calibrate LAMBDA]
+        [--calibrate LAMBDA] [--cap C|NAME:C[,NAME:C...]] [--cap-candidates N] [--cap-score logprob|logit]
 
 restores a checkpoint written by train.py, runs test.py's forward over the users of `<split>_tr.csv` (chunks of 20 000 users,
 dropout on with keep_prob 0.75 by default: Q3, RNG counter 2*10^9 + first row of the chunk) and keeps each user's k best items, the
@@ -39,6 +39,13 @@ ltg_hist_groups, then ltg_topk_calibrate): the next entry is the best remaining 
 (1 - LAMBDA) * relevance - LAMBDA * miscalibration, miscalibration = the total-variation distance between the history's group shares and
 those of the list so far plus that item.  LAMBDA 0 is the plain list.  The lists are written in pick order, and the last stdout line is
 `miscal@k: <before> -> <after>`, the mean miscalibration of the plain and of the calibrated lists over the users with a non-empty history.
+
+--cap C (C >= 0: every item) or --cap NAME:C[,NAME:C...] (only the items of those groups of --groups; not together with --min-slots,
+--diversify or --calibrate) serves lists in which no item appears more than C times (trainer.ExposureCap: ltg_topk at --cap-candidates N,
+then ltg_cap_index / ltg_cap_rounds / ltg_cap_finish once over the whole split): the stable matching in which a user prefers their N best
+items in order and an item prefers the users by --cap-score (logprob: logit - lse, the default; logit).  N defaults to min(1024, 4 k) and
+must lie in [k, 1024].  A user whose N candidates run out gets a short list.  The lists keep candidate order, and the last stdout line is
+`cap@k: max exposure <plain> -> <capped>, <items> items at their cap, <users> short lists, <rounds> rounds`.
 """
 from __future__ import annotations
 
@@ -73,6 +80,7 @@ def parse_args(argv):
     ap.add_argument("--min-slots", default=None)
     lt.add_diversify_args(ap)
     lt.add_calibrate_args(ap)
+    lt.add_cap_args(ap)
     ap.add_argument("--explain", type=int, default=None, metavar="R")
     ap.add_argument("--explain-top", type=int, default=None, metavar="N")
     ap.add_argument("--explain-space", choices=("decoder", "encoder"), default=None)
@@ -92,6 +100,7 @@ def parse_args(argv):
         ap.error(str(e))
     lt.check_diversify_args(ap, a, a.k)
     lt.check_calibrate_args(ap, a)
+    lt.check_cap_args(ap, a, a.k)
     if a.explain is None:
         if a.explain_top is not None or a.explain_space is not None or a.explain_metric is not None or a.why is not None:
             ap.error("--explain-top, --explain-space, --explain-metric and --why need --explain")
@@ -185,15 +194,19 @@ def recommend(args, h0_size, h1_size, h2_size, h3_size, LEARNING_RATE, precision
     if getattr(args, "calibrate", None) is not None:
         labels, names = lt.build_groups(d, args.group_kind, args.n_groups, n_items)
         cal = Calibrate(labels, len(names), args.calibrate)
+    cap = None
+    if getattr(args, "caps", None) is not None:
+        labels, names = lt.build_groups(d, args.group_kind, args.n_groups, n_items) if isinstance(args.caps, dict) else (None, ())
+        cap = lt.make_cap(args, labels, len(names))
     why = None
     if getattr(args, "explain", None) is not None:
         why = Explain(args.explain, top=args.explain_top, space=args.explain_space or "decoder", metric=args.explain_metric or "cosine")
     if world > 1:
         rec = ShardedRecommender(eng, EvalData(tr, te, eng.device, item_lo=lo, item_hi=hi), k=args.k, chunk=batch_size_test, rule=rule,
-                                 diversify=div, explain=why, calibrate=cal)
+                                 diversify=div, explain=why, calibrate=cal, cap=cap)
     else:
         rec = Recommender(eng, EvalData(tr, te, eng.device), k=args.k, chunk=batch_size_test, rule=rule, diversify=div, explain=why,
-                          calibrate=cal)
+                          calibrate=cal, cap=cap)
     ids, scores = rec.run(rng_step=RNG_STEP, keep_prob=args.keep_prob)
     m = long_tail_summary(ids, niche, n_items, te)
     why_tab = why.table() if why is not None else None
@@ -207,6 +220,8 @@ def recommend(args, h0_size, h1_size, h2_size, h3_size, LEARNING_RATE, precision
         print("why@%d: %d entries, %d reasons" % (why.top, n_lines, n_reasons))
     if cal is not None:
         print(lt.miscal_line(cal.stats(), tr, args.k))
+    if cap is not None:
+        print(lt.cap_line(cap.plain_ids(args.k), ids, cap.cap_vector(), cap.stats(), args.k))
     close_model(world)
     return ids, scores, m
 

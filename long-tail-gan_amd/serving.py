@@ -1,5 +1,5 @@
 """Everything that serves a trained model: validation / test scoring, top-K lists (plain, with minimum slots per item group, diversified,
-calibrated to each user's history),
+calibrated to each user's history, capped in how many lists an item may appear),
 the long-tail report read off them, the explanation of every list entry (the user's history items nearest to it), similar-item lists,
 item audiences (the k likeliest users of an item, gathered over the same chunk walk), and the set-up the CLIs (test.py, recommend.py, longtail.py, similar.py, audience.py) share.
 
@@ -15,7 +15,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from ._cabi import LTG_METRIC, LTG_SPACE
+from ._cabi import LTG_CAP_MAX_ROUNDS, LTG_CAP_STATE, LTG_METRIC, LTG_SPACE, LtgError
 
 EVAL_LOGITS_BYTES = 2 << 30
 
@@ -377,6 +377,117 @@ class Calibrate:
         return self.stat.cpu().numpy()
 
 
+class ExposureCap:
+    """A serve-time rule over the WHOLE split, passed as `cap=` to a Recommender / ShardedRecommender: no item appears in more than its
+    cap of the served lists, and the slots an over-full item gives up go to the best alternatives of the users it turned away.  cap: an
+    int (every item), an int array per GLOBAL item id, or (labels, n_groups, {group index: C}) -- only the items of those groups are
+    capped (labels: one uint8 per GLOBAL id, the labels a LongTailReport takes).  The lists are the user-optimal stable matching of
+    user-proposing deferred acceptance: a user prefers their `candidates` best items (default min(1024, 4 k), k <= candidates <= 1024)
+    in list order; an item prefers users by `score` -- `logprob`: logit - lse, the log-probability the user's softmax gives the item,
+    comparable across users and the Audience score; `logit`: the raw logit -- equal scores the lower user row.  A user whose candidates
+    run out gets a short list.  It is the first rule whose rows depend on each other: the chunk walk only stores every chunk's candidates
+    (SlabLists.topk at `candidates`) and lse, and match() runs once after the last chunk -- ltg_cap_index, then ltg_cap_rounds in batches
+    of `batch` rounds until a round raises no threshold, then ltg_cap_finish.  The fixed point does not depend on the order or the
+    batching of the rounds, so the table is bit-identical from run to run.  Over item shards every rank holds the same merged candidates
+    and the same full-row lse, so every rank runs the same matching and nothing is exchanged.  After run(): stats()."""
+
+    MAX_C = 1024
+    UNCAPPED = 2 ** 31 - 1
+
+    def __init__(self, cap, candidates=None, score="logprob", batch=4):
+        if score not in ("logprob", "logit"):
+            raise ValueError("score must be logprob or logit")
+        self.score = score
+        self.candidates = None if candidates is None else int(candidates)
+        if self.candidates is not None and not 1 <= self.candidates <= self.MAX_C:
+            raise ValueError("candidates must be in [1, %d], got %r" % (self.MAX_C, candidates))
+        self.batch = int(batch)
+        if not 1 <= self.batch <= LTG_CAP_MAX_ROUNDS:
+            raise ValueError("batch must be in [1, %d]" % LTG_CAP_MAX_ROUNDS)
+        self.uniform = self.cap_host = self.by_group = None
+        if isinstance(cap, tuple):
+            labels, n_groups, caps = cap
+            labels = np.ascontiguousarray(np.asarray(labels), dtype=np.uint8)
+            if not 1 <= int(n_groups) <= 8:
+                raise ValueError("n_groups must be in [1, 8]")
+            vec = np.full(labels.size, self.UNCAPPED, np.int64)
+            for g, cg in dict(caps).items():
+                if not 0 <= int(g) < int(n_groups):
+                    raise ValueError("group index %r outside [0, %d)" % (g, n_groups))
+                vec[labels == int(g)] = int(cg)
+            self.cap_host = vec
+        elif np.ndim(cap) == 0:
+            self.uniform = int(cap)
+            if self.uniform != cap:
+                raise ValueError("a uniform cap is an integer, got %r" % (cap,))
+        else:
+            self.cap_host = np.asarray(cap).astype(np.int64).reshape(-1)
+        low = self.uniform if self.cap_host is None else (int(self.cap_host.min()) if self.cap_host.size else 0)
+        if low < 0:
+            raise ValueError("a cap must be >= 0")
+        self.c = self.n_items = self.cap = self.cand_s = self.cand_i = self.lse = self.state = self.ws = self._stats = None
+
+    @property
+    def needs_lse(self):
+        return self.score == "logprob"
+
+    def bind(self, engine, k, n_users):
+        """the device tables for lists of k entries over a split of n_users"""
+        c = min(self.MAX_C, 4 * k) if self.candidates is None else self.candidates
+        if not 1 <= k <= c <= self.MAX_C:
+            raise ValueError("candidates must be in [k, %d] = [%d, %d], got %d" % (self.MAX_C, k, self.MAX_C, c))
+        if n_users * c >= 2 ** 31:
+            raise ValueError("%d users x %d candidates: the matching indexes fewer than 2^31 entries" % (n_users, c))
+        n_items, dev = int(engine.I_global), engine.device
+        vec = np.full(n_items, self.uniform, np.int64) if self.cap_host is None else self.cap_host
+        if vec.size != n_items:
+            raise ValueError("cap holds %d items, the catalogue %d" % (vec.size, n_items))
+        self.c, self.n_items = c, n_items
+        self.cap = torch.from_numpy(np.minimum(vec, self.UNCAPPED).astype(np.int32)).to(dev)
+        self.cand_s = torch.empty(n_users, c, dtype=torch.float32, device=dev)
+        self.cand_i = torch.empty(n_users, c, dtype=torch.int32, device=dev)
+        self.lse = torch.empty(n_users, dtype=torch.float32, device=dev) if self.needs_lse else None
+        self.state = torch.zeros(LTG_CAP_STATE, dtype=torch.int32, device=dev)
+        self.ws = torch.empty(max(1, engine.cap_ws_bytes(n_users, c, n_items)), dtype=torch.uint8, device=dev)
+
+    def gather(self, lists, acts, tr, n, lo):
+        """the candidates (and lse) of users lo .. lo + n, whose logits `acts` holds, into the tables; lists: the SlabLists they come from"""
+        lists.topk(acts, tr, n, self.c, self.cand_s[lo:lo + n], self.cand_i[lo:lo + n])
+        if self.lse is not None:
+            self.lse[lo:lo + n].copy_(acts.lse[:n])
+
+    def match(self, engine, k, score_out, id_out):
+        """the matching over the gathered tables -> score_out / id_out [n_users, k]"""
+        n = int(self.cand_i.shape[0])
+        if n == 0:
+            self._stats = dict(rounds=0, raises=0, passed_over=0, short=0)
+            return
+        engine.cap_index(self.cand_i, self.n_items, self.state, self.ws)
+        while True:
+            engine.cap_rounds(self.cand_s, self.cand_i, self.lse, self.cap, k, self.batch, self.state, self.ws)
+            raises, rounds, _, _, last = (int(x) for x in self.state[:5].cpu())
+            if last < rounds:                            # the last round raised no threshold: the fixed point
+                break
+            if rounds > n * self.c + 1:                  # (every round but the last removes at least one entry for good)
+                raise LtgError("the capped matching has not converged after %d rounds" % rounds)
+        engine.cap_finish(self.cand_s, self.cand_i, self.n_items, k, score_out, id_out, self.state, self.ws)
+        st = [int(x) for x in self.state.cpu()]
+        self._stats = dict(rounds=last + 1, raises=st[0], passed_over=st[2], short=st[3])
+
+    def plain_ids(self, k):
+        """-> [n_users, k] int32 host array: the plain top-k lists, the first k columns of the candidates"""
+        return self.cand_i[:, :k].cpu().numpy()
+
+    def cap_vector(self):
+        """-> [n_items] int32 host array: the cap per GLOBAL item id (UNCAPPED where none applies)"""
+        return self.cap.cpu().numpy()
+
+    def stats(self):
+        """-> dict: rounds (up to and including the first that raised no threshold), raises (threshold raises), passed_over (candidate
+        entries a user's walk passed over), short (users with fewer than k entries)"""
+        return dict(self._stats)
+
+
 class Explain:
     """Why a user got each list entry, passed as `explain=` to a Recommender / ShardedRecommender: for the first `top` entries of every
     user's list (default min(k, 256)) the r items of that user's fold-in history nearest to the entry -- "because you interacted with X
@@ -523,12 +634,19 @@ class Recommender:
     from each chunk's logits, right after the forward (audience.table() after run()); k = 0 then walks the chunks without user lists --
     run() returns [n_users, 0] arrays and no list kernel is launched.  explain: an Explain filled from each chunk's final lists, whichever
     kind they are (explain.table() after run()); needs k >= 1.  calibrate: a Calibrate the lists are composed by (the report and the
-    explanations then read the calibrated lists); not together with rule or diversify; needs k >= 1."""
+    explanations then read the calibrated lists); not together with rule or diversify; needs k >= 1.  cap: an ExposureCap the lists are
+    matched under -- the walk then only gathers every chunk's candidates, the matching runs once after the last chunk, and a second pass
+    over the chunks (no forward) feeds the report and the explanations from the capped lists, so item_hits <= cap; not together with rule,
+    diversify or calibrate; needs k >= 1; the audience is untouched."""
 
     sharded = False                                  # ShardedRecommender: one rank of `group` per item slab
 
     def __init__(self, engine, ev, k=100, chunk=20000, report=None, rule=None, diversify=None, group=None, audience=None, explain=None,
-                 calibrate=None):
+                 calibrate=None, cap=None):
+        if cap is not None and (rule is not None or diversify is not None or calibrate is not None):
+            raise ValueError("cap= cannot be combined with rule=, diversify= or calibrate=")
+        if int(k) == 0 and cap is not None:
+            raise ValueError("k = 0 serves no user lists: cap= needs k >= 1")
         if rule is not None and diversify is not None:
             raise ValueError("diversify= and rule= cannot be combined")
         if calibrate is not None and (rule is not None or diversify is not None):
@@ -540,7 +658,7 @@ class Recommender:
         if int(k) == 0 and explain is not None:
             raise ValueError("k = 0 serves no user lists: explain= needs k >= 1")
         self.eng, self.ev, self.k, self.report, self.rule, self.diversify, self.group = engine, ev, int(k), report, rule, diversify, group
-        self.audience, self.explain, self.calibrate = audience, explain, calibrate
+        self.audience, self.explain, self.calibrate, self.cap = audience, explain, calibrate, cap
         if report is not None:
             report.bind(engine, ev.n, self.k)
         self.chunk = chunk_rows(engine, ev, chunk)
@@ -553,6 +671,9 @@ class Recommender:
             longest = max(longest, diversify.c)
         if calibrate is not None:
             calibrate.bind(engine, self.chunk, self.k, ev.n)             # (its class lists are k long: `longest` is k already)
+        if cap is not None:
+            cap.bind(engine, self.k, ev.n)
+            longest = max(longest, cap.c)
         if explain is not None:
             explain.bind(engine, self.k, ev.n)
             longest = max(longest, explain.top * explain.r)          # (its per-slab lists are [rows * top, r])
@@ -589,6 +710,9 @@ class Recommender:
                 self.audience.add(eng, self.acts, tr, n, lo)
             if k == 0:                                   # no user lists: the walk serves the audience alone
                 continue
+            if self.cap is not None:                     # the lists depend on every chunk: only the candidates now
+                self.cap.gather(self.lists, self.acts, tr, n, lo)
+                continue
             if self.diversify is not None:
                 self.diversify.apply(self.lists, self.acts, tr, n, k, lo, self.scores[lo:hi], self.ids[lo:hi])
             elif self.rule is not None:
@@ -601,6 +725,16 @@ class Recommender:
                 self.report.add(eng, self.ids[lo:hi], te, lo)
             if self.explain is not None:
                 self.explain.apply(self.lists, tr, n, lo, self.ids[lo:hi])
+        if self.cap is not None:
+            self.cap.match(eng, k, self.scores, self.ids)
+            if self.report is not None or self.explain is not None:      # a second pass over the chunks, without a forward
+                for lo in range(0, ev.n, self.chunk):
+                    hi = min(ev.n, lo + self.chunk)
+                    tr, te = ev.rows(lo, hi)
+                    if self.report is not None:
+                        self.report.add(eng, self.ids[lo:hi], te, lo)
+                    if self.explain is not None:
+                        self.explain.apply(self.lists, tr, hi - lo, lo, self.ids[lo:hi])
         return self.ids.cpu().numpy(), self.scores.cpu().numpy()
 
 
@@ -615,16 +749,16 @@ class ShardedRecommender(Recommender):
     sharded = True
 
     def __init__(self, engine, ev, k=100, group=None, chunk=20000, report=None, rule=None, diversify=None, audience=None, explain=None,
-                 calibrate=None):
+                 calibrate=None, cap=None):
         super().__init__(engine, ev, k=k, chunk=chunk, report=report, rule=rule, diversify=diversify, group=group, audience=audience,
-                         explain=explain, calibrate=calibrate)
+                         explain=explain, calibrate=calibrate, cap=cap)
         self.rowpart = torch.zeros(self.chunk * 5, dtype=torch.float32, device=engine.device)
         self.rowpart_all = None
-        if audience is not None and audience.needs_lse:
+        if (audience is not None and audience.needs_lse) or (cap is not None and cap.needs_lse):
             self.rowpart_all = torch.zeros(dist.get_world_size(group) * self.chunk * 5, dtype=torch.float32, device=engine.device)
 
     def _forward(self, tr, n, keep_prob, rng_step):
-        """the slab's logits; with an audience that ranks by log-probability also the FULL-row lse in acts.lse: the slabs' row partials
+        """the slab's logits; with an audience or an exposure cap that ranks by log-probability also the FULL-row lse in acts.lse: the slabs' row partials
         are all-gathered and combined (ltg_rowstats_combine, as ShardedTrainer.create_phase does) -- one more small collective per chunk"""
         sharded_forward(self.eng, tr, n, self.acts, self.rowpart, keep_prob, rng_step, self.group)
         if self.rowpart_all is not None:

@@ -793,6 +793,36 @@ int ltg_cap_rounds(int32_t n_rows, int32_t c_in, const float* cand_score, const 
 int ltg_cap_finish(int32_t n_rows, int32_t c_in, const float* cand_score, const int32_t* cand_id, int32_t n_items_global, int32_t k,
                    float* score_out, int32_t* id_out, int32_t* state, void* ws, size_t ws_bytes, ltg_stream stream);
 
+/* Share-targeted top-K lists: the promoted groups get `want` of all served slots, placed where they cost the least relevance (additive in
+ * ABI v14).  Per row u a promoted list score_pro / id_pro [n_rows][m_in] and a rest list score_rest / id_rest [n_rows][m_in],
+ * both as ltg_topk_groups writes them: sorted in ltg_topk's order, padded with id -1 / score -inf, the first id < 0 ends a list (whatever
+ * lies behind it is ignored).  Ids are disjoint between the two lists and are never used as an index; a non-padding entry with a
+ * non-finite score is outside the contract.  1 <= k <= m_in <= 1024, n_rows * k < 2^31, want (int64) >= 0.
+ * Per row: np, nr = the non-padding entries of the two lists, kk = min(k, np + nr); plain list = the first kk entries of the merge of the two
+ * lists in ltg_topk's order (score descending, -0.0 == +0.0, ties lower id first); a = how many of them are promoted, b = kk - a.
+ * Steps t = 1 .. min(b, np - a): cost c_t = fp32(rest[b - t] - pro[a + t - 1]) (0-based, one IEEE fp32 subtraction; a result of +-0 is taken as
+ * +0.0), word w = ((uint64)bits(c_t) << 32) | (u * k + t - 1).  Costs are >= 0, so the bits order as the floats do, and the words of a row
+ * strictly increase with t.
+ * Over all rows: A = sum a, N = the number of steps, take = min(max(0, want - A), N), thr = the take-th smallest word, t_u = the steps of
+ * row u with w <= thr (a prefix; take = 0: t_u = 0).  Output row u = the first a + t_u entries of the promoted list and the first b - t_u of
+ * the rest list, merged in ltg_topk's order, every entry with its original score bit for bit, padded with id -1 / score -inf.
+ * Consequences: want <= A returns the plain lists bit for bit; want >= A + N returns every row at its limit; among all allocations that
+ * move `take` slots the output has the least total step cost (the step costs of a row never decrease, so the globally cheapest steps
+ * are a prefix of every row).
+ * state (device, int32 [LTG_SHARE_STATE]): [0] A, [1] N, [2] take, [3] rows with t_u > 0, [4] the bits of the threshold's cost (0 if take = 0)
+ * -- the marginal relevance price of a promoted slot -- [5] sum kk, [6..7] 0.
+ * One call enqueues everything (a fixed 19 launches, no read-back in between): the steps, a radix select over the n_rows * k words (most
+ * significant digit first, 8 bits a pass, 8 passes, LDS histograms added to global bins by integer atomics), the lists.  Integer atomics
+ * only, no sort: bit-identical from run to run.  Nothing relies on what ws held.  ws: ltg_share_ws_bytes(n_rows, k) bytes (0 for sizes
+ * the call refuses), 256-byte aligned.  LTG_EINVAL before any HIP call: a NULL pointer (stream excepted), n_rows < 0, m_in outside
+ * [1, 1024], k outside [1, m_in], n_rows * k >= 2^31, want < 0, ws_bytes too small, an output that overlaps an input.  n_rows = 0 returns
+ * LTG_OK, launches nothing and writes no state (the arguments are still checked). */
+#define LTG_SHARE_STATE 8
+size_t ltg_share_ws_bytes(int32_t n_rows, int32_t k);            /* 0 for sizes the call refuses */
+int ltg_topk_share(int32_t n_rows, int32_t m_in, const float* score_pro, const int32_t* id_pro, const float* score_rest,
+                   const int32_t* id_rest, int32_t k, int64_t want, float* score_out, int32_t* id_out,
+                   int32_t* state /* device [LTG_SHARE_STATE = 8] */, void* ws, size_t ws_bytes, ltg_stream stream);
+
 /* Verification helper of the LTG_PREC_FP8 mode: out[i] = the value the fp8 GEMM operands carry for in[i]
  * (clamp to +-448, round to nearest-even OCP e4m3) -- lets a test pin its CPU model of the rounding to the hardware. */
 int ltg_fp8_roundtrip(const float* in, float* out, int32_t n, ltg_stream stream);

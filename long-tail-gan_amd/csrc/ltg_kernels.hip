@@ -174,6 +174,7 @@ __global__ __launch_bounds__(64) void k_gate_set(LtgGate g, LtgGate g2 = LTG_NO_
 #include "ltg_topk.h"
 #include "ltg_audience.h"
 #include "ltg_cap.h"
+#include "ltg_share.h"
 #include "ltg_longtail.h"
 #include "ltg_neighbors.h"
 #include "ltg_diversify.h"
@@ -2073,6 +2074,73 @@ int ltg_cap_finish(int32_t n_rows, int32_t c_in, const float* cand_score, const 
     hipLaunchKernelGGL(k_cap_finish, dim3((n_rows + CP_NT / 64 - 1) / (CP_NT / 64)), dim3(CP_NT), 0, st, n_rows, c_in, k, cand_score, cand_id,
                        n_items_global, (const uint8_t*)w.active, score_out, id_out, w.row_over);
     hipLaunchKernelGGL(k_cap_stats, dim3(1), dim3(1024), 0, st, n_rows, k, (const int32_t*)id_out, (const int32_t*)w.row_over, state);
+    return check_launch();
+}
+
+// Share-targeted top-K lists.  The workspace holds one 64-bit word per (row, step), two int32 per row, the 8 x 256 bins of the
+// radix select and its selection block; its layout is a function of (n_rows, k) alone.  One call enqueues everything -- 2 + 2 x 8 + 1
+// launches, no read-back in between -- and every refusal comes before the first HIP call.
+struct ShareWs {
+    uint64_t* words;
+    int32_t *row_a, *row_kk, *bins;
+    sh_sel* sel;
+    size_t bytes;
+};
+static bool share_args_ok(int32_t n_rows, int32_t k) {
+    return n_rows >= 0 && k >= 1 && k <= 1024 && (int64_t)n_rows * (int64_t)k < ((int64_t)1 << 31);
+}
+static ShareWs share_carve(int32_t n_rows, int32_t k, char* base) {
+    const size_t R = (size_t)n_rows > 0 ? (size_t)n_rows : 1, E = R * (size_t)k;
+    ShareWs w;
+    size_t o = 0;
+    auto take = [&](size_t bytes) {                  // (no pointer arithmetic on the null base of the size query)
+        char* p = base ? base + o : nullptr;
+        o += align_up(bytes);
+        return p;
+    };
+    w.words = (uint64_t*)take(E * sizeof(uint64_t));
+    w.row_a = (int32_t*)take(R * sizeof(int32_t));
+    w.row_kk = (int32_t*)take(R * sizeof(int32_t));
+    w.bins = (int32_t*)take((size_t)SH_PASSES * 256 * sizeof(int32_t));
+    w.sel = (sh_sel*)take(sizeof(sh_sel));
+    w.bytes = o;
+    return w;
+}
+// [p, p + n) and [q, q + m) (bytes) share a byte, or start at the same address
+static bool share_overlap(const void* p, size_t n, const void* q, size_t m) {
+    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+    return a == b || (a < b + m && b < a + n);
+}
+
+size_t ltg_share_ws_bytes(int32_t n_rows, int32_t k) { return share_args_ok(n_rows, k) ? share_carve(n_rows, k, nullptr).bytes : 0; }
+
+int ltg_topk_share(int32_t n_rows, int32_t m_in, const float* score_pro, const int32_t* id_pro, const float* score_rest, const int32_t* id_rest,
+                   int32_t k, int64_t want, float* score_out, int32_t* id_out, int32_t* state, void* ws, size_t ws_bytes, ltg_stream stream) {
+    if (!score_pro || !id_pro || !score_rest || !id_rest || !score_out || !id_out || !state || !ws || m_in < 1 || m_in > 1024 || k < 1 ||
+        k > m_in || !share_args_ok(n_rows, k) || want < 0 || ws_bytes < share_carve(n_rows, k, nullptr).bytes)
+        return LTG_EINVAL;
+    const size_t in_b = (size_t)n_rows * (size_t)m_in * 4, out_b = (size_t)n_rows * (size_t)k * 4;
+    const void* ins[4] = {score_pro, id_pro, score_rest, id_rest};
+    for (const void* in : ins)
+        if (share_overlap(score_out, out_b, in, in_b) || share_overlap(id_out, out_b, in, in_b)) return LTG_EINVAL;
+    if (n_rows == 0) return LTG_OK;
+    const ShareWs w = share_carve(n_rows, k, (char*)ws);
+    const hipStream_t st = (hipStream_t)stream;
+    const int row_blocks = (n_rows + SH_NT / 64 - 1) / (SH_NT / 64);
+    const size_t n_words = (size_t)n_rows * (size_t)k, per = (size_t)SH_NT * SH_HIST_PER;
+    const int hist_blocks = (int)((n_words + per - 1) / per < 2048 ? (n_words + per - 1) / per : 2048);
+    clear_errors();
+    hipLaunchKernelGGL(k_share_zero, dim3(1), dim3(SH_NT), 0, st, state, w.bins, w.sel);
+    hipLaunchKernelGGL(k_share_steps, dim3(row_blocks), dim3(SH_NT), 0, st, n_rows, m_in, k, score_pro, id_pro, score_rest, id_rest, w.words,
+                       w.row_a, w.row_kk, state);
+    for (int pass = 0; pass < SH_PASSES; ++pass) {
+        hipLaunchKernelGGL(k_share_hist, dim3(hist_blocks), dim3(SH_NT), 0, st, n_words, pass, (int64_t)want, (const uint64_t*)w.words,
+                           (const int32_t*)state, (const sh_sel*)w.sel, w.bins);
+        hipLaunchKernelGGL(k_share_pick, dim3(1), dim3(256), 0, st, pass, (int64_t)want, state, w.sel, (const int32_t*)w.bins);
+    }
+    hipLaunchKernelGGL(k_share_finish, dim3(row_blocks), dim3(SH_NT), 0, st, n_rows, m_in, k, (int64_t)want, score_pro, id_pro, score_rest,
+                       id_rest, (const uint64_t*)w.words, (const int32_t*)w.row_a, (const int32_t*)w.row_kk, (const sh_sel*)w.sel, score_out,
+                       id_out, state);
     return check_launch();
 }
 

@@ -962,6 +962,29 @@ class Engine:
         cabi.check(self.lib.ltg_cap_finish(n, c, _ptr(cand_s), _ptr(cand_i), int(n_items), int(k), _ptr(score_out), _ptr(id_out), _ptr(state),
                                            _ptr(ws), ws.numel(), self.stream()), "ltg_cap_finish")
 
+    def share_ws_bytes(self, n_rows, k):
+        """the workspace of the share-targeted lists of n_rows rows of k entries (0 for sizes ltg_topk_share refuses)"""
+        return int(self.lib.ltg_share_ws_bytes(int(n_rows), int(k)))
+
+    def topk_share(self, score_pro, id_pro, score_rest, id_rest, k, want, score_out, id_out, state, ws):
+        """the lists in which the promoted lists hold `want` of all slots, placed where they cost the least score: score_pro / id_pro and
+        score_rest / id_rest [rows, m_in] as topk_groups writes them with a group mask and with its complement -> score_out / id_out
+        [rows, k], every row sorted as topk sorts, every entry with its original score; state [LTG_SHARE_STATE] int32 = {promoted entries
+        of the plain lists, steps there are, steps taken, rows changed, bits of the threshold cost, entries served, 0, 0}
+        (ltg_topk_share: one call, no read-back; the outputs must not alias an input)"""
+        n, m_in = (int(x) for x in score_pro.shape)
+        for t in (id_pro, score_rest, id_rest):
+            assert tuple(t.shape) == (n, m_in)
+        assert tuple(score_out.shape) == tuple(id_out.shape) == (n, int(k))
+        for t in (score_pro, score_rest, score_out):
+            assert t.dtype == torch.float32 and t.is_contiguous()
+        for t in (id_pro, id_rest, id_out):
+            assert t.dtype == torch.int32 and t.is_contiguous()
+        assert state.dtype == torch.int32 and state.is_contiguous() and state.numel() >= cabi.LTG_SHARE_STATE
+        assert ws.dtype == torch.uint8 and ws.numel() >= self.share_ws_bytes(n, k)
+        cabi.check(self.lib.ltg_topk_share(n, m_in, _ptr(score_pro), _ptr(id_pro), _ptr(score_rest), _ptr(id_rest), int(k), int(want),
+                                           _ptr(score_out), _ptr(id_out), _ptr(state), _ptr(ws), ws.numel(), self.stream()), "ltg_topk_share")
+
     # ------------------------------------------------------------------ views in the reference's shapes
     def generator_params_tf(self):
         """The 8 tensors in the reference's order and TF shapes (MultiVAE.py:129-141); W_p1 is a

@@ -4,7 +4,7 @@
     cd <dir holding config.ini> && python <repo>/long-tail-gan_amd/longtail.py <dataset_dir> <checkpoint>
         [--split test|validation] [--groups niche|pop:N] [--min-slots NAME:M[,NAME:M...]] [--k 100] [--keep-prob 0.75] [--json report.json]
         [--diversify LAMBDA] [--candidates N] [--div-space decoder|encoder] [--calibrate LAMBDA]
-        [--cap C|NAME:C[,NAME:C...]] [--cap-candidates N] [--cap-score logprob|logit]
+        [--cap C|NAME:C[,NAME:C...]] [--cap-candidates N] [--cap-score logprob|logit] [--share NAME[+NAME...]:S]
 
 restores a checkpoint written by train.py, runs test.py's forward over the users of `<split>_tr.csv` ONCE (chunks of 20 000 users,
 dropout on with keep_prob 0.75 by default: Q3, RNG counter 2*10^9 + first row of the chunk), keeps each user's top-K list on the GPU
@@ -46,6 +46,13 @@ ltg_topk at --cap-candidates N, then ltg_cap_index / ltg_cap_rounds / ltg_cap_fi
 which a user prefers their N best items in order and an item prefers the users by --cap-score (logprob: logit - lse, the default; logit).
 N defaults to min(1024, 4 K) and must lie in [K, 1024], K = max(100, --k).  The last line is then
 `cap@K: max exposure <plain> -> <capped>, <items> items at their cap, <users> short lists, <rounds> rounds`.
+
+--share NAME[+NAME...]:S (0 <= S <= 1; NAME a group of --groups; not together with --min-slots, --diversify, --calibrate or --cap) gives
+those groups the part S of ALL served slots before the report reads the lists (trainer.ShareTarget; two ltg_topk_groups lists per chunk,
+then ltg_topk_share once over the whole split): the promoted slots go to the users for whom they cost the least score, every list stays
+in score order, and a target the plain lists already meet changes nothing.  The last line is then
+`share@K: <names> <plain share> -> <reached share> (target S), <users> rows changed, price <cost>`, price = the score difference of the
+dearest swap made.
 """
 from __future__ import annotations
 
@@ -218,6 +225,57 @@ def cap_line(plain_ids, ids, cap_vec, stats, k):
         k, int(before.max()) if n_items else 0, int(after.max()) if n_items else 0, at_cap, stats["short"], stats["rounds"])
 
 
+def parse_share(spec, names):
+    """'NAME[+NAME...]:S' -> (sorted group indices, S); an unknown name, a name twice, no name or S outside [0, 1] raises ValueError"""
+    head, sep, val = spec.strip().rpartition(":")
+    try:
+        share = float(val) if sep else -1.0
+    except ValueError:
+        share = -1.0
+    if not sep or not head or not 0.0 <= share <= 1.0:
+        raise ValueError("--share takes NAME[+NAME...]:S with 0 <= S <= 1, got %r" % (spec,))
+    groups = []
+    for name in (x.strip() for x in head.split("+")):
+        if name not in names:
+            raise ValueError("--share: unknown group %r (the groups are %s)" % (name, ", ".join(names)))
+        if names.index(name) in groups:
+            raise ValueError("--share names group %r twice" % (name,))
+        groups.append(names.index(name))
+    return sorted(groups), share
+
+
+def add_share_args(ap):
+    """the option of the share-targeted lists (trainer.ShareTarget), shared with recommend.py"""
+    ap.add_argument("--share", default=None, metavar="NAME[+NAME...]:S")
+
+
+def check_share_args(ap, a):
+    """refuses (ap.error) what trainer.ShareTarget would refuse, and the combination with the other rules; a.shares = the parsed --share
+    (None without the option)"""
+    a.shares = None
+    if a.share is None:
+        return
+    if a.min_slots is not None or a.diversify is not None or a.calibrate is not None or a.cap is not None:
+        ap.error("--share cannot be combined with --min-slots, --diversify, --calibrate or --cap")
+    try:
+        a.shares = parse_share(a.share, group_names(a.group_kind, a.n_groups))
+    except ValueError as e:
+        ap.error(str(e))
+
+
+def make_share(a, labels, n_groups):
+    """the ShareTarget of the parsed options (labels: the --groups labels)"""
+    from ltgan.serving import ShareTarget
+    return ShareTarget(labels, n_groups, a.shares[0], a.shares[1])
+
+
+def share_line(names, stats, k):
+    """the line --share adds: the promoted groups' part of the served slots, plain -> reached, the target, the rows whose list changed and
+    the price of the dearest swap (ShareTarget.stats())"""
+    return "share@%d: %s %.6f -> %.6f (target %.6f), %d rows changed, price %.6g" % (
+        k, "+".join(names), stats["plain_share"], stats["share"], stats["target"], stats["rows_changed"], stats["price"])
+
+
 def miscal_line(stats, tr, k):
     """the line --calibrate adds: the mean miscalibration of the plain top-k lists -> of the calibrated ones (Calibrate.stats()
     [n_users, 2]), averaged in float64 over the users with a non-empty fold-in history (tr: the fold-in CSR, rows aligned with stats)"""
@@ -249,6 +307,7 @@ def parse_args(argv):
     add_diversify_args(ap)
     add_calibrate_args(ap)
     add_cap_args(ap)
+    add_share_args(ap)
     a = ap.parse_args(argv)
     try:
         a.group_kind, a.n_groups = parse_groups(a.groups)
@@ -269,6 +328,7 @@ def parse_args(argv):
     check_diversify_args(ap, a, max(K_NDCG, K_R1, K_R2, a.k))       # (the length of the lists: LongTailReport.k)
     check_calibrate_args(ap, a)
     check_cap_args(ap, a, max(K_NDCG, K_R1, K_R2, a.k))
+    check_share_args(ap, a)
     return a
 
 
@@ -377,12 +437,13 @@ def longtail(args, h0_size, h1_size, h2_size, h3_size, LEARNING_RATE, precision=
         div = Diversify(args.diversify, candidates=args.candidates, space=args.div_space)
     cal = Calibrate(labels, len(names), args.calibrate) if getattr(args, "calibrate", None) is not None else None
     cap = make_cap(args, labels, len(names)) if getattr(args, "caps", None) is not None else None
+    share = make_share(args, labels, len(names)) if getattr(args, "shares", None) is not None else None
     if world > 1:
         rec = ShardedRecommender(eng, EvalData(tr, te, eng.device, item_lo=lo, item_hi=hi), k=report.k, chunk=batch_size_test, report=report,
-                                 rule=rule, diversify=div, calibrate=cal, cap=cap)
+                                 rule=rule, diversify=div, calibrate=cal, cap=cap, share=share)
     else:
         rec = Recommender(eng, EvalData(tr, te, eng.device), k=report.k, chunk=batch_size_test, report=report, rule=rule, diversify=div,
-                          calibrate=cal, cap=cap)
+                          calibrate=cal, cap=cap, share=share)
     ids, _ = rec.run(rng_step=RNG_STEP, keep_prob=args.keep_prob)
     rep = aggregate(*report.table(), labels, names, args.k)
     rep.update(split=args.split, groups_spec=args.groups)
@@ -394,6 +455,8 @@ def longtail(args, h0_size, h1_size, h2_size, h3_size, LEARNING_RATE, precision=
         print(miscal_line(cal.stats(), tr, report.k))
     if cap is not None:
         print(cap_line(cap.plain_ids(report.k), ids, cap.cap_vector(), cap.stats(), report.k))
+    if share is not None:
+        print(share_line([names[g] for g in share.promote], share.stats(), report.k))
     if args.json and rank == 0:
         write_json(rep, args.json)
     close_model(world)

@@ -6,6 +6,7 @@
         [--groups niche|pop:N] [--min-slots NAME:M[,NAME:M...]] [--diversify LAMBDA] [--candidates N] [--div-space decoder|encoder]
         [--explain R] [--explain-top N] [--explain-space decoder|encoder] [--explain-metric cosine|dot] [--why why.tsv]
         [--calibrate LAMBDA] [--cap C|NAME:C[,NAME:C...]] [--cap-candidates N] [--cap-score logprob|logit]
+        [--share NAME[+NAME...]:S]
 
 restores a checkpoint written by train.py, runs test.py's forward over the users of `<split>_tr.csv` (chunks of 20 000 users,
 dropout on with keep_prob 0.75 by default: Q3, RNG counter 2*10^9 + first row of the chunk) and keeps each user's k best items, the
@@ -46,6 +47,13 @@ then ltg_cap_index / ltg_cap_rounds / ltg_cap_finish once over the whole split):
 items in order and an item prefers the users by --cap-score (logprob: logit - lse, the default; logit).  N defaults to min(1024, 4 k) and
 must lie in [k, 1024].  A user whose N candidates run out gets a short list.  The lists keep candidate order, and the last stdout line is
 `cap@k: max exposure <plain> -> <capped>, <items> items at their cap, <users> short lists, <rounds> rounds`.
+
+--share NAME[+NAME...]:S (0 <= S <= 1; NAME a group of --groups; not together with --min-slots, --diversify, --calibrate or --cap) gives
+those groups the part S of ALL served slots (trainer.ShareTarget: two ltg_topk_groups lists per chunk, then ltg_topk_share once over the
+whole split): where `--min-slots niche:30` forces 30 niche entries on every user, `--share niche:0.3` places the same total where the
+swaps cost the least score.  Every list stays in score order; a target the plain lists already meet changes nothing.  The last stdout
+line is `share@k: <names> <plain share> -> <reached share> (target S), <users> rows changed, price <cost>`, price = the score difference
+of the dearest swap made.
 """
 from __future__ import annotations
 
@@ -81,6 +89,7 @@ def parse_args(argv):
     lt.add_diversify_args(ap)
     lt.add_calibrate_args(ap)
     lt.add_cap_args(ap)
+    lt.add_share_args(ap)
     ap.add_argument("--explain", type=int, default=None, metavar="R")
     ap.add_argument("--explain-top", type=int, default=None, metavar="N")
     ap.add_argument("--explain-space", choices=("decoder", "encoder"), default=None)
@@ -101,6 +110,7 @@ def parse_args(argv):
     lt.check_diversify_args(ap, a, a.k)
     lt.check_calibrate_args(ap, a)
     lt.check_cap_args(ap, a, a.k)
+    lt.check_share_args(ap, a)
     if a.explain is None:
         if a.explain_top is not None or a.explain_space is not None or a.explain_metric is not None or a.why is not None:
             ap.error("--explain-top, --explain-space, --explain-metric and --why need --explain")
@@ -198,15 +208,20 @@ def recommend(args, h0_size, h1_size, h2_size, h3_size, LEARNING_RATE, precision
     if getattr(args, "caps", None) is not None:
         labels, names = lt.build_groups(d, args.group_kind, args.n_groups, n_items) if isinstance(args.caps, dict) else (None, ())
         cap = lt.make_cap(args, labels, len(names))
+    share = share_names = None
+    if getattr(args, "shares", None) is not None:
+        labels, names = lt.build_groups(d, args.group_kind, args.n_groups, n_items)
+        share = lt.make_share(args, labels, len(names))
+        share_names = [names[g] for g in share.promote]
     why = None
     if getattr(args, "explain", None) is not None:
         why = Explain(args.explain, top=args.explain_top, space=args.explain_space or "decoder", metric=args.explain_metric or "cosine")
     if world > 1:
         rec = ShardedRecommender(eng, EvalData(tr, te, eng.device, item_lo=lo, item_hi=hi), k=args.k, chunk=batch_size_test, rule=rule,
-                                 diversify=div, explain=why, calibrate=cal, cap=cap)
+                                 diversify=div, explain=why, calibrate=cal, cap=cap, share=share)
     else:
         rec = Recommender(eng, EvalData(tr, te, eng.device), k=args.k, chunk=batch_size_test, rule=rule, diversify=div, explain=why,
-                          calibrate=cal, cap=cap)
+                          calibrate=cal, cap=cap, share=share)
     ids, scores = rec.run(rng_step=RNG_STEP, keep_prob=args.keep_prob)
     m = long_tail_summary(ids, niche, n_items, te)
     why_tab = why.table() if why is not None else None
@@ -222,6 +237,8 @@ def recommend(args, h0_size, h1_size, h2_size, h3_size, LEARNING_RATE, precision
         print(lt.miscal_line(cal.stats(), tr, args.k))
     if cap is not None:
         print(lt.cap_line(cap.plain_ids(args.k), ids, cap.cap_vector(), cap.stats(), args.k))
+    if share is not None:
+        print(lt.share_line(share_names, share.stats(), args.k))
     close_model(world)
     return ids, scores, m
 

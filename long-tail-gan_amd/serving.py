@@ -1,5 +1,5 @@
 """Everything that serves a trained model: validation / test scoring, top-K lists (plain, with minimum slots per item group, diversified,
-calibrated to each user's history, capped in how many lists an item may appear),
+calibrated to each user's history, capped in how many lists an item may appear, with a set share of all slots for some item groups),
 the long-tail report read off them, the explanation of every list entry (the user's history items nearest to it), similar-item lists,
 item audiences (the k likeliest users of an item, gathered over the same chunk walk), and the set-up the CLIs (test.py, recommend.py, longtail.py, similar.py, audience.py) share.
 
@@ -15,7 +15,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from ._cabi import LTG_CAP_MAX_ROUNDS, LTG_CAP_STATE, LTG_METRIC, LTG_SPACE, LtgError
+from ._cabi import LTG_CAP_MAX_ROUNDS, LTG_CAP_STATE, LTG_METRIC, LTG_SHARE_STATE, LTG_SPACE, LtgError
 
 EVAL_LOGITS_BYTES = 2 << 30
 
@@ -488,6 +488,75 @@ class ExposureCap:
         return dict(self._stats)
 
 
+class ShareTarget:
+    """A serve-time rule over the WHOLE split, passed as `share=` to a Recommender / ShardedRecommender: the item groups `promote` (group
+    indices; labels: one uint8 per GLOBAL item id, the labels a LongTailReport takes) get the part `share` of ALL served slots, and the
+    promoted slots go where they cost the least relevance -- not the same number to every user, as MinSlots gives.  For a user, one more
+    promoted slot costs the score of the worst remaining other entry minus the score of the best promoted item not yet in the list; these
+    step costs never decrease along a user's list, so the cheapest way to a total of want = ceil(share * n_users * k) promoted slots is the
+    globally cheapest steps: one selection, no rounds.  Like the cap the rows depend on each other: the chunk walk only stores every
+    chunk's two lists of k entries (SlabLists.topk with the promoted groups' mask and with its complement), and match() makes ONE call of
+    ltg_topk_share after the last chunk.  Every row stays sorted and every entry keeps its score.  share = 0, or a target the plain
+    lists already meet, gives the plain lists bit for bit; a target beyond what the promoted groups can fill gives every row at its
+    limit (stats()["reached"] is then False).  Over item shards every rank holds the same merged lists and runs the same call: nothing
+    is exchanged.  After run(): stats()."""
+
+    def __init__(self, labels, n_groups, promote, share):
+        self.labels_host = np.ascontiguousarray(np.asarray(labels), dtype=np.uint8)
+        self.n_groups = int(n_groups)
+        if not 1 <= self.n_groups <= 8:
+            raise ValueError("n_groups must be in [1, 8]")
+        self.promote = sorted({int(g) for g in promote})
+        self.mask = group_mask_of(self.promote, self.n_groups)           # (raises for an index outside the groups and for an empty list)
+        self.rest_mask = 0x1FF & ~self.mask                              # every other label, those in no group (bit 8) included
+        self.share = float(share)
+        if not 0.0 <= self.share <= 1.0:             # (NaN fails both comparisons)
+            raise ValueError("share must be in [0, 1], got %r" % (share,))
+        self.k = self.want = self.labels = self.pro_s = self.pro_i = self.rest_s = self.rest_i = self.state = self.ws = self._stats = None
+
+    def bind(self, engine, k, n_users):
+        """the device tables for lists of k entries over a split of n_users"""
+        if not 1 <= k <= 1024:
+            raise ValueError("k must be in [1, 1024], got %d" % k)
+        if n_users * k >= 2 ** 31:
+            raise ValueError("%d users x %d entries: the selection indexes fewer than 2^31 steps" % (n_users, k))
+        if self.labels_host.size != engine.I_global:
+            raise ValueError("labels hold %d items, the catalogue %d" % (self.labels_host.size, engine.I_global))
+        dev = engine.device
+        self.k = int(k)
+        self.want = int(np.ceil(np.float64(self.share) * n_users * k))
+        self.labels = torch.from_numpy(self.labels_host).to(dev)
+        self.pro_s = torch.empty(n_users, k, dtype=torch.float32, device=dev)
+        self.pro_i = torch.empty(n_users, k, dtype=torch.int32, device=dev)
+        self.rest_s = torch.empty(n_users, k, dtype=torch.float32, device=dev)
+        self.rest_i = torch.empty(n_users, k, dtype=torch.int32, device=dev)
+        self.state = torch.zeros(LTG_SHARE_STATE, dtype=torch.int32, device=dev)
+        self.ws = torch.empty(max(1, engine.share_ws_bytes(n_users, k)), dtype=torch.uint8, device=dev)
+
+    def gather(self, lists, acts, tr, n, lo):
+        """the promoted and the rest lists of users lo .. lo + n, whose logits `acts` holds, into the tables; lists: the SlabLists they
+        come from"""
+        lists.topk(acts, tr, n, self.k, self.pro_s[lo:lo + n], self.pro_i[lo:lo + n], self.labels, self.mask)
+        lists.topk(acts, tr, n, self.k, self.rest_s[lo:lo + n], self.rest_i[lo:lo + n], self.labels, self.rest_mask)
+
+    def match(self, engine, k, score_out, id_out):
+        """the one call over the gathered tables -> score_out / id_out [n_users, k]"""
+        st = [0] * LTG_SHARE_STATE
+        if int(self.pro_i.shape[0]) > 0:
+            engine.topk_share(self.pro_s, self.pro_i, self.rest_s, self.rest_i, k, self.want, score_out, id_out, self.state, self.ws)
+            st = [int(x) for x in self.state.cpu()]
+        A, N, take, changed, bits, served = st[:6]
+        price = float(np.array([bits], np.int32).view(np.float32)[0])
+        self._stats = dict(plain_share=A / served if served else float("nan"), share=(A + take) / served if served else float("nan"),
+                           target=self.share, taken=take, available=N, rows_changed=changed, price=price, reached=A + take >= self.want)
+
+    def stats(self):
+        """-> dict: plain_share / share (the promoted part of the served slots before / after), target, taken (steps taken), available
+        (steps there are), rows_changed, price (the cost of the dearest step taken: the marginal relevance price of a promoted slot; 0.0
+        when none was taken), reached (the promoted slots are at least ceil(target * n_users * k))"""
+        return dict(self._stats)
+
+
 class Explain:
     """Why a user got each list entry, passed as `explain=` to a Recommender / ShardedRecommender: for the first `top` entries of every
     user's list (default min(k, 256)) the r items of that user's fold-in history nearest to the entry -- "because you interacted with X
@@ -637,12 +706,18 @@ class Recommender:
     explanations then read the calibrated lists); not together with rule or diversify; needs k >= 1.  cap: an ExposureCap the lists are
     matched under -- the walk then only gathers every chunk's candidates, the matching runs once after the last chunk, and a second pass
     over the chunks (no forward) feeds the report and the explanations from the capped lists, so item_hits <= cap; not together with rule,
-    diversify or calibrate; needs k >= 1; the audience is untouched."""
+    diversify or calibrate; needs k >= 1; the audience is untouched.  share: a ShareTarget the lists are composed under -- the walk then only
+    gathers every chunk's promoted and rest lists, ltg_topk_share runs once after the last chunk, and the same second pass feeds the report
+    and the explanations from the final lists; not together with rule, diversify, calibrate or cap; needs k >= 1."""
 
     sharded = False                                  # ShardedRecommender: one rank of `group` per item slab
 
     def __init__(self, engine, ev, k=100, chunk=20000, report=None, rule=None, diversify=None, group=None, audience=None, explain=None,
-                 calibrate=None, cap=None):
+                 calibrate=None, cap=None, share=None):
+        if share is not None and (rule is not None or diversify is not None or calibrate is not None or cap is not None):
+            raise ValueError("share= cannot be combined with rule=, diversify=, calibrate= or cap=")
+        if int(k) == 0 and share is not None:
+            raise ValueError("k = 0 serves no user lists: share= needs k >= 1")
         if cap is not None and (rule is not None or diversify is not None or calibrate is not None):
             raise ValueError("cap= cannot be combined with rule=, diversify= or calibrate=")
         if int(k) == 0 and cap is not None:
@@ -658,7 +733,7 @@ class Recommender:
         if int(k) == 0 and explain is not None:
             raise ValueError("k = 0 serves no user lists: explain= needs k >= 1")
         self.eng, self.ev, self.k, self.report, self.rule, self.diversify, self.group = engine, ev, int(k), report, rule, diversify, group
-        self.audience, self.explain, self.calibrate, self.cap = audience, explain, calibrate, cap
+        self.audience, self.explain, self.calibrate, self.cap, self.share = audience, explain, calibrate, cap, share
         if report is not None:
             report.bind(engine, ev.n, self.k)
         self.chunk = chunk_rows(engine, ev, chunk)
@@ -674,6 +749,8 @@ class Recommender:
         if cap is not None:
             cap.bind(engine, self.k, ev.n)
             longest = max(longest, cap.c)
+        if share is not None:
+            share.bind(engine, self.k, ev.n)                             # (its two lists are k long: `longest` is k already)
         if explain is not None:
             explain.bind(engine, self.k, ev.n)
             longest = max(longest, explain.top * explain.r)          # (its per-slab lists are [rows * top, r])
@@ -713,6 +790,9 @@ class Recommender:
             if self.cap is not None:                     # the lists depend on every chunk: only the candidates now
                 self.cap.gather(self.lists, self.acts, tr, n, lo)
                 continue
+            if self.share is not None:                   # likewise: only the promoted and the rest lists now
+                self.share.gather(self.lists, self.acts, tr, n, lo)
+                continue
             if self.diversify is not None:
                 self.diversify.apply(self.lists, self.acts, tr, n, k, lo, self.scores[lo:hi], self.ids[lo:hi])
             elif self.rule is not None:
@@ -725,8 +805,9 @@ class Recommender:
                 self.report.add(eng, self.ids[lo:hi], te, lo)
             if self.explain is not None:
                 self.explain.apply(self.lists, tr, n, lo, self.ids[lo:hi])
-        if self.cap is not None:
-            self.cap.match(eng, k, self.scores, self.ids)
+        whole = self.cap if self.cap is not None else self.share         # a rule over the whole split: its lists exist only now
+        if whole is not None:
+            whole.match(eng, k, self.scores, self.ids)
             if self.report is not None or self.explain is not None:      # a second pass over the chunks, without a forward
                 for lo in range(0, ev.n, self.chunk):
                     hi = min(ev.n, lo + self.chunk)
@@ -749,9 +830,9 @@ class ShardedRecommender(Recommender):
     sharded = True
 
     def __init__(self, engine, ev, k=100, group=None, chunk=20000, report=None, rule=None, diversify=None, audience=None, explain=None,
-                 calibrate=None, cap=None):
+                 calibrate=None, cap=None, share=None):
         super().__init__(engine, ev, k=k, chunk=chunk, report=report, rule=rule, diversify=diversify, group=group, audience=audience,
-                         explain=explain, calibrate=calibrate, cap=cap)
+                         explain=explain, calibrate=calibrate, cap=cap, share=share)
         self.rowpart = torch.zeros(self.chunk * 5, dtype=torch.float32, device=engine.device)
         self.rowpart_all = None
         if (audience is not None and audience.needs_lse) or (cap is not None and cap.needs_lse):

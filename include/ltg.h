@@ -823,6 +823,51 @@ int ltg_topk_share(int32_t n_rows, int32_t m_in, const float* score_pro, const i
                    const int32_t* id_rest, int32_t k, int64_t want, float* score_out, int32_t* id_out,
                    int32_t* state /* device [LTG_SHARE_STATE = 8] */, void* ws, size_t ws_bytes, ltg_stream stream);
 
+/* Exposure-floor top-K lists: every item with need[item] > 0 reaches need[item] of the served lists where enough users hold it among their
+ * candidates (additive in ABI v14) -- the dual of the cap.  cand_score / cand_id / lse / the word w of an entry: as for
+ * ltg_cap_*.  need [n_items_global] int32 per GLOBAL item id, <= 0: no floor.  1 <= k <= c_in <= 1024, 0 <= reserve <= k, n_rows * c_in < 2^31.
+ * A FLOOR entry (u, j): j before the row's first padding id, 0 <= id < n_items_global, need[id] > 0.  The zone of a row: the positions
+ * j >= k - reserve.  The result is the item-optimal stable matching of item-proposing deferred acceptance -- an item proposes to the users
+ * that hold it, best word first, until it holds need acceptances; a user accepts every proposal before its zone and keeps, of those in
+ * the zone, the `reserve` with the lowest positions -- stated as the greatest per-user limits lim[u] (c_in - 1 at the start, k - 1 when
+ * reserve = 0) such that, with active(item) = its need floor entries with j <= lim[u] of the largest words (all of them if it has no
+ * more), no row has more than `reserve` active entries in its zone.  A round = items (sel[item] = the need-th largest admissible word, 0 if
+ * there are no more than need) then users (a row with more than `reserve` zone entries whose w >= sel[id] lowers lim[u] to the position
+ * of the reserve-th).  Limits only fall, a round after convergence changes nothing, and the fixed point does not depend on the order or
+ * the batching of the rounds: lists are bit-identical from run to run.  No floating-point atomics, no sort.
+ * The list of row u: t = the smallest value for which the active entries at positions >= k - t are at most t (then exactly t; t <=
+ * reserve); the first k - t candidates of the row, then those active entries in candidate order, each with its original logit bit for
+ * bit; a row that ends before k - t is padded with id -1 / score -inf.  Rows stay in score order, every active entry is served, an item is
+ * in at least min(need, held) lists; need all 0, or reserve = 0, gives the first k candidates bit for bit.
+ *
+ * ltg_floor_index   once per candidate table: the per-item index of the entries (ltg_cap_index's), lim <- c_in - 1, state <- 0.
+ * ltg_floor_rounds  enqueues n_rounds rounds (1 .. LTG_FLOOR_MAX_ROUNDS) back to back, two launches each.  Converged when a round lowered
+ *                   no limit: state[4] < state[1] after a batch.  k, reserve, need, lse and the candidates must be the same in every call
+ *                   of one matching.
+ * ltg_floor_finish  recomputes sel from the limits as they stand and writes score_out / id_out [n_rows][k]; active_out (uint8 [n_rows][c_in],
+ *                   may be NULL) = the matching itself, held_out (int32 [n_items_global], may be NULL) = the active entries per item.
+ *                   Before convergence a row counts only its first `reserve` active zone entries.
+ * state (device, int32 [LTG_FLOOR_STATE]): [0] limit lowerings so far, [1] rounds run, [2] floor items that hold fewer entries than their
+ * floor, [3] rows that differ from the plain top-k (t > 0), [4] the last round that lowered a limit (0: none), [5] inserted slots (the sum
+ * of t), [6] floor items, [7] 0; [2], [3], [5..7] are filled by ltg_floor_finish.  ws: ltg_floor_ws_bytes(n_rows, c_in, n_items_global)
+ * bytes, 256-byte aligned, the same buffer through index, rounds and finish; nothing relies on what it held before the index.
+ * LTG_EINVAL before any HIP call: a NULL pointer (lse, active_out, held_out and stream excepted), n_rows < 0, c_in outside [1, 1024], k
+ * outside [1, c_in], reserve outside [0, k], n_items_global < 1, n_rows * c_in >= 2^31, n_rounds outside [1, LTG_FLOOR_MAX_ROUNDS], ws_bytes
+ * too small (ltg_floor_ws_bytes returns 0 for sizes it refuses).  n_rows = 0 returns LTG_OK and launches nothing (the arguments are still
+ * checked). */
+#define LTG_FLOOR_STATE 8
+#define LTG_FLOOR_MAX_ROUNDS 64
+size_t ltg_floor_ws_bytes(int32_t n_rows, int32_t c_in, int32_t n_items_global);
+int ltg_floor_index(int32_t n_rows, int32_t c_in, const int32_t* cand_id, int32_t n_items_global, int32_t* state /* device [LTG_FLOOR_STATE] */,
+                    void* ws, size_t ws_bytes, ltg_stream stream);
+int ltg_floor_rounds(int32_t n_rows, int32_t c_in, const float* cand_score, const int32_t* cand_id, const float* lse /* may be NULL */,
+                     const int32_t* need /* device [n_items_global] */, int32_t n_items_global, int32_t k, int32_t reserve, int32_t n_rounds,
+                     int32_t* state, void* ws, size_t ws_bytes, ltg_stream stream);
+int ltg_floor_finish(int32_t n_rows, int32_t c_in, const float* cand_score, const int32_t* cand_id, const float* lse /* may be NULL */,
+                     const int32_t* need, int32_t n_items_global, int32_t k, int32_t reserve, float* score_out, int32_t* id_out,
+                     uint8_t* active_out /* may be NULL */, int32_t* held_out /* may be NULL */, int32_t* state, void* ws, size_t ws_bytes,
+                     ltg_stream stream);
+
 /* Verification helper of the LTG_PREC_FP8 mode: out[i] = the value the fp8 GEMM operands carry for in[i]
  * (clamp to +-448, round to nearest-even OCP e4m3) -- lets a test pin its CPU model of the rounding to the hardware. */
 int ltg_fp8_roundtrip(const float* in, float* out, int32_t n, ltg_stream stream);

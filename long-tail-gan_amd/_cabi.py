@@ -27,6 +27,7 @@ LTG_WHY_MAX_TOP, LTG_WHY_MAX_R = 256, 8      # ltg_topk_explain: the entries exp
 LTG_CAL_MAX_CLASSES = 9                      # ltg_hist_groups / ltg_topk_calibrate: n_groups + 1 classes at the most
 LTG_CAP_STATE, LTG_CAP_MAX_ROUNDS = 8, 64    # ltg_cap_*: the int32 words of the state block, the rounds one call enqueues at the most
 LTG_SHARE_STATE = 8                          # ltg_topk_share: the int32 words of its state block
+LTG_FLOOR_STATE, LTG_FLOOR_MAX_ROUNDS = 8, 64  # ltg_floor_*: the int32 words of the state block, the rounds one call enqueues at the most
 
 ERRORS = {0: "LTG_OK", -1: "LTG_EINVAL", -2: "LTG_EWORKSPACE", -3: "LTG_ELAUNCH"}
 
@@ -193,6 +194,11 @@ SYMBOLS = {
     "ltg_cap_index": (C.c_int, [C.c_int32, C.c_int32, vp, C.c_int32, vp, vp, C.c_size_t, vp]),
     "ltg_cap_rounds": (C.c_int, [C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, C.c_size_t, vp]),
     "ltg_cap_finish": (C.c_int, [C.c_int32, C.c_int32, vp, vp, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_size_t, vp]),
+    "ltg_floor_ws_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "ltg_floor_index": (C.c_int, [C.c_int32, C.c_int32, vp, C.c_int32, vp, vp, C.c_size_t, vp]),
+    "ltg_floor_rounds": (C.c_int, [C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, C.c_size_t, vp]),
+    "ltg_floor_finish": (C.c_int, [C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, C.c_size_t,
+                                   vp]),
     "ltg_share_ws_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "ltg_topk_share": (C.c_int, [C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int32, C.c_int64, vp, vp, vp, vp, C.c_size_t, vp]),
     "ltg_item_audience_ws_bytes": (C.c_size_t, [C.POINTER(ltg_config), C.c_int32, C.c_int32, C.c_int32]),

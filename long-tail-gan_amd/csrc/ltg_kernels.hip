@@ -174,6 +174,7 @@ __global__ __launch_bounds__(64) void k_gate_set(LtgGate g, LtgGate g2 = LTG_NO_
 #include "ltg_topk.h"
 #include "ltg_audience.h"
 #include "ltg_cap.h"
+#include "ltg_floor.h"
 #include "ltg_share.h"
 #include "ltg_longtail.h"
 #include "ltg_neighbors.h"
@@ -2141,6 +2142,99 @@ int ltg_topk_share(int32_t n_rows, int32_t m_in, const float* score_pro, const i
     hipLaunchKernelGGL(k_share_finish, dim3(row_blocks), dim3(SH_NT), 0, st, n_rows, m_in, k, (int64_t)want, score_pro, id_pro, score_rest,
                        id_rest, (const uint64_t*)w.words, (const int32_t*)w.row_a, (const int32_t*)w.row_kk, (const sh_sel*)w.sel, score_out,
                        id_out, state);
+    return check_launch();
+}
+
+// Exposure-floor top-K lists.  The workspace holds the selection words, the per-item index (offsets, cursors, entry numbers),
+// the limits and one int32 per row, and the held counts; its layout is a function of (n_rows, c_in, n_items_global) alone.  Every refusal
+// comes before the first HIP call.
+static_assert(FL_STATE == LTG_FLOOR_STATE && CP_STATE == LTG_FLOOR_STATE, "the index zeroes the floor's state block with the cap's kernel");
+struct FloorWs {
+    uint64_t* sel;
+    int32_t *off, *cur, *seg, *lim, *row_t, *held;
+    size_t bytes;
+};
+static FloorWs floor_carve(int32_t n_rows, int32_t c_in, int32_t n_items_global, char* base) {
+    const size_t I = (size_t)n_items_global, E = (size_t)n_rows * (size_t)c_in, N = (size_t)n_rows > 0 ? (size_t)n_rows : 1;
+    FloorWs w;
+    size_t o = 0;
+    auto take = [&](size_t bytes) {                  // (no pointer arithmetic on the null base of the size query)
+        char* p = base ? base + o : nullptr;
+        o += align_up(bytes);
+        return p;
+    };
+    w.sel = (uint64_t*)take(I * sizeof(uint64_t));
+    w.off = (int32_t*)take((I + 1) * sizeof(int32_t));
+    w.cur = (int32_t*)take(I * sizeof(int32_t));
+    w.seg = (int32_t*)take((E > 0 ? E : 1) * sizeof(int32_t));
+    w.lim = (int32_t*)take(N * sizeof(int32_t));
+    w.row_t = (int32_t*)take(N * sizeof(int32_t));
+    w.held = (int32_t*)take(I * sizeof(int32_t));
+    w.bytes = o;
+    return w;
+}
+static bool floor_ws_ok(int32_t n_rows, int32_t c_in, int32_t n_items_global, const void* ws, size_t ws_bytes) {
+    return cap_args_ok(n_rows, c_in, n_items_global) && ws && ws_bytes >= floor_carve(n_rows, c_in, n_items_global, nullptr).bytes;
+}
+
+size_t ltg_floor_ws_bytes(int32_t n_rows, int32_t c_in, int32_t n_items_global) {
+    return cap_args_ok(n_rows, c_in, n_items_global) ? floor_carve(n_rows, c_in, n_items_global, nullptr).bytes : 0;
+}
+
+int ltg_floor_index(int32_t n_rows, int32_t c_in, const int32_t* cand_id, int32_t n_items_global, int32_t* state, void* ws, size_t ws_bytes,
+                    ltg_stream stream) {
+    if (!floor_ws_ok(n_rows, c_in, n_items_global, ws, ws_bytes) || !cand_id || !state) return LTG_EINVAL;
+    if (n_rows == 0) return LTG_OK;
+    const FloorWs w = floor_carve(n_rows, c_in, n_items_global, (char*)ws);
+    const hipStream_t st = (hipStream_t)stream;
+    const int I = n_items_global, row_blocks = (n_rows + CP_NT / 64 - 1) / (CP_NT / 64);
+    clear_errors();
+    hipLaunchKernelGGL(k_cap_zero, dim3((I + CP_NT - 1) / CP_NT), dim3(CP_NT), 0, st, I, w.cur, state);
+    hipLaunchKernelGGL(k_cap_count<false>, dim3(row_blocks), dim3(CP_NT), 0, st, n_rows, c_in, cand_id, I, w.cur, (const int32_t*)w.off, w.seg);
+    hipLaunchKernelGGL(k_cap_scan, dim3(1), dim3(1024), 0, st, I, w.cur, w.off, w.sel);
+    hipLaunchKernelGGL(k_cap_count<true>, dim3(row_blocks), dim3(CP_NT), 0, st, n_rows, c_in, cand_id, I, w.cur, (const int32_t*)w.off, w.seg);
+    hipLaunchKernelGGL(k_floor_lim, dim3((n_rows + FL_NT - 1) / FL_NT), dim3(FL_NT), 0, st, n_rows, c_in, w.lim);
+    return check_launch();
+}
+
+int ltg_floor_rounds(int32_t n_rows, int32_t c_in, const float* cand_score, const int32_t* cand_id, const float* lse, const int32_t* need,
+                     int32_t n_items_global, int32_t k, int32_t reserve, int32_t n_rounds, int32_t* state, void* ws, size_t ws_bytes,
+                     ltg_stream stream) {
+    if (!floor_ws_ok(n_rows, c_in, n_items_global, ws, ws_bytes) || !cand_score || !cand_id || !need || !state || k < 1 || k > c_in ||
+        reserve < 0 || reserve > k || n_rounds < 1 || n_rounds > LTG_FLOOR_MAX_ROUNDS)
+        return LTG_EINVAL;
+    if (n_rows == 0) return LTG_OK;
+    const FloorWs w = floor_carve(n_rows, c_in, n_items_global, (char*)ws);
+    const hipStream_t st = (hipStream_t)stream;
+    const int row_blocks = (n_rows + FL_NT / 64 - 1) / (FL_NT / 64);
+    clear_errors();
+    for (int r = 0; r < n_rounds; ++r) {
+        hipLaunchKernelGGL(k_floor_select, dim3(n_items_global), dim3(FL_NT), 0, st, c_in, k, reserve, cand_score, lse, need,
+                           (const int32_t*)w.off, (const int32_t*)w.seg, (const int32_t*)w.lim, w.sel, (int32_t*)nullptr, state, 1);
+        hipLaunchKernelGGL(k_floor_users, dim3(row_blocks), dim3(FL_NT), 0, st, n_rows, c_in, k, reserve, cand_score, cand_id, lse, need,
+                           n_items_global, (const uint64_t*)w.sel, w.lim, state);
+    }
+    return check_launch();
+}
+
+int ltg_floor_finish(int32_t n_rows, int32_t c_in, const float* cand_score, const int32_t* cand_id, const float* lse, const int32_t* need,
+                     int32_t n_items_global, int32_t k, int32_t reserve, float* score_out, int32_t* id_out, uint8_t* active_out,
+                     int32_t* held_out, int32_t* state, void* ws, size_t ws_bytes, ltg_stream stream) {
+    if (!floor_ws_ok(n_rows, c_in, n_items_global, ws, ws_bytes) || !cand_score || !cand_id || !need || !score_out || !id_out || !state ||
+        k < 1 || k > c_in || reserve < 0 || reserve > k)
+        return LTG_EINVAL;
+    if (n_rows == 0) return LTG_OK;
+    const FloorWs w = floor_carve(n_rows, c_in, n_items_global, (char*)ws);
+    const hipStream_t st = (hipStream_t)stream;
+    clear_errors();
+    // the selection words once more, from the limits as they stand (after convergence: the same words), and held <- 0
+    hipLaunchKernelGGL(k_floor_select, dim3(n_items_global), dim3(FL_NT), 0, st, c_in, k, reserve, cand_score, lse, need, (const int32_t*)w.off,
+                       (const int32_t*)w.seg, (const int32_t*)w.lim, w.sel, w.held, state, 0);
+    hipLaunchKernelGGL(k_floor_finish, dim3((n_rows + FL_NT / 64 - 1) / (FL_NT / 64)), dim3(FL_NT), 0, st, n_rows, c_in, k, reserve, cand_score,
+                       cand_id, lse, need, n_items_global, (const uint64_t*)w.sel, (const int32_t*)w.lim, score_out, id_out, active_out, w.held,
+                       w.row_t);
+    hipLaunchKernelGGL(k_floor_stats, dim3(1), dim3(1024), 0, st, n_rows, n_items_global, need, (const int32_t*)w.held,
+                       (const int32_t*)w.row_t, held_out, state);
     return check_launch();
 }
 

@@ -985,6 +985,49 @@ class Engine:
         cabi.check(self.lib.ltg_topk_share(n, m_in, _ptr(score_pro), _ptr(id_pro), _ptr(score_rest), _ptr(id_rest), int(k), int(want),
                                            _ptr(score_out), _ptr(id_out), _ptr(state), _ptr(ws), ws.numel(), self.stream()), "ltg_topk_share")
 
+    def floor_ws_bytes(self, n_rows, c_in, n_items=None):
+        """the workspace of the exposure-floor matching of n_rows x c_in candidates over n_items (default: the catalogue) global ids"""
+        return int(self.lib.ltg_floor_ws_bytes(int(n_rows), int(c_in), int(self.I_global if n_items is None else n_items)))
+
+    def _floor_check(self, cand_s, cand_i, lse, need, state, ws, n_items):
+        n, c = (int(x) for x in cand_i.shape)
+        assert cand_i.dtype == torch.int32 and cand_i.is_contiguous()
+        assert cand_s is None or (tuple(cand_s.shape) == (n, c) and cand_s.dtype == torch.float32 and cand_s.is_contiguous())
+        assert lse is None or (lse.dtype == torch.float32 and lse.is_contiguous() and lse.numel() >= n)
+        assert need is None or (need.dtype == torch.int32 and need.is_contiguous())
+        assert state.dtype == torch.int32 and state.is_contiguous() and state.numel() >= cabi.LTG_FLOOR_STATE
+        assert ws.dtype == torch.uint8 and ws.numel() >= self.floor_ws_bytes(n, c, n_items)
+        return n, c
+
+    def floor_index(self, cand_i, n_items, state, ws):
+        """the start of a floor matching over the candidates cand_i [rows, c] int32 (GLOBAL ids as topk / topk_merge write them): the
+        per-item index into ws, the limits at c - 1 and state [LTG_FLOOR_STATE] int32 zeroed (ltg_floor_index)"""
+        n, c = self._floor_check(None, cand_i, None, None, state, ws, n_items)
+        cabi.check(self.lib.ltg_floor_index(n, c, _ptr(cand_i), int(n_items), _ptr(state), _ptr(ws), ws.numel(), self.stream()),
+                   "ltg_floor_index")
+
+    def floor_rounds(self, cand_s, cand_i, lse, need, k, reserve, n_rounds, state, ws):
+        """n_rounds item / user rounds of the matching floor_index started: cand_s [rows, c] float32 logits, lse [rows] float32 or None
+        (None: items rank users by the logit, else by logit - lse), need [n_items] int32 per GLOBAL id (0: no floor), reserve: the slots at
+        the end of a list that floor items may take (ltg_floor_rounds).  Converged when state[4] < state[1]: the last round lowered no limit."""
+        n, c = self._floor_check(cand_s, cand_i, lse, need, state, ws, int(need.numel()))
+        cabi.check(self.lib.ltg_floor_rounds(n, c, _ptr(cand_s), _ptr(cand_i), _ptr(lse), _ptr(need), int(need.numel()), int(k), int(reserve),
+                                             int(n_rounds), _ptr(state), _ptr(ws), ws.numel(), self.stream()), "ltg_floor_rounds")
+
+    def floor_finish(self, cand_s, cand_i, lse, need, k, reserve, score_out, id_out, state, ws, active_out=None, held_out=None):
+        """the lists of the matching as it stands: score_out / id_out [rows, k] = every row's first k - t candidates, then its t active
+        entries behind them, each with its original logit; active_out [rows, c] uint8 or None: the matching itself; held_out [n_items]
+        int32 or None: the active entries per item; state[2], [3], [5], [6] = items short of their floor / rows changed / inserted slots /
+        floor items (ltg_floor_finish)"""
+        n, c = self._floor_check(cand_s, cand_i, lse, need, state, ws, int(need.numel()))
+        assert tuple(score_out.shape) == tuple(id_out.shape) == (n, int(k)) and score_out.is_contiguous() and id_out.is_contiguous()
+        assert score_out.dtype == torch.float32 and id_out.dtype == torch.int32
+        assert active_out is None or (tuple(active_out.shape) == (n, c) and active_out.dtype == torch.uint8 and active_out.is_contiguous())
+        assert held_out is None or (held_out.numel() >= need.numel() and held_out.dtype == torch.int32 and held_out.is_contiguous())
+        cabi.check(self.lib.ltg_floor_finish(n, c, _ptr(cand_s), _ptr(cand_i), _ptr(lse), _ptr(need), int(need.numel()), int(k), int(reserve),
+                                             _ptr(score_out), _ptr(id_out), _ptr(active_out), _ptr(held_out), _ptr(state), _ptr(ws),
+                                             ws.numel(), self.stream()), "ltg_floor_finish")
+
     # ------------------------------------------------------------------ views in the reference's shapes
     def generator_params_tf(self):
         """The 8 tensors in the reference's order and TF shapes (MultiVAE.py:129-141); W_p1 is a

@@ -5,6 +5,7 @@
         [--split test|validation] [--groups niche|pop:N] [--min-slots NAME:M[,NAME:M...]] [--k 100] [--keep-prob 0.75] [--json report.json]
         [--diversify LAMBDA] [--candidates N] [--div-space decoder|encoder] [--calibrate LAMBDA]
         [--cap C|NAME:C[,NAME:C...]] [--cap-candidates N] [--cap-score logprob|logit] [--share NAME[+NAME...]:S]
+        [--floor M|NAME:M[,NAME:M...] --floor-reserve R [--floor-candidates N] [--floor-score logprob|logit]]
 
 restores a checkpoint written by train.py, runs test.py's forward over the users of `<split>_tr.csv` ONCE (chunks of 20 000 users,
 dropout on with keep_prob 0.75 by default: Q3, RNG counter 2*10^9 + first row of the chunk), keeps each user's top-K list on the GPU
@@ -53,6 +54,17 @@ then ltg_topk_share once over the whole split): the promoted slots go to the use
 in score order, and a target the plain lists already meet changes nothing.  The last line is then
 `share@K: <names> <plain share> -> <reached share> (target S), <users> rows changed, price <cost>`, price = the score difference of the
 dearest swap made.
+
+--floor M (M >= 0: every item) or --floor NAME:M[,NAME:M...] (only the items of those groups of --groups) with --floor-reserve R (0 <= R
+<= K; not together with --min-slots, --diversify, --calibrate, --cap or --share) serves lists in which every floor item appears at least M
+times where enough users hold it among their candidates, before the report reads the lists (trainer.ExposureFloor: ltg_topk at
+--floor-candidates N, then ltg_floor_index / ltg_floor_rounds / ltg_floor_finish once over the whole split): the stable matching in which
+an item proposes to the users that hold it among their N best items, best --floor-score first (logprob: logit - lse, the default; logit),
+and a user gives up at most the last R slots of the list, to the proposals it likes best.  The first K - R entries of every list are the
+plain ones and every list stays in score order.  N defaults to min(1024, 4 K) and must lie in [K, 1024], K = max(100, --k).  The last
+line is then `floor@K: <items> floor items, <items> short of their floor, below the floor <plain> -> <served>, <slots> inserted slots,
+<users> rows changed, <rounds> rounds`: short of their floor = the matching holds fewer than M users for the item; below the floor = the
+floor items in fewer than M of the plain / the served lists.
 """
 from __future__ import annotations
 
@@ -225,6 +237,82 @@ def cap_line(plain_ids, ids, cap_vec, stats, k):
         k, int(before.max()) if n_items else 0, int(after.max()) if n_items else 0, at_cap, stats["short"], stats["rounds"])
 
 
+def parse_floor(spec, names):
+    """'M' -> M; 'NAME:M[,NAME:M...]' -> {group index: M}; an unknown name, a name twice or M < 0 raises ValueError"""
+    try:
+        m = int(spec)
+    except ValueError:
+        m = None
+    if m is not None:
+        if m < 0:
+            raise ValueError("--floor takes M >= 0, got %r" % (spec,))
+        return m
+    floors = {}
+    for part in spec.split(","):
+        name, sep, m = part.strip().rpartition(":")
+        try:
+            m = int(m) if sep else -1
+        except ValueError:
+            m = -1
+        if not sep or m < 0:
+            raise ValueError("--floor takes M or NAME:M[,NAME:M...] with M >= 0, got %r" % (part,))
+        if name not in names:
+            raise ValueError("--floor: unknown group %r (the groups are %s)" % (name, ", ".join(names)))
+        if names.index(name) in floors:
+            raise ValueError("--floor names group %r twice" % (name,))
+        floors[names.index(name)] = m
+    return floors
+
+
+def add_floor_args(ap):
+    """the options of the exposure-floor lists (trainer.ExposureFloor), shared with recommend.py"""
+    ap.add_argument("--floor", default=None, metavar="M|NAME:M[,NAME:M...]")
+    ap.add_argument("--floor-reserve", type=int, default=None, metavar="R")
+    ap.add_argument("--floor-candidates", type=int, default=None, metavar="N")
+    ap.add_argument("--floor-score", choices=("logprob", "logit"), default=None)
+
+
+def check_floor_args(ap, a, k):
+    """refuses (ap.error) what trainer.ExposureFloor would refuse for lists of k entries, and the combination with the other rules;
+    a.floors = the parsed --floor (None without the option)"""
+    a.floors = None
+    if a.floor is None:
+        if a.floor_reserve is not None or a.floor_candidates is not None or a.floor_score is not None:
+            ap.error("--floor-reserve, --floor-candidates and --floor-score need --floor")
+        return
+    if a.min_slots is not None or a.diversify is not None or a.calibrate is not None or a.cap is not None or a.share is not None:
+        ap.error("--floor cannot be combined with --min-slots, --diversify, --calibrate, --cap or --share")
+    if a.floor_reserve is None:
+        ap.error("--floor needs --floor-reserve R")
+    if not 0 <= a.floor_reserve <= k:
+        ap.error("--floor-reserve must be in [0, k] = [0, %d], got %d" % (k, a.floor_reserve))
+    try:
+        a.floors = parse_floor(a.floor, group_names(a.group_kind, a.n_groups))
+    except ValueError as e:
+        ap.error(str(e))
+    if a.floor_candidates is not None and not k <= a.floor_candidates <= 1024:
+        ap.error("--floor-candidates must be in [k, 1024] = [%d, 1024], got %d" % (k, a.floor_candidates))
+
+
+def make_floor(a, labels, n_groups):
+    """the ExposureFloor of the parsed options (labels: the --groups labels, needed for floors by group only)"""
+    from ltgan.serving import ExposureFloor
+    floor = (labels, n_groups, a.floors) if isinstance(a.floors, dict) else a.floors
+    return ExposureFloor(floor, a.floor_reserve, candidates=a.floor_candidates, score=a.floor_score or "logprob")
+
+
+def floor_line(plain_ids, ids, need_vec, stats, k):
+    """the line --floor adds: the floor items, those the matching leaves short of their floor, the floor items in fewer lists than their
+    floor, plain top-k -> served (plain_ids / ids [n_users, k], padding -1; need_vec: the floor per item), the inserted slots, the rows
+    changed and the rounds (ExposureFloor.stats())"""
+    need = np.asarray(need_vec)
+    before = np.bincount(plain_ids[plain_ids >= 0], minlength=len(need))
+    after = np.bincount(ids[ids >= 0], minlength=len(need))
+    return ("floor@%d: %d floor items, %d short of their floor, below the floor %d -> %d, %d inserted slots, %d rows changed, %d rounds" % (
+        k, stats["floor_items"], stats["short_items"], int(((need > 0) & (before < need)).sum()), int(((need > 0) & (after < need)).sum()),
+        stats["inserted"], stats["rows_changed"], stats["rounds"]))
+
+
 def parse_share(spec, names):
     """'NAME[+NAME...]:S' -> (sorted group indices, S); an unknown name, a name twice, no name or S outside [0, 1] raises ValueError"""
     head, sep, val = spec.strip().rpartition(":")
@@ -308,6 +396,7 @@ def parse_args(argv):
     add_calibrate_args(ap)
     add_cap_args(ap)
     add_share_args(ap)
+    add_floor_args(ap)
     a = ap.parse_args(argv)
     try:
         a.group_kind, a.n_groups = parse_groups(a.groups)
@@ -329,6 +418,7 @@ def parse_args(argv):
     check_calibrate_args(ap, a)
     check_cap_args(ap, a, max(K_NDCG, K_R1, K_R2, a.k))
     check_share_args(ap, a)
+    check_floor_args(ap, a, max(K_NDCG, K_R1, K_R2, a.k))
     return a
 
 
@@ -438,12 +528,13 @@ def longtail(args, h0_size, h1_size, h2_size, h3_size, LEARNING_RATE, precision=
     cal = Calibrate(labels, len(names), args.calibrate) if getattr(args, "calibrate", None) is not None else None
     cap = make_cap(args, labels, len(names)) if getattr(args, "caps", None) is not None else None
     share = make_share(args, labels, len(names)) if getattr(args, "shares", None) is not None else None
+    floor = make_floor(args, labels, len(names)) if getattr(args, "floors", None) is not None else None
     if world > 1:
         rec = ShardedRecommender(eng, EvalData(tr, te, eng.device, item_lo=lo, item_hi=hi), k=report.k, chunk=batch_size_test, report=report,
-                                 rule=rule, diversify=div, calibrate=cal, cap=cap, share=share)
+                                 rule=rule, diversify=div, calibrate=cal, cap=cap, share=share, floor=floor)
     else:
         rec = Recommender(eng, EvalData(tr, te, eng.device), k=report.k, chunk=batch_size_test, report=report, rule=rule, diversify=div,
-                          calibrate=cal, cap=cap, share=share)
+                          calibrate=cal, cap=cap, share=share, floor=floor)
     ids, _ = rec.run(rng_step=RNG_STEP, keep_prob=args.keep_prob)
     rep = aggregate(*report.table(), labels, names, args.k)
     rep.update(split=args.split, groups_spec=args.groups)
@@ -457,6 +548,8 @@ def longtail(args, h0_size, h1_size, h2_size, h3_size, LEARNING_RATE, precision=
         print(cap_line(cap.plain_ids(report.k), ids, cap.cap_vector(), cap.stats(), report.k))
     if share is not None:
         print(share_line([names[g] for g in share.promote], share.stats(), report.k))
+    if floor is not None:
+        print(floor_line(floor.plain_ids(report.k), ids, floor.need_vector(), floor.stats(), report.k))
     if args.json and rank == 0:
         write_json(rep, args.json)
     close_model(world)

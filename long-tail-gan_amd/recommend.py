@@ -7,6 +7,7 @@
         [--explain R] [--explain-top N] [--explain-space decoder|encoder] [--explain-metric cosine|dot] [--why why.tsv]
         [--calibrate LAMBDA] [--cap C|NAME:C[,NAME:C...]] [--cap-candidates N] [--cap-score logprob|logit]
         [--share NAME[+NAME...]:S]
+        [--floor M|NAME:M[,NAME:M...] --floor-reserve R [--floor-candidates N] [--floor-score logprob|logit]]
 
 restores a checkpoint written by train.py, runs test.py's forward over the users of `<split>_tr.csv` (chunks of 20 000 users,
 dropout on with keep_prob 0.75 by default: Q3, RNG counter 2*10^9 + first row of the chunk) and keeps each user's k best items, the
@@ -54,6 +55,16 @@ whole split): where `--min-slots niche:30` forces 30 niche entries on every user
 swaps cost the least score.  Every list stays in score order; a target the plain lists already meet changes nothing.  The last stdout
 line is `share@k: <names> <plain share> -> <reached share> (target S), <users> rows changed, price <cost>`, price = the score difference
 of the dearest swap made.
+
+--floor M (M >= 0: every item) or --floor NAME:M[,NAME:M...] (only the items of those groups of --groups) with --floor-reserve R (0 <= R
+<= k; not together with --min-slots, --diversify, --calibrate, --cap or --share) serves lists in which every floor item appears at least M
+times where enough users hold it among their candidates (trainer.ExposureFloor: ltg_topk at --floor-candidates N, then ltg_floor_index /
+ltg_floor_rounds / ltg_floor_finish once over the whole split): the dual of --cap, the first audience of a new or niche item.  An item
+proposes to the users that hold it among their N best items, best --floor-score first (logprob: logit - lse, the default; logit), and a
+user gives up at most the last R slots of the list, to the proposals it likes best; the first k - R entries of every list are the plain
+ones and every list stays in score order.  N defaults to min(1024, 4 k) and must lie in [k, 1024].  The last stdout line is `floor@k:
+<items> floor items, <items> short of their floor, below the floor <plain> -> <served>, <slots> inserted slots, <users> rows changed,
+<rounds> rounds`.
 """
 from __future__ import annotations
 
@@ -90,6 +101,7 @@ def parse_args(argv):
     lt.add_calibrate_args(ap)
     lt.add_cap_args(ap)
     lt.add_share_args(ap)
+    lt.add_floor_args(ap)
     ap.add_argument("--explain", type=int, default=None, metavar="R")
     ap.add_argument("--explain-top", type=int, default=None, metavar="N")
     ap.add_argument("--explain-space", choices=("decoder", "encoder"), default=None)
@@ -111,6 +123,7 @@ def parse_args(argv):
     lt.check_calibrate_args(ap, a)
     lt.check_cap_args(ap, a, a.k)
     lt.check_share_args(ap, a)
+    lt.check_floor_args(ap, a, a.k)
     if a.explain is None:
         if a.explain_top is not None or a.explain_space is not None or a.explain_metric is not None or a.why is not None:
             ap.error("--explain-top, --explain-space, --explain-metric and --why need --explain")
@@ -213,15 +226,19 @@ def recommend(args, h0_size, h1_size, h2_size, h3_size, LEARNING_RATE, precision
         labels, names = lt.build_groups(d, args.group_kind, args.n_groups, n_items)
         share = lt.make_share(args, labels, len(names))
         share_names = [names[g] for g in share.promote]
+    floor = None
+    if getattr(args, "floors", None) is not None:
+        labels, names = lt.build_groups(d, args.group_kind, args.n_groups, n_items) if isinstance(args.floors, dict) else (None, ())
+        floor = lt.make_floor(args, labels, len(names))
     why = None
     if getattr(args, "explain", None) is not None:
         why = Explain(args.explain, top=args.explain_top, space=args.explain_space or "decoder", metric=args.explain_metric or "cosine")
     if world > 1:
         rec = ShardedRecommender(eng, EvalData(tr, te, eng.device, item_lo=lo, item_hi=hi), k=args.k, chunk=batch_size_test, rule=rule,
-                                 diversify=div, explain=why, calibrate=cal, cap=cap, share=share)
+                                 diversify=div, explain=why, calibrate=cal, cap=cap, share=share, floor=floor)
     else:
         rec = Recommender(eng, EvalData(tr, te, eng.device), k=args.k, chunk=batch_size_test, rule=rule, diversify=div, explain=why,
-                          calibrate=cal, cap=cap, share=share)
+                          calibrate=cal, cap=cap, share=share, floor=floor)
     ids, scores = rec.run(rng_step=RNG_STEP, keep_prob=args.keep_prob)
     m = long_tail_summary(ids, niche, n_items, te)
     why_tab = why.table() if why is not None else None
@@ -239,6 +256,8 @@ def recommend(args, h0_size, h1_size, h2_size, h3_size, LEARNING_RATE, precision
         print(lt.cap_line(cap.plain_ids(args.k), ids, cap.cap_vector(), cap.stats(), args.k))
     if share is not None:
         print(lt.share_line(share_names, share.stats(), args.k))
+    if floor is not None:
+        print(lt.floor_line(floor.plain_ids(args.k), ids, floor.need_vector(), floor.stats(), args.k))
     close_model(world)
     return ids, scores, m
 

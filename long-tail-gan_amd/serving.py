@@ -1,6 +1,7 @@
 """Everything that serves a trained model: validation / test scoring, top-K lists (plain, with minimum slots per item group, diversified,
-calibrated to each user's history, capped in how many lists an item may appear, with a set share of all slots for some item groups),
-the long-tail report read off them, the explanation of every list entry (the user's history items nearest to it), similar-item lists,
+calibrated to each user's history, capped in how many lists an item may appear, with a set share of all slots for some item groups,
+with a floor under how many lists an item appears in), the long-tail report read off them, the explanation of every list entry (the
+user's history items nearest to it), similar-item lists,
 item audiences (the k likeliest users of an item, gathered over the same chunk walk), and the set-up the CLIs (test.py, recommend.py, longtail.py, similar.py, audience.py) share.
 
 One chunk walk (Recommender.run) serves every kind of list, unsharded and over item shards: the forward sits behind one method that
@@ -15,7 +16,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from ._cabi import LTG_CAP_MAX_ROUNDS, LTG_CAP_STATE, LTG_METRIC, LTG_SHARE_STATE, LTG_SPACE, LtgError
+from ._cabi import LTG_CAP_MAX_ROUNDS, LTG_CAP_STATE, LTG_FLOOR_MAX_ROUNDS, LTG_FLOOR_STATE, LTG_METRIC, LTG_SHARE_STATE, LTG_SPACE, LtgError
 
 EVAL_LOGITS_BYTES = 2 << 30
 
@@ -488,6 +489,132 @@ class ExposureCap:
         return dict(self._stats)
 
 
+class ExposureFloor:
+    """A serve-time rule over the WHOLE split, passed as `floor=` to a Recommender / ShardedRecommender, the dual of ExposureCap: every
+    item with a floor M reaches M of the served lists if that many users hold it among their candidates and can spare a slot -- the
+    first audience a new or niche item needs.  floor: an int (every item), an int array per GLOBAL item id (0: no floor), or (labels,
+    n_groups, {group index: M}) -- only the items of those groups get a floor (labels: one uint8 per GLOBAL id, the labels a
+    LongTailReport takes).  reserve: how many of the last slots of a user's list floor items may take, 0 <= reserve <= k; the first
+    k - reserve entries of every list are the plain ones.  The lists are the item-optimal stable matching of item-proposing deferred
+    acceptance: an item proposes to the users that hold it among their `candidates` best items (default min(1024, 4 k)), best `score`
+    first -- `logprob`: logit - lse, `logit`: the raw logit, equal scores the lower user row -- and a user keeps, of the proposals behind
+    position k - reserve, the `reserve` it likes best.  Every list stays in score order and every entry keeps its logit.  Like the cap
+    the rows depend on each other: the chunk walk only stores every chunk's candidates and lse, and match() runs once after the last
+    chunk -- ltg_floor_index, then ltg_floor_rounds in batches of `batch` rounds until a round lowers no limit, then ltg_floor_finish.
+    The fixed point does not depend on the order or the batching of the rounds, so the table is bit-identical from run to run.  Over
+    item shards every rank holds the same merged candidates and the same full-row lse, so every rank runs the same matching and nothing
+    is exchanged.  After run(): stats(), held()."""
+
+    MAX_C = 1024
+
+    def __init__(self, floor, reserve, candidates=None, score="logprob", batch=4):
+        if score not in ("logprob", "logit"):
+            raise ValueError("score must be logprob or logit")
+        self.score = score
+        self.reserve = int(reserve)
+        if self.reserve != reserve or self.reserve < 0:
+            raise ValueError("reserve is an integer >= 0, got %r" % (reserve,))
+        self.candidates = None if candidates is None else int(candidates)
+        if self.candidates is not None and not 1 <= self.candidates <= self.MAX_C:
+            raise ValueError("candidates must be in [1, %d], got %r" % (self.MAX_C, candidates))
+        self.batch = int(batch)
+        if not 1 <= self.batch <= LTG_FLOOR_MAX_ROUNDS:
+            raise ValueError("batch must be in [1, %d]" % LTG_FLOOR_MAX_ROUNDS)
+        self.uniform = self.need_host = None
+        if isinstance(floor, tuple):
+            labels, n_groups, floors = floor
+            labels = np.ascontiguousarray(np.asarray(labels), dtype=np.uint8)
+            if not 1 <= int(n_groups) <= 8:
+                raise ValueError("n_groups must be in [1, 8]")
+            vec = np.zeros(labels.size, np.int64)
+            for g, mg in dict(floors).items():
+                if not 0 <= int(g) < int(n_groups):
+                    raise ValueError("group index %r outside [0, %d)" % (g, n_groups))
+                vec[labels == int(g)] = int(mg)
+            self.need_host = vec
+        elif np.ndim(floor) == 0:
+            self.uniform = int(floor)
+            if self.uniform != floor:
+                raise ValueError("a uniform floor is an integer, got %r" % (floor,))
+        else:
+            self.need_host = np.asarray(floor).astype(np.int64).reshape(-1)
+        low = self.uniform if self.need_host is None else (int(self.need_host.min()) if self.need_host.size else 0)
+        if low < 0:
+            raise ValueError("a floor must be >= 0")
+        self.c = self.n_items = self.need = self.cand_s = self.cand_i = self.lse = self.state = self.ws = self.held_d = self._stats = None
+
+    @property
+    def needs_lse(self):
+        return self.score == "logprob"
+
+    def bind(self, engine, k, n_users):
+        """the device tables for lists of k entries over a split of n_users"""
+        c = min(self.MAX_C, 4 * k) if self.candidates is None else self.candidates
+        if not 1 <= k <= c <= self.MAX_C:
+            raise ValueError("candidates must be in [k, %d] = [%d, %d], got %d" % (self.MAX_C, k, self.MAX_C, c))
+        if self.reserve > k:
+            raise ValueError("reserve must be in [0, k] = [0, %d], got %d" % (k, self.reserve))
+        if n_users * c >= 2 ** 31:
+            raise ValueError("%d users x %d candidates: the matching indexes fewer than 2^31 entries" % (n_users, c))
+        n_items, dev = int(engine.I_global), engine.device
+        vec = np.full(n_items, self.uniform, np.int64) if self.need_host is None else self.need_host
+        if vec.size != n_items:
+            raise ValueError("floor holds %d items, the catalogue %d" % (vec.size, n_items))
+        self.c, self.n_items = c, n_items
+        self.need = torch.from_numpy(np.minimum(vec, 2 ** 31 - 1).astype(np.int32)).to(dev)
+        self.cand_s = torch.empty(n_users, c, dtype=torch.float32, device=dev)
+        self.cand_i = torch.empty(n_users, c, dtype=torch.int32, device=dev)
+        self.lse = torch.empty(n_users, dtype=torch.float32, device=dev) if self.needs_lse else None
+        self.state = torch.zeros(LTG_FLOOR_STATE, dtype=torch.int32, device=dev)
+        self.held_d = torch.zeros(n_items, dtype=torch.int32, device=dev)
+        self.ws = torch.empty(max(1, engine.floor_ws_bytes(n_users, c, n_items)), dtype=torch.uint8, device=dev)
+
+    def gather(self, lists, acts, tr, n, lo):
+        """the candidates (and lse) of users lo .. lo + n, whose logits `acts` holds, into the tables; lists: the SlabLists they come from"""
+        lists.topk(acts, tr, n, self.c, self.cand_s[lo:lo + n], self.cand_i[lo:lo + n])
+        if self.lse is not None:
+            self.lse[lo:lo + n].copy_(acts.lse[:n])
+
+    def match(self, engine, k, score_out, id_out):
+        """the matching over the gathered tables -> score_out / id_out [n_users, k]"""
+        n = int(self.cand_i.shape[0])
+        if n == 0:
+            self.held_d.zero_()
+            self._stats = dict(rounds=0, lowerings=0, floor_items=int((self.need > 0).sum()), short_items=0, rows_changed=0, inserted=0)
+            return
+        engine.floor_index(self.cand_i, self.n_items, self.state, self.ws)
+        while True:
+            engine.floor_rounds(self.cand_s, self.cand_i, self.lse, self.need, k, self.reserve, self.batch, self.state, self.ws)
+            _, rounds, _, _, last = (int(x) for x in self.state[:5].cpu())
+            if last < rounds:                            # the last round lowered no limit: the fixed point
+                break
+            if rounds > n * self.c + 1:                  # (every round but the last takes at least one position from a row for good)
+                raise LtgError("the floor matching has not converged after %d rounds" % rounds)
+        engine.floor_finish(self.cand_s, self.cand_i, self.lse, self.need, k, self.reserve, score_out, id_out, self.state, self.ws,
+                            held_out=self.held_d)
+        st = [int(x) for x in self.state.cpu()]
+        self._stats = dict(rounds=last + 1, lowerings=st[0], floor_items=st[6], short_items=st[2], rows_changed=st[3], inserted=st[5])
+
+    def plain_ids(self, k):
+        """-> [n_users, k] int32 host array: the plain top-k lists, the first k columns of the candidates"""
+        return self.cand_i[:, :k].cpu().numpy()
+
+    def need_vector(self):
+        """-> [n_items] int32 host array: the floor per GLOBAL item id (0 where none applies)"""
+        return self.need.cpu().numpy()
+
+    def held(self):
+        """-> [n_items] int32 host array: the lists the matching gives every item (0 for items without a floor); an item is served in at
+        least min(floor, held) lists, and held < floor means too few users hold it among their candidates or can spare a slot"""
+        return self.held_d.cpu().numpy()
+
+    def stats(self):
+        """-> dict: rounds (up to and including the first that lowered no limit), lowerings (limit lowerings), floor_items, short_items
+        (floor items that hold fewer entries than their floor), rows_changed (users whose list differs from the plain top-k), inserted
+        (slots that went to entries from behind position k - t, summed over the users)"""
+        return dict(self._stats)
+
+
 class ShareTarget:
     """A serve-time rule over the WHOLE split, passed as `share=` to a Recommender / ShardedRecommender: the item groups `promote` (group
     indices; labels: one uint8 per GLOBAL item id, the labels a LongTailReport takes) get the part `share` of ALL served slots, and the
@@ -708,12 +835,19 @@ class Recommender:
     over the chunks (no forward) feeds the report and the explanations from the capped lists, so item_hits <= cap; not together with rule,
     diversify or calibrate; needs k >= 1; the audience is untouched.  share: a ShareTarget the lists are composed under -- the walk then only
     gathers every chunk's promoted and rest lists, ltg_topk_share runs once after the last chunk, and the same second pass feeds the report
-    and the explanations from the final lists; not together with rule, diversify, calibrate or cap; needs k >= 1."""
+    and the explanations from the final lists; not together with rule, diversify, calibrate or cap; needs k >= 1.  floor: an ExposureFloor
+    the lists are matched under -- the cap's flow: the walk gathers every chunk's candidates, the matching runs once after the last chunk
+    and the same second pass feeds the report and the explanations, so item_hits >= min(floor, held); not together with rule, diversify,
+    calibrate, cap or share; needs k >= 1."""
 
     sharded = False                                  # ShardedRecommender: one rank of `group` per item slab
 
     def __init__(self, engine, ev, k=100, chunk=20000, report=None, rule=None, diversify=None, group=None, audience=None, explain=None,
-                 calibrate=None, cap=None, share=None):
+                 calibrate=None, cap=None, share=None, floor=None):
+        if floor is not None and (rule is not None or diversify is not None or calibrate is not None or cap is not None or share is not None):
+            raise ValueError("floor= cannot be combined with rule=, diversify=, calibrate=, cap= or share=")
+        if int(k) == 0 and floor is not None:
+            raise ValueError("k = 0 serves no user lists: floor= needs k >= 1")
         if share is not None and (rule is not None or diversify is not None or calibrate is not None or cap is not None):
             raise ValueError("share= cannot be combined with rule=, diversify=, calibrate= or cap=")
         if int(k) == 0 and share is not None:
@@ -733,7 +867,7 @@ class Recommender:
         if int(k) == 0 and explain is not None:
             raise ValueError("k = 0 serves no user lists: explain= needs k >= 1")
         self.eng, self.ev, self.k, self.report, self.rule, self.diversify, self.group = engine, ev, int(k), report, rule, diversify, group
-        self.audience, self.explain, self.calibrate, self.cap, self.share = audience, explain, calibrate, cap, share
+        self.audience, self.explain, self.calibrate, self.cap, self.share, self.floor = audience, explain, calibrate, cap, share, floor
         if report is not None:
             report.bind(engine, ev.n, self.k)
         self.chunk = chunk_rows(engine, ev, chunk)
@@ -751,6 +885,9 @@ class Recommender:
             longest = max(longest, cap.c)
         if share is not None:
             share.bind(engine, self.k, ev.n)                             # (its two lists are k long: `longest` is k already)
+        if floor is not None:
+            floor.bind(engine, self.k, ev.n)
+            longest = max(longest, floor.c)
         if explain is not None:
             explain.bind(engine, self.k, ev.n)
             longest = max(longest, explain.top * explain.r)          # (its per-slab lists are [rows * top, r])
@@ -793,6 +930,9 @@ class Recommender:
             if self.share is not None:                   # likewise: only the promoted and the rest lists now
                 self.share.gather(self.lists, self.acts, tr, n, lo)
                 continue
+            if self.floor is not None:                   # likewise: only the candidates now
+                self.floor.gather(self.lists, self.acts, tr, n, lo)
+                continue
             if self.diversify is not None:
                 self.diversify.apply(self.lists, self.acts, tr, n, k, lo, self.scores[lo:hi], self.ids[lo:hi])
             elif self.rule is not None:
@@ -805,7 +945,8 @@ class Recommender:
                 self.report.add(eng, self.ids[lo:hi], te, lo)
             if self.explain is not None:
                 self.explain.apply(self.lists, tr, n, lo, self.ids[lo:hi])
-        whole = self.cap if self.cap is not None else self.share         # a rule over the whole split: its lists exist only now
+        # a rule over the whole split: its lists exist only now
+        whole = self.cap if self.cap is not None else self.share if self.share is not None else self.floor
         if whole is not None:
             whole.match(eng, k, self.scores, self.ids)
             if self.report is not None or self.explain is not None:      # a second pass over the chunks, without a forward
@@ -830,16 +971,16 @@ class ShardedRecommender(Recommender):
     sharded = True
 
     def __init__(self, engine, ev, k=100, group=None, chunk=20000, report=None, rule=None, diversify=None, audience=None, explain=None,
-                 calibrate=None, cap=None, share=None):
+                 calibrate=None, cap=None, share=None, floor=None):
         super().__init__(engine, ev, k=k, chunk=chunk, report=report, rule=rule, diversify=diversify, group=group, audience=audience,
-                         explain=explain, calibrate=calibrate, cap=cap, share=share)
+                         explain=explain, calibrate=calibrate, cap=cap, share=share, floor=floor)
         self.rowpart = torch.zeros(self.chunk * 5, dtype=torch.float32, device=engine.device)
         self.rowpart_all = None
-        if (audience is not None and audience.needs_lse) or (cap is not None and cap.needs_lse):
+        if (audience is not None and audience.needs_lse) or (cap is not None and cap.needs_lse) or (floor is not None and floor.needs_lse):
             self.rowpart_all = torch.zeros(dist.get_world_size(group) * self.chunk * 5, dtype=torch.float32, device=engine.device)
 
     def _forward(self, tr, n, keep_prob, rng_step):
-        """the slab's logits; with an audience or an exposure cap that ranks by log-probability also the FULL-row lse in acts.lse: the slabs' row partials
+        """the slab's logits; with an audience, an exposure cap or an exposure floor that ranks by log-probability also the FULL-row lse in acts.lse: the slabs' row partials
         are all-gathered and combined (ltg_rowstats_combine, as ShardedTrainer.create_phase does) -- one more small collective per chunk"""
         sharded_forward(self.eng, tr, n, self.acts, self.rowpart, keep_prob, rng_step, self.group)
         if self.rowpart_all is not None:

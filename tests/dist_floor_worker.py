@@ -1,0 +1,95 @@
+"""Worker of tests/test_gpu_floor.py::test_sharded_recommender_with_floor: `torchrun --nproc-per-node N` on ONE GPU (gloo backend, every
+rank on cuda:0).  ShardedRecommender with floor= (sharded forward; with score logprob the full-row lse combined from the slabs' partials;
+per slab ltg_topk at the candidates' length; list all-gathers; ltg_topk_merge; then the same matching on every rank, nothing exchanged)
+against the unsharded Recommender on the whole catalogue, bit for bit, for both scores, over several chunks with a short last one and
+with a LongTailReport reading the final lists.
+
+The sharded forward all-reduces the encoder's partial pre-activations, which in general sums in another order than the unsharded forward
+(tests/dist_topk_worker.py).  Here that sum is exact, so the two forwards' logits agree bit for bit (tests/dist_calibrate_worker.py):
+W_q0 holds multiples of 1/64 in [-1, 1], every user has 16 fold-in items and dropout is off.  The full-row lse of the sharded forward is
+combined from per-slab partials and may differ from the unsharded one in its last bits; the worker prints how many rows do."""
+import os
+import sys
+
+import numpy as np
+import torch
+import torch.distributed as dist
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def main():
+    import scipy.sparse as sp
+    from ltgan.dataset import EvalData
+    from ltgan.engine import Engine
+    from ltgan.sharded import ExposureFloor, ShardedRecommender, item_slab
+    from ltgan.trainer import LongTailReport, Recommender
+    I, n_ev = int(sys.argv[1]), int(sys.argv[2])
+    dist.init_process_group("gloo")
+    rank, world = dist.get_rank(), dist.get_world_size()
+    dev = "cuda:0"
+    torch.cuda.set_device(dev)
+    hs = (16, 24, 40, 32)
+    ref = Engine(I, h_sizes=hs, lr=1e-3, precision="bf16", seed=77, d_seed=3, device=dev)
+    lo, hi = item_slab(I, rank, world)
+    eng = Engine(I, h_sizes=hs, lr=1e-3, precision="bf16", seed=77, d_seed=3, device=dev, item_lo=lo, item_hi=hi)
+    rng = np.random.default_rng(3)
+    bias = torch.from_numpy(rng.uniform(1.0, 3.0, I).astype(np.float32)).to(dev)          # (see dist_topk_worker.py)
+    wq0 = torch.from_numpy((rng.integers(-64, 65, (I, ref.H)) / 64.0).astype(np.float32)).to(dev)
+    ref.g_p[7].copy_(bias)
+    eng.g_p[7].copy_(bias[lo:hi])
+    ref.g_p[0].copy_(wq0)
+    eng.g_p[0].copy_(wq0[lo:hi])
+    cols = np.concatenate([rng.choice(I, 16, replace=False) for _ in range(n_ev)])
+    fold = sp.csr_matrix((np.ones(16 * n_ev, np.float32), (np.repeat(np.arange(n_ev), 16), cols)), shape=(n_ev, I))
+    fold.sort_indices()
+    ev_full = EvalData(fold, fold, dev)
+    ev_sh = EvalData(fold, fold, dev, item_lo=lo, item_hi=hi)
+    labels = rng.integers(0, 3, I).astype(np.uint8)
+    k, step = 100, 900
+    bits = lambda a: np.ascontiguousarray(a).view(np.uint32)
+    plain, _ = ShardedRecommender(eng, ev_sh, k=k, chunk=100).run(rng_step=step, keep_prob=1.0)
+    hits0 = np.bincount(plain.ravel(), minlength=I)
+    M, Rv = max(2, int(np.median(hits0))), 10
+    need = np.where(hits0 <= np.median(hits0), M, 0).astype(np.int32)                    # a floor that binds: the lower half up to the median
+    assert ((need > 0) & (hits0 < need)).any()
+    line = []
+    for score in ("logprob", "logit"):
+        fl_s, fl_r = ExposureFloor(need, Rv, score=score), ExposureFloor(need, Rv, score=score)
+        rep = LongTailReport(labels, 2)
+        sh = ShardedRecommender(eng, ev_sh, k=k, chunk=100, floor=fl_s, report=rep)
+        ids, sc = sh.run(rng_step=step, keep_prob=1.0)
+        assert (sh.rowpart_all is not None) == (score == "logprob")                      # the logit needs no extra collective
+        hits = np.bincount(ids[ids >= 0], minlength=I)
+        assert (hits >= np.minimum(need, fl_s.held())).all() and np.array_equal(rep.table()[1], hits)      # the report read the final lists
+        for a in (sh.ids, sh.scores, fl_s.cand_i, fl_s.cand_s, fl_s.state, fl_s.held_d, rep.item_hits) + (
+                (fl_s.lse,) if score == "logprob" else ()):
+            a0 = a.clone()                                                               # every rank holds the same tables
+            dist.broadcast(a0, 0)
+            assert torch.equal(a, a0)
+        ids_r, sc_r = Recommender(ref, ev_full, k=k, chunk=100, floor=fl_r).run(rng_step=step, keep_prob=1.0)
+        assert torch.equal(fl_s.cand_i, fl_r.cand_i) and torch.equal(fl_s.cand_s.view(torch.int32), fl_r.cand_s.view(torch.int32))
+        if score == "logprob":
+            off = int((fl_s.lse.view(torch.int32) != fl_r.lse.view(torch.int32)).sum())
+            print("rank %d: rows whose combined lse differs from the unsharded one in its bits: %d of %d" % (rank, off, n_ev), flush=True)
+        same = (ids == ids_r).all(1)
+        print("rank %d %s: rows with identical ids %.4f" % (rank, score, same.mean()), flush=True)
+        assert same.all(), ("rows whose ids differ from the unsharded recommender's", score, np.nonzero(~same)[0][:10])
+        assert np.array_equal(bits(sc), bits(sc_r)) and fl_s.stats() == fl_r.stats() and np.array_equal(fl_s.held(), fl_r.held()), score
+        assert not np.array_equal(ids, plain)
+        line.append("%s %s" % (score, fl_s.stats()))
+    dist.barrier()
+    if rank == 0:
+        print("FLOOR_SHARDED_OK world=%d items=%d slabs=%s %s" % (world, I, sorted({y - x for x, y in slabs(I, world)}), "; ".join(line)))
+    dist.destroy_process_group()
+
+
+def slabs(I, world):
+    from ltgan.sharded import item_slab
+    return [item_slab(I, r, world) for r in range(world)]
+
+
+if __name__ == "__main__":
+    main()

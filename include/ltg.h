@@ -868,6 +868,47 @@ int ltg_floor_finish(int32_t n_rows, int32_t c_in, const float* cand_score, cons
                      uint8_t* active_out /* may be NULL */, int32_t* held_out /* may be NULL */, int32_t* state, void* ws, size_t ws_bytes,
                      ltg_stream stream);
 
+/* Niche companions: the discriminator's top-K partners of an item (additive in ABI v14).  The score of a (popular a, niche b)
+ * pair is the discriminator's logit at keep = 1 (no dropout):
+ *   s(a, b) = b4 + sum_{j < h3} w4[j] tanh(U[a][j] + V[b][j]),   U[a] = tanh(emb[a] w1 + b1) w3[0:h1],   V[b] = tanh(emb[b] w2 + b2) w3[h1:h1+h2] + b3
+ * and sigmoid(s) is y of ltg_fake_tower_batched / ltg_d_step without dropout.  It does not separate into a product of item vectors, but
+ * tanh(u + v) = 1 - 2 / (1 + exp(2u) exp(2v)) does: a SIDE IMAGE stores E = exp(2 x) per item and column, and the pair loop holds no
+ * exponential.
+ * ltg_pair_ld: floats per image row, >= d_h3 (d_h3 rounded up to a multiple of 4); 0 for a cfg the calls refuse (NULL, a layer width < 1,
+ * d_feat < 1, d_h3 > 352, d_h0 + max(d_h1, d_h2) > 2048).
+ * ltg_pair_pack: image_out [n][ld] fp32, row i for ids[i] (DEVICE int32, rows of disc->emb: 0 <= id < d_feat; other ids are outside the
+ * contract, the host layer validates them), side LTG_PAIR_POP (branch A: w1, b1, w3[0:h1]) or LTG_PAIR_NICHE (branch B: w2, b2,
+ * w3[h1:h1+h2], + b3).  Always computed from the fp32 MASTER weights disc->emb / disc->p[0..5] in fp32 (fmaf chains, tanhf), whatever
+ * cfg->d_precision / d_arith the engine trains with: the operand shadows are not read.  Element = expf(2 clamp(x, -40, 40)) with libm's expf
+ * (1 ulp), so E lies in [e^-80, e^80] and a product of two is never inf x 0; padding columns [d_h3, ld) are written (1.0) and are never
+ * read by ltg_pair_companions.  Every element is one chain in a fixed order: an id's row is bit-identical wherever it sits in ids and
+ * whatever n is.  LTG_EINVAL before any HIP call: a NULL pointer (stream excepted), an unknown side, n < 0, a cfg as above; n = 0 returns
+ * LTG_OK.
+ * ltg_pair_companions: per query row r of q_image [n_q][ld] (an image of one side) its k best candidates of c_image [n_c][ld] (an image of
+ * the OTHER side; the kernel does not care which is which -- popular queries over niche candidates is the shelf of a head item, niche
+ * queries over popular candidates its anchors).  Score of (r, c) = fma(-2, acc, c0) with c0 = (float)(b4 + sum_j w4[j]) summed in fp64 in
+ * ascending j and acc the ONE chain acc <- fma(w4[j], rcp(fma(Eq[j], Ec[j], 1)), acc) from 0 over j = 0 .. d_h3 - 1 ascending (rcp =
+ * v_rcp_f32, 1 ulp); it depends on nothing but the two image rows and disc->p[6], p[7], so candidates or queries split across calls
+ * reproduce the same bits and item shards merge.  Candidate c is eligible for row r iff c_gid[c] != q_gid[r] (q_gid = -1 excludes
+ * nothing); c_gid [n_c] DEVICE, strictly ascending global ids >= 0.  score_out / id_out [n_q][k] exactly as ltg_topk writes a list: scores
+ * descending, equal scores lower global id first, -0.0 == +0.0, padding id -1 / score -inf when fewer than k are eligible, bit-identical
+ * from run to run, NaN outside the contract -- per-part lists go straight into ltg_topk_merge.  1 <= k <= LTG_PAIR_MAX_K.  The workspace
+ * (ltg_pair_companions_ws_bytes; 0 for arguments the call refuses and for n_q = 0) holds one list per (candidate segment, query row) --
+ * at most 64 segments -- never a block of scores.  No atomics, no inline assembly.
+ * Before any HIP call: LTG_EINVAL for a cfg as above, n_q < 0, n_c < 0, k out of range, a NULL pointer (stream excepted; c_image / c_gid
+ * may be NULL when n_c = 0; the pointers are not looked at when n_q = 0); LTG_EWORKSPACE for ws_bytes too small.  n_q = 0 returns LTG_OK and
+ * touches nothing; n_c = 0 gives all-padding lists. */
+#define LTG_PAIR_POP 0
+#define LTG_PAIR_NICHE 1
+#define LTG_PAIR_MAX_K 256
+int32_t ltg_pair_ld(const ltg_config* cfg);
+int ltg_pair_pack(const ltg_config* cfg, const ltg_disc_state* disc, int32_t side, const int32_t* ids /* DEVICE [n], rows of emb */, int32_t n,
+                  float* image_out /* [n][ld] */, ltg_stream stream);
+size_t ltg_pair_companions_ws_bytes(const ltg_config* cfg, int32_t n_q, int32_t n_c, int32_t k);
+int ltg_pair_companions(const ltg_config* cfg, const ltg_disc_state* disc, const float* q_image, const int32_t* q_gid, int32_t n_q,
+                        const float* c_image, const int32_t* c_gid /* DEVICE [n_c], strictly ascending global ids */, int32_t n_c, int32_t k,
+                        float* score_out, int32_t* id_out, void* ws, size_t ws_bytes, ltg_stream stream);
+
 /* Verification helper of the LTG_PREC_FP8 mode: out[i] = the value the fp8 GEMM operands carry for in[i]
  * (clamp to +-448, round to nearest-even OCP e4m3) -- lets a test pin its CPU model of the rounding to the hardware. */
 int ltg_fp8_roundtrip(const float* in, float* out, int32_t n, ltg_stream stream);

@@ -178,6 +178,7 @@ __global__ __launch_bounds__(64) void k_gate_set(LtgGate g, LtgGate g2 = LTG_NO_
 #include "ltg_share.h"
 #include "ltg_longtail.h"
 #include "ltg_neighbors.h"
+#include "ltg_companions.h"
 #include "ltg_diversify.h"
 #include "ltg_explain.h"
 #include "ltg_calibrate.h"
@@ -1933,6 +1934,82 @@ int ltg_item_neighbors(const ltg_config* cfg, const uint16_t* table_image, const
     if (k <= 128) { if (labels) LTG_NBR(2, true); else LTG_NBR(2, false); }
     else { if (labels) LTG_NBR(1, true); else LTG_NBR(1, false); }
 #undef LTG_NBR
+    if (hipGetLastError() != hipSuccess) return LTG_ELAUNCH;
+    hipLaunchKernelGGL(k_topk_merge, dim3(n_q), dim3(NT), 0, (hipStream_t)stream, nseg, n_q, k, ws_score, ws_id, k, score_out, id_out);
+    return check_launch();
+}
+
+// Niche companions.  The segmentation is a function of (n_q, n_c, k) alone, so ltg_pair_companions_ws_bytes and the call agree:
+// enough (query block x segment) workgroups for two per CU (one is resident at a time), a segment at least 1 024 candidates and a multiple
+// of the 64-candidate step, at most 64 segments; never fewer than one, so that n_c = 0 has a workspace size too.
+static int pair_plan(int n_q, int n_c, int k, int* seg_len) {
+    const int rows = k <= 128 ? 32 : 16;
+    const int nqb = (n_q + rows - 1) / rows;
+    int want = (512 + nqb - 1) / nqb;
+    const int kib = (n_c + 1023) / 1024;
+    const int most = kib < 1 ? 1 : kib < 64 ? kib : 64;
+    want = want > most ? most : want;
+    int len = ((n_c + want - 1) / want + PC_CT - 1) / PC_CT * PC_CT;
+    len = len < PC_CT ? PC_CT : len;
+    *seg_len = len;
+    const int nseg = (n_c + len - 1) / len;
+    return nseg < 1 ? 1 : nseg;
+}
+static bool pair_cfg_ok(const ltg_config* cfg) {
+    return cfg && cfg->d_feat >= 1 && cfg->d_h0 >= 1 && cfg->d_h1 >= 1 && cfg->d_h2 >= 1 && cfg->d_h3 >= 1 && cfg->d_h3 <= PC_MAX_H3 &&
+           (int64_t)cfg->d_h0 + (cfg->d_h1 > cfg->d_h2 ? cfg->d_h1 : cfg->d_h2) <= PK_MAX_H;
+}
+
+int32_t ltg_pair_ld(const ltg_config* cfg) { return pair_cfg_ok(cfg) ? (cfg->d_h3 + 3) / 4 * 4 : 0; }
+
+int ltg_pair_pack(const ltg_config* cfg, const ltg_disc_state* disc, int32_t side, const int32_t* ids, int32_t n, float* image_out,
+                  ltg_stream stream) {
+    if (!pair_cfg_ok(cfg) || !disc || !ids || !image_out || n < 0 || (side != LTG_PAIR_POP && side != LTG_PAIR_NICHE)) return LTG_EINVAL;
+    const bool niche = side == LTG_PAIR_NICHE;
+    const float *wb = disc->p[niche ? 2 : 0], *bb = disc->p[niche ? 3 : 1], *w3 = disc->p[4], *b3 = disc->p[5];
+    if (!disc->emb || !disc->p[0] || !disc->p[1] || !disc->p[2] || !disc->p[3] || !w3 || !b3) return LTG_EINVAL;
+    if (n == 0) return LTG_OK;
+    const int hb = niche ? cfg->d_h2 : cfg->d_h1;
+    clear_errors();
+    hipLaunchKernelGGL(k_pair_pack, dim3((n + PK_IDS - 1) / PK_IDS), dim3(NT), (size_t)PK_IDS * (cfg->d_h0 + hb) * sizeof(float), (hipStream_t)stream, n,
+                       cfg->d_h0, hb, cfg->d_h3, ltg_pair_ld(cfg), disc->emb, wb, bb, niche ? w3 + (size_t)cfg->d_h1 * cfg->d_h3 : w3,
+                       niche ? b3 : (const float*)nullptr, ids, image_out);
+    return check_launch();
+}
+
+size_t ltg_pair_companions_ws_bytes(const ltg_config* cfg, int32_t n_q, int32_t n_c, int32_t k) {
+    if (!pair_cfg_ok(cfg) || n_q <= 0 || n_c < 0 || k < 1 || k > LTG_PAIR_MAX_K) return 0;
+    int seg_len;
+    const int nseg = pair_plan(n_q, n_c, k, &seg_len);
+    return align_up((size_t)nseg * (size_t)n_q * (size_t)k * (sizeof(float) + sizeof(int32_t)));
+}
+
+int ltg_pair_companions(const ltg_config* cfg, const ltg_disc_state* disc, const float* q_image, const int32_t* q_gid, int32_t n_q,
+                        const float* c_image, const int32_t* c_gid, int32_t n_c, int32_t k, float* score_out, int32_t* id_out, void* ws,
+                        size_t ws_bytes, ltg_stream stream) {
+    if (!pair_cfg_ok(cfg) || n_q < 0 || n_c < 0 || k < 1 || k > LTG_PAIR_MAX_K) return LTG_EINVAL;
+    if (n_q == 0) return LTG_OK;
+    if (!disc || !disc->p[6] || !disc->p[7] || !q_image || !q_gid || !score_out || !id_out || !ws || (n_c > 0 && (!c_image || !c_gid)))
+        return LTG_EINVAL;
+    if (ws_bytes < ltg_pair_companions_ws_bytes(cfg, n_q, n_c, k)) return LTG_EWORKSPACE;
+    clear_errors();
+    if (n_c == 0) {
+        const size_t n = (size_t)n_q * k;
+        const size_t gx = (n + NT - 1) / NT;
+        hipLaunchKernelGGL(k_pair_fill, dim3((unsigned)(gx < 4096 ? gx : 4096)), dim3(NT), 0, (hipStream_t)stream, n, score_out, id_out);
+        return check_launch();
+    }
+    int seg_len;
+    const int nseg = pair_plan(n_q, n_c, k, &seg_len);
+    float* ws_score = (float*)ws;
+    int32_t* ws_id = (int32_t*)(ws_score + (size_t)nseg * n_q * k);
+    const int ld = ltg_pair_ld(cfg);
+    const size_t lds = (size_t)PC_ENT * 8 + (size_t)PC_CT * (ld | 1) * sizeof(float);
+#define LTG_PAIR(R)                                                                                                                          \
+    hipLaunchKernelGGL((k_pair_companions<R>), dim3((n_q + 8 * R - 1) / (8 * R), nseg), dim3(PC_NT), lds, (hipStream_t)stream, n_q, n_c, seg_len, k, \
+                       cfg->d_h3, ld, q_image, q_gid, c_image, c_gid, disc->p[6], disc->p[7], ws_score, ws_id)
+    if (k <= 128) LTG_PAIR(4); else LTG_PAIR(2);
+#undef LTG_PAIR
     if (hipGetLastError() != hipSuccess) return LTG_ELAUNCH;
     hipLaunchKernelGGL(k_topk_merge, dim3(n_q), dim3(NT), 0, (hipStream_t)stream, nseg, n_q, k, ws_score, ws_id, k, score_out, id_out);
     return check_launch();

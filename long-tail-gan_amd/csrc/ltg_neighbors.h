@@ -53,12 +53,12 @@ __global__ __launch_bounds__(NT) void k_item_pack(int I, int H, const float* __r
 }
 
 // bitonic sort, descending, of every row [CAP] of buf [NB_ENT / CAP][CAP] at once (CAP a power of two).  only_over >= 0: rows holding at most
-// that many entries are left alone.  Ends with a barrier.
-template <int CAP>
+// that many entries are left alone.  Ends with a barrier.  NTH = the threads of the workgroup (ltg_companions.h sorts with 512).
+template <int CAP, int NTH = NB_NT>
 __device__ __forceinline__ void nb_sort_rows(uint64_t* buf, const int* cnt, int only_over) {
     for (int size = 2; size <= CAP; size <<= 1) {
         for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int i = threadIdx.x; i < NB_ENT / 2; i += NB_NT) {
+            for (int i = threadIdx.x; i < NB_ENT / 2; i += NTH) {
                 const int lo = 2 * i - (i & (stride - 1)), hi = lo + stride;
                 if (cnt[lo / CAP] <= only_over) continue;
                 const bool desc = ((lo & (CAP - 1)) & size) == 0;
@@ -73,12 +73,12 @@ __device__ __forceinline__ void nb_sort_rows(uint64_t* buf, const int* cnt, int 
     }
 }
 // entries past a row's count -> 0 (no entry), then the sort
-template <int CAP>
+template <int CAP, int NTH = NB_NT>
 __device__ __forceinline__ void nb_pad_sort(uint64_t* buf, const int* cnt, int only_over) {
-    for (int e = threadIdx.x; e < NB_ENT; e += NB_NT)
+    for (int e = threadIdx.x; e < NB_ENT; e += NTH)
         if ((e & (CAP - 1)) >= cnt[e / CAP]) buf[e] = 0ull;
     __syncthreads();
-    nb_sort_rows<CAP>(buf, cnt, only_over);
+    nb_sort_rows<CAP, NTH>(buf, cnt, only_over);
 }
 
 // Workgroup (x, y) = query block x (16 NTB rows) against item segment y ([y seg_len, (y + 1) seg_len) of the slab, seg_len % 128 == 0).

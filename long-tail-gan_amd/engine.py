@@ -898,6 +898,50 @@ class Engine:
                                                int(group_mask), int(k), _ptr(score_out), _ptr(id_out), _ptr(ws), ws.numel(), self.stream()),
                    "ltg_item_neighbors")
 
+    # ------------------------------------------------------------------ niche companions (the discriminator's pair score)
+    def pair_ld(self):
+        """floats per row of a side image (ltg_pair_ld: h3 rounded up to a multiple of 4)"""
+        ld = int(self.lib.ltg_pair_ld(C.byref(self.cfg)))
+        if ld <= 0:
+            raise cabi.LtgError("ltg_pair_ld refused the discriminator's layer sizes %r" % ((self.h0, self.h1, self.h2, self.h3),))
+        return ld
+
+    def pair_pack(self, side, ids, out=None):
+        """the side image of the items `ids` (device int32, rows of the embedding table): side `popular` = branch A, `niche` = branch B of
+        the discriminator, from the fp32 master weights -> out [n, pair_ld()] float32, E = exp(2 x) of what the side adds to the fc
+        layer's pre-activation (ltg_pair_pack).  Ids outside [0, feature_len) are the caller's to refuse (serving.PairCompanions does)."""
+        n, ld = int(ids.numel()), self.pair_ld()
+        assert ids.dtype == torch.int32 and ids.is_contiguous() and ids.dim() == 1
+        if out is None:
+            out = torch.empty(n, ld, dtype=torch.float32, device=self.device)
+        assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (n, ld)
+        if n:
+            cabi.check(self.lib.ltg_pair_pack(C.byref(self.cfg), C.byref(self.disc_c), cabi.LTG_PAIR_SIDE[side], _ptr(ids), n, _ptr(out),
+                                              self.stream()), "ltg_pair_pack")
+        return out
+
+    def pair_companions_ws_bytes(self, n_q, n_c, k):
+        return int(self.lib.ltg_pair_companions_ws_bytes(C.byref(self.cfg), int(n_q), int(n_c), int(k)))
+
+    def pair_companions(self, q_image, q_gid, c_image, c_gid, k, score_out, id_out, ws=None):
+        """the k best candidates of every query under the discriminator's pair score: q_image [n_q, ld] / c_image [n_c, ld] float32 side
+        images of OPPOSITE sides (pair_pack), q_gid [n_q] int32 = the global id a query must not return (-1: none), c_gid [n_c] int32 =
+        the candidates' global ids, strictly ascending -> score_out [n_q, k] float32 (the logit: sigmoid gives the discriminator's y
+        without dropout), id_out [n_q, k] int32, ordered and padded as topk writes them (ltg_pair_companions).  ws: a uint8 tensor of
+        pair_companions_ws_bytes(n_q, n_c, k) bytes (allocated when absent)."""
+        n, m, ld = int(q_image.shape[0]), int(c_image.shape[0]), self.pair_ld()
+        assert q_image.dtype == c_image.dtype == torch.float32 and q_image.is_contiguous() and c_image.is_contiguous()
+        assert tuple(q_image.shape) == (n, ld) and tuple(c_image.shape) == (m, ld)
+        for g, cnt in ((q_gid, n), (c_gid, m)):
+            assert g.dtype == torch.int32 and g.is_contiguous() and g.numel() == cnt
+        assert tuple(score_out.shape) == tuple(id_out.shape) == (n, k) and score_out.is_contiguous() and id_out.is_contiguous()
+        assert score_out.dtype == torch.float32 and id_out.dtype == torch.int32
+        if ws is None:
+            ws = torch.empty(max(self.pair_companions_ws_bytes(n, m, k), 1), dtype=torch.uint8, device=self.device)
+        cabi.check(self.lib.ltg_pair_companions(C.byref(self.cfg), C.byref(self.disc_c), _ptr(q_image), _ptr(q_gid), n, _ptr(c_image),
+                                                _ptr(c_gid), m, int(k), _ptr(score_out), _ptr(id_out), _ptr(ws), ws.numel(), self.stream()),
+                   "ltg_pair_companions")
+
     # ------------------------------------------------------------------ item audiences
     def item_audience_ws_bytes(self, n_rows, n_q, k):
         return int(self.lib.ltg_item_audience_ws_bytes(C.byref(self.cfg), int(n_rows), int(n_q), int(k)))

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from ._cabi import LTG_CAP_MAX_ROUNDS, LTG_CAP_STATE, LTG_FLOOR_MAX_ROUNDS, LTG_FLOOR_STATE, LTG_METRIC, LTG_SHARE_STATE, LTG_SPACE, LtgError
+from ._cabi import LTG_CAP_MAX_ROUNDS, LTG_CAP_STATE, LTG_FLOOR_MAX_ROUNDS, LTG_FLOOR_STATE, LTG_METRIC, LTG_PAIR_MAX_K, LTG_SHARE_STATE, LTG_SPACE, LtgError
 
 EVAL_LOGITS_BYTES = 2 << 30
 
@@ -1103,7 +1103,83 @@ class ShardedItemNeighbors(ItemNeighbors):
         return ids.cpu().numpy(), scores.cpu().numpy()
 
 
-# ---------------------------------------------------------------- what the CLIs share (test.py, recommend.py, longtail.py, similar.py, audience.py)
+class PairCompanions:
+    """The k likeliest partners of items under the DISCRIMINATOR's pair score (ltg_pair_pack / ltg_pair_companions): queries `popular` =
+    head items, whose candidates are niche items (the niche shelf of a head item), or `niche`, whose candidates are popular items (the
+    anchors of a tail item).  The score is the discriminator's logit without dropout; sigmoid(score) is its probability that a real user
+    holds the pair.  Ids are rows of the discriminator's embedding table (item ids).  The candidates' side image is packed once, the
+    queries are packed and walked in chunks of `chunk`; the workspace is lists, never scores.  A query never returns itself."""
+
+    def __init__(self, engine, k=20, queries="popular", chunk=4096):
+        if queries not in ("popular", "niche"):
+            raise ValueError("queries must be 'popular' or 'niche', got %r" % (queries,))
+        if not 1 <= int(k) <= LTG_PAIR_MAX_K:
+            raise ValueError("k must be in [1, %d]" % LTG_PAIR_MAX_K)
+        self.eng, self.k, self.chunk = engine, int(k), max(1, int(chunk))
+        self.q_side, self.c_side = queries, "niche" if queries == "popular" else "popular"
+
+    def _ids(self, query_ids, cand_ids):
+        n = self.eng.feature_len
+        q = np.ascontiguousarray(query_ids, dtype=np.int32).reshape(-1)
+        c = np.ascontiguousarray(cand_ids, dtype=np.int32).reshape(-1)
+        for name, a in (("query", q), ("candidate", c)):
+            if a.size and (a.min() < 0 or a.max() >= n):
+                raise ValueError("%s ids outside [0, %d)" % (name, n))
+        if c.size > 1 and np.any(np.diff(c) <= 0):
+            raise ValueError("candidate ids must be strictly ascending")
+        return q, c
+
+    def _slab(self, c):
+        """the candidates this engine searches: all of them"""
+        return c
+
+    def _merge(self, n):
+        """-> the SlabLists that turns this engine's lists into everybody's (one part: they already are)"""
+        return SlabLists(self.eng, n, self.k)
+
+    def run(self, query_ids, cand_ids):
+        """-> (ids [n_q, k] int32 item ids, scores [n_q, k] float32 logits) as host arrays; cand_ids strictly ascending"""
+        eng, k = self.eng, self.k
+        dev = eng.device
+        q, c = self._ids(query_ids, cand_ids)
+        cd = torch.from_numpy(np.ascontiguousarray(self._slab(c))).to(dev)
+        c_img = eng.pair_pack(self.c_side, cd)
+        ids = torch.empty(len(q), k, dtype=torch.int32, device=dev)
+        scores = torch.empty(len(q), k, dtype=torch.float32, device=dev)
+        qd = torch.from_numpy(q).to(dev)
+        step = min(self.chunk, max(1, len(q)))
+        ws = torch.empty(neighbors_ws_bytes(lambda n, kk: eng.pair_companions_ws_bytes(n, cd.numel(), kk), len(q), step, k), dtype=torch.uint8,
+                         device=dev)
+        q_img = torch.empty(step, eng.pair_ld(), dtype=torch.float32, device=dev)
+        lists = self._merge(step)
+        for lo in range(0, len(q), step):
+            hi = min(len(q), lo + step)
+            qi = eng.pair_pack(self.q_side, qd[lo:hi], out=q_img[: hi - lo])
+            ls, li = lists.local(hi - lo, k, scores[lo:hi], ids[lo:hi])
+            eng.pair_companions(qi, qd[lo:hi], c_img, cd, k, ls, li, ws=ws)
+            lists.merge(ls, li, scores[lo:hi], ids[lo:hi])
+        return ids.cpu().numpy(), scores.cpu().numpy()
+
+
+class ShardedPairCompanions(PairCompanions):
+    """PairCompanions over item shards.  The discriminator is replicated, so every rank packs the whole query chunk itself and nothing is
+    exchanged for it; each rank searches the candidates whose ids lie in its own item slab, and a SlabLists gathers and merges the lists
+    as it does for ShardedItemNeighbors.  A pair's score does not depend on the call that holds the candidate, so every rank ends with
+    the table of the unsharded run, bit for bit."""
+
+    def __init__(self, engine, k=20, queries="popular", chunk=4096, group=None):
+        super().__init__(engine, k=k, queries=queries, chunk=chunk)
+        self.group = group
+        self.R = dist.get_world_size(group)
+
+    def _slab(self, c):
+        return c[(c >= self.eng.item_lo) & (c < self.eng.item_hi)]
+
+    def _merge(self, n):
+        return SlabLists(self.eng, n, self.k, self.group, self.R)
+
+
+# ---------------------------------------------------------------- what the CLIs share (test.py, recommend.py, longtail.py, similar.py, audience.py, companions.py)
 class _Counters:
     """load_checkpoint also restores the trainer's counters; the serving flows have no trainer."""
     update_count = 0.0

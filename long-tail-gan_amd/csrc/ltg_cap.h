@@ -14,10 +14,10 @@
 //   value, so nothing computed depends on it.
 // k_cap_propose: one wave per row, 64 entries per step, a ballot / popcount prefix up to the k-th admissible entry, one active byte per
 //   entry (zero past the k-th, past the row's end and for ids outside the catalogue).
-// k_cap_accept: one workgroup per item.  It leaves at once if the segment cannot exceed the cap; else a radix select over the 64-bit words
-//   of the active entries of its segment, most significant digit first, 8 bits a pass: a 256-bin LDS histogram by integer atomics (sums:
-//   order-free), the segment re-read per digit -- a head item's segment holds an entry of almost every row and fits no LDS.  The first
-//   pass's total is the active count: at most cap, and the workgroup leaves.
+// k_cap_accept: one workgroup per item.  It leaves at once if the segment cannot exceed the cap; else a radix select (cp_select, shared
+//   with ltg_floor.h) over the 64-bit words of the active entries of its segment, most significant digit first, 8 bits a pass: a 256-bin
+//   LDS histogram by integer atomics (sums: order-free), the segment re-read per digit -- a head item's segment holds an entry of almost
+//   every row and fits no LDS.  The first pass's total is the active count: at most cap, and the workgroup leaves.
 // k_cap_finish / k_cap_stats: the lists from the active bytes, every entry with its original logit bit for bit, and the stats block.
 // An id is used as an index only after it has been found inside [0, n_items); an entry number only comes out of the index.
 #pragma once
@@ -117,33 +117,32 @@ __global__ __launch_bounds__(CP_NT) void k_cap_propose(int n_rows, int c, int k,
     }
 }
 
-__global__ __launch_bounds__(CP_NT) void k_cap_accept(int c, const float* __restrict__ cand_score, const float* __restrict__ lse,
-                                                      const int32_t* __restrict__ cap, const int32_t* __restrict__ off, const int32_t* __restrict__ seg,
-                                                      const uint8_t* __restrict__ active, uint64_t* __restrict__ thr, int32_t* __restrict__ state) {
-    __shared__ int s_hist[256];
-    __shared__ int s_sel[3];                         // the digit chosen, the rank left inside it, leave (nothing over the cap)
-    const int tid = threadIdx.x, item = blockIdx.x;
-    const int e0 = off[item], e1 = off[item + 1], capi = cap[item];
-    if (capi < 1 || e1 - e0 <= capi) return;         // (uniform over the workgroup)
-    uint64_t prefix = 0ull, mask = 0ull;
-    int rank = capi;                                 // the rank-th largest of the active words that agree with prefix under mask
+// The radix select of k_cap_accept and k_floor_select: the rank-th largest 64-bit word among the entries seg[e0 .. e1) that `word_of`
+// counts, most significant digit first, 8 bits a pass, the segment re-read per digit.  word_of(entry number, w&) -> the entry counts, and
+// then w is its word.  The first pass's total is the number of entries that count: with at most `rank` of them -> false, at once; else
+// -> true with `out` = the selected word.  Both are uniform over the workgroup: all CP_NT threads call it, with s_hist[256] and s_sel[3]
+// (the digit chosen, the rank left inside it, leave) in LDS.
+template <typename F>
+__device__ __forceinline__ bool cp_select(int e0, int e1, int rank, const int32_t* __restrict__ seg, int* s_hist, int* s_sel, uint64_t& out,
+                                          F word_of) {
+    const int tid = threadIdx.x;
+    uint64_t prefix = 0ull, mask = 0ull;             // the rank-th largest of the counting words that agree with prefix under mask
 #pragma unroll 1
     for (int shift = 56; shift >= 0; shift -= 8) {
         s_hist[tid] = 0;
         __syncthreads();
         for (int e = e0 + tid; e < e1; e += CP_NT) {
-            const int ent = seg[e];
-            if (!active[ent]) continue;
-            const uint64_t w = cp_word(cand_score[ent], lse, ent / c);
+            uint64_t w;
+            if (!word_of(seg[e], w)) continue;
             if ((w & mask) == prefix) atomicAdd(&s_hist[(int)(w >> shift) & 255], 1);
         }
         __syncthreads();
         int above = 0;
         for (int b = 255; b > tid; --b) above += s_hist[b];
         const int mine = s_hist[tid];
-        if (shift == 56 && tid == 0) s_sel[2] = above + mine > capi ? 0 : 1;       // the active count: nothing to do at or under the cap
+        if (shift == 56 && tid == 0) s_sel[2] = above + mine > rank ? 0 : 1;       // (rank is still the caller's: the count is at or under it)
         __syncthreads();
-        if (shift == 56 && s_sel[2] != 0) return;
+        if (shift == 56 && s_sel[2] != 0) return false;
         if (above < rank && rank <= above + mine) {  // exactly one thread: the counts of the bins above tid are a partition
             s_sel[0] = tid;
             s_sel[1] = rank - above;
@@ -154,8 +153,27 @@ __global__ __launch_bounds__(CP_NT) void k_cap_accept(int c, const float* __rest
         rank = s_sel[1];
         __syncthreads();                             // (everyone has read the choice before the next pass clears the bins)
     }
-    if (tid == 0 && thr[item] != prefix) {
-        thr[item] = prefix;
+    out = prefix;
+    return true;
+}
+
+__global__ __launch_bounds__(CP_NT) void k_cap_accept(int c, const float* __restrict__ cand_score, const float* __restrict__ lse,
+                                                      const int32_t* __restrict__ cap, const int32_t* __restrict__ off, const int32_t* __restrict__ seg,
+                                                      const uint8_t* __restrict__ active, uint64_t* __restrict__ thr, int32_t* __restrict__ state) {
+    __shared__ int s_hist[256];
+    __shared__ int s_sel[3];
+    const int tid = threadIdx.x, item = blockIdx.x;
+    const int e0 = off[item], e1 = off[item + 1], capi = cap[item];
+    if (capi < 1 || e1 - e0 <= capi) return;         // (uniform over the workgroup)
+    uint64_t word;                                   // the capi-th largest active word; nothing to do with the active count at or under the cap
+    if (!cp_select(e0, e1, capi, seg, s_hist, s_sel, word, [&](int ent, uint64_t& w) {
+            if (!active[ent]) return false;
+            w = cp_word(cand_score[ent], lse, ent / c);
+            return true;
+        }))
+        return;
+    if (tid == 0 && thr[item] != word) {
+        thr[item] = word;
         atomicAdd(&state[0], 1);
         state[4] = state[1];                         // (every workgroup of a round writes the same number)
     }

@@ -11,10 +11,9 @@
 // but lim.  A row with more than reserve active entries at positions >= k - reserve (its zone) lowers lim to the reserve-th of them.
 //
 // k_floor_lim: lim <- c - 1 (the index is ltg_cap.h's k_cap_zero / k_cap_count / k_cap_scan, sel in the place of thr).
-// k_floor_select: one workgroup per item.  It leaves at once, sel = 0, if need < 1 or the segment is no longer than need; else a radix
-//   select of the need-th largest word among the ADMISSIBLE entries of its segment, most significant digit first, 8 bits a pass: a 256-bin
-//   LDS histogram by integer atomics (sums: order-free), the segment re-read per digit -- a head item's segment holds an entry of almost
-//   every row and fits no LDS.  The first pass's total is the admissible count: at most need, and sel = 0.
+// k_floor_select: one workgroup per item.  It leaves at once, sel = 0, if need < 1 or the segment is no longer than need; else the radix
+//   select of ltg_cap.h (cp_select) of the need-th largest word among the ADMISSIBLE entries of its segment.  The first pass's total is
+//   the admissible count: at most need, and sel = 0.
 // k_floor_users: one wave per row, 64 positions a step up to lim[u]; an entry is active iff it is a floor entry and w >= sel[id]; a
 //   ballot / popcount prefix over the zone finds the reserve-th active entry; with more than reserve of them the row stores its new limit.
 // k_floor_finish: one wave per row.  The active flags of a row live in registers (one bit per 64-step and lane, c <= 1024).  With m zone
@@ -28,6 +27,7 @@
 
 constexpr int FL_NT = 256;           // 4 waves
 constexpr int FL_STATE = 8;          // == LTG_FLOOR_STATE
+static_assert(FL_NT == CP_NT, "k_floor_select strides its segment as cp_select does");
 
 __global__ __launch_bounds__(FL_NT) void k_floor_lim(int n_rows, int c, int32_t* __restrict__ lim) {
     const int r = blockIdx.x * FL_NT + threadIdx.x;
@@ -45,7 +45,7 @@ __global__ __launch_bounds__(FL_NT) void k_floor_select(int c, int k, int reserv
                                                         const int32_t* __restrict__ seg, const int32_t* __restrict__ lim, uint64_t* __restrict__ sel,
                                                         int32_t* __restrict__ held, int32_t* __restrict__ state, int bump) {
     __shared__ int s_hist[256];
-    __shared__ int s_sel[3];                         // the digit chosen, the rank left inside it, leave (no more admissible entries than need)
+    __shared__ int s_sel[3];
     const int tid = threadIdx.x, item = blockIdx.x;
     if (bump && item == 0 && tid == 0) state[1] += 1;
     if (held && tid == 0) held[item] = 0;
@@ -54,39 +54,15 @@ __global__ __launch_bounds__(FL_NT) void k_floor_select(int c, int k, int reserv
         if (tid == 0) sel[item] = 0ull;
         return;
     }
-    uint64_t prefix = 0ull, mask = 0ull;
-    int rank = needi;                                // the rank-th largest of the admissible words that agree with prefix under mask
-#pragma unroll 1
-    for (int shift = 56; shift >= 0; shift -= 8) {
-        s_hist[tid] = 0;
-        __syncthreads();
-        for (int e = e0 + tid; e < e1; e += FL_NT) {
-            const int ent = seg[e], u = ent / c;
-            if (ent - u * c > fl_limit(lim, u, c, k, reserve)) continue;
-            const uint64_t w = cp_word(cand_score[ent], lse, u);
-            if ((w & mask) == prefix) atomicAdd(&s_hist[(int)(w >> shift) & 255], 1);
-        }
-        __syncthreads();
-        int above = 0;
-        for (int b = 255; b > tid; --b) above += s_hist[b];
-        const int mine = s_hist[tid];
-        if (shift == 56 && tid == 0) s_sel[2] = above + mine > needi ? 0 : 1;      // the admissible count: every one is active at or under need
-        __syncthreads();
-        if (shift == 56 && s_sel[2] != 0) {
-            if (tid == 0) sel[item] = 0ull;
-            return;
-        }
-        if (above < rank && rank <= above + mine) {  // exactly one thread: the counts of the bins above tid are a partition
-            s_sel[0] = tid;
-            s_sel[1] = rank - above;
-        }
-        __syncthreads();
-        prefix |= (uint64_t)s_sel[0] << shift;
-        mask |= 255ull << shift;
-        rank = s_sel[1];
-        __syncthreads();                             // (everyone has read the choice before the next pass clears the bins)
-    }
-    if (tid == 0) sel[item] = prefix;
+    uint64_t word;                                   // the needi-th largest admissible word
+    if (!cp_select(e0, e1, needi, seg, s_hist, s_sel, word, [&](int ent, uint64_t& w) {
+            const int u = ent / c;
+            if (ent - u * c > fl_limit(lim, u, c, k, reserve)) return false;
+            w = cp_word(cand_score[ent], lse, u);
+            return true;
+        }))
+        word = 0ull;                                 // the admissible count is at or under need: every one is active
+    if (tid == 0) sel[item] = word;
 }
 
 // is the entry at position j of the row (its id read, `live`: before the first padding id) active under sel?  Admissibility is the caller's.

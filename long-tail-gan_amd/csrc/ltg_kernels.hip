@@ -2072,6 +2072,17 @@ int ltg_item_audience(const ltg_config* cfg, const float* logits, const float* l
 // Exposure-capped top-K lists.  The workspace holds the thresholds, the per-item index (offsets, cursors, entry numbers), one
 // active byte per candidate entry and one int32 per row; its layout is a function of (n_rows, c_in, n_items_global) alone.  Every refusal
 // comes before the first HIP call.
+// a workspace handed out piece by piece: take(bytes) -> the next aligned piece of `base`; on the null base of a size query nullptr, without
+// arithmetic on it; `o` ends as the bytes the pieces need
+struct Carve {
+    char* base;
+    size_t o = 0;
+    char* take(size_t bytes) {
+        char* p = base ? base + o : nullptr;
+        o += align_up(bytes);
+        return p;
+    }
+};
 struct CapWs {
     uint64_t* thr;
     int32_t *off, *cur, *seg, *row_over;
@@ -2084,20 +2095,26 @@ static bool cap_args_ok(int32_t n_rows, int32_t c_in, int32_t n_items_global) {
 static CapWs cap_carve(int32_t n_rows, int32_t c_in, int32_t n_items_global, char* base) {
     const size_t I = (size_t)n_items_global, E = (size_t)n_rows * (size_t)c_in;
     CapWs w;
-    size_t o = 0;
-    auto take = [&](size_t bytes) {                  // (no pointer arithmetic on the null base of the size query)
-        char* p = base ? base + o : nullptr;
-        o += align_up(bytes);
-        return p;
-    };
-    w.thr = (uint64_t*)take(I * sizeof(uint64_t));
-    w.off = (int32_t*)take((I + 1) * sizeof(int32_t));
-    w.cur = (int32_t*)take(I * sizeof(int32_t));
-    w.seg = (int32_t*)take((E > 0 ? E : 1) * sizeof(int32_t));
-    w.row_over = (int32_t*)take(((size_t)n_rows > 0 ? (size_t)n_rows : 1) * sizeof(int32_t));
-    w.active = (uint8_t*)take(E > 0 ? E : 1);
-    w.bytes = o;
+    Carve ws{base};
+    w.thr = (uint64_t*)ws.take(I * sizeof(uint64_t));
+    w.off = (int32_t*)ws.take((I + 1) * sizeof(int32_t));
+    w.cur = (int32_t*)ws.take(I * sizeof(int32_t));
+    w.seg = (int32_t*)ws.take((E > 0 ? E : 1) * sizeof(int32_t));
+    w.row_over = (int32_t*)ws.take(((size_t)n_rows > 0 ? (size_t)n_rows : 1) * sizeof(int32_t));
+    w.active = (uint8_t*)ws.take(E > 0 ? E : 1);
+    w.bytes = ws.o;
     return w;
+}
+
+// the per-item index of the candidates, a CSR over entry numbers (ltg_cap.h): zero, count, scan, scatter; words (the cap's thresholds, the
+// floor's selection words) <- 0 and the state block <- 0 on the way
+static void cap_enqueue_index(int32_t n_rows, int32_t c_in, const int32_t* cand_id, int32_t I, int32_t* state, int32_t* cur, int32_t* off,
+                              int32_t* seg, uint64_t* words, hipStream_t st) {
+    const int row_blocks = (n_rows + CP_NT / 64 - 1) / (CP_NT / 64);
+    hipLaunchKernelGGL(k_cap_zero, dim3((I + CP_NT - 1) / CP_NT), dim3(CP_NT), 0, st, I, cur, state);
+    hipLaunchKernelGGL(k_cap_count<false>, dim3(row_blocks), dim3(CP_NT), 0, st, n_rows, c_in, cand_id, I, cur, (const int32_t*)off, seg);
+    hipLaunchKernelGGL(k_cap_scan, dim3(1), dim3(1024), 0, st, I, cur, off, words);
+    hipLaunchKernelGGL(k_cap_count<true>, dim3(row_blocks), dim3(CP_NT), 0, st, n_rows, c_in, cand_id, I, cur, (const int32_t*)off, seg);
 }
 
 size_t ltg_cap_ws_bytes(int32_t n_rows, int32_t c_in, int32_t n_items_global) {
@@ -2111,13 +2128,8 @@ int ltg_cap_index(int32_t n_rows, int32_t c_in, const int32_t* cand_id, int32_t 
         return LTG_EINVAL;
     if (n_rows == 0) return LTG_OK;
     const CapWs w = cap_carve(n_rows, c_in, n_items_global, (char*)ws);
-    const hipStream_t st = (hipStream_t)stream;
-    const int I = n_items_global, row_blocks = (n_rows + CP_NT / 64 - 1) / (CP_NT / 64);
     clear_errors();
-    hipLaunchKernelGGL(k_cap_zero, dim3((I + CP_NT - 1) / CP_NT), dim3(CP_NT), 0, st, I, w.cur, state);
-    hipLaunchKernelGGL(k_cap_count<false>, dim3(row_blocks), dim3(CP_NT), 0, st, n_rows, c_in, cand_id, I, w.cur, (const int32_t*)w.off, w.seg);
-    hipLaunchKernelGGL(k_cap_scan, dim3(1), dim3(1024), 0, st, I, w.cur, w.off, w.thr);
-    hipLaunchKernelGGL(k_cap_count<true>, dim3(row_blocks), dim3(CP_NT), 0, st, n_rows, c_in, cand_id, I, w.cur, (const int32_t*)w.off, w.seg);
+    cap_enqueue_index(n_rows, c_in, cand_id, n_items_global, state, w.cur, w.off, w.seg, w.thr, (hipStream_t)stream);
     return check_launch();
 }
 
@@ -2170,18 +2182,13 @@ static bool share_args_ok(int32_t n_rows, int32_t k) {
 static ShareWs share_carve(int32_t n_rows, int32_t k, char* base) {
     const size_t R = (size_t)n_rows > 0 ? (size_t)n_rows : 1, E = R * (size_t)k;
     ShareWs w;
-    size_t o = 0;
-    auto take = [&](size_t bytes) {                  // (no pointer arithmetic on the null base of the size query)
-        char* p = base ? base + o : nullptr;
-        o += align_up(bytes);
-        return p;
-    };
-    w.words = (uint64_t*)take(E * sizeof(uint64_t));
-    w.row_a = (int32_t*)take(R * sizeof(int32_t));
-    w.row_kk = (int32_t*)take(R * sizeof(int32_t));
-    w.bins = (int32_t*)take((size_t)SH_PASSES * 256 * sizeof(int32_t));
-    w.sel = (sh_sel*)take(sizeof(sh_sel));
-    w.bytes = o;
+    Carve ws{base};
+    w.words = (uint64_t*)ws.take(E * sizeof(uint64_t));
+    w.row_a = (int32_t*)ws.take(R * sizeof(int32_t));
+    w.row_kk = (int32_t*)ws.take(R * sizeof(int32_t));
+    w.bins = (int32_t*)ws.take((size_t)SH_PASSES * 256 * sizeof(int32_t));
+    w.sel = (sh_sel*)ws.take(sizeof(sh_sel));
+    w.bytes = ws.o;
     return w;
 }
 // [p, p + n) and [q, q + m) (bytes) share a byte, or start at the same address
@@ -2234,20 +2241,15 @@ struct FloorWs {
 static FloorWs floor_carve(int32_t n_rows, int32_t c_in, int32_t n_items_global, char* base) {
     const size_t I = (size_t)n_items_global, E = (size_t)n_rows * (size_t)c_in, N = (size_t)n_rows > 0 ? (size_t)n_rows : 1;
     FloorWs w;
-    size_t o = 0;
-    auto take = [&](size_t bytes) {                  // (no pointer arithmetic on the null base of the size query)
-        char* p = base ? base + o : nullptr;
-        o += align_up(bytes);
-        return p;
-    };
-    w.sel = (uint64_t*)take(I * sizeof(uint64_t));
-    w.off = (int32_t*)take((I + 1) * sizeof(int32_t));
-    w.cur = (int32_t*)take(I * sizeof(int32_t));
-    w.seg = (int32_t*)take((E > 0 ? E : 1) * sizeof(int32_t));
-    w.lim = (int32_t*)take(N * sizeof(int32_t));
-    w.row_t = (int32_t*)take(N * sizeof(int32_t));
-    w.held = (int32_t*)take(I * sizeof(int32_t));
-    w.bytes = o;
+    Carve ws{base};
+    w.sel = (uint64_t*)ws.take(I * sizeof(uint64_t));
+    w.off = (int32_t*)ws.take((I + 1) * sizeof(int32_t));
+    w.cur = (int32_t*)ws.take(I * sizeof(int32_t));
+    w.seg = (int32_t*)ws.take((E > 0 ? E : 1) * sizeof(int32_t));
+    w.lim = (int32_t*)ws.take(N * sizeof(int32_t));
+    w.row_t = (int32_t*)ws.take(N * sizeof(int32_t));
+    w.held = (int32_t*)ws.take(I * sizeof(int32_t));
+    w.bytes = ws.o;
     return w;
 }
 static bool floor_ws_ok(int32_t n_rows, int32_t c_in, int32_t n_items_global, const void* ws, size_t ws_bytes) {
@@ -2264,12 +2266,8 @@ int ltg_floor_index(int32_t n_rows, int32_t c_in, const int32_t* cand_id, int32_
     if (n_rows == 0) return LTG_OK;
     const FloorWs w = floor_carve(n_rows, c_in, n_items_global, (char*)ws);
     const hipStream_t st = (hipStream_t)stream;
-    const int I = n_items_global, row_blocks = (n_rows + CP_NT / 64 - 1) / (CP_NT / 64);
     clear_errors();
-    hipLaunchKernelGGL(k_cap_zero, dim3((I + CP_NT - 1) / CP_NT), dim3(CP_NT), 0, st, I, w.cur, state);
-    hipLaunchKernelGGL(k_cap_count<false>, dim3(row_blocks), dim3(CP_NT), 0, st, n_rows, c_in, cand_id, I, w.cur, (const int32_t*)w.off, w.seg);
-    hipLaunchKernelGGL(k_cap_scan, dim3(1), dim3(1024), 0, st, I, w.cur, w.off, w.sel);
-    hipLaunchKernelGGL(k_cap_count<true>, dim3(row_blocks), dim3(CP_NT), 0, st, n_rows, c_in, cand_id, I, w.cur, (const int32_t*)w.off, w.seg);
+    cap_enqueue_index(n_rows, c_in, cand_id, n_items_global, state, w.cur, w.off, w.seg, w.sel, st);
     hipLaunchKernelGGL(k_floor_lim, dim3((n_rows + FL_NT - 1) / FL_NT), dim3(FL_NT), 0, st, n_rows, c_in, w.lim);
     return check_launch();
 }

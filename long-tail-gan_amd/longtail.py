@@ -69,6 +69,7 @@ floor items in fewer than M of the plain / the served lists.
 from __future__ import annotations
 
 import argparse
+import functools
 import json
 import os
 import sys
@@ -129,188 +130,56 @@ def parse_min_slots(spec, names, k):
     return slots
 
 
-def add_diversify_args(ap):
-    """the options of the MMR re-ranking (trainer.Diversify), shared with recommend.py"""
+RULE_OPTIONS = ("min_slots", "diversify", "calibrate", "cap", "share", "floor")     # at most one of them; a refusal names the later first
+
+
+def add_rule_args(ap):
+    """the options of the serve-time rules besides --min-slots (trainer.Diversify, Calibrate, ExposureCap, ShareTarget, ExposureFloor),
+    shared with recommend.py"""
     ap.add_argument("--diversify", type=float, default=None, metavar="LAMBDA")
     ap.add_argument("--candidates", type=int, default=None, metavar="N")
     ap.add_argument("--div-space", choices=("decoder", "encoder"), default="decoder")
-
-
-def check_diversify_args(ap, a, k):
-    """refuses (ap.error) what trainer.Diversify would refuse for lists of k entries, and the combination with --min-slots"""
-    if a.diversify is None:
-        if a.candidates is not None:
-            ap.error("--candidates needs --diversify")
-        return
-    if a.min_slots is not None:
-        ap.error("--diversify cannot be combined with --min-slots")
-    if not 0.0 <= a.diversify <= 1.0:
-        ap.error("--diversify takes LAMBDA in [0, 1]")
-    if k > 256:
-        ap.error("--diversify re-ranks at most 256 candidates: lists of %d entries are too long" % k)
-    if a.candidates is not None and not k <= a.candidates <= 256:
-        ap.error("--candidates must be in [k, 256] = [%d, 256], got %d" % (k, a.candidates))
-
-
-def add_calibrate_args(ap):
-    """the option of the calibrated lists (trainer.Calibrate), shared with recommend.py"""
     ap.add_argument("--calibrate", type=float, default=None, metavar="LAMBDA")
-
-
-def check_calibrate_args(ap, a):
-    """refuses (ap.error) what trainer.Calibrate would refuse, and the combination with --min-slots or --diversify"""
-    if a.calibrate is None:
-        return
-    if a.min_slots is not None or a.diversify is not None:
-        ap.error("--calibrate cannot be combined with --min-slots or --diversify")
-    if not 0.0 <= a.calibrate <= 1.0:
-        ap.error("--calibrate takes LAMBDA in [0, 1]")
-
-
-def parse_cap(spec, names):
-    """'C' -> C; 'NAME:C[,NAME:C...]' -> {group index: C}; an unknown name, a name twice or C < 0 raises ValueError"""
-    try:
-        c = int(spec)
-    except ValueError:
-        c = None
-    if c is not None:
-        if c < 0:
-            raise ValueError("--cap takes C >= 0, got %r" % (spec,))
-        return c
-    caps = {}
-    for part in spec.split(","):
-        name, sep, m = part.strip().rpartition(":")
-        try:
-            m = int(m) if sep else -1
-        except ValueError:
-            m = -1
-        if not sep or m < 0:
-            raise ValueError("--cap takes C or NAME:C[,NAME:C...] with C >= 0, got %r" % (part,))
-        if name not in names:
-            raise ValueError("--cap: unknown group %r (the groups are %s)" % (name, ", ".join(names)))
-        if names.index(name) in caps:
-            raise ValueError("--cap names group %r twice" % (name,))
-        caps[names.index(name)] = m
-    return caps
-
-
-def add_cap_args(ap):
-    """the options of the exposure-capped lists (trainer.ExposureCap), shared with recommend.py"""
     ap.add_argument("--cap", default=None, metavar="C|NAME:C[,NAME:C...]")
     ap.add_argument("--cap-candidates", type=int, default=None, metavar="N")
     ap.add_argument("--cap-score", choices=("logprob", "logit"), default=None)
-
-
-def check_cap_args(ap, a, k):
-    """refuses (ap.error) what trainer.ExposureCap would refuse for lists of k entries, and the combination with the per-user rules;
-    a.caps = the parsed --cap (None without the option)"""
-    a.caps = None
-    if a.cap is None:
-        if a.cap_candidates is not None or a.cap_score is not None:
-            ap.error("--cap-candidates and --cap-score need --cap")
-        return
-    if a.min_slots is not None or a.diversify is not None or a.calibrate is not None:
-        ap.error("--cap cannot be combined with --min-slots, --diversify or --calibrate")
-    try:
-        a.caps = parse_cap(a.cap, group_names(a.group_kind, a.n_groups))
-    except ValueError as e:
-        ap.error(str(e))
-    if a.cap_candidates is not None and not k <= a.cap_candidates <= 1024:
-        ap.error("--cap-candidates must be in [k, 1024] = [%d, 1024], got %d" % (k, a.cap_candidates))
-
-
-def make_cap(a, labels, n_groups):
-    """the ExposureCap of the parsed options (labels: the --groups labels, needed for NAME:C)"""
-    from ltgan.serving import ExposureCap
-    cap = (labels, n_groups, a.caps) if isinstance(a.caps, dict) else a.caps
-    return ExposureCap(cap, candidates=a.cap_candidates, score=a.cap_score or "logprob")
-
-
-def cap_line(plain_ids, ids, cap_vec, stats, k):
-    """the line --cap adds: the largest number of lists one item appears in, plain top-k -> capped (plain_ids / ids [n_users, k],
-    padding -1; cap_vec: the cap per item), the items that sit exactly at their cap, the short lists and the rounds (ExposureCap.stats())"""
-    n_items = len(cap_vec)
-    before = np.bincount(plain_ids[plain_ids >= 0], minlength=n_items)
-    after = np.bincount(ids[ids >= 0], minlength=n_items)
-    at_cap = int(((after == np.asarray(cap_vec)) & (np.asarray(cap_vec) > 0)).sum())
-    return "cap@%d: max exposure %d -> %d, %d items at their cap, %d short lists, %d rounds" % (
-        k, int(before.max()) if n_items else 0, int(after.max()) if n_items else 0, at_cap, stats["short"], stats["rounds"])
-
-
-def parse_floor(spec, names):
-    """'M' -> M; 'NAME:M[,NAME:M...]' -> {group index: M}; an unknown name, a name twice or M < 0 raises ValueError"""
-    try:
-        m = int(spec)
-    except ValueError:
-        m = None
-    if m is not None:
-        if m < 0:
-            raise ValueError("--floor takes M >= 0, got %r" % (spec,))
-        return m
-    floors = {}
-    for part in spec.split(","):
-        name, sep, m = part.strip().rpartition(":")
-        try:
-            m = int(m) if sep else -1
-        except ValueError:
-            m = -1
-        if not sep or m < 0:
-            raise ValueError("--floor takes M or NAME:M[,NAME:M...] with M >= 0, got %r" % (part,))
-        if name not in names:
-            raise ValueError("--floor: unknown group %r (the groups are %s)" % (name, ", ".join(names)))
-        if names.index(name) in floors:
-            raise ValueError("--floor names group %r twice" % (name,))
-        floors[names.index(name)] = m
-    return floors
-
-
-def add_floor_args(ap):
-    """the options of the exposure-floor lists (trainer.ExposureFloor), shared with recommend.py"""
+    ap.add_argument("--share", default=None, metavar="NAME[+NAME...]:S")
     ap.add_argument("--floor", default=None, metavar="M|NAME:M[,NAME:M...]")
     ap.add_argument("--floor-reserve", type=int, default=None, metavar="R")
     ap.add_argument("--floor-candidates", type=int, default=None, metavar="N")
     ap.add_argument("--floor-score", choices=("logprob", "logit"), default=None)
 
 
-def check_floor_args(ap, a, k):
-    """refuses (ap.error) what trainer.ExposureFloor would refuse for lists of k entries, and the combination with the other rules;
-    a.floors = the parsed --floor (None without the option)"""
-    a.floors = None
-    if a.floor is None:
-        if a.floor_reserve is not None or a.floor_candidates is not None or a.floor_score is not None:
-            ap.error("--floor-reserve, --floor-candidates and --floor-score need --floor")
-        return
-    if a.min_slots is not None or a.diversify is not None or a.calibrate is not None or a.cap is not None or a.share is not None:
-        ap.error("--floor cannot be combined with --min-slots, --diversify, --calibrate, --cap or --share")
-    if a.floor_reserve is None:
-        ap.error("--floor needs --floor-reserve R")
-    if not 0 <= a.floor_reserve <= k:
-        ap.error("--floor-reserve must be in [0, k] = [0, %d], got %d" % (k, a.floor_reserve))
+def parse_item_values(opt, v, spec, names):
+    """the per-item value of option `opt`, written with the letter `v` in messages: 'V' -> V; 'NAME:V[,NAME:V...]' -> {group index: V};
+    an unknown name, a name twice or V < 0 raises ValueError"""
     try:
-        a.floors = parse_floor(a.floor, group_names(a.group_kind, a.n_groups))
-    except ValueError as e:
-        ap.error(str(e))
-    if a.floor_candidates is not None and not k <= a.floor_candidates <= 1024:
-        ap.error("--floor-candidates must be in [k, 1024] = [%d, 1024], got %d" % (k, a.floor_candidates))
+        n = int(spec)
+    except ValueError:
+        n = None
+    if n is not None:
+        if n < 0:
+            raise ValueError("%s takes %s >= 0, got %r" % (opt, v, spec))
+        return n
+    values = {}
+    for part in spec.split(","):
+        name, sep, m = part.strip().rpartition(":")
+        try:
+            m = int(m) if sep else -1
+        except ValueError:
+            m = -1
+        if not sep or m < 0:
+            raise ValueError("%s takes %s or NAME:%s[,NAME:%s...] with %s >= 0, got %r" % (opt, v, v, v, v, part))
+        if name not in names:
+            raise ValueError("%s: unknown group %r (the groups are %s)" % (opt, name, ", ".join(names)))
+        if names.index(name) in values:
+            raise ValueError("%s names group %r twice" % (opt, name))
+        values[names.index(name)] = m
+    return values
 
 
-def make_floor(a, labels, n_groups):
-    """the ExposureFloor of the parsed options (labels: the --groups labels, needed for floors by group only)"""
-    from ltgan.serving import ExposureFloor
-    floor = (labels, n_groups, a.floors) if isinstance(a.floors, dict) else a.floors
-    return ExposureFloor(floor, a.floor_reserve, candidates=a.floor_candidates, score=a.floor_score or "logprob")
-
-
-def floor_line(plain_ids, ids, need_vec, stats, k):
-    """the line --floor adds: the floor items, those the matching leaves short of their floor, the floor items in fewer lists than their
-    floor, plain top-k -> served (plain_ids / ids [n_users, k], padding -1; need_vec: the floor per item), the inserted slots, the rows
-    changed and the rounds (ExposureFloor.stats())"""
-    need = np.asarray(need_vec)
-    before = np.bincount(plain_ids[plain_ids >= 0], minlength=len(need))
-    after = np.bincount(ids[ids >= 0], minlength=len(need))
-    return ("floor@%d: %d floor items, %d short of their floor, below the floor %d -> %d, %d inserted slots, %d rows changed, %d rounds" % (
-        k, stats["floor_items"], stats["short_items"], int(((need > 0) & (before < need)).sum()), int(((need > 0) & (after < need)).sum()),
-        stats["inserted"], stats["rows_changed"], stats["rounds"]))
+parse_cap = functools.partial(parse_item_values, "--cap", "C")
+parse_floor = functools.partial(parse_item_values, "--floor", "M")
 
 
 def parse_share(spec, names):
@@ -332,29 +201,115 @@ def parse_share(spec, names):
     return sorted(groups), share
 
 
-def add_share_args(ap):
-    """the option of the share-targeted lists (trainer.ShareTarget), shared with recommend.py"""
-    ap.add_argument("--share", default=None, metavar="NAME[+NAME...]:S")
+def check_rule_args(ap, a, k):
+    """refuses (ap.error) two rules together, an option without the rule it belongs to, and what the rule's class would refuse for lists
+    of k entries; leaves the parsed --cap / --share / --floor in a.caps / a.shares / a.floors (None without the option)"""
+    given = ["--" + o.replace("_", "-") for o in RULE_OPTIONS if getattr(a, o) is not None]
+    if len(given) > 1:
+        ap.error("%s cannot be combined with %s" % (given[1], given[0]))
+    names = group_names(a.group_kind, a.n_groups)
+    a.caps = a.shares = a.floors = None
+
+    def parsed(parse, spec):
+        try:
+            return parse(spec, names)
+        except ValueError as e:
+            ap.error(str(e))
+
+    if a.diversify is None:
+        if a.candidates is not None:
+            ap.error("--candidates needs --diversify")
+    else:
+        if not 0.0 <= a.diversify <= 1.0:
+            ap.error("--diversify takes LAMBDA in [0, 1]")
+        if k > 256:
+            ap.error("--diversify re-ranks at most 256 candidates: lists of %d entries are too long" % k)
+        if a.candidates is not None and not k <= a.candidates <= 256:
+            ap.error("--candidates must be in [k, 256] = [%d, 256], got %d" % (k, a.candidates))
+    if a.calibrate is not None and not 0.0 <= a.calibrate <= 1.0:
+        ap.error("--calibrate takes LAMBDA in [0, 1]")
+    if a.cap is None:
+        if a.cap_candidates is not None or a.cap_score is not None:
+            ap.error("--cap-candidates and --cap-score need --cap")
+    else:
+        a.caps = parsed(parse_cap, a.cap)
+        if a.cap_candidates is not None and not k <= a.cap_candidates <= 1024:
+            ap.error("--cap-candidates must be in [k, 1024] = [%d, 1024], got %d" % (k, a.cap_candidates))
+    if a.share is not None:
+        a.shares = parsed(parse_share, a.share)
+    if a.floor is None:
+        if a.floor_reserve is not None or a.floor_candidates is not None or a.floor_score is not None:
+            ap.error("--floor-reserve, --floor-candidates and --floor-score need --floor")
+    else:
+        if a.floor_reserve is None:
+            ap.error("--floor needs --floor-reserve R")
+        if not 0 <= a.floor_reserve <= k:
+            ap.error("--floor-reserve must be in [0, k] = [0, %d], got %d" % (k, a.floor_reserve))
+        a.floors = parsed(parse_floor, a.floor)
+        if a.floor_candidates is not None and not k <= a.floor_candidates <= 1024:
+            ap.error("--floor-candidates must be in [k, 1024] = [%d, 1024], got %d" % (k, a.floor_candidates))
 
 
-def check_share_args(ap, a):
-    """refuses (ap.error) what trainer.ShareTarget would refuse, and the combination with the other rules; a.shares = the parsed --share
-    (None without the option)"""
-    a.shares = None
-    if a.share is None:
-        return
-    if a.min_slots is not None or a.diversify is not None or a.calibrate is not None or a.cap is not None:
-        ap.error("--share cannot be combined with --min-slots, --diversify, --calibrate or --cap")
-    try:
-        a.shares = parse_share(a.share, group_names(a.group_kind, a.n_groups))
-    except ValueError as e:
-        ap.error(str(e))
+def build_rules(args, dataset_dir, n_items, groups=None):
+    """the serve-time rule of the parsed options -> (its keyword for a Recommender: {} or one entry, the stdout lines it adds after
+    run(): callables (ids, tr, k) -> str).  groups: (labels, names) of --groups where the caller has built them; else they are built
+    here, and only for a rule that refers to them"""
+    from ltgan.serving import Calibrate, Diversify, ExposureCap, ExposureFloor, MinSlots, ShareTarget
+
+    def grouped():
+        labels, names = groups or build_groups(dataset_dir, args.group_kind, args.n_groups, n_items)
+        return labels, names, len(names)
+
+    def per_item(values):                                # an int for every item, or {group index: value} with the labels it refers to
+        if not isinstance(values, dict):
+            return values
+        labels, _, n = grouped()
+        return labels, n, values
+
+    if getattr(args, "slots", None):
+        labels, _, n = grouped()
+        return dict(rule=MinSlots(labels, n, args.slots)), []
+    if getattr(args, "diversify", None) is not None:
+        div = Diversify(args.diversify, candidates=args.candidates, space=args.div_space)
+        return dict(diversify=div), [lambda ids, tr, k: ils_line(div.stats(), ids, k)]
+    if getattr(args, "calibrate", None) is not None:
+        labels, _, n = grouped()
+        cal = Calibrate(labels, n, args.calibrate)
+        return dict(calibrate=cal), [lambda ids, tr, k: miscal_line(cal.stats(), tr, k)]
+    if getattr(args, "caps", None) is not None:
+        cap = ExposureCap(per_item(args.caps), candidates=args.cap_candidates, score=args.cap_score or "logprob")
+        return dict(cap=cap), [lambda ids, tr, k: cap_line(cap.plain_ids(k), ids, cap.cap_vector(), cap.stats(), k)]
+    if getattr(args, "shares", None) is not None:
+        labels, names, n = grouped()
+        share = ShareTarget(labels, n, args.shares[0], args.shares[1])
+        return dict(share=share), [lambda ids, tr, k: share_line([names[g] for g in share.promote], share.stats(), k)]
+    if getattr(args, "floors", None) is not None:
+        floor = ExposureFloor(per_item(args.floors), args.floor_reserve, candidates=args.floor_candidates, score=args.floor_score or "logprob")
+        return dict(floor=floor), [lambda ids, tr, k: floor_line(floor.plain_ids(k), ids, floor.need_vector(), floor.stats(), k)]
+    return {}, []
 
 
-def make_share(a, labels, n_groups):
-    """the ShareTarget of the parsed options (labels: the --groups labels)"""
-    from ltgan.serving import ShareTarget
-    return ShareTarget(labels, n_groups, a.shares[0], a.shares[1])
+def cap_line(plain_ids, ids, cap_vec, stats, k):
+    """the line --cap adds: the largest number of lists one item appears in, plain top-k -> capped (plain_ids / ids [n_users, k],
+    padding -1; cap_vec: the cap per item), the items that sit exactly at their cap, the short lists and the rounds (ExposureCap.stats())"""
+    n_items = len(cap_vec)
+    before = np.bincount(plain_ids[plain_ids >= 0], minlength=n_items)
+    after = np.bincount(ids[ids >= 0], minlength=n_items)
+    at_cap = int(((after == np.asarray(cap_vec)) & (np.asarray(cap_vec) > 0)).sum())
+    return "cap@%d: max exposure %d -> %d, %d items at their cap, %d short lists, %d rounds" % (
+        k, int(before.max()) if n_items else 0, int(after.max()) if n_items else 0, at_cap, stats["short"], stats["rounds"])
+
+
+def floor_line(plain_ids, ids, need_vec, stats, k):
+    """the line --floor adds: the floor items, those the matching leaves short of their floor, the floor items in fewer lists than their
+    floor, plain top-k -> served (plain_ids / ids [n_users, k], padding -1; need_vec: the floor per item), the inserted slots, the rows
+    changed and the rounds (ExposureFloor.stats())"""
+    need = np.asarray(need_vec)
+    before = np.bincount(plain_ids[plain_ids >= 0], minlength=len(need))
+    after = np.bincount(ids[ids >= 0], minlength=len(need))
+    return ("floor@%d: %d floor items, %d short of their floor, below the floor %d -> %d, %d inserted slots, %d rows changed, %d rounds" % (
+        k, stats["floor_items"], stats["short_items"], int(((need > 0) & (before < need)).sum()), int(((need > 0) & (after < need)).sum()),
+        stats["inserted"], stats["rows_changed"], stats["rounds"]))
 
 
 def share_line(names, stats, k):
@@ -392,11 +347,7 @@ def parse_args(argv):
     ap.add_argument("--k", type=int, default=100)
     ap.add_argument("--keep-prob", type=float, default=0.75)
     ap.add_argument("--json", default=None)
-    add_diversify_args(ap)
-    add_calibrate_args(ap)
-    add_cap_args(ap)
-    add_share_args(ap)
-    add_floor_args(ap)
+    add_rule_args(ap)
     a = ap.parse_args(argv)
     try:
         a.group_kind, a.n_groups = parse_groups(a.groups)
@@ -414,11 +365,7 @@ def parse_args(argv):
             a.slots = parse_min_slots(a.min_slots, group_names(a.group_kind, a.n_groups), a.k)
         except ValueError as e:
             ap.error(str(e))
-    check_diversify_args(ap, a, max(K_NDCG, K_R1, K_R2, a.k))       # (the length of the lists: LongTailReport.k)
-    check_calibrate_args(ap, a)
-    check_cap_args(ap, a, max(K_NDCG, K_R1, K_R2, a.k))
-    check_share_args(ap, a)
-    check_floor_args(ap, a, max(K_NDCG, K_R1, K_R2, a.k))
+    check_rule_args(ap, a, max(K_NDCG, K_R1, K_R2, a.k))           # (the length of the lists: LongTailReport.k)
     return a
 
 
@@ -514,42 +461,25 @@ def write_json(rep, path):
 
 def longtail(args, h0_size, h1_size, h2_size, h3_size, LEARNING_RATE, precision="bf16", batch_size_test=20000, **_):
     from ltgan.dataset import EvalData
-    from ltgan.serving import Calibrate, Diversify, LongTailReport, MinSlots, Recommender, ShardedRecommender, close_model, open_model
+    from ltgan.serving import LongTailReport, Recommender, ShardedRecommender, close_model, open_model
     d = args.dataset_dir
     eng, lo, hi, rank, world, print = open_model(d, args.checkpoint, (h0_size, h1_size, h2_size, h3_size), LEARNING_RATE, precision)  # noqa: A001
     n_items = eng.I_global
     tr, te, _ = dp.load_tr_te_data(os.path.join(d, "%s_tr.csv" % args.split), os.path.join(d, "%s_te.csv" % args.split), n_items)
     labels, names = build_groups(d, args.group_kind, args.n_groups, n_items)
     report = LongTailReport(labels, len(names), k_ndcg=K_NDCG, k_r1=K_R1, k_r2=K_R2, k_exp=args.k)
-    rule = MinSlots(labels, len(names), args.slots) if getattr(args, "slots", None) else None
-    div = None
-    if getattr(args, "diversify", None) is not None:
-        div = Diversify(args.diversify, candidates=args.candidates, space=args.div_space)
-    cal = Calibrate(labels, len(names), args.calibrate) if getattr(args, "calibrate", None) is not None else None
-    cap = make_cap(args, labels, len(names)) if getattr(args, "caps", None) is not None else None
-    share = make_share(args, labels, len(names)) if getattr(args, "shares", None) is not None else None
-    floor = make_floor(args, labels, len(names)) if getattr(args, "floors", None) is not None else None
+    rule, rule_lines = build_rules(args, d, n_items, (labels, names))
     if world > 1:
-        rec = ShardedRecommender(eng, EvalData(tr, te, eng.device, item_lo=lo, item_hi=hi), k=report.k, chunk=batch_size_test, report=report,
-                                 rule=rule, diversify=div, calibrate=cal, cap=cap, share=share, floor=floor)
+        rec = ShardedRecommender(eng, EvalData(tr, te, eng.device, item_lo=lo, item_hi=hi), k=report.k, chunk=batch_size_test, report=report, **rule)
     else:
-        rec = Recommender(eng, EvalData(tr, te, eng.device), k=report.k, chunk=batch_size_test, report=report, rule=rule, diversify=div,
-                          calibrate=cal, cap=cap, share=share, floor=floor)
+        rec = Recommender(eng, EvalData(tr, te, eng.device), k=report.k, chunk=batch_size_test, report=report, **rule)
     ids, _ = rec.run(rng_step=RNG_STEP, keep_prob=args.keep_prob)
     rep = aggregate(*report.table(), labels, names, args.k)
     rep.update(split=args.split, groups_spec=args.groups)
     for line in report_lines(rep):
         print(line)
-    if div is not None:
-        print(ils_line(div.stats(), ids, report.k))
-    if cal is not None:
-        print(miscal_line(cal.stats(), tr, report.k))
-    if cap is not None:
-        print(cap_line(cap.plain_ids(report.k), ids, cap.cap_vector(), cap.stats(), report.k))
-    if share is not None:
-        print(share_line([names[g] for g in share.promote], share.stats(), report.k))
-    if floor is not None:
-        print(floor_line(floor.plain_ids(report.k), ids, floor.need_vector(), floor.stats(), report.k))
+    for line in rule_lines:
+        print(line(ids, tr, report.k))
     if args.json and rank == 0:
         write_json(rep, args.json)
     close_model(world)

@@ -97,11 +97,7 @@ def parse_args(argv):
     ap.add_argument("--npz", default=None)
     ap.add_argument("--groups", default="niche")
     ap.add_argument("--min-slots", default=None)
-    lt.add_diversify_args(ap)
-    lt.add_calibrate_args(ap)
-    lt.add_cap_args(ap)
-    lt.add_share_args(ap)
-    lt.add_floor_args(ap)
+    lt.add_rule_args(ap)
     ap.add_argument("--explain", type=int, default=None, metavar="R")
     ap.add_argument("--explain-top", type=int, default=None, metavar="N")
     ap.add_argument("--explain-space", choices=("decoder", "encoder"), default=None)
@@ -119,11 +115,7 @@ def parse_args(argv):
             a.slots = lt.parse_min_slots(a.min_slots, lt.group_names(a.group_kind, a.n_groups), a.k)
     except ValueError as e:
         ap.error(str(e))
-    lt.check_diversify_args(ap, a, a.k)
-    lt.check_calibrate_args(ap, a)
-    lt.check_cap_args(ap, a, a.k)
-    lt.check_share_args(ap, a)
-    lt.check_floor_args(ap, a, a.k)
+    lt.check_rule_args(ap, a, a.k)
     if a.explain is None:
         if a.explain_top is not None or a.explain_space is not None or a.explain_metric is not None or a.why is not None:
             ap.error("--explain-top, --explain-space, --explain-metric and --why need --explain")
@@ -199,65 +191,35 @@ def summary_line(m, k):
 
 def recommend(args, h0_size, h1_size, h2_size, h3_size, LEARNING_RATE, precision="bf16", batch_size_test=20000, **_):
     from ltgan.dataset import EvalData
-    from ltgan.serving import Calibrate, Diversify, Explain, MinSlots, Recommender, ShardedRecommender, close_model, open_model
+    from ltgan.serving import Explain, Recommender, ShardedRecommender, close_model, open_model
     d = args.dataset_dir
     eng, lo, hi, rank, world, print = open_model(d, args.checkpoint, (h0_size, h1_size, h2_size, h3_size), LEARNING_RATE, precision)  # noqa: A001
     n_items = eng.I_global
     tr, te, uid0 = dp.load_tr_te_data(os.path.join(d, "%s_tr.csv" % args.split), os.path.join(d, "%s_te.csv" % args.split), n_items)
     _, _, niche, _, _ = dp.load_pop_niche_tags(os.path.join(d, "item2id.txt"), os.path.join(d, "item_list.txt"),
                                                os.path.join(d, "niche_items.txt"), n_items)
-    rule = None
-    if getattr(args, "slots", None):
-        labels, names = lt.build_groups(d, args.group_kind, args.n_groups, n_items)
-        rule = MinSlots(labels, len(names), args.slots)
-    div = None
-    if getattr(args, "diversify", None) is not None:
-        div = Diversify(args.diversify, candidates=args.candidates, space=args.div_space)
-    cal = None
-    if getattr(args, "calibrate", None) is not None:
-        labels, names = lt.build_groups(d, args.group_kind, args.n_groups, n_items)
-        cal = Calibrate(labels, len(names), args.calibrate)
-    cap = None
-    if getattr(args, "caps", None) is not None:
-        labels, names = lt.build_groups(d, args.group_kind, args.n_groups, n_items) if isinstance(args.caps, dict) else (None, ())
-        cap = lt.make_cap(args, labels, len(names))
-    share = share_names = None
-    if getattr(args, "shares", None) is not None:
-        labels, names = lt.build_groups(d, args.group_kind, args.n_groups, n_items)
-        share = lt.make_share(args, labels, len(names))
-        share_names = [names[g] for g in share.promote]
-    floor = None
-    if getattr(args, "floors", None) is not None:
-        labels, names = lt.build_groups(d, args.group_kind, args.n_groups, n_items) if isinstance(args.floors, dict) else (None, ())
-        floor = lt.make_floor(args, labels, len(names))
+    rule, rule_lines = lt.build_rules(args, d, n_items)
     why = None
     if getattr(args, "explain", None) is not None:
         why = Explain(args.explain, top=args.explain_top, space=args.explain_space or "decoder", metric=args.explain_metric or "cosine")
     if world > 1:
-        rec = ShardedRecommender(eng, EvalData(tr, te, eng.device, item_lo=lo, item_hi=hi), k=args.k, chunk=batch_size_test, rule=rule,
-                                 diversify=div, explain=why, calibrate=cal, cap=cap, share=share, floor=floor)
+        rec = ShardedRecommender(eng, EvalData(tr, te, eng.device, item_lo=lo, item_hi=hi), k=args.k, chunk=batch_size_test, explain=why, **rule)
     else:
-        rec = Recommender(eng, EvalData(tr, te, eng.device), k=args.k, chunk=batch_size_test, rule=rule, diversify=div, explain=why,
-                          calibrate=cal, cap=cap, share=share, floor=floor)
+        rec = Recommender(eng, EvalData(tr, te, eng.device), k=args.k, chunk=batch_size_test, explain=why, **rule)
     ids, scores = rec.run(rng_step=RNG_STEP, keep_prob=args.keep_prob)
     m = long_tail_summary(ids, niche, n_items, te)
     why_tab = why.table() if why is not None else None
     if rank == 0:
         write_recs(ids, scores, uid0, args.out, args.npz, why=why_tab)
     print(summary_line(m, args.k))
-    if div is not None:
-        print(lt.ils_line(div.stats(), ids, args.k))
+    ils_first = "diversify" in rule                      # the ils line stands before the why line, every other rule's line after it
+    for line in rule_lines if ils_first else []:
+        print(line(ids, tr, args.k))
     if why is not None:
         n_lines, n_reasons = write_why(why_tab[0], why_tab[1], ids, uid0, args.why) if rank == 0 else (0, 0)
         print("why@%d: %d entries, %d reasons" % (why.top, n_lines, n_reasons))
-    if cal is not None:
-        print(lt.miscal_line(cal.stats(), tr, args.k))
-    if cap is not None:
-        print(lt.cap_line(cap.plain_ids(args.k), ids, cap.cap_vector(), cap.stats(), args.k))
-    if share is not None:
-        print(lt.share_line(share_names, share.stats(), args.k))
-    if floor is not None:
-        print(lt.floor_line(floor.plain_ids(args.k), ids, floor.need_vector(), floor.stats(), args.k))
+    for line in [] if ils_first else rule_lines:
+        print(line(ids, tr, args.k))
     close_model(world)
     return ids, scores, m
 

@@ -6,7 +6,8 @@ item audiences (the k likeliest users of an item, gathered over the same chunk w
 
 One chunk walk (Recommender.run) serves every kind of list, unsharded and over item shards: the forward sits behind one method that
 ShardedRecommender overrides, and every catalogue-wide list comes from one SlabLists, which alone knows whether the catalogue is cut
-into slabs.  A new kind of list is one branch of that walk and one apply(lists, ...) of its own.
+into slabs.  The walk knows no kind of list: it asks the one rule it was given (a Rule) the few questions of the protocol, so a new kind
+of list is one class.
 """
 from __future__ import annotations
 
@@ -154,6 +155,20 @@ class SlabLists:
         self.merge(ls, li, score_out, id_out)
 
 
+def group_labels(labels, n_groups, engine=None):
+    """the item-group labels everything grouped takes: one uint8 per GLOBAL item id, a label >= n_groups is in no group, 1 <= n_groups
+    <= 8 -> the contiguous uint8 host array.  engine given (bind time): there must be one label per item of its catalogue -> the labels
+    on its device"""
+    if not 1 <= int(n_groups) <= 8:
+        raise ValueError("n_groups must be in [1, 8]")
+    labels = np.ascontiguousarray(np.asarray(labels), dtype=np.uint8)
+    if engine is None:
+        return labels
+    if labels.size != engine.I_global:
+        raise ValueError("labels hold %d items, the catalogue %d" % (labels.size, engine.I_global))
+    return torch.from_numpy(labels).to(engine.device)
+
+
 class LongTailReport:
     """The long-tail report a Recommender / ShardedRecommender fills when it is passed as `report=`: per user and item group
     NDCG@k_ndcg / Recall@k_r1 / Recall@k_r2 (plus the all-items slot, which is Evaluator's table) and the exposure counts at k_exp,
@@ -162,11 +177,8 @@ class LongTailReport:
     `item_hits` [n_items] on the device; table() brings both to the host."""
 
     def __init__(self, labels, n_groups, k_ndcg=100, k_r1=20, k_r2=50, k_exp=100):
-        self.labels_host = np.ascontiguousarray(np.asarray(labels), dtype=np.uint8)
-        self.n_groups = int(n_groups)
+        self.labels_host, self.n_groups = group_labels(labels, n_groups), int(n_groups)
         self.cut = dict(k_ndcg=int(k_ndcg), k_r1=int(k_r1), k_r2=int(k_r2), k_exp=int(k_exp))
-        if not 1 <= self.n_groups <= 8:
-            raise ValueError("n_groups must be in [1, 8]")
         if min(self.cut.values()) < 1 or max(self.cut.values()) > 1024:
             raise ValueError("every cutoff must be in [1, 1024]")
         self.k = max(self.cut.values())                  # the list length the report needs
@@ -175,10 +187,8 @@ class LongTailReport:
     def bind(self, engine, n_users, k):
         if k < self.k:
             raise ValueError("top-K lists of %d entries are shorter than the report's largest cutoff %d" % (k, self.k))
-        if self.labels_host.size != engine.I_global:
-            raise ValueError("labels hold %d items, the catalogue %d" % (self.labels_host.size, engine.I_global))
         dev = engine.device
-        self.labels = torch.from_numpy(self.labels_host).to(dev)
+        self.labels = group_labels(self.labels_host, self.n_groups, engine)
         self.out = torch.zeros(n_users, self.n_groups + 1, 4, dtype=torch.float32, device=dev)
         self.item_hits = torch.zeros(self.labels_host.size, dtype=torch.int32, device=dev)
 
@@ -190,20 +200,37 @@ class LongTailReport:
         return self.out.cpu().numpy(), self.item_hits.cpu().numpy()
 
 
-class MinSlots:
+class Rule:
+    """What the chunk walk (Recommender.run) asks of the one serve-time rule it is given -- the whole protocol:
+      bind(engine, rows, k, n_users)   once: the buffers for chunks of up to `rows` users, lists of k entries and a split of n_users;
+                                       sets `longest`, the longest list the rule will ask the SlabLists for
+      begin(engine, group)             at the start of every run()
+      whole = False:  apply(lists, acts, tr, n, k, lo, score_out, id_out)   per chunk: the lists of users lo .. lo + n, whose logits
+                                       `acts` holds, from the SlabLists `lists` into score_out / id_out [n, k]
+      whole = True:   gather(lists, acts, tr, n, lo)   per chunk: only what the rule needs of the chunk, since its rows depend on each
+                      match(engine, k, score_out, id_out)   other; after the last chunk the lists of the whole split [n_users, k]
+      needs_lse                        the rule reads acts.lse: over item shards the walk then combines the full-row lse per chunk"""
+
+    whole = False
+    needs_lse = False
+    longest = 0
+
+    def begin(self, engine, group=None):
+        pass
+
+
+class MinSlots(Rule):
     """A serve-time rule, passed as `rule=` to a Recommender / ShardedRecommender: at least slots[g] of every user's k list entries come
     from item group g (labels: one uint8 per GLOBAL item id, a label >= n_groups is in no group; the labels a LongTailReport takes).  Walking
     a user's ranking from the top, an item is taken if its group still owes slots, or if a slot is left that no group's outstanding minimum
     claims; a group with fewer eligible items than its minimum hands the rest to the free slots.  slots all 0 is the plain list; slots[g] = k
     is the k best items of group g.  Per chunk: the plain list, one reserved list per group with slots[g] > 0 (ltg_topk_groups with that
     group's bit, every one max(slots) entries long so that they share one array), composed by ltg_topk_quota.  Over item shards every one
-    of those lists is gathered and merged by the SlabLists, and every rank composes the same ruled lists."""
+    of those lists is gathered and merged by the SlabLists, and every rank composes the same ruled lists.  The report and the
+    explanations read the ruled lists."""
 
     def __init__(self, labels, n_groups, slots):
-        self.labels_host = np.ascontiguousarray(np.asarray(labels), dtype=np.uint8)
-        self.n_groups = int(n_groups)
-        if not 1 <= self.n_groups <= 8:
-            raise ValueError("n_groups must be in [1, 8]")
+        self.labels_host, self.n_groups = group_labels(labels, n_groups), int(n_groups)
         self.slots = [int(x) for x in slots]
         if len(self.slots) != self.n_groups:
             raise ValueError("slots holds %d counts for %d groups" % (len(self.slots), self.n_groups))
@@ -211,17 +238,14 @@ class MinSlots:
             raise ValueError("a group's minimum must be >= 0")
         self.groups = [g for g, m in enumerate(self.slots) if m > 0]        # the groups with a reserved list
         self.quota = [self.slots[g] for g in self.groups]
-        self.m = max(self.slots)
+        self.m = self.longest = max(self.slots)
         self.labels = None
 
-    def bind(self, engine, rows, k):
-        """buffers for chunks of up to `rows` users and lists of k entries"""
+    def bind(self, engine, rows, k, n_users):
         if sum(self.slots) > k:
             raise ValueError("the minimum slots sum to %d, more than the %d entries of a list" % (sum(self.slots), k))
-        if self.labels_host.size != engine.I_global:
-            raise ValueError("labels hold %d items, the catalogue %d" % (self.labels_host.size, engine.I_global))
         dev = engine.device
-        self.labels = torch.from_numpy(self.labels_host).to(dev)
+        self.labels = group_labels(self.labels_host, self.n_groups, engine)
         n_l, m = max(1, len(self.groups)), max(1, self.m)
         self.all_s = torch.empty(rows * k, dtype=torch.float32, device=dev)
         self.all_i = torch.empty(rows * k, dtype=torch.int32, device=dev)
@@ -237,8 +261,7 @@ class MinSlots:
         n_l = len(self.groups)
         return self.grp_s[: n_l * n * self.m].view(n_l, n, self.m), self.grp_i[: n_l * n * self.m].view(n_l, n, self.m)
 
-    def apply(self, lists, acts, tr, n, k, score_out, id_out):
-        """the ruled lists of the n rows whose logits `acts` holds; lists: the SlabLists the plain and the reserved lists come from"""
+    def apply(self, lists, acts, tr, n, k, lo, score_out, id_out):
         a_s, a_i = self.plain(n, k)
         lists.topk(acts, tr, n, k, a_s, a_i)
         if not self.groups:                              # nothing reserved: the plain list
@@ -265,7 +288,7 @@ def catalogue_image(engine, space, metric, image=None, group=None):
     return image
 
 
-class Diversify:
+class Diversify(Rule):
     """A serve-time re-ranking, passed as `diversify=` to a Recommender / ShardedRecommender: greedy maximal marginal relevance.  Each
     user's `candidates` best items (ltg_topk; default min(256, 2 k), k <= candidates <= 256) are re-ranked so that the next entry is the
     one with the largest  lam * relevance - (1 - lam) * (largest similarity to what the list already holds)  -- relevance = the score
@@ -274,7 +297,8 @@ class Diversify:
     ltg_topk at `candidates`, then ONE launch of ltg_topk_diversify: the candidates' similarity matrix never leaves the chip.  The lists
     keep every pick's original score, so they are generally not descending.  After run(): stats() [n_users, 2] = the mean pair similarity
     of the plain top-k list and of the diversified one.  Over item shards the candidates are gathered and merged at their own length by
-    the SlabLists and every rank re-ranks the same candidates against the image of the whole catalogue."""
+    the SlabLists and every rank re-ranks the same candidates against the image of the whole catalogue.  The report and the
+    explanations read the diversified lists."""
 
     def __init__(self, lam, candidates=None, space="decoder", metric="cosine"):
         self.lam = float(lam)
@@ -288,17 +312,16 @@ class Diversify:
         self.image_lo = 0
 
     def bind(self, engine, rows, k, n_users):
-        """buffers for chunks of up to `rows` users, lists of k entries and a table of n_users"""
         c = min(256, 2 * k) if self.candidates is None else self.candidates
         if not k <= c <= 256:
             raise ValueError("candidates must be in [k, 256] = [%d, 256], got %d" % (k, c))
-        self.c = c
+        self.c = self.longest = c
         dev = engine.device
         self.cand_s = torch.empty(rows * c, dtype=torch.float32, device=dev)
         self.cand_i = torch.empty(rows * c, dtype=torch.int32, device=dev)
         self.stat = torch.zeros(n_users, 2, dtype=torch.float32, device=dev)
 
-    def pack(self, engine, group=None):
+    def begin(self, engine, group=None):
         """the image of the whole catalogue, once per run().  group given (item shards): every rank packs its slab into a zeroed
         [I_global, 608] buffer at its item_lo, and the buffer is all-reduced viewed as int32 -- exactly one rank contributes each row."""
         self.image = catalogue_image(engine, self.space, self.metric, self.image, group)
@@ -308,7 +331,6 @@ class Diversify:
         return self.cand_s[: n * self.c].view(n, self.c), self.cand_i[: n * self.c].view(n, self.c)
 
     def apply(self, lists, acts, tr, n, k, lo, score_out, id_out):
-        """the diversified lists of users lo .. lo + n, whose logits `acts` holds; lists: the SlabLists the candidates come from"""
         c_s, c_i = self.candidates_of(n)
         lists.topk(acts, tr, n, self.c, c_s, c_i)
         lists.eng.topk_diversify(self.image, self.image_lo, c_s, c_i, self.lam, k, score_out, id_out, self.stat[lo:lo + n])
@@ -318,7 +340,7 @@ class Diversify:
         return self.stat.cpu().numpy()
 
 
-class Calibrate:
+class Calibrate(Rule):
     """A serve-time re-ranking, passed as `calibrate=` to a Recommender / ShardedRecommender: calibrated recommendation (Steck, RecSys
     2018) with the total-variation distance in place of the KL divergence.  Every user's list follows the class mix of that user's
     fold-in history (labels: one uint8 per GLOBAL item id, the class of an item = min(label, n_groups), the last class is "in no group";
@@ -330,26 +352,20 @@ class Calibrate:
     then ONE launch of ltg_topk_calibrate.  The lists keep every pick's original score, so they are generally not descending.  After
     run(): stats() [n_users, 2] = the miscalibration of the plain top-k list and of the calibrated one.  Over item shards every class
     list is gathered and merged by the SlabLists, every rank counts its slab's part of the histories and the counts are all-reduced: no
-    logit is exchanged and every rank composes the same lists."""
+    logit is exchanged and every rank composes the same lists.  The report and the explanations read the calibrated lists."""
 
     def __init__(self, labels, n_groups, lam):
-        self.labels_host = np.ascontiguousarray(np.asarray(labels), dtype=np.uint8)
-        self.n_groups = int(n_groups)
-        if not 1 <= self.n_groups <= 8:
-            raise ValueError("n_groups must be in [1, 8]")
+        self.labels_host, self.n_groups = group_labels(labels, n_groups), int(n_groups)
         self.lam = float(lam)
         if not 0.0 <= self.lam <= 1.0:               # (NaN fails both comparisons)
             raise ValueError("lam must be in [0, 1], got %r" % (lam,))
         self.classes = self.masks = self.labels = self.stat = None
 
     def bind(self, engine, rows, k, n_users):
-        """buffers for chunks of up to `rows` users, lists of k entries and a table of n_users"""
-        if self.labels_host.size != engine.I_global:
-            raise ValueError("labels hold %d items, the catalogue %d" % (self.labels_host.size, engine.I_global))
-        g, dev = self.n_groups, engine.device
+        self.labels = group_labels(self.labels_host, self.n_groups, engine)
+        g, dev, self.longest = self.n_groups, engine.device, k
         self.classes = [int(c) for c in np.unique(np.minimum(self.labels_host, g))]      # a class with no item needs no list
         self.masks = [1 << c if c < g else (0x1FF >> g) << g for c in self.classes]       # the last class: bits n_groups .. 8
-        self.labels = torch.from_numpy(self.labels_host).to(dev)
         n_l = len(self.classes)
         self.grp_s = torch.empty(n_l * rows * k, dtype=torch.float32, device=dev)
         self.grp_i = torch.empty(n_l * rows * k, dtype=torch.int32, device=dev)
@@ -362,7 +378,6 @@ class Calibrate:
         return self.grp_s[: n_l * n * k].view(n_l, n, k), self.grp_i[: n_l * n * k].view(n_l, n, k)
 
     def apply(self, lists, acts, tr, n, k, lo, score_out, id_out):
-        """the calibrated lists of users lo .. lo + n, whose logits `acts` holds; lists: the SlabLists the class lists come from"""
         eng = lists.eng
         g_s, g_i = self.class_lists(n, k)
         for j, mask in enumerate(self.masks):
@@ -378,24 +393,24 @@ class Calibrate:
         return self.stat.cpu().numpy()
 
 
-class ExposureCap:
-    """A serve-time rule over the WHOLE split, passed as `cap=` to a Recommender / ShardedRecommender: no item appears in more than its
-    cap of the served lists, and the slots an over-full item gives up go to the best alternatives of the users it turned away.  cap: an
-    int (every item), an int array per GLOBAL item id, or (labels, n_groups, {group index: C}) -- only the items of those groups are
-    capped (labels: one uint8 per GLOBAL id, the labels a LongTailReport takes).  The lists are the user-optimal stable matching of
-    user-proposing deferred acceptance: a user prefers their `candidates` best items (default min(1024, 4 k), k <= candidates <= 1024)
-    in list order; an item prefers users by `score` -- `logprob`: logit - lse, the log-probability the user's softmax gives the item,
-    comparable across users and the Audience score; `logit`: the raw logit -- equal scores the lower user row.  A user whose candidates
-    run out gets a short list.  It is the first rule whose rows depend on each other: the chunk walk only stores every chunk's candidates
-    (SlabLists.topk at `candidates`) and lse, and match() runs once after the last chunk -- ltg_cap_index, then ltg_cap_rounds in batches
-    of `batch` rounds until a round raises no threshold, then ltg_cap_finish.  The fixed point does not depend on the order or the
-    batching of the rounds, so the table is bit-identical from run to run.  Over item shards every rank holds the same merged candidates
-    and the same full-row lse, so every rank runs the same matching and nothing is exchanged.  After run(): stats()."""
+class _Matching(Rule):
+    """What ExposureCap and ExposureFloor share: a rule over the WHOLE split that is a stable matching between users and items.  The per-item
+    value (NOUN: the word for it in messages) is an int (every item), an int array per GLOBAL item id, or (labels, n_groups, {group index:
+    value}) -- only the items of those groups, every other item gets FILL (labels: one uint8 per GLOBAL id, the labels a LongTailReport
+    takes).  A user's side of the matching is their `candidates` best items (default min(1024, 4 k), k <= candidates <= 1024) in list
+    order; an item ranks users by `score` -- `logprob`: logit - lse, the log-probability the user's softmax gives the item, comparable
+    across users and the Audience score; `logit`: the raw logit -- equal scores the lower user row.  The rows depend on each other, so the
+    chunk walk only stores every chunk's candidates (SlabLists.topk at `candidates`) and lse, and match() runs once after the last chunk:
+    the subclass's index call, its rounds call in batches of `batch` rounds until a round changes nothing (state[4] < state[1]), its
+    finish call.  The fixed point does not depend on the order or the batching of the rounds, so the table is bit-identical from run to
+    run.  Over item shards every rank holds the same merged candidates and the same full-row lse, so every rank runs the same matching and
+    nothing is exchanged.  The report and the explanations read the matched lists, in a second pass over the chunks."""
 
+    whole = True
     MAX_C = 1024
-    UNCAPPED = 2 ** 31 - 1
+    NOUN, FILL, MAX_ROUNDS, N_STATE = None, 0, 0, 0
 
-    def __init__(self, cap, candidates=None, score="logprob", batch=4):
+    def __init__(self, value, candidates, score, batch):
         if score not in ("logprob", "logit"):
             raise ValueError("score must be logprob or logit")
         self.score = score
@@ -403,201 +418,149 @@ class ExposureCap:
         if self.candidates is not None and not 1 <= self.candidates <= self.MAX_C:
             raise ValueError("candidates must be in [1, %d], got %r" % (self.MAX_C, candidates))
         self.batch = int(batch)
-        if not 1 <= self.batch <= LTG_CAP_MAX_ROUNDS:
-            raise ValueError("batch must be in [1, %d]" % LTG_CAP_MAX_ROUNDS)
-        self.uniform = self.cap_host = self.by_group = None
-        if isinstance(cap, tuple):
-            labels, n_groups, caps = cap
-            labels = np.ascontiguousarray(np.asarray(labels), dtype=np.uint8)
-            if not 1 <= int(n_groups) <= 8:
-                raise ValueError("n_groups must be in [1, 8]")
-            vec = np.full(labels.size, self.UNCAPPED, np.int64)
-            for g, cg in dict(caps).items():
+        if not 1 <= self.batch <= self.MAX_ROUNDS:
+            raise ValueError("batch must be in [1, %d]" % self.MAX_ROUNDS)
+        self.uniform = self.vec_host = None
+        if isinstance(value, tuple):
+            labels, n_groups, by_group = value
+            labels = group_labels(labels, n_groups)
+            self.vec_host = np.full(labels.size, self.FILL, np.int64)
+            for g, v in dict(by_group).items():
                 if not 0 <= int(g) < int(n_groups):
                     raise ValueError("group index %r outside [0, %d)" % (g, n_groups))
-                vec[labels == int(g)] = int(cg)
-            self.cap_host = vec
-        elif np.ndim(cap) == 0:
-            self.uniform = int(cap)
-            if self.uniform != cap:
-                raise ValueError("a uniform cap is an integer, got %r" % (cap,))
+                self.vec_host[labels == int(g)] = int(v)
+        elif np.ndim(value) == 0:
+            self.uniform = int(value)
+            if self.uniform != value:
+                raise ValueError("a uniform %s is an integer, got %r" % (self.NOUN, value))
         else:
-            self.cap_host = np.asarray(cap).astype(np.int64).reshape(-1)
-        low = self.uniform if self.cap_host is None else (int(self.cap_host.min()) if self.cap_host.size else 0)
+            self.vec_host = np.asarray(value).astype(np.int64).reshape(-1)
+        low = self.uniform if self.vec_host is None else (int(self.vec_host.min()) if self.vec_host.size else 0)
         if low < 0:
-            raise ValueError("a cap must be >= 0")
-        self.c = self.n_items = self.cap = self.cand_s = self.cand_i = self.lse = self.state = self.ws = self._stats = None
+            raise ValueError("a %s must be >= 0" % self.NOUN)
+        self.c = self.n_items = self.cand_s = self.cand_i = self.lse = self.state = self.ws = self._stats = None
 
     @property
     def needs_lse(self):
         return self.score == "logprob"
 
-    def bind(self, engine, k, n_users):
-        """the device tables for lists of k entries over a split of n_users"""
+    def bind(self, engine, rows, k, n_users):
+        """-> the per-item values [n_items] int32 on the device; the subclass names them and sizes its workspace"""
         c = min(self.MAX_C, 4 * k) if self.candidates is None else self.candidates
         if not 1 <= k <= c <= self.MAX_C:
             raise ValueError("candidates must be in [k, %d] = [%d, %d], got %d" % (self.MAX_C, k, self.MAX_C, c))
         if n_users * c >= 2 ** 31:
             raise ValueError("%d users x %d candidates: the matching indexes fewer than 2^31 entries" % (n_users, c))
         n_items, dev = int(engine.I_global), engine.device
-        vec = np.full(n_items, self.uniform, np.int64) if self.cap_host is None else self.cap_host
+        vec = np.full(n_items, self.uniform, np.int64) if self.vec_host is None else self.vec_host
         if vec.size != n_items:
-            raise ValueError("cap holds %d items, the catalogue %d" % (vec.size, n_items))
-        self.c, self.n_items = c, n_items
-        self.cap = torch.from_numpy(np.minimum(vec, self.UNCAPPED).astype(np.int32)).to(dev)
+            raise ValueError("%s holds %d items, the catalogue %d" % (self.NOUN, vec.size, n_items))
+        self.c, self.n_items, self.longest = c, n_items, c
         self.cand_s = torch.empty(n_users, c, dtype=torch.float32, device=dev)
         self.cand_i = torch.empty(n_users, c, dtype=torch.int32, device=dev)
         self.lse = torch.empty(n_users, dtype=torch.float32, device=dev) if self.needs_lse else None
-        self.state = torch.zeros(LTG_CAP_STATE, dtype=torch.int32, device=dev)
-        self.ws = torch.empty(max(1, engine.cap_ws_bytes(n_users, c, n_items)), dtype=torch.uint8, device=dev)
+        self.state = torch.zeros(self.N_STATE, dtype=torch.int32, device=dev)
+        return torch.from_numpy(np.minimum(vec, 2 ** 31 - 1).astype(np.int32)).to(dev)
 
     def gather(self, lists, acts, tr, n, lo):
-        """the candidates (and lse) of users lo .. lo + n, whose logits `acts` holds, into the tables; lists: the SlabLists they come from"""
         lists.topk(acts, tr, n, self.c, self.cand_s[lo:lo + n], self.cand_i[lo:lo + n])
         if self.lse is not None:
             self.lse[lo:lo + n].copy_(acts.lse[:n])
 
-    def match(self, engine, k, score_out, id_out):
-        """the matching over the gathered tables -> score_out / id_out [n_users, k]"""
-        n = int(self.cand_i.shape[0])
-        if n == 0:
-            self._stats = dict(rounds=0, raises=0, passed_over=0, short=0)
-            return
-        engine.cap_index(self.cand_i, self.n_items, self.state, self.ws)
+    def rounds(self, batch_of_rounds, what):
+        """batches of rounds (batch_of_rounds(): the engine's rounds call, bound) until one changes nothing -> the index of that round"""
         while True:
-            engine.cap_rounds(self.cand_s, self.cand_i, self.lse, self.cap, k, self.batch, self.state, self.ws)
-            raises, rounds, _, _, last = (int(x) for x in self.state[:5].cpu())
-            if last < rounds:                            # the last round raised no threshold: the fixed point
-                break
-            if rounds > n * self.c + 1:                  # (every round but the last removes at least one entry for good)
-                raise LtgError("the capped matching has not converged after %d rounds" % rounds)
-        engine.cap_finish(self.cand_s, self.cand_i, self.n_items, k, score_out, id_out, self.state, self.ws)
-        st = [int(x) for x in self.state.cpu()]
-        self._stats = dict(rounds=last + 1, raises=st[0], passed_over=st[2], short=st[3])
+            batch_of_rounds()
+            _, rounds, _, _, last = (int(x) for x in self.state[:5].cpu())
+            if last < rounds:                            # the last round changed nothing: the fixed point
+                return last
+            if rounds > int(self.cand_i.shape[0]) * self.c + 1:      # (every round but the last removes at least one entry for good)
+                raise LtgError("the %s matching has not converged after %d rounds" % (what, rounds))
 
     def plain_ids(self, k):
         """-> [n_users, k] int32 host array: the plain top-k lists, the first k columns of the candidates"""
         return self.cand_i[:, :k].cpu().numpy()
+
+    def stats(self):
+        return dict(self._stats)
+
+
+class ExposureCap(_Matching):
+    """A serve-time rule over the WHOLE split, passed as `cap=` to a Recommender / ShardedRecommender: no item appears in more than its
+    cap of the served lists (so the report's item_hits <= cap), and the slots an over-full item gives up go to the best alternatives of
+    the users it turned away.  cap, candidates, score, batch: _Matching's; an item outside the capped groups is UNCAPPED.  The lists are
+    the user-optimal stable matching of user-proposing deferred acceptance; a user whose candidates run out gets a short list.  match():
+    ltg_cap_index, ltg_cap_rounds until a round raises no threshold, ltg_cap_finish.  After run(): stats() -> dict: rounds (up to and
+    including the first that raised no threshold), raises (threshold raises), passed_over (candidate entries a user's walk passed
+    over), short (users with fewer than k entries)."""
+
+    UNCAPPED = 2 ** 31 - 1
+    NOUN, FILL, MAX_ROUNDS, N_STATE = "cap", UNCAPPED, LTG_CAP_MAX_ROUNDS, LTG_CAP_STATE
+
+    def __init__(self, cap, candidates=None, score="logprob", batch=4):
+        super().__init__(cap, candidates, score, batch)
+        self.cap = None
+
+    def bind(self, engine, rows, k, n_users):
+        self.cap = super().bind(engine, rows, k, n_users)
+        self.ws = torch.empty(max(1, engine.cap_ws_bytes(n_users, self.c, self.n_items)), dtype=torch.uint8, device=engine.device)
+
+    def match(self, engine, k, score_out, id_out):
+        if int(self.cand_i.shape[0]) == 0:
+            self._stats = dict(rounds=0, raises=0, passed_over=0, short=0)
+            return
+        engine.cap_index(self.cand_i, self.n_items, self.state, self.ws)
+        last = self.rounds(lambda: engine.cap_rounds(self.cand_s, self.cand_i, self.lse, self.cap, k, self.batch, self.state, self.ws), "capped")
+        engine.cap_finish(self.cand_s, self.cand_i, self.n_items, k, score_out, id_out, self.state, self.ws)
+        st = [int(x) for x in self.state.cpu()]
+        self._stats = dict(rounds=last + 1, raises=st[0], passed_over=st[2], short=st[3])
 
     def cap_vector(self):
         """-> [n_items] int32 host array: the cap per GLOBAL item id (UNCAPPED where none applies)"""
         return self.cap.cpu().numpy()
 
-    def stats(self):
-        """-> dict: rounds (up to and including the first that raised no threshold), raises (threshold raises), passed_over (candidate
-        entries a user's walk passed over), short (users with fewer than k entries)"""
-        return dict(self._stats)
 
-
-class ExposureFloor:
+class ExposureFloor(_Matching):
     """A serve-time rule over the WHOLE split, passed as `floor=` to a Recommender / ShardedRecommender, the dual of ExposureCap: every
-    item with a floor M reaches M of the served lists if that many users hold it among their candidates and can spare a slot -- the
-    first audience a new or niche item needs.  floor: an int (every item), an int array per GLOBAL item id (0: no floor), or (labels,
-    n_groups, {group index: M}) -- only the items of those groups get a floor (labels: one uint8 per GLOBAL id, the labels a
-    LongTailReport takes).  reserve: how many of the last slots of a user's list floor items may take, 0 <= reserve <= k; the first
+    item with a floor M reaches M of the served lists if that many users hold it among their candidates and can spare a slot (so the
+    report's item_hits >= min(floor, held)) -- the first audience a new or niche item needs.  floor, candidates, score, batch:
+    _Matching's; 0 is no floor.  reserve: how many of the last slots of a user's list floor items may take, 0 <= reserve <= k; the first
     k - reserve entries of every list are the plain ones.  The lists are the item-optimal stable matching of item-proposing deferred
-    acceptance: an item proposes to the users that hold it among their `candidates` best items (default min(1024, 4 k)), best `score`
-    first -- `logprob`: logit - lse, `logit`: the raw logit, equal scores the lower user row -- and a user keeps, of the proposals behind
-    position k - reserve, the `reserve` it likes best.  Every list stays in score order and every entry keeps its logit.  Like the cap
-    the rows depend on each other: the chunk walk only stores every chunk's candidates and lse, and match() runs once after the last
-    chunk -- ltg_floor_index, then ltg_floor_rounds in batches of `batch` rounds until a round lowers no limit, then ltg_floor_finish.
-    The fixed point does not depend on the order or the batching of the rounds, so the table is bit-identical from run to run.  Over
-    item shards every rank holds the same merged candidates and the same full-row lse, so every rank runs the same matching and nothing
-    is exchanged.  After run(): stats(), held()."""
+    acceptance: an item proposes to the users that hold it among their candidates, best score first, and a user keeps, of the proposals
+    behind position k - reserve, the `reserve` it likes best.  Every list stays in score order and every entry keeps its logit.  match():
+    ltg_floor_index, ltg_floor_rounds until a round lowers no limit, ltg_floor_finish.  After run(): held(), and stats() -> dict: rounds
+    (up to and including the first that lowered no limit), lowerings (limit lowerings), floor_items, short_items (floor items that hold
+    fewer entries than their floor), rows_changed (users whose list differs from the plain top-k), inserted (slots that went to entries
+    from behind position k - t, summed over the users)."""
 
-    MAX_C = 1024
+    NOUN, FILL, MAX_ROUNDS, N_STATE = "floor", 0, LTG_FLOOR_MAX_ROUNDS, LTG_FLOOR_STATE
 
     def __init__(self, floor, reserve, candidates=None, score="logprob", batch=4):
-        if score not in ("logprob", "logit"):
-            raise ValueError("score must be logprob or logit")
-        self.score = score
         self.reserve = int(reserve)
         if self.reserve != reserve or self.reserve < 0:
             raise ValueError("reserve is an integer >= 0, got %r" % (reserve,))
-        self.candidates = None if candidates is None else int(candidates)
-        if self.candidates is not None and not 1 <= self.candidates <= self.MAX_C:
-            raise ValueError("candidates must be in [1, %d], got %r" % (self.MAX_C, candidates))
-        self.batch = int(batch)
-        if not 1 <= self.batch <= LTG_FLOOR_MAX_ROUNDS:
-            raise ValueError("batch must be in [1, %d]" % LTG_FLOOR_MAX_ROUNDS)
-        self.uniform = self.need_host = None
-        if isinstance(floor, tuple):
-            labels, n_groups, floors = floor
-            labels = np.ascontiguousarray(np.asarray(labels), dtype=np.uint8)
-            if not 1 <= int(n_groups) <= 8:
-                raise ValueError("n_groups must be in [1, 8]")
-            vec = np.zeros(labels.size, np.int64)
-            for g, mg in dict(floors).items():
-                if not 0 <= int(g) < int(n_groups):
-                    raise ValueError("group index %r outside [0, %d)" % (g, n_groups))
-                vec[labels == int(g)] = int(mg)
-            self.need_host = vec
-        elif np.ndim(floor) == 0:
-            self.uniform = int(floor)
-            if self.uniform != floor:
-                raise ValueError("a uniform floor is an integer, got %r" % (floor,))
-        else:
-            self.need_host = np.asarray(floor).astype(np.int64).reshape(-1)
-        low = self.uniform if self.need_host is None else (int(self.need_host.min()) if self.need_host.size else 0)
-        if low < 0:
-            raise ValueError("a floor must be >= 0")
-        self.c = self.n_items = self.need = self.cand_s = self.cand_i = self.lse = self.state = self.ws = self.held_d = self._stats = None
+        super().__init__(floor, candidates, score, batch)
+        self.need = self.held_d = None
 
-    @property
-    def needs_lse(self):
-        return self.score == "logprob"
-
-    def bind(self, engine, k, n_users):
-        """the device tables for lists of k entries over a split of n_users"""
-        c = min(self.MAX_C, 4 * k) if self.candidates is None else self.candidates
-        if not 1 <= k <= c <= self.MAX_C:
-            raise ValueError("candidates must be in [k, %d] = [%d, %d], got %d" % (self.MAX_C, k, self.MAX_C, c))
+    def bind(self, engine, rows, k, n_users):
         if self.reserve > k:
             raise ValueError("reserve must be in [0, k] = [0, %d], got %d" % (k, self.reserve))
-        if n_users * c >= 2 ** 31:
-            raise ValueError("%d users x %d candidates: the matching indexes fewer than 2^31 entries" % (n_users, c))
-        n_items, dev = int(engine.I_global), engine.device
-        vec = np.full(n_items, self.uniform, np.int64) if self.need_host is None else self.need_host
-        if vec.size != n_items:
-            raise ValueError("floor holds %d items, the catalogue %d" % (vec.size, n_items))
-        self.c, self.n_items = c, n_items
-        self.need = torch.from_numpy(np.minimum(vec, 2 ** 31 - 1).astype(np.int32)).to(dev)
-        self.cand_s = torch.empty(n_users, c, dtype=torch.float32, device=dev)
-        self.cand_i = torch.empty(n_users, c, dtype=torch.int32, device=dev)
-        self.lse = torch.empty(n_users, dtype=torch.float32, device=dev) if self.needs_lse else None
-        self.state = torch.zeros(LTG_FLOOR_STATE, dtype=torch.int32, device=dev)
-        self.held_d = torch.zeros(n_items, dtype=torch.int32, device=dev)
-        self.ws = torch.empty(max(1, engine.floor_ws_bytes(n_users, c, n_items)), dtype=torch.uint8, device=dev)
-
-    def gather(self, lists, acts, tr, n, lo):
-        """the candidates (and lse) of users lo .. lo + n, whose logits `acts` holds, into the tables; lists: the SlabLists they come from"""
-        lists.topk(acts, tr, n, self.c, self.cand_s[lo:lo + n], self.cand_i[lo:lo + n])
-        if self.lse is not None:
-            self.lse[lo:lo + n].copy_(acts.lse[:n])
+        self.need = super().bind(engine, rows, k, n_users)
+        self.held_d = torch.zeros(self.n_items, dtype=torch.int32, device=engine.device)
+        self.ws = torch.empty(max(1, engine.floor_ws_bytes(n_users, self.c, self.n_items)), dtype=torch.uint8, device=engine.device)
 
     def match(self, engine, k, score_out, id_out):
-        """the matching over the gathered tables -> score_out / id_out [n_users, k]"""
-        n = int(self.cand_i.shape[0])
-        if n == 0:
+        if int(self.cand_i.shape[0]) == 0:
             self.held_d.zero_()
             self._stats = dict(rounds=0, lowerings=0, floor_items=int((self.need > 0).sum()), short_items=0, rows_changed=0, inserted=0)
             return
         engine.floor_index(self.cand_i, self.n_items, self.state, self.ws)
-        while True:
-            engine.floor_rounds(self.cand_s, self.cand_i, self.lse, self.need, k, self.reserve, self.batch, self.state, self.ws)
-            _, rounds, _, _, last = (int(x) for x in self.state[:5].cpu())
-            if last < rounds:                            # the last round lowered no limit: the fixed point
-                break
-            if rounds > n * self.c + 1:                  # (every round but the last takes at least one position from a row for good)
-                raise LtgError("the floor matching has not converged after %d rounds" % rounds)
+        last = self.rounds(lambda: engine.floor_rounds(self.cand_s, self.cand_i, self.lse, self.need, k, self.reserve, self.batch, self.state,
+                                                       self.ws), "floor")
         engine.floor_finish(self.cand_s, self.cand_i, self.lse, self.need, k, self.reserve, score_out, id_out, self.state, self.ws,
                             held_out=self.held_d)
         st = [int(x) for x in self.state.cpu()]
         self._stats = dict(rounds=last + 1, lowerings=st[0], floor_items=st[6], short_items=st[2], rows_changed=st[3], inserted=st[5])
-
-    def plain_ids(self, k):
-        """-> [n_users, k] int32 host array: the plain top-k lists, the first k columns of the candidates"""
-        return self.cand_i[:, :k].cpu().numpy()
 
     def need_vector(self):
         """-> [n_items] int32 host array: the floor per GLOBAL item id (0 where none applies)"""
@@ -608,14 +571,8 @@ class ExposureFloor:
         least min(floor, held) lists, and held < floor means too few users hold it among their candidates or can spare a slot"""
         return self.held_d.cpu().numpy()
 
-    def stats(self):
-        """-> dict: rounds (up to and including the first that lowered no limit), lowerings (limit lowerings), floor_items, short_items
-        (floor items that hold fewer entries than their floor), rows_changed (users whose list differs from the plain top-k), inserted
-        (slots that went to entries from behind position k - t, summed over the users)"""
-        return dict(self._stats)
 
-
-class ShareTarget:
+class ShareTarget(Rule):
     """A serve-time rule over the WHOLE split, passed as `share=` to a Recommender / ShardedRecommender: the item groups `promote` (group
     indices; labels: one uint8 per GLOBAL item id, the labels a LongTailReport takes) get the part `share` of ALL served slots, and the
     promoted slots go where they cost the least relevance -- not the same number to every user, as MinSlots gives.  For a user, one more
@@ -626,13 +583,12 @@ class ShareTarget:
     ltg_topk_share after the last chunk.  Every row stays sorted and every entry keeps its score.  share = 0, or a target the plain
     lists already meet, gives the plain lists bit for bit; a target beyond what the promoted groups can fill gives every row at its
     limit (stats()["reached"] is then False).  Over item shards every rank holds the same merged lists and runs the same call: nothing
-    is exchanged.  After run(): stats()."""
+    is exchanged.  The report and the explanations read the final lists, in a second pass over the chunks.  After run(): stats()."""
+
+    whole = True
 
     def __init__(self, labels, n_groups, promote, share):
-        self.labels_host = np.ascontiguousarray(np.asarray(labels), dtype=np.uint8)
-        self.n_groups = int(n_groups)
-        if not 1 <= self.n_groups <= 8:
-            raise ValueError("n_groups must be in [1, 8]")
+        self.labels_host, self.n_groups = group_labels(labels, n_groups), int(n_groups)
         self.promote = sorted({int(g) for g in promote})
         self.mask = group_mask_of(self.promote, self.n_groups)           # (raises for an index outside the groups and for an empty list)
         self.rest_mask = 0x1FF & ~self.mask                              # every other label, those in no group (bit 8) included
@@ -641,18 +597,15 @@ class ShareTarget:
             raise ValueError("share must be in [0, 1], got %r" % (share,))
         self.k = self.want = self.labels = self.pro_s = self.pro_i = self.rest_s = self.rest_i = self.state = self.ws = self._stats = None
 
-    def bind(self, engine, k, n_users):
-        """the device tables for lists of k entries over a split of n_users"""
+    def bind(self, engine, rows, k, n_users):
         if not 1 <= k <= 1024:
             raise ValueError("k must be in [1, 1024], got %d" % k)
         if n_users * k >= 2 ** 31:
             raise ValueError("%d users x %d entries: the selection indexes fewer than 2^31 steps" % (n_users, k))
-        if self.labels_host.size != engine.I_global:
-            raise ValueError("labels hold %d items, the catalogue %d" % (self.labels_host.size, engine.I_global))
+        self.labels = group_labels(self.labels_host, self.n_groups, engine)
         dev = engine.device
-        self.k = int(k)
+        self.k = self.longest = int(k)
         self.want = int(np.ceil(np.float64(self.share) * n_users * k))
-        self.labels = torch.from_numpy(self.labels_host).to(dev)
         self.pro_s = torch.empty(n_users, k, dtype=torch.float32, device=dev)
         self.pro_i = torch.empty(n_users, k, dtype=torch.int32, device=dev)
         self.rest_s = torch.empty(n_users, k, dtype=torch.float32, device=dev)
@@ -661,13 +614,10 @@ class ShareTarget:
         self.ws = torch.empty(max(1, engine.share_ws_bytes(n_users, k)), dtype=torch.uint8, device=dev)
 
     def gather(self, lists, acts, tr, n, lo):
-        """the promoted and the rest lists of users lo .. lo + n, whose logits `acts` holds, into the tables; lists: the SlabLists they
-        come from"""
         lists.topk(acts, tr, n, self.k, self.pro_s[lo:lo + n], self.pro_i[lo:lo + n], self.labels, self.mask)
         lists.topk(acts, tr, n, self.k, self.rest_s[lo:lo + n], self.rest_i[lo:lo + n], self.labels, self.rest_mask)
 
     def match(self, engine, k, score_out, id_out):
-        """the one call over the gathered tables -> score_out / id_out [n_users, k]"""
         st = [0] * LTG_SHARE_STATE
         if int(self.pro_i.shape[0]) > 0:
             engine.topk_share(self.pro_s, self.pro_i, self.rest_s, self.rest_i, k, self.want, score_out, id_out, self.state, self.ws)
@@ -723,8 +673,9 @@ class Explain:
         self.why_i = torch.empty(n_users, top, self.r, dtype=torch.int32, device=dev)
 
     def pack(self, engine, group=None, share=None):
-        """the image of the whole catalogue, once per run(); share: a Diversify whose image (already packed for this run) is the same"""
-        if share is not None and (share.space, share.metric) == (self.space, self.metric):
+        """the image of the whole catalogue, once per run(); share: the walk's policy -- a Diversify of the same space and metric has
+        packed the same image for this run already"""
+        if isinstance(share, Diversify) and (share.space, share.metric) == (self.space, self.metric):
             self.image = share.image
         else:
             self.image = catalogue_image(engine, self.space, self.metric, self.image, group)
@@ -823,71 +774,36 @@ class Audience:
 class Recommender:
     """Top-K recommendations per user (the forward of Evaluator, then ltg_topk instead of the metrics): the same chunks of
     `chunk` users capped by eval_chunk_rows, the same dropout-on forward (Q3) with counter rng_step + lo per chunk, fold-in
-    items excluded.  keep_prob = 1.0 gives dropout-free, deterministic recommendations.  report: a LongTailReport to fill from
-    each chunk's lists (k >= its largest cutoff); absent, nothing else runs.  rule: a MinSlots the lists are to satisfy (the report then
-    reads the ruled lists); absent, the plain top-K.  diversify: a Diversify the lists are re-ranked by (the report then reads the
-    diversified lists); not together with rule.  Every list comes out of one SlabLists (self.lists).  audience: an Audience to gather
-    from each chunk's logits, right after the forward (audience.table() after run()); k = 0 then walks the chunks without user lists --
-    run() returns [n_users, 0] arrays and no list kernel is launched.  explain: an Explain filled from each chunk's final lists, whichever
-    kind they are (explain.table() after run()); needs k >= 1.  calibrate: a Calibrate the lists are composed by (the report and the
-    explanations then read the calibrated lists); not together with rule or diversify; needs k >= 1.  cap: an ExposureCap the lists are
-    matched under -- the walk then only gathers every chunk's candidates, the matching runs once after the last chunk, and a second pass
-    over the chunks (no forward) feeds the report and the explanations from the capped lists, so item_hits <= cap; not together with rule,
-    diversify or calibrate; needs k >= 1; the audience is untouched.  share: a ShareTarget the lists are composed under -- the walk then only
-    gathers every chunk's promoted and rest lists, ltg_topk_share runs once after the last chunk, and the same second pass feeds the report
-    and the explanations from the final lists; not together with rule, diversify, calibrate or cap; needs k >= 1.  floor: an ExposureFloor
-    the lists are matched under -- the cap's flow: the walk gathers every chunk's candidates, the matching runs once after the last chunk
-    and the same second pass feeds the report and the explanations, so item_hits >= min(floor, held); not together with rule, diversify,
-    calibrate, cap or share; needs k >= 1."""
+    items excluded.  keep_prob = 1.0 gives dropout-free, deterministic recommendations.  Every list comes out of one SlabLists
+    (self.lists).  At most one of rule= (MinSlots), diversify=, calibrate=, cap= (ExposureCap), share= (ShareTarget) and floor=
+    (ExposureFloor) decides what the lists are: it becomes self.policy, a Rule, and the walk asks it only what Rule's protocol holds;
+    without one the lists are the plain top-K.  Per chunk: the forward; audience= (an Audience, audience.table() after run()) gathered
+    from the logits; the lists, or with a policy over the whole split only what it gathers; then report= (a LongTailReport, k >= its
+    largest cutoff) and explain= (an Explain, explain.table() after run()) read the chunk's final lists.  A policy over the whole split
+    matches after the last chunk, and a second pass over the chunks (no forward) feeds the report and the explanations.  k = 0 walks the
+    chunks for the audience alone: run() returns [n_users, 0] arrays, no list kernel is launched, and nothing that needs lists goes
+    with it."""
 
     sharded = False                                  # ShardedRecommender: one rank of `group` per item slab
 
     def __init__(self, engine, ev, k=100, chunk=20000, report=None, rule=None, diversify=None, group=None, audience=None, explain=None,
                  calibrate=None, cap=None, share=None, floor=None):
-        if floor is not None and (rule is not None or diversify is not None or calibrate is not None or cap is not None or share is not None):
-            raise ValueError("floor= cannot be combined with rule=, diversify=, calibrate=, cap= or share=")
-        if int(k) == 0 and floor is not None:
-            raise ValueError("k = 0 serves no user lists: floor= needs k >= 1")
-        if share is not None and (rule is not None or diversify is not None or calibrate is not None or cap is not None):
-            raise ValueError("share= cannot be combined with rule=, diversify=, calibrate= or cap=")
-        if int(k) == 0 and share is not None:
-            raise ValueError("k = 0 serves no user lists: share= needs k >= 1")
-        if cap is not None and (rule is not None or diversify is not None or calibrate is not None):
-            raise ValueError("cap= cannot be combined with rule=, diversify= or calibrate=")
-        if int(k) == 0 and cap is not None:
-            raise ValueError("k = 0 serves no user lists: cap= needs k >= 1")
-        if rule is not None and diversify is not None:
-            raise ValueError("diversify= and rule= cannot be combined")
-        if calibrate is not None and (rule is not None or diversify is not None):
-            raise ValueError("calibrate= cannot be combined with rule= or diversify=")
-        if int(k) == 0 and calibrate is not None:
-            raise ValueError("k = 0 serves no user lists: calibrate= needs k >= 1")
-        if int(k) == 0 and (report is not None or rule is not None or diversify is not None):
-            raise ValueError("k = 0 serves no user lists: report=, rule= and diversify= need k >= 1")
-        if int(k) == 0 and explain is not None:
-            raise ValueError("k = 0 serves no user lists: explain= needs k >= 1")
-        self.eng, self.ev, self.k, self.report, self.rule, self.diversify, self.group = engine, ev, int(k), report, rule, diversify, group
-        self.audience, self.explain, self.calibrate, self.cap, self.share, self.floor = audience, explain, calibrate, cap, share, floor
+        rules = dict(rule=rule, diversify=diversify, calibrate=calibrate, cap=cap, share=share, floor=floor)
+        given = [name for name, r in rules.items() if r is not None]
+        if len(given) > 1:
+            raise ValueError("%s= cannot be combined with %s=" % (given[-1], "= or ".join(given[:-1])))
+        self.policy = rules[given[0]] if given else None
+        if int(k) == 0 and (self.policy is not None or report is not None or explain is not None):
+            raise ValueError("k = 0 serves no user lists: report=, explain= and every rule need k >= 1")
+        self.rule, self.diversify, self.calibrate, self.cap, self.share, self.floor = rule, diversify, calibrate, cap, share, floor
+        self.eng, self.ev, self.k, self.report, self.group, self.audience, self.explain = engine, ev, int(k), report, group, audience, explain
         if report is not None:
             report.bind(engine, ev.n, self.k)
         self.chunk = chunk_rows(engine, ev, chunk)
         longest = self.k
-        if rule is not None:
-            rule.bind(engine, self.chunk, self.k)
-            longest = max(longest, rule.m)
-        if diversify is not None:
-            diversify.bind(engine, self.chunk, self.k, ev.n)
-            longest = max(longest, diversify.c)
-        if calibrate is not None:
-            calibrate.bind(engine, self.chunk, self.k, ev.n)             # (its class lists are k long: `longest` is k already)
-        if cap is not None:
-            cap.bind(engine, self.k, ev.n)
-            longest = max(longest, cap.c)
-        if share is not None:
-            share.bind(engine, self.k, ev.n)                             # (its two lists are k long: `longest` is k already)
-        if floor is not None:
-            floor.bind(engine, self.k, ev.n)
-            longest = max(longest, floor.c)
+        if self.policy is not None:
+            self.policy.bind(engine, self.chunk, self.k, ev.n)
+            longest = max(longest, self.policy.longest)
         if explain is not None:
             explain.bind(engine, self.k, ev.n)
             longest = max(longest, explain.top * explain.r)          # (its per-slab lists are [rows * top, r])
@@ -903,20 +819,27 @@ class Recommender:
         """the logits of the n rows `tr` into self.acts"""
         self.eng.forward(tr, self.acts, keep_prob=keep_prob, is_training=0.0, rng_step=rng_step)
 
+    def _read(self, tr, te, lo, hi):
+        """the report and the explanations of users lo .. hi, from their final lists"""
+        if self.report is not None:
+            self.report.add(self.eng, self.ids[lo:hi], te, lo)
+        if self.explain is not None:
+            self.explain.apply(self.lists, tr, hi - lo, lo, self.ids[lo:hi])
+
     def run(self, rng_step=0, keep_prob=0.75):
         """-> (ids [n_users, k] int32 global item ids, scores [n_users, k] float32 logits) as host arrays (over item shards: identical
         on every rank)"""
-        eng, ev, k = self.eng, self.ev, self.k
+        eng, ev, k, policy = self.eng, self.ev, self.k, self.policy
+        chunks = [(lo, min(ev.n, lo + self.chunk)) for lo in range(0, ev.n, self.chunk)]
         if self.report is not None:
             self.report.item_hits.zero_()
-        if self.diversify is not None:
-            self.diversify.pack(eng, group=self.group)
+        if policy is not None:
+            policy.begin(eng, self.group)
         if self.explain is not None:
-            self.explain.pack(eng, group=self.group, share=self.diversify)
+            self.explain.pack(eng, group=self.group, share=policy)
         if self.audience is not None:
             self.audience.reset()
-        for lo in range(0, ev.n, self.chunk):
-            hi = min(ev.n, lo + self.chunk)
+        for lo, hi in chunks:
             n = hi - lo
             tr, te = ev.rows(lo, hi)
             self._forward(tr, n, keep_prob, rng_step + lo)
@@ -924,39 +847,19 @@ class Recommender:
                 self.audience.add(eng, self.acts, tr, n, lo)
             if k == 0:                                   # no user lists: the walk serves the audience alone
                 continue
-            if self.cap is not None:                     # the lists depend on every chunk: only the candidates now
-                self.cap.gather(self.lists, self.acts, tr, n, lo)
+            if policy is not None and policy.whole:      # the lists depend on every chunk: only what the rule gathers now
+                policy.gather(self.lists, self.acts, tr, n, lo)
                 continue
-            if self.share is not None:                   # likewise: only the promoted and the rest lists now
-                self.share.gather(self.lists, self.acts, tr, n, lo)
-                continue
-            if self.floor is not None:                   # likewise: only the candidates now
-                self.floor.gather(self.lists, self.acts, tr, n, lo)
-                continue
-            if self.diversify is not None:
-                self.diversify.apply(self.lists, self.acts, tr, n, k, lo, self.scores[lo:hi], self.ids[lo:hi])
-            elif self.rule is not None:
-                self.rule.apply(self.lists, self.acts, tr, n, k, self.scores[lo:hi], self.ids[lo:hi])
-            elif self.calibrate is not None:
-                self.calibrate.apply(self.lists, self.acts, tr, n, k, lo, self.scores[lo:hi], self.ids[lo:hi])
+            if policy is not None:
+                policy.apply(self.lists, self.acts, tr, n, k, lo, self.scores[lo:hi], self.ids[lo:hi])
             else:
                 self.lists.topk(self.acts, tr, n, k, self.scores[lo:hi], self.ids[lo:hi])
-            if self.report is not None:
-                self.report.add(eng, self.ids[lo:hi], te, lo)
-            if self.explain is not None:
-                self.explain.apply(self.lists, tr, n, lo, self.ids[lo:hi])
-        # a rule over the whole split: its lists exist only now
-        whole = self.cap if self.cap is not None else self.share if self.share is not None else self.floor
-        if whole is not None:
-            whole.match(eng, k, self.scores, self.ids)
+            self._read(tr, te, lo, hi)
+        if policy is not None and policy.whole:          # its lists exist only now
+            policy.match(eng, k, self.scores, self.ids)
             if self.report is not None or self.explain is not None:      # a second pass over the chunks, without a forward
-                for lo in range(0, ev.n, self.chunk):
-                    hi = min(ev.n, lo + self.chunk)
-                    tr, te = ev.rows(lo, hi)
-                    if self.report is not None:
-                        self.report.add(eng, self.ids[lo:hi], te, lo)
-                    if self.explain is not None:
-                        self.explain.apply(self.lists, tr, hi - lo, lo, self.ids[lo:hi])
+                for lo, hi in chunks:
+                    self._read(*ev.rows(lo, hi), lo, hi)
         return self.ids.cpu().numpy(), self.scores.cpu().numpy()
 
 
@@ -965,22 +868,20 @@ class ShardedRecommender(Recommender):
     `group`, so that every list -- plain, reserved, candidates -- is this slab's list, gathered and merged (ltg_topk_merge).  Every rank
     ends with the identical table, bit-identical to the unsharded Recommender's; the lists a report reads are identical on every rank, so
     the report (item_hits included) needs no exchange, and neither do ltg_topk_quota and ltg_topk_diversify (against the image of the
-    whole catalogue, Diversify.pack: one all-reduce per run()).  An Explain sees this slab's part of every history: its per-slab
+    whole catalogue, Diversify.begin: one all-reduce per run()).  An Explain sees this slab's part of every history: its per-slab
     explanations are one more gathered and merged list per chunk."""
 
     sharded = True
 
-    def __init__(self, engine, ev, k=100, group=None, chunk=20000, report=None, rule=None, diversify=None, audience=None, explain=None,
-                 calibrate=None, cap=None, share=None, floor=None):
-        super().__init__(engine, ev, k=k, chunk=chunk, report=report, rule=rule, diversify=diversify, group=group, audience=audience,
-                         explain=explain, calibrate=calibrate, cap=cap, share=share, floor=floor)
+    def __init__(self, engine, ev, k=100, group=None, **kw):
+        super().__init__(engine, ev, k=k, group=group, **kw)
         self.rowpart = torch.zeros(self.chunk * 5, dtype=torch.float32, device=engine.device)
         self.rowpart_all = None
-        if (audience is not None and audience.needs_lse) or (cap is not None and cap.needs_lse) or (floor is not None and floor.needs_lse):
+        if any(x is not None and x.needs_lse for x in (self.audience, self.policy)):
             self.rowpart_all = torch.zeros(dist.get_world_size(group) * self.chunk * 5, dtype=torch.float32, device=engine.device)
 
     def _forward(self, tr, n, keep_prob, rng_step):
-        """the slab's logits; with an audience, an exposure cap or an exposure floor that ranks by log-probability also the FULL-row lse in acts.lse: the slabs' row partials
+        """the slab's logits; with an audience or a policy that needs it (needs_lse) also the FULL-row lse in acts.lse: the slabs' row partials
         are all-gathered and combined (ltg_rowstats_combine, as ShardedTrainer.create_phase does) -- one more small collective per chunk"""
         sharded_forward(self.eng, tr, n, self.acts, self.rowpart, keep_prob, rng_step, self.group)
         if self.rowpart_all is not None:

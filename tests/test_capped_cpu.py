@@ -108,25 +108,25 @@ def test_exposure_cap_validation():
         with pytest.raises(ValueError):
             ExposureCap(bad)
     with pytest.raises(ValueError):
-        ExposureCap(np.ones(49, np.int32)).bind(_FakeEngine(), 10, 33)          # a cap count that differs from the catalogue
+        ExposureCap(np.ones(49, np.int32)).bind(_FakeEngine(), 10, 10, 33)      # a cap count that differs from the catalogue
     with pytest.raises(ValueError):
-        ExposureCap((labels[:49], 2, {0: 3})).bind(_FakeEngine(), 10, 33)
+        ExposureCap((labels[:49], 2, {0: 3})).bind(_FakeEngine(), 10, 10, 33)
     with pytest.raises(ValueError):
-        ExposureCap(5, candidates=9).bind(_FakeEngine(), 10, 33)               # fewer candidates than list entries
+        ExposureCap(5, candidates=9).bind(_FakeEngine(), 10, 10, 33)           # fewer candidates than list entries
     with pytest.raises(ValueError):
-        ExposureCap(5).bind(_FakeEngine(), 300, 2 ** 21)                        # 2^21 users x 1024 candidates: 2^31 entries
+        ExposureCap(5).bind(_FakeEngine(), 10, 300, 2 ** 21)                    # 2^21 users x 1024 candidates: 2^31 entries
     c = ExposureCap(5)
-    c.bind(_FakeEngine(), 10, 33)
+    c.bind(_FakeEngine(), 10, 10, 33)
     assert c.c == 40 and c.needs_lse and tuple(c.cand_i.shape) == (33, 40) and tuple(c.lse.shape) == (33,) and (c.cap_vector() == 5).all()
     c = ExposureCap(0, score="logit")
-    c.bind(_FakeEngine(), 300, 7)
+    c.bind(_FakeEngine(), 10, 300, 7)
     assert c.c == 1024 and not c.needs_lse and c.lse is None and (c.cap_vector() == 0).all()
     c = ExposureCap((labels, 2, {1: 3}), candidates=12)
-    c.bind(_FakeEngine(), 10, 33)
+    c.bind(_FakeEngine(), 10, 10, 33)
     v = c.cap_vector()
     assert c.c == 12 and (v[labels == 1] == 3).all() and (v[labels != 1] == ExposureCap.UNCAPPED).all()
     c = ExposureCap(np.arange(50))
-    c.bind(_FakeEngine(), 1, 2)
+    c.bind(_FakeEngine(), 10, 1, 2)
     assert c.c == 4 and c.cap_vector().tolist() == list(range(50)) and c.cap_vector().dtype == np.int32
     good = ExposureCap(5)
     for kw in (dict(rule=object()), dict(diversify=Diversify(0.5)), dict(calibrate=Calibrate(labels, 2, 0.5))):

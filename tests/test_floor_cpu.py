@@ -116,31 +116,31 @@ def test_exposure_floor_validation():
         with pytest.raises(ValueError):
             ExposureFloor(bad, 2)
     with pytest.raises(ValueError):
-        ExposureFloor(np.ones(49, np.int32), 2).bind(_FakeEngine(), 10, 33)       # a floor count that differs from the catalogue
+        ExposureFloor(np.ones(49, np.int32), 2).bind(_FakeEngine(), 10, 10, 33)   # a floor count that differs from the catalogue
     with pytest.raises(ValueError):
-        ExposureFloor((labels[:49], 2, {0: 3}), 2).bind(_FakeEngine(), 10, 33)
+        ExposureFloor((labels[:49], 2, {0: 3}), 2).bind(_FakeEngine(), 10, 10, 33)
     with pytest.raises(ValueError):
-        ExposureFloor(5, 2, candidates=9).bind(_FakeEngine(), 10, 33)            # fewer candidates than list entries
+        ExposureFloor(5, 2, candidates=9).bind(_FakeEngine(), 10, 10, 33)        # fewer candidates than list entries
     with pytest.raises(ValueError):
-        ExposureFloor(5, 11).bind(_FakeEngine(), 10, 33)                         # a reserve beyond the list
+        ExposureFloor(5, 11).bind(_FakeEngine(), 10, 10, 33)                     # a reserve beyond the list
     with pytest.raises(ValueError):
-        ExposureFloor(5, 2).bind(_FakeEngine(), 300, 2 ** 21)                    # 2^21 users x 1024 candidates: 2^31 entries
+        ExposureFloor(5, 2).bind(_FakeEngine(), 10, 300, 2 ** 21)                # 2^21 users x 1024 candidates: 2^31 entries
     f = ExposureFloor(5, 10)
-    f.bind(_FakeEngine(), 10, 33)
+    f.bind(_FakeEngine(), 10, 10, 33)
     assert f.c == 40 and f.needs_lse and tuple(f.cand_i.shape) == (33, 40) and tuple(f.lse.shape) == (33,) and (f.need_vector() == 5).all()
     assert f.reserve == 10 and tuple(f.held_d.shape) == (50,)
     f = ExposureFloor(0, 0, score="logit")
-    f.bind(_FakeEngine(), 300, 7)
+    f.bind(_FakeEngine(), 10, 300, 7)
     assert f.c == 1024 and not f.needs_lse and f.lse is None and (f.need_vector() == 0).all()
     f = ExposureFloor((labels, 2, {1: 3}), 2, candidates=12)
-    f.bind(_FakeEngine(), 10, 33)
+    f.bind(_FakeEngine(), 10, 10, 33)
     v = f.need_vector()
     assert f.c == 12 and (v[labels == 1] == 3).all() and (v[labels != 1] == 0).all()
     f = ExposureFloor(np.arange(50), 1)
-    f.bind(_FakeEngine(), 1, 2)
+    f.bind(_FakeEngine(), 10, 1, 2)
     assert f.c == 4 and f.need_vector().tolist() == list(range(50)) and f.need_vector().dtype == np.int32
     f = ExposureFloor(3, 1)
-    f.bind(_FakeEngine(), 4, 0)                          # no users: no launch, empty statistics
+    f.bind(_FakeEngine(), 10, 4, 0)                      # no users: no launch, empty statistics
     f.match(None, 4, None, None)
     assert f.stats() == dict(rounds=0, lowerings=0, floor_items=50, short_items=0, rows_changed=0, inserted=0) and not f.held().any()
     good = ExposureFloor(5, 2)

@@ -104,14 +104,14 @@ def test_minslots_validation():
         with pytest.raises(ValueError):
             MinSlots(labels, n_groups, slots)
     with pytest.raises(ValueError):
-        r.bind(_FakeEngine(), 10, 6)                                    # 5 + 2 slots do not fit a list of 6
+        r.bind(_FakeEngine(), 10, 6, 33)                                # 5 + 2 slots do not fit a list of 6
     with pytest.raises(ValueError):
-        MinSlots(labels[:49], 3, [0, 5, 2]).bind(_FakeEngine(), 10, 100)    # labels of another catalogue
-    r.bind(_FakeEngine(), 10, 7)
+        MinSlots(labels[:49], 3, [0, 5, 2]).bind(_FakeEngine(), 10, 100, 33)    # labels of another catalogue
+    r.bind(_FakeEngine(), 10, 7, 33)
     assert r.labels.dtype.is_floating_point is False and tuple(r.labels.shape) == (50,)
     assert tuple(r.plain(4, 7)[1].shape) == (4, 7) and tuple(r.reserved(4)[0].shape) == (2, 4, 5)
     z = MinSlots(labels, 3, [0, 0, 0])
-    z.bind(_FakeEngine(), 10, 7)
+    z.bind(_FakeEngine(), 10, 7, 33)
     assert z.groups == [] and z.m == 0
 
 

@@ -106,18 +106,18 @@ def test_share_target_validation():
         with pytest.raises(ValueError):
             ShareTarget(labels, 2, [1], share)
     with pytest.raises(ValueError):
-        ShareTarget(labels[:49], 2, [1], 0.3).bind(_FakeEngine(), 10, 33)       # a label count that differs from the catalogue
+        ShareTarget(labels[:49], 2, [1], 0.3).bind(_FakeEngine(), 10, 10, 33)   # a label count that differs from the catalogue
     with pytest.raises(ValueError):
-        ShareTarget(labels, 2, [1], 0.3).bind(_FakeEngine(), 1024, 2 ** 21)      # 2^21 users x 1024 entries: 2^31 steps
+        ShareTarget(labels, 2, [1], 0.3).bind(_FakeEngine(), 10, 1024, 2 ** 21)  # 2^21 users x 1024 entries: 2^31 steps
     with pytest.raises(ValueError):
-        ShareTarget(labels, 2, [1], 0.3).bind(_FakeEngine(), 1025, 3)
+        ShareTarget(labels, 2, [1], 0.3).bind(_FakeEngine(), 10, 1025, 3)
     t = ShareTarget(labels, 2, [1], 0.3)
-    t.bind(_FakeEngine(), 10, 33)
+    t.bind(_FakeEngine(), 10, 10, 33)
     assert t.mask == group_mask_of([1], 2) == 0b10 and t.rest_mask == 0x1FF & ~0b10 and t.rest_mask & 0x100
     assert t.want == int(np.ceil(np.float64(0.3) * 33 * 10)) == 99
     assert tuple(t.pro_i.shape) == tuple(t.rest_s.shape) == (33, 10) and t.state.numel() == 8
     t = ShareTarget(labels, 3, [2, 0, 2], 1.0)
-    t.bind(_FakeEngine(), 7, 5)
+    t.bind(_FakeEngine(), 10, 7, 5)
     assert t.promote == [0, 2] and t.mask == 0b101 and t.rest_mask == 0x1FA and t.want == 35
     assert ShareTarget(labels, 2, [0], 0.0).share == 0.0
     good = ShareTarget(labels, 2, [1], 0.3)

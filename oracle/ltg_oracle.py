@@ -202,34 +202,47 @@ def init_discriminator(feature_len, h0, h1, h2, h3, seed=0):
     }
 
 
-def d_tower(D, pop_ids, niche_ids, masks, keep, dtype=np.float64, dq=None):
+def _jit(x, jitter):
+    """a model of a GEMM pipe's accumulation error for the tolerances of the quantised modes: jitter = (rng, rel) multiplies every element
+    of the product x by 1 + rel N(0, 1); None returns x itself (not one bit changes)."""
+    if jitter is None:
+        return x
+    rng, rel = jitter
+    return x * (1.0 + rel * rng.standard_normal(x.shape)).astype(x.dtype)
+
+
+def d_tower(D, pop_ids, niche_ids, masks, keep, dtype=np.float64, dq=None, jitter=None):
     """t(a,b) of discriminator.py:16-19,25,30,33,44-45 (same code serves :51-55).
     masks = (mA [K,h1], mB [K,h2], mC [K,h3]) keep indicators.  dq: operand precision of the three GEMMs of the
-    ltg_config.d_precision modes (None = fp32 like the reference, "bf16", "fp8"); the output layer is always fp32."""
+    ltg_config.d_precision modes (None = fp32 like the reference, "bf16", "fp8"); the output layer is always fp32.
+    jitter = (rng, rel): every one of the three products is multiplied element-wise by 1 + rel N(0, 1) before its bias is added (and so
+    before anything is quantised again) -- the noise model the quantised-mode tests take their bounds from (_jit); None: no change."""
     f = lambda a: np.asarray(a, dtype=dtype)
     mA, mB, mC = (f(m) for m in masks)
     ea = f(D["emb"])[pop_ids]
     eb = f(D["emb"])[niche_ids]
-    tA = np.tanh(_dq(ea, dq, "emb") @ _dq(f(D["w1"]), dq, "w") + f(D["b1"]))
-    tB = np.tanh(_dq(eb, dq, "emb") @ _dq(f(D["w2"]), dq, "w") + f(D["b2"]))
+    tA = np.tanh(_jit(_dq(ea, dq, "emb") @ _dq(f(D["w1"]), dq, "w"), jitter) + f(D["b1"]))
+    tB = np.tanh(_jit(_dq(eb, dq, "emb") @ _dq(f(D["w2"]), dq, "w"), jitter) + f(D["b2"]))
     aA = tA / dtype(keep) * mA
     aB = tB / dtype(keep) * mB
     hin = np.concatenate([aA, aB], 1)
     if dq is not None:
         hin = hin.astype(np.float32).astype(dtype)      # activations live in fp32 buffers between the kernels
-    tC = np.tanh(_dq(hin, dq, "act") @ _dq(f(D["w3"]), dq, "w") + f(D["b3"]))
+    tC = np.tanh(_jit(_dq(hin, dq, "act") @ _dq(f(D["w3"]), dq, "w"), jitter) + f(D["b3"]))
     aC = tC / dtype(keep) * mC
     s = aC @ f(D["w4"]) + f(D["b4"])
     y = 1.0 / (1.0 + np.exp(-s))
     return dict(ea=ea, eb=eb, tA=tA, tB=tB, hin=hin, tC=tC, aC=aC, s=s[:, 0], y=y[:, 0])
 
 
-def d_tower_backward(D, T, masks, keep, ds, dtype=np.float64, dq=None, dact16=True):
+def d_tower_backward(D, T, masks, keep, ds, dtype=np.float64, dq=None, dact16=True, jitter=None):
     """gradients of sum(ds * s) wrt the 8 trainable tensors (emb is frozen: discriminator.py:47).  dq as in d_tower:
     the bias gradients of the quantised GEMMs are column sums of the QUANTISED operand (ones-augmented row).
     dact16 (fp8 mode only): round d a / d pre of the branch layers to bf16 as the device stores it (dA1T_16).  False = the same
     pipeline WITHOUT that storage rounding: the independent variant tests pin the approximation's cost against
-    (tests/test_gpu_parity.py::test_d_step_precision_modes)."""
+    (tests/test_gpu_parity.py::test_d_step_precision_modes).
+    jitter: as in d_tower, on the products of the quantised GEMMs (dw3 | db3, dhin, dw1 | db1, dw2 | db2: a bias gradient is the
+    ones-augmented row of its weight gradient's product); None: no change."""
     f = lambda a: np.asarray(a, dtype=dtype)
     mA, mB, mC = (f(m) for m in masks)
     ds = f(ds)[:, None]
@@ -241,9 +254,9 @@ def d_tower_backward(D, T, masks, keep, ds, dtype=np.float64, dq=None, dact16=Tr
     if dq is not None:
         dpC = dpC.astype(np.float32).astype(dtype)
     qC = _dq(dpC, dq, "g3")
-    g["w3"] = _dq(T["hin"], dq, "act").T @ qC
-    g["b3"] = qC.sum(0)
-    dhin = qC @ _dq(f(D["w3"]), dq, "w").T
+    g["w3"] = _jit(_dq(T["hin"], dq, "act").T @ qC, jitter)
+    g["b3"] = _jit(qC.sum(0), jitter)
+    dhin = _jit(qC @ _dq(f(D["w3"]), dq, "w").T, jitter)
     h1 = mA.shape[1]
     fA, fB = mA / dtype(keep) * (1 - T["tA"] ** 2), mB / dtype(keep) * (1 - T["tB"] ** 2)
     if dq == "fp8" and dact16:     # the fp8 mode keeps d a / d pre of the branch layers as bf16 (csrc/ltg_fp8bwd.h: dA1T_16), not an fp32 copy of a
@@ -253,10 +266,10 @@ def d_tower_backward(D, T, masks, keep, ds, dtype=np.float64, dq=None, dact16=Tr
     if dq is not None:
         dpA, dpB = dpA.astype(np.float32).astype(dtype), dpB.astype(np.float32).astype(dtype)
     qA, qB = _dq(dpA, dq, "g1"), _dq(dpB, dq, "g1")
-    g["w1"] = _dq(T["ea"], dq, "emb").T @ qA
-    g["b1"] = qA.sum(0)
-    g["w2"] = _dq(T["eb"], dq, "emb").T @ qB
-    g["b2"] = qB.sum(0)
+    g["w1"] = _jit(_dq(T["ea"], dq, "emb").T @ qA, jitter)
+    g["b1"] = _jit(qA.sum(0), jitter)
+    g["w2"] = _jit(_dq(T["eb"], dq, "emb").T @ qB, jitter)
+    g["b2"] = _jit(qB.sum(0), jitter)
     return g
 
 

@@ -281,11 +281,13 @@ def _g_case_ids(cases):
     return ["%d-%d-%s%s" % (I, B, path, "" if hs == G_D else ("-config-d" if hs == CONFIG_D else "-d" + _d_case_id(hs))) for I, B, path, hs in cases]
 
 
-def _g_step_case(precision, I, B, path, warm, hs=G_D, history="uniform", P=None, D=None, pairs=_fake_pairs, tol=None, figures=None):
+def _g_step_case(precision, I, B, path, warm, hs=G_D, history="uniform", P=None, D=None, pairs=_fake_pairs, tol=None, figures=None, d_precision=None):
     """history "uniform": Hh.random_history, a hand-built batch 0.  "skewed" / "skewed-values": batch 1 of Hh.long_tail_batch through
     DeviceData (uitem, row_norm2, non-zero offsets, `values` for the second) with Hh.skewed_fake_pairs (> FU * NT pairs, a user past NT).
     P, D: the generator / discriminator parameter sets instead of the initialisers'; pairs(rng, X, I): the fake pairs of a "uniform" batch;
-    tol: (first, second) moment bounds of a cold step instead of gtol and 2 gtol; figures: a dict that receives the measured moment errors."""
+    tol: (first, second) moment bounds of a cold step instead of gtol and 2 gtol; figures: a dict that receives the measured moment errors.
+    d_precision "bf16" / "fp8": the discriminator's operand mode -- the oracle's tower quantises alike, and sum_y (all the G step takes from
+    the tower) is held to n x the median bound + the max bound of tests/quantised_ref.py's noise model; everything else as without it."""
     import torch
     from ltgan.engine import Pairs, Pipe
     rng, X, P0 = _problem(I, B, seed=11 * I + B)
@@ -307,8 +309,18 @@ def _g_step_case(precision, I, B, path, warm, hs=G_D, history="uniform", P=None,
     dm = Hh.d_masks(SEED, dstep, n, hs[1:], dkeep)
     gid = np.where(valid, gen, 0)
     pid = np.where(valid, pop, 0)
-    T = O.d_tower(D, pid, gid, dm, dkeep)
+    dq = None if d_precision in (None, "fp32") else d_precision
+    T = O.d_tower(D, pid, gid, dm, dkeep, dq=dq)
     sum_y = float((T["y"] * valid).sum())
+    sum_y_bound = 1e-4 * max(1.0, abs(sum_y))
+    if dq is not None:
+        import quantised_ref as Qr
+        fmax = fmed = 0.0
+        for k in range(Qr.DRAWS):
+            yj = O.d_tower(D, pid, gid, dm, dkeep, dq=dq, jitter=(np.random.default_rng(7000 + k), Qr.REL[dq]))["y"]
+            a, b = Qr.y_figures(yj, T["y"], valid)
+            fmax, fmed = max(fmax, a), max(fmed, b)
+        sum_y_bound = Qr.FACTOR * (cnt * fmed + fmax)
     losses, g, F = O.g_loss_and_grads(P, X.toarray(), mask, keep, eps, anneal, lam, rows[valid], gen[valid], cnt, sum_y,
                                       1.0, np.float64, quant=q)
     ad = O.SharedAdam(1e-3)
@@ -321,7 +333,7 @@ def _g_step_case(precision, I, B, path, warm, hs=G_D, history="uniform", P=None,
     P64 = {k: np.asarray(v, np.float64) for k, v in P.items()}
     ad.apply(P64, g, O.G_KEYS)
     # ---- device
-    eng = _engine(I, precision, hs=hs, lr=1e-3)
+    eng = _engine(I, precision, hs=hs, lr=1e-3, **({} if d_precision is None else {"d_precision": d_precision}))
     assert eng.Z == 200
     if path.endswith("-generic"):
         eng.cfg.tuning = 1 << 18
@@ -365,7 +377,10 @@ def _g_step_case(precision, I, B, path, warm, hs=G_D, history="uniform", P=None,
     eng.g_flush()
     torch.cuda.synchronize()
     loss = loss.cpu().numpy()
-    assert abs(loss[4] - sum_y) < 1e-4 * max(1.0, abs(sum_y))
+    if dq is not None:
+        print("G step %s d_precision %s: sum_y %.6f, device off by %.2e, bound %.2e (floor max / median %.2e / %.2e over %d pairs)" % (
+            hs, d_precision, sum_y, abs(loss[4] - sum_y), sum_y_bound, fmax, fmed, cnt))
+    assert abs(loss[4] - sum_y) < sum_y_bound
     assert abs(loss[3] - losses["sum_p"]) < 2e-3 * abs(losses["sum_p"]) + 1e-7
     for i, k in enumerate(("g_loss", "vae_loss", "gan_loss")):
         assert abs(loss[i] - losses[k]) < 1e-3 * abs(losses[k]) + 1e-6, k
@@ -1179,6 +1194,12 @@ def test_d_step_precision_modes(dq, hs, tol):
         # (fp32 tanh / products vs the fp64 oracle); one flipped e4m3 operand moves one product term by 6 %
         assert np.linalg.norm(got - want) < tol * np.linalg.norm(want), ("m", k)
         assert Hh.rel_err(got, want) < tol, ("m max", k)
+        # second moments (v = 0.001 g^2 after one step: twice the relative error) and the theta move
+        v_got, v_want = eng.d_v[i].cpu().numpy().reshape(-1).astype(np.float64), ad.v[k].reshape(-1)
+        assert np.linalg.norm(v_got - v_want) < 2 * tol * np.linalg.norm(v_want), ("v", k)
+        assert Hh.rel_err(v_got, v_want) < 2 * tol, ("v max", k)
+        p0 = np.asarray(D[k], np.float64).reshape(-1)
+        _check_adam_move(eng.d_p[i].cpu().numpy().reshape(-1) - p0, D64[k].reshape(-1) - p0, want, ad.lr_t(1), ("theta", k))
     if dq == "fp8":
         # The oracle above rounds d a / d pre of the branch layers to bf16 BECAUSE the device stores it so (dA1T_16): for that term the comparison
         # is against a model of the device.  The cost of the approximation is pinned here against the pipeline WITHOUT the storage rounding: the

@@ -909,6 +909,43 @@ int ltg_pair_companions(const ltg_config* cfg, const ltg_disc_state* disc, const
                         const float* c_image, const int32_t* c_gid /* DEVICE [n_c], strictly ascending global ids */, int32_t n_c, int32_t k,
                         float* score_out, int32_t* id_out, void* ws, size_t ws_bytes, ltg_stream stream);
 
+/* Critic-checked lists: the discriminator scores and gates each user's niche entries (additive in ABI v14).  s(a, b) is the pair
+ * logit of ltg_pair_companions -- the same images, chain and c0, hence the same bits for the same two image rows.  For a user row u the
+ * ANCHORS A_u are the history items (tr / hist_lo exactly as ltg_topk_explain takes them) whose global id g lies in [0, n_items_global)
+ * with 0 <= pop_row[g] < n_pop; entry e < top of the row's list id_in [n_rows][k_in] is a CANDIDATE iff its id g lies in
+ * [0, n_items_global) with 0 <= niche_row[g] < n_niche, and it is SCORED iff the user also has at least one anchor.  pop_row / niche_row:
+ * DEVICE int32 [n_items_global], item id -> row of pop_image [n_pop][ld] / niche_image [n_niche][ld] (ltg_pair_pack images of the two
+ * sides), -1 = not on that side.  No id of a list, a history or a map indexes anything unchecked.
+ * Every pair logit becomes q = llrint((double) s * 2^24) (round to nearest even) and the integers are added: the sums do not depend on the
+ * wave, workgroup, history block, call or rank that held an anchor.  Contract: |s| < 2^17 and fewer than 2^20 anchors per user.
+ * ltg_pair_critic: per (row, entry e < top) sum_out [n_rows][top] int64 = the sum of q over the anchors of THIS call's histories (0 for an
+ * entry that is no candidate), cnt_out [n_rows] int32 = those anchors' number, best_s / best_i [n_rows][top] = the anchor with the largest
+ * s as a length-1 list in ltg_topk's format (equal scores the lower global id, -0.0 == +0.0; id -1 / score -inf when the entry is no
+ * candidate or the call saw no anchor) -- over item shards the sums and counts are added as integers and the best anchors go through
+ * ltg_topk_merge (n_rows = n_rows * top, k_in = k = 1).  One launch, one workgroup per row, no workspace, no atomics, bit-identical from
+ * run to run.  1 <= top <= min(k_in, LTG_CRITIC_MAX_TOP), 1 <= k_in <= 1024.
+ * ltg_critic_finish: crit_out [n_rows][top] = (float)((double) sum / ((double) cnt * 16777216.0)) for a scored entry (cnt = the user's
+ * anchors over all parts), 0.0 for every other -- best_i = -1 flags those; scored_out [n_rows] int32 = the row's scored entries.
+ * ltg_topk_gate: cand_score / cand_id [n_rows][c_in] lists as ltg_topk / ltg_topk_merge write them, crit [n_rows][c_in] and flag
+ * [n_rows][c_in] (int32, >= 0: the entry is scored -- ltg_pair_critic's best_i), k <= c_in <= LTG_GATE_MAX_C.  Walking a row's candidates in
+ * order, a non-padding entry passes iff it is unscored or crit >= tau; score_out / id_out [n_rows][k] = the first k passing entries with
+ * their scores (a subsequence of the candidates, so in score order), padded with id -1 / score -inf; stat_out [n_rows][3] int32 = the
+ * scored candidates, the candidates rejected before the list was full, the list's length.  tau = -inf passes everything: the plain
+ * top-k.  One wave per row, ballot and prefix count, no sort.
+ * All three: LTG_EINVAL before any HIP call for a NULL pointer (stream excepted), n_rows < 0, tr->n_rows != n_rows, hist_lo < 0, a size out
+ * of the ranges above, n_items_global < 1, n_pop < 0, n_niche < 0, a NaN tau, and for ltg_pair_critic a cfg ltg_pair_ld refuses; n_rows = 0
+ * returns LTG_OK and launches nothing. */
+#define LTG_CRITIC_MAX_TOP 256
+#define LTG_GATE_MAX_C 256
+int ltg_pair_critic(const ltg_config* cfg, const ltg_disc_state* disc, const float* pop_image, int32_t n_pop, const float* niche_image,
+                    int32_t n_niche, const int32_t* pop_row, const int32_t* niche_row, int32_t n_items_global, const ltg_batch* tr,
+                    int32_t hist_lo, int32_t n_rows, int32_t k_in, const int32_t* id_in, int32_t top, int64_t* sum_out, int32_t* cnt_out,
+                    float* best_s, int32_t* best_i, ltg_stream stream);
+int ltg_critic_finish(int32_t n_rows, int32_t k_in, const int32_t* id_in, int32_t top, const int32_t* niche_row, int32_t n_items_global,
+                      int32_t n_niche, const int64_t* sum, const int32_t* cnt, float* crit_out, int32_t* scored_out, ltg_stream stream);
+int ltg_topk_gate(int32_t n_rows, int32_t c_in, const float* cand_score, const int32_t* cand_id, const float* crit, const int32_t* flag,
+                  float tau, int32_t k, float* score_out, int32_t* id_out, int32_t* stat_out, ltg_stream stream);
+
 /* Verification helper of the LTG_PREC_FP8 mode: out[i] = the value the fp8 GEMM operands carry for in[i]
  * (clamp to +-448, round to nearest-even OCP e4m3) -- lets a test pin its CPU model of the rounding to the hardware. */
 int ltg_fp8_roundtrip(const float* in, float* out, int32_t n, ltg_stream stream);

@@ -23,7 +23,8 @@ LTG_METRIC = {"cosine": 0, "dot": 1}
 LTG_NBR_MAX_K = 256
 LTG_PAIR_SIDE = {"popular": 0, "niche": 1}   # ltg_pair_pack
 LTG_PAIR_MAX_K = 256                         # ltg_pair_companions: the longest companion list
-LTG_AUD_MAX_K = 256                        # ltg_item_audience: the longest audience list
+LTG_CRITIC_MAX_TOP, LTG_GATE_MAX_C = 256, 256   # ltg_pair_critic: the entries scored per row; ltg_topk_gate: the longest candidate list
+LTG_AUD_MAX_K = 256                       # ltg_item_audience: the longest audience list
 LTG_DIV_MAX_C = 256                          # ltg_topk_diversify: the longest candidate list
 LTG_WHY_MAX_TOP, LTG_WHY_MAX_R = 256, 8      # ltg_topk_explain: the entries explained per row, the history items per entry
 LTG_CAL_MAX_CLASSES = 9                      # ltg_hist_groups / ltg_topk_calibrate: n_groups + 1 classes at the most
@@ -191,6 +192,10 @@ SYMBOLS = {
     "ltg_pair_companions_ws_bytes": (C.c_size_t, [C.POINTER(ltg_config), C.c_int32, C.c_int32, C.c_int32]),
     "ltg_pair_companions": (C.c_int, [C.POINTER(ltg_config), C.POINTER(ltg_disc_state), vp, vp, C.c_int32, vp, vp, C.c_int32, C.c_int32, vp, vp,
                                       vp, C.c_size_t, vp]),
+    "ltg_pair_critic": (C.c_int, [C.POINTER(ltg_config), C.POINTER(ltg_disc_state), vp, C.c_int32, vp, C.c_int32, vp, vp, C.c_int32,
+                                  C.POINTER(ltg_batch), C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, vp, vp, vp, vp, vp]),
+    "ltg_critic_finish": (C.c_int, [C.c_int32, C.c_int32, vp, C.c_int32, vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp]),
+    "ltg_topk_gate": (C.c_int, [C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_float, C.c_int32, vp, vp, vp, vp]),
     "ltg_topk_diversify": (C.c_int, [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, C.c_float, C.c_int32, vp, vp, vp, vp]),
     "ltg_topk_explain": (C.c_int, [vp, C.c_int32, C.c_int32, C.POINTER(ltg_batch), C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, vp,
                                    vp, vp]),

@@ -182,6 +182,7 @@ __global__ __launch_bounds__(64) void k_gate_set(LtgGate g, LtgGate g2 = LTG_NO_
 #include "ltg_diversify.h"
 #include "ltg_explain.h"
 #include "ltg_calibrate.h"
+#include "ltg_critic.h"
 
 // ---------------------------------------------------------------------------------------------
 // host side
@@ -2386,6 +2387,49 @@ int ltg_topk_calibrate(int32_t n_rows, int32_t n_lists, int32_t m_in, const floa
     hipLaunchKernelGGL(stage ? k_topk_calibrate<true> : k_topk_calibrate<false>, dim3((n_rows + CAL_ROWS - 1) / CAL_ROWS), dim3(64),
                        stage ? lds : 0, (hipStream_t)stream, n_rows, n_lists, m_in, score_grp, id_grp, map, n_groups, hist, lambda, k, score_out,
                        id_out, stat_out);
+    return check_launch();
+}
+
+// Critic-checked lists: one launch each, no workspace.  Every refusal comes before the first HIP call.
+int ltg_pair_critic(const ltg_config* cfg, const ltg_disc_state* disc, const float* pop_image, int32_t n_pop, const float* niche_image,
+                    int32_t n_niche, const int32_t* pop_row, const int32_t* niche_row, int32_t n_items_global, const ltg_batch* tr,
+                    int32_t hist_lo, int32_t n_rows, int32_t k_in, const int32_t* id_in, int32_t top, int64_t* sum_out, int32_t* cnt_out,
+                    float* best_s, int32_t* best_i, ltg_stream stream) {
+    if (!pair_cfg_ok(cfg) || !disc || !disc->p[6] || !disc->p[7] || !pop_image || !niche_image || !pop_row || !niche_row || !tr || !tr->indptr ||
+        !tr->indices || !id_in || !sum_out || !cnt_out || !best_s || !best_i || n_rows < 0 || tr->n_rows != n_rows || hist_lo < 0 ||
+        n_items_global < 1 || n_pop < 0 || n_niche < 0 || k_in < 1 || k_in > 1024 || top < 1 || top > k_in || top > LTG_CRITIC_MAX_TOP)
+        return LTG_EINVAL;
+    if (n_rows == 0) return LTG_OK;
+    clear_errors();
+    const int ld = ltg_pair_ld(cfg);
+    hipLaunchKernelGGL(k_pair_critic, dim3(n_rows), dim3(CR_NT), ((size_t)CR_ET * (ld | 1) + (size_t)CR_AB * ld) * sizeof(float), (hipStream_t)stream,
+                       cfg->d_h3, ld,
+                       pop_image, n_pop, niche_image, n_niche, pop_row, niche_row, n_items_global, tr->indptr, tr->indices, hist_lo, k_in, id_in,
+                       top, disc->p[6], disc->p[7], (long long*)sum_out, cnt_out, best_s, best_i);
+    return check_launch();
+}
+
+int ltg_critic_finish(int32_t n_rows, int32_t k_in, const int32_t* id_in, int32_t top, const int32_t* niche_row, int32_t n_items_global,
+                      int32_t n_niche, const int64_t* sum, const int32_t* cnt, float* crit_out, int32_t* scored_out, ltg_stream stream) {
+    if (!id_in || !niche_row || !sum || !cnt || !crit_out || !scored_out || n_rows < 0 || n_items_global < 1 || n_niche < 0 || k_in < 1 ||
+        k_in > 1024 || top < 1 || top > k_in || top > LTG_CRITIC_MAX_TOP)
+        return LTG_EINVAL;
+    if (n_rows == 0) return LTG_OK;
+    clear_errors();
+    hipLaunchKernelGGL(k_critic_finish, dim3(n_rows), dim3(256), 0, (hipStream_t)stream, k_in, id_in, top, niche_row, n_items_global, n_niche,
+                       (const long long*)sum, cnt, crit_out, scored_out);
+    return check_launch();
+}
+
+int ltg_topk_gate(int32_t n_rows, int32_t c_in, const float* cand_score, const int32_t* cand_id, const float* crit, const int32_t* flag,
+                  float tau, int32_t k, float* score_out, int32_t* id_out, int32_t* stat_out, ltg_stream stream) {
+    if (!cand_score || !cand_id || !crit || !flag || !score_out || !id_out || !stat_out || n_rows < 0 || c_in < 1 || c_in > LTG_GATE_MAX_C ||
+        k < 1 || k > c_in || tau != tau)
+        return LTG_EINVAL;
+    if (n_rows == 0) return LTG_OK;
+    clear_errors();
+    hipLaunchKernelGGL(k_topk_gate, dim3((n_rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, n_rows, c_in, cand_score, cand_id, crit, flag, tau, k,
+                       score_out, id_out, stat_out);
     return check_launch();
 }
 

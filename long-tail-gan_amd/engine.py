@@ -942,6 +942,57 @@ class Engine:
                                                 _ptr(c_gid), m, int(k), _ptr(score_out), _ptr(id_out), _ptr(ws), ws.numel(), self.stream()),
                    "ltg_pair_companions")
 
+    # ------------------------------------------------------------------ critic-checked lists (the discriminator over a user's anchors x entries)
+    def pair_critic(self, pop_image, niche_image, pop_row, niche_row, tr, id_in, top, sum_out, cnt_out, best_s, best_i, hist_lo=None):
+        """the discriminator's view of the first `top` entries of the lists id_in [n, k_in] int32: pop_image / niche_image the side images
+        (pair_pack) of the popular / niche items with features, pop_row / niche_row [I_global] int32 item id -> image row (-1: not on that
+        side), tr the fold-in rows of the same users (a CsrRows with this slab's LOCAL ids; hist_lo, default this slab's item_lo, makes
+        them GLOBAL) -> sum_out [n, top] int64 the fixed-point sums of the pair logits over the anchors of these histories, cnt_out [n]
+        int32 their number, best_s / best_i [n, top] the best anchor as a length-1 topk list (ltg_pair_critic)"""
+        n, k_in = (int(x) for x in id_in.shape)
+        ld, top = self.pair_ld(), int(top)
+        for img in (pop_image, niche_image):
+            assert img.dtype == torch.float32 and img.is_contiguous() and img.dim() == 2 and int(img.shape[1]) == ld
+        for m in (pop_row, niche_row):
+            assert m.dtype == torch.int32 and m.is_contiguous() and m.numel() == self.I_global
+        assert sum_out.dtype == torch.int64 and sum_out.is_contiguous() and tuple(sum_out.shape) == (n, top)
+        assert cnt_out.dtype == torch.int32 and cnt_out.is_contiguous() and cnt_out.numel() == n
+        assert best_s.dtype == torch.float32 and best_s.is_contiguous() and tuple(best_s.shape) == (n, top)
+        for t in (id_in, best_i):
+            assert t.dtype == torch.int32 and t.is_contiguous()
+        assert tuple(best_i.shape) == (n, top)
+        cabi.check(self.lib.ltg_pair_critic(C.byref(self.cfg), C.byref(self.disc_c), _ptr(pop_image), int(pop_image.shape[0]), _ptr(niche_image),
+                                            int(niche_image.shape[0]), _ptr(pop_row), _ptr(niche_row), int(self.I_global), C.byref(tr.c),
+                                            int(self.item_lo if hist_lo is None else hist_lo), n, k_in, _ptr(id_in), top, _ptr(sum_out),
+                                            _ptr(cnt_out), _ptr(best_s), _ptr(best_i), self.stream()), "ltg_pair_critic")
+
+    def critic_finish(self, id_in, top, niche_row, n_niche, sum_in, cnt, crit_out, scored_out):
+        """sum_in [n, top] int64 / cnt [n] int32 (pair_critic's, added over the slabs) -> crit_out [n, top] float32 the mean anchor logit of
+        every scored entry (0.0 elsewhere), scored_out [n] int32 the scored entries per row (ltg_critic_finish)"""
+        n, k_in = (int(x) for x in id_in.shape)
+        top = int(top)
+        assert id_in.dtype == torch.int32 and id_in.is_contiguous() and niche_row.dtype == torch.int32 and niche_row.is_contiguous()
+        assert sum_in.dtype == torch.int64 and sum_in.is_contiguous() and tuple(sum_in.shape) == (n, top)
+        assert cnt.dtype == torch.int32 and cnt.is_contiguous() and cnt.numel() == n
+        assert crit_out.dtype == torch.float32 and crit_out.is_contiguous() and tuple(crit_out.shape) == (n, top)
+        assert scored_out.dtype == torch.int32 and scored_out.is_contiguous() and scored_out.numel() == n
+        cabi.check(self.lib.ltg_critic_finish(n, k_in, _ptr(id_in), top, _ptr(niche_row), int(niche_row.numel()), int(n_niche), _ptr(sum_in),
+                                              _ptr(cnt), _ptr(crit_out), _ptr(scored_out), self.stream()), "ltg_critic_finish")
+
+    def topk_gate(self, cand_score, cand_id, crit, flag, tau, k, score_out, id_out, stat_out):
+        """the gated lists: cand_score / cand_id [n, c_in] as topk / topk_merge write them, crit [n, c_in] float32, flag [n, c_in] int32
+        (>= 0: the entry is scored) -> score_out / id_out [n, k] = the first k candidates that are unscored or have crit >= tau, padded
+        with id -1 / score -inf; stat_out [n, 3] int32 = scored, rejected before the list was full, length (ltg_topk_gate)"""
+        n, c_in = (int(x) for x in cand_score.shape)
+        for t in (cand_score, crit, score_out):
+            assert t.dtype == torch.float32 and t.is_contiguous()
+        for t in (cand_id, flag, id_out, stat_out):
+            assert t.dtype == torch.int32 and t.is_contiguous()
+        assert tuple(cand_id.shape) == tuple(crit.shape) == tuple(flag.shape) == (n, c_in)
+        assert tuple(score_out.shape) == tuple(id_out.shape) == (n, int(k)) and tuple(stat_out.shape) == (n, 3)
+        cabi.check(self.lib.ltg_topk_gate(n, c_in, _ptr(cand_score), _ptr(cand_id), _ptr(crit), _ptr(flag), float(tau), int(k), _ptr(score_out),
+                                          _ptr(id_out), _ptr(stat_out), self.stream()), "ltg_topk_gate")
+
     # ------------------------------------------------------------------ item audiences
     def item_audience_ws_bytes(self, n_rows, n_q, k):
         return int(self.lib.ltg_item_audience_ws_bytes(C.byref(self.cfg), int(n_rows), int(n_q), int(k)))

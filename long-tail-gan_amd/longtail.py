@@ -6,6 +6,7 @@
         [--diversify LAMBDA] [--candidates N] [--div-space decoder|encoder] [--calibrate LAMBDA]
         [--cap C|NAME:C[,NAME:C...]] [--cap-candidates N] [--cap-score logprob|logit] [--share NAME[+NAME...]:S]
         [--floor M|NAME:M[,NAME:M...] --floor-reserve R [--floor-candidates N] [--floor-score logprob|logit]]
+        [--gate P [--gate-candidates N]] [--critic [TOP]]
 
 restores a checkpoint written by train.py, runs test.py's forward over the users of `<split>_tr.csv` ONCE (chunks of 20 000 users,
 dropout on with keep_prob 0.75 by default: Q3, RNG counter 2*10^9 + first row of the chunk), keeps each user's top-K list on the GPU
@@ -65,6 +66,17 @@ plain ones and every list stays in score order.  N defaults to min(1024, 4 K) an
 line is then `floor@K: <items> floor items, <items> short of their floor, below the floor <plain> -> <served>, <slots> inserted slots,
 <users> rows changed, <rounds> rounds`: short of their floor = the matching holds fewer than M users for the item; below the floor = the
 floor items in fewer than M of the plain / the served lists.
+
+--gate P (0 <= P < 1; not together with any rule above) lets a niche entry into a user's list only if the DISCRIMINATOR gives it at least
+P beside that user's popular history items, before the report reads the lists (trainer.CriticGate: ltg_topk at --gate-candidates N, then
+ltg_pair_critic / ltg_critic_finish / ltg_topk_gate): the critic of a niche entry with features is the mean of the discriminator's pair
+logit over the user's popular history items with features, an entry passes iff it has no critic or sigmoid(critic) >= P, and the first K
+passing candidates are the list.  N defaults to min(256, 2 K) and must lie in [K, 256], K = max(100, --k).  The table is then what the gate
+costs each group; the last line is `gate@K: <entries> scored candidates, <entries> rejected, <users> short lists (min_prob P)`.
+
+--critic [TOP] scores the first TOP entries (default min(K, 256)) of whatever lists are served the same way without changing them
+(trainer.Critic); the last line is `critic@TOP: <entries> scored entries, <users> users with anchors, mean prob <p>` and --json gets the
+same numbers under "critic".
 """
 from __future__ import annotations
 
@@ -130,12 +142,12 @@ def parse_min_slots(spec, names, k):
     return slots
 
 
-RULE_OPTIONS = ("min_slots", "diversify", "calibrate", "cap", "share", "floor")     # at most one of them; a refusal names the later first
+RULE_OPTIONS = ("min_slots", "diversify", "calibrate", "cap", "share", "floor", "gate")     # at most one of them; a refusal names the later first
 
 
 def add_rule_args(ap):
-    """the options of the serve-time rules besides --min-slots (trainer.Diversify, Calibrate, ExposureCap, ShareTarget, ExposureFloor),
-    shared with recommend.py"""
+    """the options of the serve-time rules besides --min-slots (trainer.Diversify, Calibrate, ExposureCap, ShareTarget, ExposureFloor,
+    CriticGate) and of the critic (trainer.Critic), shared with recommend.py"""
     ap.add_argument("--diversify", type=float, default=None, metavar="LAMBDA")
     ap.add_argument("--candidates", type=int, default=None, metavar="N")
     ap.add_argument("--div-space", choices=("decoder", "encoder"), default="decoder")
@@ -148,6 +160,9 @@ def add_rule_args(ap):
     ap.add_argument("--floor-reserve", type=int, default=None, metavar="R")
     ap.add_argument("--floor-candidates", type=int, default=None, metavar="N")
     ap.add_argument("--floor-score", choices=("logprob", "logit"), default=None)
+    ap.add_argument("--gate", type=float, default=None, metavar="P")
+    ap.add_argument("--gate-candidates", type=int, default=None, metavar="N")
+    ap.add_argument("--critic", type=int, nargs="?", const=0, default=None, metavar="TOP")      # (0: the default, min(k, 256))
 
 
 def parse_item_values(opt, v, spec, names):
@@ -248,13 +263,25 @@ def check_rule_args(ap, a, k):
         a.floors = parsed(parse_floor, a.floor)
         if a.floor_candidates is not None and not k <= a.floor_candidates <= 1024:
             ap.error("--floor-candidates must be in [k, 1024] = [%d, 1024], got %d" % (k, a.floor_candidates))
+    if a.gate is None:
+        if a.gate_candidates is not None:
+            ap.error("--gate-candidates needs --gate")
+    else:
+        if not 0.0 <= a.gate < 1.0:
+            ap.error("--gate takes P in [0, 1)")
+        if k > 256:
+            ap.error("--gate walks at most 256 candidates: lists of %d entries are too long" % k)
+        if a.gate_candidates is not None and not k <= a.gate_candidates <= 256:
+            ap.error("--gate-candidates must be in [k, 256] = [%d, 256], got %d" % (k, a.gate_candidates))
+    if a.critic is not None and a.critic != 0 and not 1 <= a.critic <= min(k, 256):
+        ap.error("--critic takes TOP in [1, min(k, 256)] = [1, %d]" % min(k, 256))
 
 
 def build_rules(args, dataset_dir, n_items, groups=None):
     """the serve-time rule of the parsed options -> (its keyword for a Recommender: {} or one entry, the stdout lines it adds after
     run(): callables (ids, tr, k) -> str).  groups: (labels, names) of --groups where the caller has built them; else they are built
     here, and only for a rule that refers to them"""
-    from ltgan.serving import Calibrate, Diversify, ExposureCap, ExposureFloor, MinSlots, ShareTarget
+    from ltgan.serving import Calibrate, CriticGate, Diversify, ExposureCap, ExposureFloor, MinSlots, ShareTarget
 
     def grouped():
         labels, names = groups or build_groups(dataset_dir, args.group_kind, args.n_groups, n_items)
@@ -286,7 +313,40 @@ def build_rules(args, dataset_dir, n_items, groups=None):
     if getattr(args, "floors", None) is not None:
         floor = ExposureFloor(per_item(args.floors), args.floor_reserve, candidates=args.floor_candidates, score=args.floor_score or "logprob")
         return dict(floor=floor), [lambda ids, tr, k: floor_line(floor.plain_ids(k), ids, floor.need_vector(), floor.stats(), k)]
+    if getattr(args, "gate", None) is not None:
+        gate = CriticGate(*critic_sides(dataset_dir, n_items), args.gate, candidates=args.gate_candidates)
+        return dict(gate=gate), [lambda ids, tr, k: gate_line(gate.stats(), gate.min_prob, k)]
     return {}, []
+
+
+def critic_sides(dataset_dir, n_items):
+    """-> (niche ids, ids with features): what a Critic / CriticGate takes, read as companions.py reads them"""
+    d = dataset_dir
+    show2id, _, niche, _, _ = dp.load_pop_niche_tags(os.path.join(d, "item2id.txt"), os.path.join(d, "item_list.txt"),
+                                                     os.path.join(d, "niche_items.txt"), n_items)
+    return niche, dp.load_valid_item_ids(os.path.join(d, "item_list.txt"), show2id)
+
+
+def build_critic(args, dataset_dir, n_items):
+    """the Critic of --critic [TOP], or None"""
+    if getattr(args, "critic", None) is None:
+        return None
+    from ltgan.serving import Critic
+    return Critic(*critic_sides(dataset_dir, n_items), top=args.critic or None)
+
+
+def gate_line(stats, min_prob, k):
+    """the line --gate adds: the scored candidates, those rejected before their list was full and the short lists (CriticGate.stats()
+    [n_users, 3])"""
+    st = np.asarray(stats).astype(np.int64).reshape(-1, 3)
+    return "gate@%d: %d scored candidates, %d rejected, %d short lists (min_prob %.6g)" % (
+        k, int(st[:, 0].sum()), int(st[:, 1].sum()), int((st[:, 2] < k).sum()), min_prob)
+
+
+def critic_line(summary, top):
+    """the line --critic adds (Critic.summary())"""
+    return "critic@%d: %d scored entries, %d users with anchors, mean prob %.6f" % (
+        top, summary["scored"], summary["users_with_anchors"], summary["mean_prob"])
 
 
 def cap_line(plain_ids, ids, cap_vec, stats, k):
@@ -469,6 +529,9 @@ def longtail(args, h0_size, h1_size, h2_size, h3_size, LEARNING_RATE, precision=
     labels, names = build_groups(d, args.group_kind, args.n_groups, n_items)
     report = LongTailReport(labels, len(names), k_ndcg=K_NDCG, k_r1=K_R1, k_r2=K_R2, k_exp=args.k)
     rule, rule_lines = build_rules(args, d, n_items, (labels, names))
+    critic = build_critic(args, d, n_items)
+    if critic is not None:
+        rule = dict(rule, critic=critic)
     if world > 1:
         rec = ShardedRecommender(eng, EvalData(tr, te, eng.device, item_lo=lo, item_hi=hi), k=report.k, chunk=batch_size_test, report=report, **rule)
     else:
@@ -480,6 +543,9 @@ def longtail(args, h0_size, h1_size, h2_size, h3_size, LEARNING_RATE, precision=
         print(line)
     for line in rule_lines:
         print(line(ids, tr, report.k))
+    if critic is not None:
+        rep["critic"] = dict(critic.summary(), top=critic.top)
+        print(critic_line(rep["critic"], critic.top))
     if args.json and rank == 0:
         write_json(rep, args.json)
     close_model(world)

@@ -8,6 +8,7 @@
         [--calibrate LAMBDA] [--cap C|NAME:C[,NAME:C...]] [--cap-candidates N] [--cap-score logprob|logit]
         [--share NAME[+NAME...]:S]
         [--floor M|NAME:M[,NAME:M...] --floor-reserve R [--floor-candidates N] [--floor-score logprob|logit]]
+        [--gate P [--gate-candidates N]] [--critic [TOP] [--critic-out critic.tsv]]
 
 restores a checkpoint written by train.py, runs test.py's forward over the users of `<split>_tr.csv` (chunks of 20 000 users,
 dropout on with keep_prob 0.75 by default: Q3, RNG counter 2*10^9 + first row of the chunk) and keeps each user's k best items, the
@@ -65,6 +66,20 @@ user gives up at most the last R slots of the list, to the proposals it likes be
 ones and every list stays in score order.  N defaults to min(1024, 4 k) and must lie in [k, 1024].  The last stdout line is `floor@k:
 <items> floor items, <items> short of their floor, below the floor <plain> -> <served>, <slots> inserted slots, <users> rows changed,
 <rounds> rounds`.
+
+--gate P (0 <= P < 1; not together with any rule above) serves lists into which a niche item comes only if the DISCRIMINATOR gives it at
+least P beside the user's popular history items (trainer.CriticGate: ltg_topk at --gate-candidates N, then ltg_pair_critic /
+ltg_critic_finish / ltg_topk_gate): the critic of a niche entry with features is the mean of the discriminator's pair logit (companions.py's
+score) over the user's popular history items with features; an entry passes iff it has no critic or sigmoid(critic) >= P, and the first k
+passing candidates are the list, in score order.  N defaults to min(256, 2 k) and must lie in [k, 256].  P = 0 is the plain list.  The last
+stdout line is `gate@k: <entries> scored candidates, <entries> rejected, <users> short lists (min_prob P)`.
+
+--critic [TOP] scores the first TOP entries (default min(k, 256)) of every list, whichever kind it is, the same way without changing it
+(trainer.Critic: one ltg_pair_critic per chunk).  --critic-out (default critic.tsv) gets one line per scored entry,
+`uid<TAB>sid<TAB>prob<TAB>anchor_sid:prob`: prob = sigmoid(critic), then the popular history item that speaks most for the entry with the
+discriminator's probability of that pair, to 6 places; --npz also stores crit / anchor_ids / anchor_scores [users, TOP] (0 / -1 / -inf
+where unscored) and n_anchor [users].  One more stdout line follows: `critic@TOP: <entries> scored entries, <users> users with anchors,
+mean prob <p>`.
 """
 from __future__ import annotations
 
@@ -103,6 +118,7 @@ def parse_args(argv):
     ap.add_argument("--explain-space", choices=("decoder", "encoder"), default=None)
     ap.add_argument("--explain-metric", choices=("cosine", "dot"), default=None)
     ap.add_argument("--why", default=None)
+    ap.add_argument("--critic-out", default=None)
     a = ap.parse_args(argv)
     if not 1 <= a.k <= 1024:
         ap.error("--k must be in [1, 1024]")
@@ -125,12 +141,17 @@ def parse_args(argv):
         if a.explain_top is not None and not 1 <= a.explain_top <= min(a.k, 256):
             ap.error("--explain-top must be in [1, min(k, 256)] = [1, %d]" % min(a.k, 256))
         a.why = a.why or "why.tsv"
+    if a.critic is None:
+        if a.critic_out is not None:
+            ap.error("--critic-out needs --critic")
+    else:
+        a.critic_out = a.critic_out or "critic.tsv"
     return a
 
 
-def write_recs(ids, scores, uid_start, tsv_path=None, npz_path=None, why=None):
+def write_recs(ids, scores, uid_start, tsv_path=None, npz_path=None, why=None, critic=None):
     """ids / scores [n_users, k] (padding id -1 dropped from the TSV); row r is uid uid_start + r; the ids are the CSV's sids.
-    why: (why_ids, why_scores) of an Explain, stored in the npz as well."""
+    why: (why_ids, why_scores) of an Explain, critic: the table() of a Critic, stored in the npz as well."""
     ids = np.asarray(ids)
     uids = np.arange(ids.shape[0], dtype=np.int64) + int(uid_start)
     if tsv_path:
@@ -139,6 +160,9 @@ def write_recs(ids, scores, uid_start, tsv_path=None, npz_path=None, why=None):
                 f.write("%d\t%s\n" % (u, ",".join(str(i) for i in row if i >= 0)))
     if npz_path:
         extra = {} if why is None else dict(why_ids=np.asarray(why[0], np.int32), why_scores=np.asarray(why[1], np.float32))
+        if critic is not None:
+            extra.update(crit=np.asarray(critic["crit"], np.float32), anchor_ids=np.asarray(critic["anchor_i"], np.int32),
+                         anchor_scores=np.asarray(critic["anchor_s"], np.float32), n_anchor=np.asarray(critic["n_anchor"], np.int32))
         np.savez(npz_path, uids=uids, ids=ids.astype(np.int32), scores=np.asarray(scores, np.float32), **extra)
     return uids
 
@@ -161,6 +185,19 @@ def write_why(why_ids, why_scores, ids, uid_start, tsv_path):
                 n_lines += 1
                 n_reasons += int(keep.sum())
     return n_lines, n_reasons
+
+
+def write_critic(table, ids, uid_start, tsv_path):
+    """table: Critic.table(), ids [n_users, k] the lists it scored: one line per scored entry (anchor id >= 0),
+    `uid<TAB>sid<TAB>prob<TAB>anchor_sid:prob` with prob = sigmoid of the critic / of the best anchor's pair logit -> lines written"""
+    crit, a_i, a_s, ids = np.asarray(table["crit"]), np.asarray(table["anchor_i"]), np.asarray(table["anchor_s"]), np.asarray(ids)
+    sig = lambda x: 1.0 / (1.0 + np.exp(-np.asarray(x, np.float64)))
+    n = 0
+    with open(tsv_path, "w") as f:
+        for u, e in zip(*np.nonzero(a_i >= 0)):
+            f.write("%d\t%d\t%.6f\t%d:%.6f\n" % (int(uid_start) + u, int(ids[u, e]), sig(crit[u, e]), int(a_i[u, e]), sig(a_s[u, e])))
+            n += 1
+    return n
 
 
 def long_tail_summary(ids, niche, n_items, te=None, k_recall=20):
@@ -202,6 +239,9 @@ def recommend(args, h0_size, h1_size, h2_size, h3_size, LEARNING_RATE, precision
     why = None
     if getattr(args, "explain", None) is not None:
         why = Explain(args.explain, top=args.explain_top, space=args.explain_space or "decoder", metric=args.explain_metric or "cosine")
+    critic = lt.build_critic(args, d, n_items)
+    if critic is not None:
+        rule = dict(rule, critic=critic)
     if world > 1:
         rec = ShardedRecommender(eng, EvalData(tr, te, eng.device, item_lo=lo, item_hi=hi), k=args.k, chunk=batch_size_test, explain=why, **rule)
     else:
@@ -209,8 +249,9 @@ def recommend(args, h0_size, h1_size, h2_size, h3_size, LEARNING_RATE, precision
     ids, scores = rec.run(rng_step=RNG_STEP, keep_prob=args.keep_prob)
     m = long_tail_summary(ids, niche, n_items, te)
     why_tab = why.table() if why is not None else None
+    critic_tab = critic.table() if critic is not None else None
     if rank == 0:
-        write_recs(ids, scores, uid0, args.out, args.npz, why=why_tab)
+        write_recs(ids, scores, uid0, args.out, args.npz, why=why_tab, critic=critic_tab)
     print(summary_line(m, args.k))
     ils_first = "diversify" in rule                      # the ils line stands before the why line, every other rule's line after it
     for line in rule_lines if ils_first else []:
@@ -220,6 +261,10 @@ def recommend(args, h0_size, h1_size, h2_size, h3_size, LEARNING_RATE, precision
         print("why@%d: %d entries, %d reasons" % (why.top, n_lines, n_reasons))
     for line in [] if ils_first else rule_lines:
         print(line(ids, tr, args.k))
+    if critic is not None:
+        if rank == 0:
+            write_critic(critic_tab, ids, uid0, args.critic_out)
+        print(lt.critic_line(critic.summary(), critic.top))
     close_model(world)
     return ids, scores, m
 

@@ -1,7 +1,7 @@
 """Everything that serves a trained model: validation / test scoring, top-K lists (plain, with minimum slots per item group, diversified,
 calibrated to each user's history, capped in how many lists an item may appear, with a set share of all slots for some item groups,
-with a floor under how many lists an item appears in), the long-tail report read off them, the explanation of every list entry (the
-user's history items nearest to it), similar-item lists,
+with a floor under how many lists an item appears in, gated by the discriminator), the long-tail report read off them, the explanation
+of every list entry (the user's history items nearest to it), the discriminator's critic of every niche entry, similar-item lists,
 item audiences (the k likeliest users of an item, gathered over the same chunk walk), and the set-up the CLIs (test.py, recommend.py, longtail.py, similar.py, audience.py) share.
 
 One chunk walk (Recommender.run) serves every kind of list, unsharded and over item shards: the forward sits behind one method that
@@ -694,6 +694,175 @@ class Explain:
         return self.why_i.cpu().numpy(), self.why_s.cpu().numpy()
 
 
+def gate_tau(min_prob):
+    """the logit threshold of a CriticGate: float32(log(p / (1 - p))) computed in fp64; p = 0 -> -inf (everything passes)"""
+    p = float(min_prob)
+    if not 0.0 <= p < 1.0:                           # (NaN fails both comparisons)
+        raise ValueError("min_prob must be in [0, 1), got %r" % (min_prob,))
+    return np.float32(-np.inf) if p == 0.0 else np.float32(np.log(np.float64(p)) - np.log1p(-np.float64(p)))
+
+
+class _CriticSides:
+    """What Critic and CriticGate share: the two sides of the discriminator among the items with features (niche_ids: load_pop_niche_tags'
+    niche items, valid_ids: load_valid_item_ids' items with features; both GLOBAL ids), their side images and the item id -> image row
+    maps, packed once per run(), and the evaluation of a chunk's lists (ltg_pair_critic, over item shards the exchange, ltg_critic_finish)."""
+
+    def __init__(self, niche_ids, valid_ids):
+        niche = np.unique(np.fromiter((int(x) for x in niche_ids), np.int64))
+        valid = np.unique(np.fromiter((int(x) for x in valid_ids), np.int64))
+        if (niche.size and niche.min() < 0) or (valid.size and valid.min() < 0):
+            raise ValueError("item ids must be >= 0")
+        self.niche_host = np.intersect1d(niche, valid).astype(np.int32)              # niche with features, ascending
+        self.pop_host = np.setdiff1d(valid, niche).astype(np.int32)                  # popular with features, ascending
+        self.pop_ids = self.niche_ids = self.pop_row = self.niche_row = self.pop_img = self.niche_img = None
+
+    def bind(self, engine):
+        n_items, dev = int(engine.I_global), engine.device
+        for name, a in (("niche", self.niche_host), ("popular", self.pop_host)):
+            if a.size and a.max() >= min(n_items, int(engine.feature_len)):
+                raise ValueError("%s ids outside [0, %d)" % (name, min(n_items, int(engine.feature_len))))
+        maps = []
+        for a in (self.pop_host, self.niche_host):
+            m = np.full(n_items, -1, np.int32)
+            m[a] = np.arange(a.size, dtype=np.int32)
+            maps.append(torch.from_numpy(m).to(dev))
+        self.pop_row, self.niche_row = maps
+        self.pop_ids, self.niche_ids = torch.from_numpy(self.pop_host).to(dev), torch.from_numpy(self.niche_host).to(dev)
+
+    def pack(self, engine):
+        """both side images, from the discriminator as it is now (replicated over item shards: every rank packs for itself)"""
+        self.pop_img = engine.pair_pack("popular", self.pop_ids, out=self.pop_img)
+        self.niche_img = engine.pair_pack("niche", self.niche_ids, out=self.niche_img)
+
+    def evaluate(self, lists, tr, ids, top, acc, cnt, best_s, best_i, crit, scored):
+        """the first `top` entries of the lists ids [n, k_in] -> crit / best_s / best_i [n, top], cnt [n] (the users' anchors), scored [n];
+        acc [n, top] int64 is the buffer of the fixed-point sums.  lists: the SlabLists whose buffers the per-slab best anchors are
+        gathered through -- over item shards every rank sees its slab's part of the histories, the sums and counts are added as
+        integers and the best anchors merged, so every rank finishes identically."""
+        eng, n = lists.eng, int(ids.shape[0])
+        ls, li = lists.local(n * top, 1, best_s.view(n * top, 1), best_i.view(n * top, 1))
+        eng.pair_critic(self.pop_img, self.niche_img, self.pop_row, self.niche_row, tr, ids, top, acc, cnt, ls.view(n, top), li.view(n, top),
+                        hist_lo=eng.item_lo if lists.parts > 1 else 0)
+        if lists.parts > 1:
+            dist.all_reduce(acc, op=dist.ReduceOp.SUM, group=lists.group)
+            dist.all_reduce(cnt, op=dist.ReduceOp.SUM, group=lists.group)
+            lists.merge(ls, li, best_s.view(n * top, 1), best_i.view(n * top, 1))
+        eng.critic_finish(ids, top, self.niche_row, int(self.niche_host.size), acc, cnt, crit, scored)
+
+
+class Critic:
+    """What the discriminator thinks of every list entry, passed as `critic=` to a Recommender / ShardedRecommender: for the first `top`
+    entries of every user's list (default min(k, 256)) that are niche items with features, the mean pair logit crit(u, b) = mean over the
+    user's anchors a (the popular items with features of the fold-in history) of s(a, b), PairCompanions' score -- sigmoid(crit) is the
+    geometric-mean-odds probability the discriminator gives "a real user with these head items holds b" -- and the best anchor argmax_a
+    s(a, b).  An entry is scored iff it is such a niche item and its user has an anchor.  The mean is taken over 64-bit fixed-point
+    integers (ltg_pair_critic), so it does not depend on how the anchors are split.  An attachment like Explain: it reads the final lists,
+    plain, ruled, diversified or matched.  niche_ids / valid_ids: GLOBAL ids, load_pop_niche_tags' niche items and load_valid_item_ids'
+    items with features.  Both images are packed once per run(); per chunk ONE launch of ltg_pair_critic and one of ltg_critic_finish.
+    Over item shards every rank scores its slab's part of the histories; the sums and counts are all-reduced as integers and the best
+    anchors merged by the SlabLists: every rank ends with the table of the unsharded run, bit for bit.  After run(): table(), summary()."""
+
+    MAX_TOP = 256                                    # LTG_CRITIC_MAX_TOP
+
+    def __init__(self, niche_ids, valid_ids, top=None):
+        self.top_arg = None if top is None else int(top)
+        if self.top_arg is not None and not 1 <= self.top_arg <= self.MAX_TOP:
+            raise ValueError("top must be in [1, %d], got %r" % (self.MAX_TOP, top))
+        self.sides = _CriticSides(niche_ids, valid_ids)
+        self.top = self.crit = self.anchor_s = self.anchor_i = self.n_anchor = self.scored = self.acc = None
+
+    def bind(self, engine, rows, k, n_users):
+        """the device tables for chunks of up to `rows` users, lists of k entries and a split of n_users"""
+        top = min(k, self.MAX_TOP) if self.top_arg is None else self.top_arg
+        if not 1 <= top <= min(k, self.MAX_TOP):
+            raise ValueError("top must be in [1, min(k, %d)] = [1, %d], got %d" % (self.MAX_TOP, min(k, self.MAX_TOP), top))
+        self.top = top
+        self.sides.bind(engine)
+        dev = engine.device
+        self.crit = torch.zeros(n_users, top, dtype=torch.float32, device=dev)
+        self.anchor_s = torch.full((n_users, top), float("-inf"), dtype=torch.float32, device=dev)
+        self.anchor_i = torch.full((n_users, top), -1, dtype=torch.int32, device=dev)
+        self.n_anchor = torch.zeros(n_users, dtype=torch.int32, device=dev)
+        self.scored = torch.zeros(n_users, dtype=torch.int32, device=dev)
+        self.acc = torch.empty(rows * top, dtype=torch.int64, device=dev)
+
+    def pack(self, engine):
+        self.sides.pack(engine)
+
+    def apply(self, lists, tr, n, lo, ids):
+        """the critic of users lo .. lo + n, whose final lists are ids [n, k]"""
+        top = self.top
+        self.sides.evaluate(lists, tr, ids, top, self.acc[: n * top].view(n, top), self.n_anchor[lo:lo + n], self.anchor_s[lo:lo + n],
+                            self.anchor_i[lo:lo + n], self.crit[lo:lo + n], self.scored[lo:lo + n])
+
+    def table(self):
+        """-> dict of host arrays: crit [n_users, top] float32 (0.0 where unscored), anchor_i [n_users, top] int32 GLOBAL ids (-1 where
+        unscored: the flag), anchor_s [n_users, top] float32 (-inf where unscored), n_anchor [n_users] int32"""
+        return dict(crit=self.crit.cpu().numpy(), anchor_i=self.anchor_i.cpu().numpy(), anchor_s=self.anchor_s.cpu().numpy(),
+                    n_anchor=self.n_anchor.cpu().numpy())
+
+    def summary(self):
+        """-> dict: scored (entries), users_with_anchors, mean_prob (the mean sigmoid(crit) over the scored entries; nan without any)"""
+        t = self.table()
+        ok = t["anchor_i"] >= 0
+        with np.errstate(over="ignore"):
+            prob = 1.0 / (1.0 + np.exp(-t["crit"][ok].astype(np.float64)))
+        return dict(scored=int(ok.sum()), users_with_anchors=int((t["n_anchor"] > 0).sum()),
+                    mean_prob=float(prob.mean()) if prob.size else float("nan"))
+
+
+class CriticGate(Rule):
+    """A serve-time rule, passed as `gate=` to a Recommender / ShardedRecommender: a niche entry stays in a user's list only if the
+    discriminator gives it at least min_prob beside that user's popular history items.  Each user's `candidates` best items (ltg_topk;
+    default min(256, 2 k), k <= candidates <= 256) get Critic's mean anchor logit; walking them in order, an entry passes iff it is
+    unscored (a popular item, an item without features, a user without anchors) or crit >= tau = float32(logit(min_prob)), and the first k
+    passing entries are the list, with their scores -- a subsequence of the plain ranking, so in score order; fewer than k passing
+    entries leave a short list.  min_prob = 0 is the plain list.  Both images are packed once per run(); per chunk ltg_topk at
+    `candidates`, ltg_pair_critic, ltg_critic_finish and ltg_topk_gate.  Over item shards the candidates are merged by the SlabLists and
+    the critic's sums, counts and best anchors exchanged as Critic's are, so every rank gates the same candidates identically.  After
+    run(): stats() [n_users, 3] = scored candidates, candidates rejected before the list was full, list length."""
+
+    MAX_C = 256                                      # LTG_GATE_MAX_C
+
+    def __init__(self, niche_ids, valid_ids, min_prob, candidates=None):
+        self.tau = gate_tau(min_prob)
+        self.min_prob = float(min_prob)
+        self.candidates = None if candidates is None else int(candidates)
+        if self.candidates is not None and not 1 <= self.candidates <= self.MAX_C:
+            raise ValueError("candidates must be in [1, %d], got %r" % (self.MAX_C, candidates))
+        self.sides = _CriticSides(niche_ids, valid_ids)
+        self.c = self.stat = None
+
+    def bind(self, engine, rows, k, n_users):
+        c = min(self.MAX_C, 2 * k) if self.candidates is None else self.candidates
+        if not k <= c <= self.MAX_C:
+            raise ValueError("candidates must be in [k, %d] = [%d, %d], got %d" % (self.MAX_C, k, self.MAX_C, c))
+        self.c = self.longest = c
+        self.sides.bind(engine)
+        dev = engine.device
+        f32 = lambda n: torch.empty(n, dtype=torch.float32, device=dev)
+        i32 = lambda n: torch.empty(n, dtype=torch.int32, device=dev)
+        self.cand_s, self.cand_i, self.crit, self.best_s, self.best_i = f32(rows * c), i32(rows * c), f32(rows * c), f32(rows * c), i32(rows * c)
+        self.acc = torch.empty(rows * c, dtype=torch.int64, device=dev)
+        self.cnt, self.scored = i32(rows), i32(rows)
+        self.stat = torch.zeros(n_users, 3, dtype=torch.int32, device=dev)
+
+    def begin(self, engine, group=None):
+        self.sides.pack(engine)
+
+    def apply(self, lists, acts, tr, n, k, lo, score_out, id_out):
+        c = self.c
+        v = lambda t: t[: n * c].view(n, c)
+        c_s, c_i, crit, b_s, b_i = v(self.cand_s), v(self.cand_i), v(self.crit), v(self.best_s), v(self.best_i)
+        lists.topk(acts, tr, n, c, c_s, c_i)
+        self.sides.evaluate(lists, tr, c_i, c, v(self.acc), self.cnt[:n], b_s, b_i, crit, self.scored[:n])
+        lists.eng.topk_gate(c_s, c_i, crit, b_i, self.tau, k, score_out, id_out, self.stat[lo:lo + n])
+
+    def stats(self):
+        """-> [n_users, 3] int32 host array: scored candidates, candidates rejected before the list was full, list length"""
+        return self.stat.cpu().numpy()
+
+
 class Audience:
     """The item audiences a Recommender / ShardedRecommender gathers when it is passed as `audience=`: for every query item (GLOBAL ids,
     any order, repeats allowed) the k users of the split with the largest score -- `logprob`: logit - lse, the log-probability the user's
@@ -775,11 +944,12 @@ class Recommender:
     """Top-K recommendations per user (the forward of Evaluator, then ltg_topk instead of the metrics): the same chunks of
     `chunk` users capped by eval_chunk_rows, the same dropout-on forward (Q3) with counter rng_step + lo per chunk, fold-in
     items excluded.  keep_prob = 1.0 gives dropout-free, deterministic recommendations.  Every list comes out of one SlabLists
-    (self.lists).  At most one of rule= (MinSlots), diversify=, calibrate=, cap= (ExposureCap), share= (ShareTarget) and floor=
-    (ExposureFloor) decides what the lists are: it becomes self.policy, a Rule, and the walk asks it only what Rule's protocol holds;
+    (self.lists).  At most one of rule= (MinSlots), diversify=, calibrate=, cap= (ExposureCap), share= (ShareTarget), floor=
+    (ExposureFloor) and gate= (CriticGate) decides what the lists are: it becomes self.policy, a Rule, and the walk asks it only what Rule's protocol holds;
     without one the lists are the plain top-K.  Per chunk: the forward; audience= (an Audience, audience.table() after run()) gathered
     from the logits; the lists, or with a policy over the whole split only what it gathers; then report= (a LongTailReport, k >= its
-    largest cutoff) and explain= (an Explain, explain.table() after run()) read the chunk's final lists.  A policy over the whole split
+    largest cutoff), explain= (an Explain, explain.table() after run()) and critic= (a Critic, critic.table() after run()) read the chunk's
+    final lists.  A policy over the whole split
     matches after the last chunk, and a second pass over the chunks (no forward) feeds the report and the explanations.  k = 0 walks the
     chunks for the audience alone: run() returns [n_users, 0] arrays, no list kernel is launched, and nothing that needs lists goes
     with it."""
@@ -787,15 +957,16 @@ class Recommender:
     sharded = False                                  # ShardedRecommender: one rank of `group` per item slab
 
     def __init__(self, engine, ev, k=100, chunk=20000, report=None, rule=None, diversify=None, group=None, audience=None, explain=None,
-                 calibrate=None, cap=None, share=None, floor=None):
-        rules = dict(rule=rule, diversify=diversify, calibrate=calibrate, cap=cap, share=share, floor=floor)
+                 calibrate=None, cap=None, share=None, floor=None, gate=None, critic=None):
+        rules = dict(rule=rule, diversify=diversify, calibrate=calibrate, cap=cap, share=share, floor=floor, gate=gate)
         given = [name for name, r in rules.items() if r is not None]
         if len(given) > 1:
             raise ValueError("%s= cannot be combined with %s=" % (given[-1], "= or ".join(given[:-1])))
         self.policy = rules[given[0]] if given else None
-        if int(k) == 0 and (self.policy is not None or report is not None or explain is not None):
+        if int(k) == 0 and (self.policy is not None or report is not None or explain is not None or critic is not None):
             raise ValueError("k = 0 serves no user lists: report=, explain= and every rule need k >= 1")
         self.rule, self.diversify, self.calibrate, self.cap, self.share, self.floor = rule, diversify, calibrate, cap, share, floor
+        self.gate, self.critic = gate, critic
         self.eng, self.ev, self.k, self.report, self.group, self.audience, self.explain = engine, ev, int(k), report, group, audience, explain
         if report is not None:
             report.bind(engine, ev.n, self.k)
@@ -807,6 +978,9 @@ class Recommender:
         if explain is not None:
             explain.bind(engine, self.k, ev.n)
             longest = max(longest, explain.top * explain.r)          # (its per-slab lists are [rows * top, r])
+        if critic is not None:
+            critic.bind(engine, self.chunk, self.k, ev.n)
+            longest = max(longest, critic.top)                       # (its per-slab best anchors are [rows * top, 1])
         self.lists = SlabLists(engine, self.chunk, longest, group, dist.get_world_size(group) if self.sharded else 1)
         if audience is not None:
             audience.bind(engine, self.chunk, ev.n, group=group, sharded=self.sharded)
@@ -820,11 +994,13 @@ class Recommender:
         self.eng.forward(tr, self.acts, keep_prob=keep_prob, is_training=0.0, rng_step=rng_step)
 
     def _read(self, tr, te, lo, hi):
-        """the report and the explanations of users lo .. hi, from their final lists"""
+        """the report, the explanations and the critic of users lo .. hi, from their final lists"""
         if self.report is not None:
             self.report.add(self.eng, self.ids[lo:hi], te, lo)
         if self.explain is not None:
             self.explain.apply(self.lists, tr, hi - lo, lo, self.ids[lo:hi])
+        if self.critic is not None:
+            self.critic.apply(self.lists, tr, hi - lo, lo, self.ids[lo:hi])
 
     def run(self, rng_step=0, keep_prob=0.75):
         """-> (ids [n_users, k] int32 global item ids, scores [n_users, k] float32 logits) as host arrays (over item shards: identical
@@ -837,6 +1013,8 @@ class Recommender:
             policy.begin(eng, self.group)
         if self.explain is not None:
             self.explain.pack(eng, group=self.group, share=policy)
+        if self.critic is not None:
+            self.critic.pack(eng)
         if self.audience is not None:
             self.audience.reset()
         for lo, hi in chunks:
@@ -857,7 +1035,7 @@ class Recommender:
             self._read(tr, te, lo, hi)
         if policy is not None and policy.whole:          # its lists exist only now
             policy.match(eng, k, self.scores, self.ids)
-            if self.report is not None or self.explain is not None:      # a second pass over the chunks, without a forward
+            if self.report is not None or self.explain is not None or self.critic is not None:      # a second pass over the chunks, without a forward
                 for lo, hi in chunks:
                     self._read(*ev.rows(lo, hi), lo, hi)
         return self.ids.cpu().numpy(), self.scores.cpu().numpy()

@@ -22,7 +22,6 @@ import sys
 
 import numpy as np
 import torch
-import torch.distributed as dist
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -32,16 +31,13 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 def main():
     import scipy.sparse as sp
     import audience_ref as AR
+    import serving_harness as H
     from ltgan.dataset import EvalData
-    from ltgan.engine import Engine
     from ltgan.sharded import ShardedRecommender, item_slab
     from ltgan.synthetic import synthetic_index
     from ltgan.trainer import Audience, Recommender
     workload, users = sys.argv[1], int(sys.argv[2])
-    dist.init_process_group("gloo")
-    rank, world = dist.get_rank(), dist.get_world_size()
-    dev = "cuda:0"
-    torch.cuda.set_device(dev)
+    rank, world, dev = H.open_ranks()
     idx, _ = synthetic_index(workload, users=users, seed=5)
     I = idx.n_items
     hs = (16, 24, 40, 32)
@@ -57,10 +53,8 @@ def main():
     rs = np.random.default_rng(11)
     n_take = min(I, 600)
     items = np.concatenate([rs.permutation(I)[:n_take], [0, I - 1, I - 1]]).astype(np.int32)   # every slab, shuffled, one repeated
-    slabs = [item_slab(I, r, world) for r in range(world)]
     for precision in ("bf16", "fp32"):
-        ref = Engine(I, h_sizes=hs, lr=1e-3, precision=precision, seed=77, d_seed=3, device=dev)
-        eng = Engine(I, h_sizes=hs, lr=1e-3, precision=precision, seed=77, d_seed=3, device=dev, item_lo=lo, item_hi=hi)
+        ref, eng, _, _ = H.slab_engines(I, hs, rank, world, precision=precision)
         # item biases of a trained model's size (dist_topk_worker.py): the near-tie bound below is stated for logits of order one
         bias = torch.from_numpy(np.random.default_rng(3).uniform(1.0, 3.0, I).astype(np.float32)).to(dev)
         ref.g_p[7].copy_(bias)
@@ -72,20 +66,12 @@ def main():
             ids0, _ = sh.run(rng_step=step)
             assert ids0.shape == (n_ev, 0)
             ids, sc = aud.table()
-            wmax = max(b - a for a, b in slabs)
-            mine = torch.zeros(n_ev, wmax, dtype=torch.float32, device=dev)
-            mine[:, : hi - lo] = sh.acts.logits[:n_ev]
-            parts = [torch.empty_like(mine) for _ in range(world)]
-            dist.all_gather(parts, mine)
-            full = torch.cat([p[:, : b - a] for p, (a, b) in zip(parts, slabs)], dim=1).cpu().numpy()
+            full = H.gathered_logits(sh.acts.logits[:n_ev], lo, hi, I, world).cpu().numpy()
             lse = sh.acts.lse[:n_ev].cpu().numpy() if score == "logprob" else None
             wS, wID = AR.audience_lists(full, lse, folds, items, k)
             assert np.array_equal(ids, wID), ("sharded table differs from the reference on the gathered logits", score)
             assert np.array_equal(sc.view(np.uint32), wS.view(np.uint32)), score
-            t = torch.from_numpy(np.concatenate([ids, sc.view(np.int32)], axis=1)).to(dev)       # every rank holds the same table
-            t0 = t.clone()
-            dist.broadcast(t0, 0)
-            assert torch.equal(t, t0)
+            H.same_on_every_rank(torch.from_numpy(np.concatenate([ids, sc.view(np.int32)], axis=1)).to(dev))
             # ---- several chunks (the last one short), against the unsharded walk
             # (the unsharded lists one entry longer: the last position of a list has a neighbour to be compared with, too)
             aud_c, aud_r = Audience(items, k=k, score=score), Audience(items, k=k + 1, score=score)
@@ -113,11 +99,8 @@ def main():
             if precision == "fp32":                                                          # (the docstring says why)
                 assert close[ok].all(), ("scores differ beyond the near-tie bound", score, float(rel.max()))
                 assert bad_ids == 0, ("ids differ away from near-ties", score, bad_ids)
-    dist.barrier()
-    if rank == 0:
-        print("AUDIENCE_SHARDED_OK world=%d workload=%s queries=%d clear=%.4f slabs=%s" % (world, workload, len(items), clear.mean(),
-                                                                                          sorted({b - a for a, b in slabs})))
-    dist.destroy_process_group()
+    H.close_ranks("AUDIENCE_SHARDED_OK world=%d workload=%s queries=%d clear=%.4f slabs=%s" % (world, workload, len(items), clear.mean(),
+                                                                                              H.slab_sizes(I, world)))
 
 
 if __name__ == "__main__":

@@ -4,16 +4,11 @@ ltg_topk_merge; ltg_hist_groups on the slab's part of the histories and one int3
 rank) against, bit for bit: the class histogram of the whole histories; and the unsharded Recommender on the whole catalogue, ids, scores
 and stats, in one chunk and over several chunks with a short last one, with a LongTailReport reading the calibrated lists.
 
-The sharded forward all-reduces the encoder's partial pre-activations, which in general sums in another order than the unsharded forward
-(tests/dist_topk_worker.py).  Here that sum is exact, so the two forwards agree bit for bit and what is left is the claim under test:
-W_q0 holds multiples of 1/64 in [-1, 1], every user has 16 fold-in items and dropout is off, so every partial sum is a multiple of 1/64
-below 16 and the row scale is 1/4."""
+The two forwards agree bit for bit by the model of serving_harness.exact_sum_model, so what is left is the claim under test."""
 import os
 import sys
 
 import numpy as np
-import torch
-import torch.distributed as dist
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -21,36 +16,18 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
 def main():
-    import scipy.sparse as sp
     import calibrate_ref as R
-    from ltgan.dataset import EvalData
-    from ltgan.engine import Engine
-    from ltgan.sharded import Calibrate, ShardedRecommender, item_slab
+    import serving_harness as H
+    from ltgan.sharded import Calibrate, ShardedRecommender
     from ltgan.trainer import LongTailReport, Recommender
     I, n_ev = int(sys.argv[1]), int(sys.argv[2])
-    dist.init_process_group("gloo")
-    rank, world = dist.get_rank(), dist.get_world_size()
-    dev = "cuda:0"
-    torch.cuda.set_device(dev)
-    hs = (16, 24, 40, 32)
-    ref = Engine(I, h_sizes=hs, lr=1e-3, precision="bf16", seed=77, d_seed=3, device=dev)
-    lo, hi = item_slab(I, rank, world)
-    eng = Engine(I, h_sizes=hs, lr=1e-3, precision="bf16", seed=77, d_seed=3, device=dev, item_lo=lo, item_hi=hi)
+    rank, world, dev = H.open_ranks()
+    ref, eng, lo, hi = H.slab_engines(I, (16, 24, 40, 32), rank, world)
     rng = np.random.default_rng(3)
-    bias = torch.from_numpy(rng.uniform(1.0, 3.0, I).astype(np.float32)).to(dev)          # (see dist_topk_worker.py)
-    wq0 = torch.from_numpy((rng.integers(-64, 65, (I, ref.H)) / 64.0).astype(np.float32)).to(dev)
-    ref.g_p[7].copy_(bias)
-    eng.g_p[7].copy_(bias[lo:hi])
-    ref.g_p[0].copy_(wq0)
-    eng.g_p[0].copy_(wq0[lo:hi])
-    cols = np.concatenate([rng.choice(I, 16, replace=False) for _ in range(n_ev)])
-    fold = sp.csr_matrix((np.ones(16 * n_ev, np.float32), (np.repeat(np.arange(n_ev), 16), cols)), shape=(n_ev, I))
-    fold.sort_indices()
-    ev_full = EvalData(fold, fold, dev)
-    ev_sh = EvalData(fold, fold, dev, item_lo=lo, item_hi=hi)
+    fold, ev_full, ev_sh = H.exact_sum_model(rng, ref, eng, n_ev)
     labels = rng.integers(0, 4, I).astype(np.uint8)                    # n_groups = 3: label 3 is "in no group"
     k, lam, step = 100, 0.8, 900
-    bits = lambda a: np.ascontiguousarray(a).view(np.uint32)
+    bits = H.bits
     # ---- one chunk: the all-reduced histogram is the histogram of the whole histories
     cal = Calibrate(labels, 3, lam)
     rep = LongTailReport(labels, 3)
@@ -59,10 +36,7 @@ def main():
     want_h = R.hist_groups(fold.indptr, fold.indices, 0, labels, 3)
     assert np.array_equal(cal.hist.view(n_ev, 4).cpu().numpy(), want_h) and (want_h.sum(1) == 16).all()
     assert np.array_equal(rep.table()[1], np.bincount(ids.ravel(), minlength=I))          # the report read the calibrated lists
-    for a in (sh.ids, sh.scores, cal.stat, cal.hist, rep.item_hits):   # every rank holds the same tables
-        a0 = a.clone()
-        dist.broadcast(a0, 0)
-        assert torch.equal(a, a0)
+    H.same_on_every_rank(sh.ids, sh.scores, cal.stat, cal.hist, rep.item_hits)
     cal_1 = Calibrate(labels, 3, lam)
     ids_1, sc_1 = Recommender(ref, ev_full, k=k, chunk=n_ev, calibrate=cal_1).run(rng_step=step, keep_prob=1.0)
     assert np.array_equal(ids, ids_1), "sharded calibrated ids differ from the unsharded recommender's"
@@ -80,16 +54,8 @@ def main():
     assert not np.array_equal(plain, ids_c)
     st = cal_c.stats()
     assert st[:, 1].mean() < st[:, 0].mean()
-    dist.barrier()
-    if rank == 0:
-        print("CALIBRATE_SHARDED_OK world=%d items=%d slabs=%s miscal %.4f -> %.4f" % (world, I, sorted({y - x for x, y in slabs(I, world)}),
-                                                                                        st[:, 0].mean(), st[:, 1].mean()))
-    dist.destroy_process_group()
-
-
-def slabs(I, world):
-    from ltgan.sharded import item_slab
-    return [item_slab(I, r, world) for r in range(world)]
+    H.close_ranks("CALIBRATE_SHARDED_OK world=%d items=%d slabs=%s miscal %.4f -> %.4f" % (world, I, H.slab_sizes(I, world),
+                                                                                             st[:, 0].mean(), st[:, 1].mean()))
 
 
 if __name__ == "__main__":

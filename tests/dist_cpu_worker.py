@@ -7,7 +7,6 @@ import sys
 
 import numpy as np
 import torch
-import torch.distributed as dist
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -16,10 +15,10 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 def main():
     import helpers as Hh
+    import serving_harness as H
     from ltgan.sharded import ShardedTrainer, item_slab
     from oracle import ltg_oracle as O
-    dist.init_process_group("gloo")
-    rank, R = dist.get_rank(), dist.get_world_size()
+    rank, R, _ = H.open_ranks(dev=None)
     I, B = (300 if R <= 2 else 64 * R - 12), 24         # world size 8: seven slabs of 64 items and an uneven last one (52)
     rng = np.random.default_rng(0)                      # same problem on every rank
     X = Hh.random_history(rng, B, I, mean_nnz=9).toarray().astype(np.float64)
@@ -97,10 +96,7 @@ def main():
     for r in range(R):
         assert torch.equal(rp_all[r * B * 5:(r + 1) * B * 5], torch.arange(B * 5, dtype=torch.float32) + 1000 * r)
     assert ar(12345, 12345, 4, cabi.LTG_NCCL_FLOAT32, cabi.LTG_NCCL_SUM, None, None) != 0       # not a registered buffer: an error code, no exception
-    dist.barrier()
-    if rank == 0:
-        print("DIST_CPU_OK")
-    dist.destroy_process_group()
+    H.close_ranks("DIST_CPU_OK")
 
 
 if __name__ == "__main__":

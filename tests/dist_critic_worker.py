@@ -5,14 +5,12 @@ the fixed-point sums and the anchor counts all-reduced as integers, the best anc
 rank finishes and gates identically) against the unsharded Recommender on the whole catalogue, bit for bit: ids, scores, the critic's
 tables and the gate's stats, over several chunks with a short last one, identical on every rank.
 
-The two forwards agree bit for bit by the construction of tests/dist_diversify_worker.py: W_q0 holds multiples of 1/64 in [-1, 1],
-every user has 16 fold-in items and dropout is off, so the all-reduced encoder sum is exact."""
+The two forwards agree bit for bit by the model of serving_harness.exact_sum_model."""
 import os
 import sys
 
 import numpy as np
 import torch
-import torch.distributed as dist
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -20,38 +18,19 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
 def main():
-    import scipy.sparse as sp
-    from ltgan.dataset import EvalData
-    from ltgan.engine import Engine
+    import serving_harness as H
     from ltgan.serving import Critic, CriticGate, Recommender, ShardedRecommender
-    from ltgan.sharded import item_slab
     I, n_ev = int(sys.argv[1]), int(sys.argv[2])
-    dist.init_process_group("gloo")
-    rank, world = dist.get_rank(), dist.get_world_size()
-    dev = "cuda:0"
-    torch.cuda.set_device(dev)
-    hs = (16, 24, 40, 37)
-    ref = Engine(I, h_sizes=hs, lr=1e-3, precision="bf16", seed=77, d_seed=3, device=dev)
-    lo, hi = item_slab(I, rank, world)
-    eng = Engine(I, h_sizes=hs, lr=1e-3, precision="bf16", seed=77, d_seed=3, device=dev, item_lo=lo, item_hi=hi)
+    rank, world, dev = H.open_ranks()
+    ref, eng, lo, hi = H.slab_engines(I, (16, 24, 40, 37), rank, world)
     assert eng.feature_len == ref.feature_len == I and torch.equal(eng.d_emb, ref.d_emb)
     rng = np.random.default_rng(3)
-    bias = torch.from_numpy(rng.uniform(1.0, 3.0, I).astype(np.float32)).to(dev)          # (see dist_topk_worker.py)
-    wq0 = torch.from_numpy((rng.integers(-64, 65, (I, ref.H)) / 64.0).astype(np.float32)).to(dev)
-    ref.g_p[7].copy_(bias)
-    eng.g_p[7].copy_(bias[lo:hi])
-    ref.g_p[0].copy_(wq0)
-    eng.g_p[0].copy_(wq0[lo:hi])
-    cols = np.concatenate([rng.choice(I, 16, replace=False) for _ in range(n_ev)])
-    fold = sp.csr_matrix((np.ones(16 * n_ev, np.float32), (np.repeat(np.arange(n_ev), 16), cols)), shape=(n_ev, I))
-    fold.sort_indices()
-    ev_full = EvalData(fold, fold, dev)
-    ev_sh = EvalData(fold, fold, dev, item_lo=lo, item_hi=hi)
+    fold, ev_full, ev_sh = H.exact_sum_model(rng, ref, eng, n_ev)
     niche = set(rng.choice(I, I // 2, replace=False).tolist())
     valid = set(range(I)) - set(rng.choice(I, 40, replace=False).tolist())
     k, top, step = 100, 60, 900
-    bits = lambda a: np.ascontiguousarray(a).view(np.uint32) if a.dtype == np.float32 else a
-    slabs = [item_slab(I, q, world) for q in range(world)]
+    bits = lambda a: H.bits(a) if a.dtype == np.float32 else a         # (the critic's tables hold integers too)
+    slabs = H.slabs(I, world)
 
     def same_tables(a, b, what):
         for key in ("crit", "anchor_i", "anchor_s", "n_anchor"):
@@ -81,14 +60,9 @@ def main():
     assert np.array_equal(g_s.stats(), g_r.stats()) and g_r.stats()[:, 1].sum() > n_ev and not np.array_equal(ids_r2, ids_r)
     same_tables(c2_s.table(), c2_r.table(), "critic of the gated lists")
     print("rank %d: %d scored entries, %d rejected by the gate" % (rank, c_s.summary()["scored"], int(g_s.stats()[:, 1].sum())))
-    for a in (sh.ids, sh.scores, c_s.crit, c_s.anchor_i, c_s.anchor_s, c_s.n_anchor, sh2.ids, sh2.scores, g_s.stat, c2_s.crit, c2_s.anchor_i):
-        a0 = a.clone()                                                 # every rank holds the same tables
-        dist.broadcast(a0, 0)
-        assert torch.equal(a, a0)
-    dist.barrier()
-    if rank == 0:
-        print("CRITIC_SHARDED_OK world=%d items=%d slabs=%s" % (world, I, sorted({y - x for x, y in slabs})))
-    dist.destroy_process_group()
+    H.same_on_every_rank(sh.ids, sh.scores, c_s.crit, c_s.anchor_i, c_s.anchor_s, c_s.n_anchor, sh2.ids, sh2.scores, g_s.stat, c2_s.crit,
+                         c2_s.anchor_i)
+    H.close_ranks("CRITIC_SHARDED_OK world=%d items=%d slabs=%s" % (world, I, H.slab_sizes(I, world)))
 
 
 if __name__ == "__main__":

@@ -11,31 +11,25 @@ import sys
 
 import numpy as np
 import torch
-import torch.distributed as dist
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
 def main():
     import scipy.sparse as sp
+    import serving_harness as H
     from ltgan import longtail as lt
     from ltgan.dataset import EvalData
-    from ltgan.engine import Engine
-    from ltgan.sharded import ShardedRecommender, item_slab
+    from ltgan.sharded import ShardedRecommender
     from ltgan.synthetic import synthetic_index
     from ltgan.trainer import LongTailReport, Recommender
     workload, users = sys.argv[1], int(sys.argv[2])
-    dist.init_process_group("gloo")
-    rank, world = dist.get_rank(), dist.get_world_size()
-    dev = "cuda:0"
-    torch.cuda.set_device(dev)
+    rank, world, dev = H.open_ranks()
     idx, _ = synthetic_index(workload, users=users, seed=5)
     I = idx.n_items
-    hs = (16, 24, 40, 32)
-    ref = Engine(I, h_sizes=hs, lr=1e-3, precision="bf16", seed=77, d_seed=3, device=dev)
-    lo, hi = item_slab(I, rank, world)
-    eng = Engine(I, h_sizes=hs, lr=1e-3, precision="bf16", seed=77, d_seed=3, device=dev, item_lo=lo, item_hi=hi)
+    ref, eng, lo, hi = H.slab_engines(I, (16, 24, 40, 32), rank, world)
     # item biases of a trained model's size (see dist_topk_worker.py): near-ties then are ties of logits of order one
     bias = torch.from_numpy(np.random.default_rng(3).uniform(1.0, 3.0, I).astype(np.float32)).to(dev)
     ref.g_p[7].copy_(bias)
@@ -65,13 +59,7 @@ def main():
     sh = ShardedRecommender(eng, ev_sh, k=rep.k, chunk=n_ev, report=rep)
     ids, _ = sh.run(rng_step=step)
     out, hits = rep.table()
-    slabs = [item_slab(I, r, world) for r in range(world)]
-    wmax = max(b - a for a, b in slabs)
-    mine = torch.zeros(n_ev, wmax, dtype=torch.float32, device=dev)
-    mine[:, : hi - lo] = sh.acts.logits[:n_ev]
-    parts = [torch.empty_like(mine) for _ in range(world)]
-    dist.all_gather(parts, mine)
-    full = torch.cat([p[:, : b - a] for p, (a, b) in zip(parts, slabs)], dim=1).contiguous()
+    full = H.gathered_logits(sh.acts.logits[:n_ev], lo, hi, I, world)
     want_s = torch.empty(n_ev, rep.k, dtype=torch.float32, device=dev)
     want_i = torch.empty(n_ev, rep.k, dtype=torch.int32, device=dev)
     tr_full, te_full = ev_full.rows(0, n_ev)
@@ -83,11 +71,7 @@ def main():
     assert np.array_equal(out.view(np.uint32), want_out.cpu().numpy().view(np.uint32)), "sharded report differs from the gathered logits'"
     assert np.array_equal(hits, want_hits.cpu().numpy())
     assert hits.sum() == n_ev * k_exp                                  # NOT all-reduced: every rank counted every user once
-    # every rank holds the same tables
-    for a in (rep.out, rep.item_hits):
-        a0 = a.clone()
-        dist.broadcast(a0, 0)
-        assert torch.equal(a, a0)
+    H.same_on_every_rank(rep.out, rep.item_hits)
     # ---- several chunks (the last one short), against the unsharded report
     rep_c = LongTailReport(labels, 3, k_exp=k_exp)
     ShardedRecommender(eng, ev_sh, k=rep_c.k, chunk=100, report=rep_c).run(rng_step=step)
@@ -105,13 +89,9 @@ def main():
             assert abs(ra[key] - rb[key]) < 3e-3, (ra["name"], key, ra[key], rb[key])
     assert abs(a["all"]["gini"] - b["all"]["gini"]) < 3e-3
     assert a["all"]["ndcg"] > 0.0
-    dist.barrier()
-    if rank == 0:
-        print("SEEN max |sharded - unsharded| over the rows: %s gini %.3g" % (" ".join("%s %.3g" % kv for kv in seen.items()),
-                                                                             abs(a["all"]["gini"] - b["all"]["gini"])))
-        print("LONGTAIL_SHARDED_OK world=%d workload=%s users=%s slabs=%s" % (world, workload, [g["users"] for g in a["groups"]],
-                                                                            sorted({y - x for x, y in slabs})))
-    dist.destroy_process_group()
+    H.close_ranks("SEEN max |sharded - unsharded| over the rows: %s gini %.3g\nLONGTAIL_SHARDED_OK world=%d workload=%s users=%s slabs=%s" % (
+        " ".join("%s %.3g" % kv for kv in seen.items()), abs(a["all"]["gini"] - b["all"]["gini"]), world, workload,
+        [g["users"] for g in a["groups"]], H.slab_sizes(I, world)))
 
 
 if __name__ == "__main__":

@@ -8,25 +8,19 @@ import sys
 
 import numpy as np
 import torch
-import torch.distributed as dist
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
 def main():
-    from ltgan.engine import Engine
-    from ltgan.sharded import ShardedItemNeighbors, item_slab
+    import serving_harness as H
+    from ltgan.sharded import ShardedItemNeighbors
     from ltgan.trainer import ItemNeighbors
     I = int(sys.argv[1])
-    dist.init_process_group("gloo")
-    rank, world = dist.get_rank(), dist.get_world_size()
-    dev = "cuda:0"
-    torch.cuda.set_device(dev)
-    hs = (16, 24, 40, 32)
-    ref = Engine(I, h_sizes=hs, lr=1e-3, precision="bf16", seed=77, d_seed=3, device=dev)
-    lo, hi = item_slab(I, rank, world)
-    eng = Engine(I, h_sizes=hs, lr=1e-3, precision="bf16", seed=77, d_seed=3, device=dev, item_lo=lo, item_hi=hi)
+    rank, world, dev = H.open_ranks()
+    ref, eng, lo, hi = H.slab_engines(I, (16, 24, 40, 32), rank, world)
     # the same tables on both: rows of a trained model's spread, a few exact duplicates across the slabs (ties by id)
     rng = np.random.default_rng(3)
     for p in (0, 3):
@@ -45,15 +39,9 @@ def main():
         got_i, got_s = ShardedItemNeighbors(eng, chunk=1500, **kw).run(q)
         assert np.array_equal(got_i, want_i), "sharded ids differ from the unsharded table (%s %s k=%d)" % (space, metric, k)
         assert np.array_equal(got_s.view(np.uint32), want_s.view(np.uint32)), "sharded scores differ (%s %s k=%d)" % (space, metric, k)
-        t = torch.from_numpy(got_i).to(dev)                      # every rank holds the same table
-        t0 = t.clone()
-        dist.broadcast(t0, 0)
-        assert torch.equal(t, t0)
+        H.same_on_every_rank(torch.from_numpy(got_i).to(dev))
         n += got_i.shape[0]
-    dist.barrier()
-    if rank == 0:
-        print("NEIGHBORS_SHARDED_OK world=%d items=%d rows=%d slab=%d" % (world, I, n, hi - lo))
-    dist.destroy_process_group()
+    H.close_ranks("NEIGHBORS_SHARDED_OK world=%d items=%d rows=%d slab=%d" % (world, I, n, hi - lo))
 
 
 if __name__ == "__main__":

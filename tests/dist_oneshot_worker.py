@@ -10,18 +10,17 @@ import torch.distributed as dist
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
 def main():
+    import serving_harness as H
     from ltgan.dataset import DeviceData
     from ltgan.engine import Engine
     from ltgan.sharded import ShardedTrainer, item_slab
     from ltgan.synthetic import synthetic_index
     workload, users = sys.argv[1], int(sys.argv[2])
-    dist.init_process_group("gloo")
-    rank, world = dist.get_rank(), dist.get_world_size()
-    dev = "cuda:0"
-    torch.cuda.set_device(dev)
+    rank, world, dev = H.open_ranks()
     idx, _ = synthetic_index(workload, users=users, seed=5)
     I = idx.n_items
     lo, hi = item_slab(I, rank, world)
@@ -78,10 +77,7 @@ def main():
         assert torch.equal(x, y), "losses differ"
     for k, (x, y) in enumerate(zip(a[2], b[2])):
         assert torch.equal(x, y), ("generator tensor / moment differs", k, (x - y).abs().max().item())
-    dist.barrier()
-    if rank == 0:
-        print("ONESHOT_OK world=%d workload=%s exchanges=%d slabs=%s" % (world, workload, n_exch, sorted({b_ - a_ for a_, b_ in (item_slab(I, r, world) for r in range(world))})))
-    dist.destroy_process_group()
+    H.close_ranks("ONESHOT_OK world=%d workload=%s exchanges=%d slabs=%s" % (world, workload, n_exch, H.slab_sizes(I, world)))
 
 
 if __name__ == "__main__":

@@ -9,7 +9,6 @@ import sys
 
 import numpy as np
 import torch
-import torch.distributed as dist
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -18,22 +17,16 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 def main():
     import quota_ref as Q
+    import serving_harness as H
     from ltgan.dataset import EvalData
-    from ltgan.engine import Engine
-    from ltgan.sharded import ShardedRecommender, item_slab
+    from ltgan.sharded import ShardedRecommender
     from ltgan.synthetic import synthetic_index
     from ltgan.trainer import LongTailReport, MinSlots
     workload, users = sys.argv[1], int(sys.argv[2])
-    dist.init_process_group("gloo")
-    rank, world = dist.get_rank(), dist.get_world_size()
-    dev = "cuda:0"
-    torch.cuda.set_device(dev)
+    rank, world, dev = H.open_ranks()
     idx, _ = synthetic_index(workload, users=users, seed=5)
     I = idx.n_items
-    hs = (16, 24, 40, 32)
-    ref = Engine(I, h_sizes=hs, lr=1e-3, precision="bf16", seed=77, d_seed=3, device=dev)
-    lo, hi = item_slab(I, rank, world)
-    eng = Engine(I, h_sizes=hs, lr=1e-3, precision="bf16", seed=77, d_seed=3, device=dev, item_lo=lo, item_hi=hi)
+    ref, eng, lo, hi = H.slab_engines(I, (16, 24, 40, 32), rank, world)
     bias = torch.from_numpy(np.random.default_rng(3).uniform(1.0, 3.0, I).astype(np.float32)).to(dev)    # (see dist_topk_worker.py)
     eng.g_p[7].copy_(bias[lo:hi])
     n_ev = min(idx.N, users)
@@ -48,13 +41,7 @@ def main():
     rep = LongTailReport(labels, 3)
     sh = ShardedRecommender(eng, ev_sh, k=k, chunk=n_ev, rule=rule, report=rep)
     ids, sc = sh.run(rng_step=step)
-    slabs = [item_slab(I, r, world) for r in range(world)]
-    wmax = max(b - a for a, b in slabs)
-    mine = torch.zeros(n_ev, wmax, dtype=torch.float32, device=dev)
-    mine[:, : hi - lo] = sh.acts.logits[:n_ev]
-    parts = [torch.empty_like(mine) for _ in range(world)]
-    dist.all_gather(parts, mine)
-    full = torch.cat([p[:, : b - a] for p, (a, b) in zip(parts, slabs)], dim=1).contiguous()
+    full = H.gathered_logits(sh.acts.logits[:n_ev], lo, hi, I, world)
     tr_full, _ = ev_full.rows(0, n_ev)
     new = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=dev)
     a_s, a_i = new(n_ev, k), new(n_ev, k, dt=torch.int32)
@@ -76,10 +63,7 @@ def main():
         n_g = int((labels == g).sum()) - np.asarray(fold[:, np.nonzero(labels == g)[0]].getnnz(axis=1)).ravel()
         assert n_g.min() >= slots[g] and ((labels[ids] == g).sum(1) >= slots[g]).all()
     assert np.array_equal(rep.table()[1], np.bincount(ids.ravel(), minlength=I))          # the report read the ruled lists
-    for a in (sh.ids, sh.scores, rep.item_hits):                       # every rank holds the same tables
-        a0 = a.clone()
-        dist.broadcast(a0, 0)
-        assert torch.equal(a, a0)
+    H.same_on_every_rank(sh.ids, sh.scores, rep.item_hits)
     # ---- several chunks, the last one short: the rule holds for every user; all-zero slots == no rule
     ids_c, _ = ShardedRecommender(eng, ev_sh, k=k, chunk=100, rule=MinSlots(labels, 3, slots)).run(rng_step=step)
     for g in groups:
@@ -88,10 +72,7 @@ def main():
     p_i, p_s = ShardedRecommender(eng, ev_sh, k=k, chunk=100).run(rng_step=step)
     z_i, z_s = ShardedRecommender(eng, ev_sh, k=k, chunk=100, rule=MinSlots(labels, 3, [0, 0, 0])).run(rng_step=step)
     assert np.array_equal(p_i, z_i) and np.array_equal(p_s.view(np.uint32), z_s.view(np.uint32))
-    dist.barrier()
-    if rank == 0:
-        print("QUOTA_SHARDED_OK world=%d workload=%s slabs=%s" % (world, workload, sorted({y - x for x, y in slabs})))
-    dist.destroy_process_group()
+    H.close_ranks("QUOTA_SHARDED_OK world=%d workload=%s slabs=%s" % (world, workload, H.slab_sizes(I, world)))
 
 
 if __name__ == "__main__":

@@ -10,9 +10,11 @@ import torch.distributed as dist
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
 def main():
+    import serving_harness as H
     from ltgan.dataset import DeviceData
     from ltgan.engine import Engine
     from ltgan.sharded import ShardedTrainer
@@ -50,9 +52,7 @@ def main():
         assert torch.equal(x, y), "losses differ"
     for k, (x, y) in enumerate(zip(a[2], b[2])):
         assert torch.equal(x, y), ("tensor", k)
-    dist.barrier()
-    print("RCCL_DIRECT_OK")
-    dist.destroy_process_group()
+    H.close_ranks("RCCL_DIRECT_OK")
 
 
 if __name__ == "__main__":

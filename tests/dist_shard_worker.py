@@ -6,13 +6,14 @@ import sys
 
 import numpy as np
 import torch
-import torch.distributed as dist
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
 def main():
+    import serving_harness as H
     from ltgan.dataset import DeviceData
     from ltgan.engine import Engine
     from ltgan.sharded import ShardedTrainer, item_slab
@@ -27,10 +28,7 @@ def main():
     # LTGAN_TEST_BACKEND=nccl (tests/test_gpu_sharded.py::test_two_ranks_on_two_gpus_over_rccl, boxes with >= 2 GPUs): one GPU per
     # rank, the exchanges issued in-stream by RCCL itself -- the transport of a real node
     backend = os.environ.get("LTGAN_TEST_BACKEND", "gloo")
-    dist.init_process_group(backend)
-    rank, world = dist.get_rank(), dist.get_world_size()
-    dev = "cuda:%d" % int(os.environ.get("LOCAL_RANK", "0")) if backend == "nccl" else "cuda:0"
-    torch.cuda.set_device(dev)
+    rank, world, dev = H.open_ranks(backend, "cuda:%d" % int(os.environ.get("LOCAL_RANK", "0")) if backend == "nccl" else "cuda:0")
     idx, _ = synthetic_index(workload, users=users, seed=5)
     I = idx.n_items
     hs = (2048, 1024, 512, 256) if mode == "wide_fp8_full" else ((512, 256, 256, 128) if wide else (16, 24, 40, 32))
@@ -46,7 +44,7 @@ def main():
     tr = ShardedTrainer(eng, data, num_sub_epochs=S, shuffle_seed=1, d_split=d_split)
     assert tr.d_split == d_split
     # (every rank takes the same path: one slab below the one-call step's 8 192 items sends ALL ranks onto the cut-point sequence)
-    smallest = min(b - a for a, b in (item_slab(I, r, world) for r in range(world)))
+    smallest = min(H.slab_sizes(I, world))
     one_call = precision == "bf16" and smallest >= 8192 and mode != "cutpoints"
     assert (tr.pipe is not None) == one_call and (tr.comm is not None) == one_call, (tr.pipe, tr.comm)
     if backend == "nccl" and one_call:
@@ -128,12 +126,9 @@ def main():
         assert tr.pipe.expired_waits() == 0 and (ref_tr.pipe is None or ref_tr.pipe.expired_waits() == 0)
     transport = getattr(tr.comm, "kind", "torch.distributed")
     tr.close()
-    dist.barrier()
-    if rank == 0:
-        print("SHARDED_OK world=%d workload=%s precision=%s d_split=%s d_precision=%s backend=%s transport=%s handover=%s path=%s slabs=%s" % (
-            world, workload, precision, d_split, dq, backend, transport, getattr(tr.pipe, "handover", None),
-            "one-call" if one_call else "cut-points", sorted({b - a for a, b in (item_slab(I, r, world) for r in range(world))})))
-    dist.destroy_process_group()
+    H.close_ranks("SHARDED_OK world=%d workload=%s precision=%s d_split=%s d_precision=%s backend=%s transport=%s handover=%s path=%s slabs=%s" % (
+        world, workload, precision, d_split, dq, backend, transport, getattr(tr.pipe, "handover", None),
+        "one-call" if one_call else "cut-points", H.slab_sizes(I, world)))
 
 
 if __name__ == "__main__":

@@ -4,15 +4,12 @@ complement's; list all-gathers; ltg_topk_merge; then the same ltg_topk_share on 
 Recommender on the whole catalogue, bit for bit, over several chunks with a short last one and with a LongTailReport reading the final
 lists.
 
-The sharded forward all-reduces the encoder's partial pre-activations, which in general sums in another order than the unsharded forward
-(tests/dist_topk_worker.py).  Here that sum is exact, so the two forwards' logits agree bit for bit (tests/dist_calibrate_worker.py):
-W_q0 holds multiples of 1/64 in [-1, 1], every user has 16 fold-in items and dropout is off."""
+The two forwards' logits agree bit for bit by the model of serving_harness.exact_sum_model."""
 import os
 import sys
 
 import numpy as np
 import torch
-import torch.distributed as dist
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -20,35 +17,17 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
 def main():
-    import scipy.sparse as sp
-    from ltgan.dataset import EvalData
-    from ltgan.engine import Engine
-    from ltgan.sharded import ShardedRecommender, ShareTarget, item_slab
+    import serving_harness as H
+    from ltgan.sharded import ShardedRecommender, ShareTarget
     from ltgan.trainer import LongTailReport, Recommender
     I, n_ev = int(sys.argv[1]), int(sys.argv[2])
-    dist.init_process_group("gloo")
-    rank, world = dist.get_rank(), dist.get_world_size()
-    dev = "cuda:0"
-    torch.cuda.set_device(dev)
-    hs = (16, 24, 40, 32)
-    ref = Engine(I, h_sizes=hs, lr=1e-3, precision="bf16", seed=77, d_seed=3, device=dev)
-    lo, hi = item_slab(I, rank, world)
-    eng = Engine(I, h_sizes=hs, lr=1e-3, precision="bf16", seed=77, d_seed=3, device=dev, item_lo=lo, item_hi=hi)
+    rank, world, dev = H.open_ranks()
+    ref, eng, lo, hi = H.slab_engines(I, (16, 24, 40, 32), rank, world)
     rng = np.random.default_rng(3)
-    bias = torch.from_numpy(rng.uniform(1.0, 3.0, I).astype(np.float32)).to(dev)          # (see dist_topk_worker.py)
-    wq0 = torch.from_numpy((rng.integers(-64, 65, (I, ref.H)) / 64.0).astype(np.float32)).to(dev)
-    ref.g_p[7].copy_(bias)
-    eng.g_p[7].copy_(bias[lo:hi])
-    ref.g_p[0].copy_(wq0)
-    eng.g_p[0].copy_(wq0[lo:hi])
-    cols = np.concatenate([rng.choice(I, 16, replace=False) for _ in range(n_ev)])
-    fold = sp.csr_matrix((np.ones(16 * n_ev, np.float32), (np.repeat(np.arange(n_ev), 16), cols)), shape=(n_ev, I))
-    fold.sort_indices()
-    ev_full = EvalData(fold, fold, dev)
-    ev_sh = EvalData(fold, fold, dev, item_lo=lo, item_hi=hi)
+    fold, ev_full, ev_sh = H.exact_sum_model(rng, ref, eng, n_ev)
     labels = rng.integers(0, 3, I).astype(np.uint8)      # two groups; label 2 is in no group and belongs to the rest lists
     k, step = 100, 900
-    bits = lambda a: np.ascontiguousarray(a).view(np.uint32)
+    bits = H.bits
     plain, plain_sc = ShardedRecommender(eng, ev_sh, k=k, chunk=100).run(rng_step=step, keep_prob=1.0)
     zero = ShareTarget(labels, 2, [1], 0.0)              # share = 0: the plain table, and the sizes of the problem
     ids0, sc0 = ShardedRecommender(eng, ev_sh, k=k, chunk=100, share=zero).run(rng_step=step, keep_prob=1.0)
@@ -62,10 +41,7 @@ def main():
     ids, sc = sh.run(rng_step=step, keep_prob=1.0)
     assert sh.rowpart_all is None                        # no lse, no extra collective
     assert np.array_equal(rep.table()[1], np.bincount(ids[ids >= 0], minlength=I))       # the report read the final lists
-    for a in (sh.ids, sh.scores, tgt_s.pro_i, tgt_s.pro_s, tgt_s.rest_i, tgt_s.rest_s, tgt_s.state, rep.item_hits):
-        a0 = a.clone()                                   # every rank holds the same tables
-        dist.broadcast(a0, 0)
-        assert torch.equal(a, a0)
+    H.same_on_every_rank(sh.ids, sh.scores, tgt_s.pro_i, tgt_s.pro_s, tgt_s.rest_i, tgt_s.rest_s, tgt_s.state, rep.item_hits)
     ids_r, sc_r = Recommender(ref, ev_full, k=k, chunk=100, share=tgt_r).run(rng_step=step, keep_prob=1.0)
     for a, b in ((tgt_s.pro_i, tgt_r.pro_i), (tgt_s.rest_i, tgt_r.rest_i), (tgt_s.pro_s.view(torch.int32), tgt_r.pro_s.view(torch.int32)),
                  (tgt_s.rest_s.view(torch.int32), tgt_r.rest_s.view(torch.int32))):
@@ -77,15 +53,7 @@ def main():
     st = tgt_s.stats()
     assert 0 < st["taken"] < st["available"] and st["reached"] and st["rows_changed"] > 0 and not np.array_equal(ids, plain)
     assert int(np.isin(ids, np.nonzero(labels == 1)[0]).sum()) == tgt_s.want
-    dist.barrier()
-    if rank == 0:
-        print("SHARE_SHARDED_OK world=%d items=%d slabs=%s %s" % (world, I, sorted({y - x for x, y in slabs(I, world)}), st))
-    dist.destroy_process_group()
-
-
-def slabs(I, world):
-    from ltgan.sharded import item_slab
-    return [item_slab(I, r, world) for r in range(world)]
+    H.close_ranks("SHARE_SHARDED_OK world=%d items=%d slabs=%s %s" % (world, I, H.slab_sizes(I, world), st))
 
 
 if __name__ == "__main__":

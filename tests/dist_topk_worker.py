@@ -8,30 +8,24 @@ import sys
 
 import numpy as np
 import torch
-import torch.distributed as dist
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
 def main():
     import scipy.sparse as sp
+    import serving_harness as H
     from ltgan.dataset import EvalData
-    from ltgan.engine import Engine
-    from ltgan.sharded import ShardedRecommender, item_slab
+    from ltgan.sharded import ShardedRecommender
     from ltgan.synthetic import synthetic_index
     from ltgan.trainer import Recommender
     workload, users = sys.argv[1], int(sys.argv[2])
-    dist.init_process_group("gloo")
-    rank, world = dist.get_rank(), dist.get_world_size()
-    dev = "cuda:0"
-    torch.cuda.set_device(dev)
+    rank, world, dev = H.open_ranks()
     idx, _ = synthetic_index(workload, users=users, seed=5)
     I = idx.n_items
-    hs = (16, 24, 40, 32)
-    ref = Engine(I, h_sizes=hs, lr=1e-3, precision="bf16", seed=77, d_seed=3, device=dev)
-    lo, hi = item_slab(I, rank, world)
-    eng = Engine(I, h_sizes=hs, lr=1e-3, precision="bf16", seed=77, d_seed=3, device=dev, item_lo=lo, item_hi=hi)
+    ref, eng, lo, hi = H.slab_engines(I, (16, 24, 40, 32), rank, world)
     # item biases of a trained model's size: the logits of a fresh initialisation are ~1e-2, where the 1e-7 the encoder all-reduce's
     # order moves a logit by would be a relative 1e-5 -- the near-tie bound below is stated for logits of order one
     bias = torch.from_numpy(np.random.default_rng(3).uniform(1.0, 3.0, I).astype(np.float32)).to(dev)
@@ -49,13 +43,7 @@ def main():
     # ---- exact: one chunk, so that the sharded forward's slab logits of every row are still in the activations
     sh = ShardedRecommender(eng, ev_sh, k=k, chunk=n_ev)
     ids, sc = sh.run(rng_step=step)
-    slabs = [item_slab(I, r, world) for r in range(world)]
-    wmax = max(b - a for a, b in slabs)
-    mine = torch.zeros(n_ev, wmax, dtype=torch.float32, device=dev)
-    mine[:, : hi - lo] = sh.acts.logits[:n_ev]
-    parts = [torch.empty_like(mine) for _ in range(world)]
-    dist.all_gather(parts, mine)
-    full = torch.cat([p[:, : b - a] for p, (a, b) in zip(parts, slabs)], dim=1).contiguous()
+    full = H.gathered_logits(sh.acts.logits[:n_ev], lo, hi, I, world)
     want_s = torch.empty(n_ev, k, dtype=torch.float32, device=dev)
     want_i = torch.empty(n_ev, k, dtype=torch.int32, device=dev)
     tr_full, _ = ev_full.rows(0, n_ev)
@@ -63,11 +51,7 @@ def main():
     torch.cuda.synchronize()
     assert np.array_equal(ids, want_i.cpu().numpy()), "sharded table differs from ltg_topk on the gathered logits"
     assert np.array_equal(sc.view(np.uint32), want_s.cpu().numpy().view(np.uint32))
-    # every rank holds the same table
-    t = torch.from_numpy(ids).to(dev)
-    t0 = t.clone()
-    dist.broadcast(t0, 0)
-    assert torch.equal(t, t0)
+    H.same_on_every_rank(torch.from_numpy(ids).to(dev))
     # ---- several chunks (the last one short), against the unsharded recommender
     ids_c, sc_c = ShardedRecommender(eng, ev_sh, k=k, chunk=100).run(rng_step=step)
     ids_r, sc_r = Recommender(ref, ev_full, k=k, chunk=100).run(rng_step=step)
@@ -77,10 +61,7 @@ def main():
         d = ids_c[r] != ids_r[r]
         a, b = sc_c[r, d].astype(np.float64), sc_r[r, d].astype(np.float64)
         assert np.all(np.abs(a - b) <= 1e-5 * np.maximum(np.abs(a), np.abs(b))), ("not a near-tie", r, a, b)
-    dist.barrier()
-    if rank == 0:
-        print("TOPK_SHARDED_OK world=%d workload=%s rows_identical=%.4f slabs=%s" % (world, workload, same.mean(), sorted({b - a for a, b in slabs})))
-    dist.destroy_process_group()
+    H.close_ranks("TOPK_SHARDED_OK world=%d workload=%s rows_identical=%.4f slabs=%s" % (world, workload, same.mean(), H.slab_sizes(I, world)))
 
 
 if __name__ == "__main__":

@@ -1,23 +1,17 @@
 """N>1 path on CPU: world_size-2 gloo run of the item-sharded exchange steps (tests/dist_cpu_worker.py),
 plus the host-side sharding of the data."""
 import pytest
-import os
-import subprocess
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from serving_harness import run_ranks
 
 
 @pytest.mark.parametrize("world", [2, 8])
 def test_gloo_exchange_algebra(world):
     """world 8 = the node the item sharding is built for: eight slabs with an uneven last one, rowpart_all [8][B][5]"""
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="1")
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
-           "--master-port", str(29611 + world), os.path.join(ROOT, "tests", "dist_cpu_worker.py")]
-    out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600)
-    assert out.returncode == 0 and "DIST_CPU_OK" in out.stdout, out.stdout[-2000:] + out.stderr[-4000:]
+    run_ranks("dist_cpu_worker.py", [], world, "DIST_CPU_OK", port_of="test_dist_cpu::test_gloo_exchange_algebra[%d]" % world, limit=600,
+              env={"OMP_NUM_THREADS": "1"})
 
 
 def test_item_slabs_partition_and_shard_data():

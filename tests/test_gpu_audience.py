@@ -4,30 +4,14 @@ Recommender(..., audience=...) on a real forward, audience.py on the Askubuntu f
 (tests/dist_audience_worker.py)."""
 import ctypes as C
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import audience_ref as AR
+from serving_harness import askubuntu_run, run_cli, run_ranks
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-CONFIG = """[Long-Tail-GAN]
-h0_size = 100
-h1_size = 150
-h2_size = 250
-h3_size = 300
-NUM_EPOCH = 8
-BATCH_SIZE = 100
-DISPLAY_ITER = 50
-LEARNING_RATE = 0.0001
-to_restore = 0
-model_name = LT_GAN
-GANLAMBDA = 1.0
-"""
 
 N_SPECIAL = 9          # the injected columns sit at 3, 3 + step, ... so that they fall into different column blocks
 
@@ -201,30 +185,14 @@ def test_audience_on_a_real_forward():
 def test_audience_cli_on_the_askubuntu_fixture(tmp_path):
     import torch
     from ltgan import data_processing as dp
-    from ltgan.dataset import count_items, materialize_askubuntu
-    from ltgan.generator import generator_VAECF
-    from ltgan.test import _Counters
-    from ltgan.train import save_checkpoint
-    ds = str(tmp_path / "Askubuntu_Sample")
-    materialize_askubuntu(os.path.join(ROOT, "tests", "golden", "askubuntu_raw.npz"), ds)
-    cwd = str(tmp_path / "run")
-    os.makedirs(cwd)
-    open(os.path.join(cwd, "config.ini"), "w").write(CONFIG)
-    n_items = count_items(ds)
-    gen, *_ = generator_VAECF(ds + "/", h_sizes=(100, 150, 250, 300), lr=1e-4, precision="bf16", device="cuda:0")
-    ck = os.path.join(cwd, "model_0.pt")
-    save_checkpoint(ck, gen.engine, _Counters(), 0)
+    ds, cwd, n_items, _, ck, tr, _, uid0 = askubuntu_run(tmp_path)
     torch.cuda.synchronize()
-    tr, _, uid0 = dp.load_tr_te_data(os.path.join(ds, "test_tr.csv"), os.path.join(ds, "test_te.csv"), n_items)
     tr = tr.tocsr()
     _, _, niche, _, _ = dp.load_pop_niche_tags(os.path.join(ds, "item2id.txt"), os.path.join(ds, "item_list.txt"),
                                                os.path.join(ds, "niche_items.txt"), n_items)
     niche = sorted(int(x) for x in niche)
     users = tr.shape[0]
-    script = os.path.join(ROOT, "long-tail-gan_amd", "audience.py")
-    r = subprocess.run(["timeout", "-k", "10", "600", sys.executable, script, ds, ck, "--items", "niche", "--k", "20", "--npz", "aud.npz"],
-                       cwd=cwd, capture_output=True, text=True, timeout=700)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    out = run_cli("audience.py", [ds, ck, "--items", "niche", "--k", "20", "--npz", "aud.npz"], cwd)
     lines = open(os.path.join(cwd, "audience.tsv")).read().splitlines()
     assert len(lines) == len(niche) > 0
     held = tr.tocsc()
@@ -242,7 +210,7 @@ def test_audience_cli_on_the_askubuntu_fixture(tmp_path):
     z = np.load(os.path.join(cwd, "aud.npz"))
     assert z["items"].tolist() == niche and z["uids"].shape == (len(niche), 20) and z["scores"].shape == (len(niche), 20)
     assert z["scores"].dtype == np.float32
-    f = dict(x.split(": ") for x in r.stdout.strip().splitlines()[-1].split("\t"))
+    f = dict(x.split(": ") for x in out[-1].split("\t"))
     assert int(f["items"]) == len(niche) and int(f["users"]) == users and 0.0 < float(f["user_coverage@20"]) <= 1.0
 
 
@@ -252,8 +220,4 @@ def test_sharded_audience(world, workload):
     against the unsharded walk within 1e-5 relative at every position with fp32 operands, where the all-reduce order is the only source of
     difference the bound was derived for (with bf16 operands a rounding of an operand flips here and there: 1.3e-05 at custom:1001, printed
     by the worker, which says where that comes from)"""
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="2")
-    cmd = ["timeout", "-k", "10", "900", sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
-           "--master-addr", "127.0.0.1", "--master-port", "29681", os.path.join(ROOT, "tests", "dist_audience_worker.py"), workload, "230"]
-    out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=1000)      # fresh children only
-    assert out.returncode == 0 and ("AUDIENCE_SHARDED_OK world=%d" % world) in out.stdout, out.stdout[-3000:] + out.stderr[-6000:]
+    run_ranks("dist_audience_worker.py", [workload, "230"], world, "AUDIENCE_SHARDED_OK world=%d" % world)

@@ -5,28 +5,16 @@ memory) and k = 1; Recommender(calibrate=) against the entry points called by ha
 the item-sharded recommender (tests/dist_calibrate_worker.py) and both CLIs on Askubuntu_Sample in fresh child processes."""
 import ctypes as C
 import os
-import subprocess
-import sys
 from fractions import Fraction
 
 import numpy as np
 import pytest
 
 import calibrate_ref as R
+from serving_harness import DEV, _bits, _t, askubuntu_run, run_cli, run_ranks
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEV = "cuda:0"
 LAMBDAS = (0.0, 0.25, 0.5, 0.99, 1.0)
-
-
-def _t(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def _cal_dev(S, I, list_class, n_groups, hist, lam, k, stat=True):
@@ -213,40 +201,16 @@ def test_recommender_with_calibrate(I):
 
 @pytest.mark.parametrize("world", [2, 3])
 def test_sharded_recommender_with_calibrate(world):
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="2")
-    cmd = ["timeout", "-k", "10", "900", sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
-           "--master-addr", "127.0.0.1", "--master-port", "29673", os.path.join(ROOT, "tests", "dist_calibrate_worker.py"), "1001", "230"]
-    out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=1000)      # fresh children only
-    print(out.stdout[-3000:])
-    assert out.returncode == 0 and ("CALIBRATE_SHARDED_OK world=%d" % world) in out.stdout, out.stdout[-3000:] + out.stderr[-6000:]
+    run_ranks("dist_calibrate_worker.py", ["1001", "230"], world, "CALIBRATE_SHARDED_OK world=%d" % world)
 
 
 def test_clis_on_askubuntu(tmp_path):
     import torch
     from ltgan import data_processing as dp
     from ltgan import recommend as rc
-    from ltgan.dataset import EvalData, count_items, materialize_askubuntu
-    from ltgan.generator import generator_VAECF
-    from ltgan.test import _Counters
-    from ltgan.train import save_checkpoint
+    from ltgan.dataset import EvalData
     from ltgan.trainer import Recommender
-    from test_gpu_neighbors import CONFIG
-    ds = str(tmp_path / "Askubuntu_Sample")
-    materialize_askubuntu(os.path.join(ROOT, "tests", "golden", "askubuntu_raw.npz"), ds)
-    cwd = str(tmp_path / "run")
-    os.makedirs(cwd)
-    open(os.path.join(cwd, "config.ini"), "w").write(CONFIG)
-    n_items = count_items(ds)
-    gen, *_ = generator_VAECF(ds + "/", h_sizes=(100, 150, 250, 300), lr=1e-4, precision="bf16", device=DEV)
-    eng = gen.engine
-    ck = os.path.join(cwd, "model_0.pt")
-    save_checkpoint(ck, eng, _Counters(), 0)
-    tr, te, uid0 = dp.load_tr_te_data(os.path.join(ds, "test_tr.csv"), os.path.join(ds, "test_te.csv"), n_items)
-
-    def run(cmd):
-        r = subprocess.run(["timeout", "-k", "10", "600", sys.executable] + cmd, cwd=cwd, capture_output=True, text=True, timeout=700)
-        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-        return r.stdout.strip().splitlines()
+    ds, cwd, n_items, eng, ck, tr, te, uid0 = askubuntu_run(tmp_path)
 
     def miscal(line):
         assert line.startswith("miscal@100: ") and " -> " in line, line
@@ -254,9 +218,7 @@ def test_clis_on_askubuntu(tmp_path):
         assert np.isfinite(before) and np.isfinite(after) and after <= before, line
         return before, after
 
-    rscript = os.path.join(ROOT, "long-tail-gan_amd", "recommend.py")
-    lscript = os.path.join(ROOT, "long-tail-gan_amd", "longtail.py")
-    out = run([rscript, ds, ck, "--calibrate", "0.9", "--out", "cal.tsv"])
+    out = run_cli("recommend.py", [ds, ck, "--calibrate", "0.9", "--out", "cal.tsv"], cwd)
     assert out[-2].startswith("users: %d\tniche_share@100: " % tr.shape[0])
     print(out[-1])
     miscal(out[-1])
@@ -266,11 +228,11 @@ def test_clis_on_askubuntu(tmp_path):
         u, items = line.split("\t")
         items = [int(x) for x in items.split(",")]
         assert int(u) == uid0 + n and len(items) == 100 == len(set(items)) and min(items) >= 0 and max(items) < n_items
-    out = run([lscript, ds, ck, "--calibrate", "0.9", "--groups", "pop:3"])
+    out = run_cli("longtail.py", [ds, ck, "--calibrate", "0.9", "--groups", "pop:3"], cwd)
     miscal(out[-1])
     assert out[-2].startswith("all\t") and len(out[-2].split("\t")) == 9
     # without the option: the summary of the plain Recommender as the last line, and no other
-    plain = run([rscript, ds, ck, "--out", "plain.tsv"])
+    plain = run_cli("recommend.py", [ds, ck, "--out", "plain.tsv"], cwd)
     ids, _ = Recommender(eng, EvalData(tr, te, eng.device), k=100).run(rng_step=rc.RNG_STEP)
     _, _, niche, _, _ = dp.load_pop_niche_tags(os.path.join(ds, "item2id.txt"), os.path.join(ds, "item_list.txt"),
                                                os.path.join(ds, "niche_items.txt"), n_items)

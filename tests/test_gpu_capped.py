@@ -6,17 +6,14 @@ need no reference (exposure, no blocking pair, order, run-to-run bits, rounds af
 points called by hand, with a LongTailReport reading the capped lists; the item-sharded recommender (tests/dist_capped_worker.py) and
 both CLIs on Askubuntu_Sample in fresh child processes."""
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import capped_ref as R
+from serving_harness import DEV, _bits, _t, askubuntu_run, run_cli, run_ranks
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEV = "cuda:0"
 
 #        n,    I,    c,    k,   cap, quant
 SHAPES = [(64, 24, 24, 5, 14, None),                      # a row shorter than a wave
@@ -26,15 +23,6 @@ SHAPES = [(64, 24, 24, 5, 14, None),                      # a row shorter than a
           (130, 70, 65, 64, 125, None),                   # c not a multiple of 64, k ~ c
           (777, 129, 129, 10, 61, 0.5),                   # quantised scores: items break ties by user row
           (3000, 1000, 256, 100, 330, None)]
-
-
-def _t(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 _CASES = {}
@@ -279,39 +267,14 @@ def test_recommender_with_cap(I):
 
 @pytest.mark.parametrize("world", [2, 3])
 def test_sharded_recommender_with_cap(world):
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="2")
-    cmd = ["timeout", "-k", "10", "900", sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
-           "--master-addr", "127.0.0.1", "--master-port", "29674", os.path.join(ROOT, "tests", "dist_capped_worker.py"), "1001", "230"]
-    out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=1000)      # fresh children only
-    print(out.stdout[-3000:])
-    assert out.returncode == 0 and ("CAPPED_SHARDED_OK world=%d" % world) in out.stdout, out.stdout[-3000:] + out.stderr[-6000:]
+    run_ranks("dist_capped_worker.py", ["1001", "230"], world, "CAPPED_SHARDED_OK world=%d" % world)
 
 
 def test_clis_on_askubuntu(tmp_path):
     import torch
-    from ltgan import data_processing as dp
-    from ltgan.dataset import count_items, materialize_askubuntu
-    from ltgan.generator import generator_VAECF
-    from ltgan.test import _Counters
-    from ltgan.train import save_checkpoint
-    from test_gpu_neighbors import CONFIG
-    ds = str(tmp_path / "Askubuntu_Sample")
-    materialize_askubuntu(os.path.join(ROOT, "tests", "golden", "askubuntu_raw.npz"), ds)
-    cwd = str(tmp_path / "run")
-    os.makedirs(cwd)
-    open(os.path.join(cwd, "config.ini"), "w").write(CONFIG)
-    n_items = count_items(ds)
-    gen, *_ = generator_VAECF(ds + "/", h_sizes=(100, 150, 250, 300), lr=1e-4, precision="bf16", device=DEV)
-    ck = os.path.join(cwd, "model_0.pt")
-    save_checkpoint(ck, gen.engine, _Counters(), 0)
-    tr, te, uid0 = dp.load_tr_te_data(os.path.join(ds, "test_tr.csv"), os.path.join(ds, "test_te.csv"), n_items)
+    ds, cwd, n_items, _, ck, tr, te, uid0 = askubuntu_run(tmp_path)
     n_users = tr.shape[0]
     C = max(2, n_users // 10)                            # far below the head's plain exposure, and enough places for full lists
-
-    def run(cmd):
-        r = subprocess.run(["timeout", "-k", "10", "600", sys.executable] + cmd, cwd=cwd, capture_output=True, text=True, timeout=700)
-        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-        return r.stdout.strip().splitlines()
 
     def cap_line(line, bound):
         import re
@@ -321,9 +284,7 @@ def test_clis_on_askubuntu(tmp_path):
         assert (bound is None or after <= bound) and rounds >= 1, line
         return before, after, at_cap, short, rounds
 
-    rscript = os.path.join(ROOT, "long-tail-gan_amd", "recommend.py")
-    lscript = os.path.join(ROOT, "long-tail-gan_amd", "longtail.py")
-    out = run([rscript, ds, ck, "--cap", str(C), "--out", "cap.tsv"])
+    out = run_cli("recommend.py", [ds, ck, "--cap", str(C), "--out", "cap.tsv"], cwd)
     assert out[-2].startswith("users: %d\tniche_share@100: " % n_users)
     print(out[-1])
     before, after, at_cap, short, _ = cap_line(out[-1], C)
@@ -339,7 +300,7 @@ def test_clis_on_askubuntu(tmp_path):
         n_short += len(items) < 100
         np.add.at(hits, items, 1)
     assert hits.max() == after and n_short == short
-    out = run([lscript, ds, ck, "--cap", "popular:%d" % C, "--cap-score", "logit", "--cap-candidates", "300", "--groups", "niche"])
+    out = run_cli("longtail.py", [ds, ck, "--cap", "popular:%d" % C, "--cap-score", "logit", "--cap-candidates", "300", "--groups", "niche"], cwd)
     print(out[-1])
     # only the popular items are capped, and the users they turn away land on niche items: the largest exposure has no bound
     assert cap_line(out[-1], None)[2] >= 1

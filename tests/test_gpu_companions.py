@@ -7,8 +7,6 @@ ShardedPairCompanions (tests/dist_companions_worker.py).  The reference is tests
 import ctypes as C
 import functools
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -17,27 +15,13 @@ import companions_ref as CR
 import helpers as Hh
 import test_companions_cpu as TC
 from oracle import ltg_oracle as O
+from serving_harness import askubuntu_run, run_cli, run_ranks
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 U = 2.0 ** -24                      # fp32 unit roundoff
 SMALL, CONFIG = (16, 24, 40, 37), (100, 150, 250, 300)     # h3 = 37 is a multiple of nothing (ld = 40: three padding columns); config.ini's sizes
 F = 4000                            # rows of the embedding table
 N_Q, N_C = 130, 3001
-
-CONFIG_INI = """[Long-Tail-GAN]
-h0_size = 100
-h1_size = 150
-h2_size = 250
-h3_size = 300
-NUM_EPOCH = 8
-BATCH_SIZE = 100
-DISPLAY_ITER = 50
-LEARNING_RATE = 0.0001
-to_restore = 0
-model_name = LT_GAN
-GANLAMBDA = 1.0
-"""
 
 
 class Disc:
@@ -478,21 +462,8 @@ def test_companions_cli_equals_the_class(tmp_path):
     import torch
     from ltgan import companions as CP
     from ltgan import data_processing as dp
-    from ltgan.dataset import count_items, materialize_askubuntu
-    from ltgan.generator import generator_VAECF
-    from ltgan.test import _Counters
-    from ltgan.train import save_checkpoint
     from ltgan.trainer import PairCompanions
-    ds = str(tmp_path / "Askubuntu_Sample")
-    materialize_askubuntu(os.path.join(ROOT, "tests", "golden", "askubuntu_raw.npz"), ds)
-    cwd = str(tmp_path / "run")
-    os.makedirs(cwd)
-    open(os.path.join(cwd, "config.ini"), "w").write(CONFIG_INI)
-    n_items = count_items(ds)
-    gen, *_ = generator_VAECF(ds + "/", h_sizes=CONFIG, lr=1e-4, precision="bf16", device="cuda:0")
-    eng = gen.engine
-    ck = os.path.join(cwd, "model_0.pt")
-    save_checkpoint(ck, eng, _Counters(), 0)
+    ds, cwd, n_items, eng, ck, _, _, _ = askubuntu_run(tmp_path, split=None)
     show2id, _, niche, _, _ = dp.load_pop_niche_tags(os.path.join(ds, "item2id.txt"), os.path.join(ds, "item_list.txt"),
                                                      os.path.join(ds, "niche_items.txt"), n_items)
     valid = dp.load_valid_item_ids(os.path.join(ds, "item_list.txt"), show2id)
@@ -500,16 +471,12 @@ def test_companions_cli_equals_the_class(tmp_path):
     assert side == "popular" and q.size and cand.size and not np.intersect1d(q, cand).size
     want_i, want_s = PairCompanions(eng, k=10).run(q, cand)
     torch.cuda.synchronize()
-    script = os.path.join(ROOT, "long-tail-gan_amd", "companions.py")
 
     def summary(out):
-        last = [l for l in out.strip().splitlines() if l.startswith("items: ")][-1]
+        last = [l for l in out if l.startswith("items: ")][-1]
         return dict(x.split(": ") for x in last.split("\t"))
 
-    r = subprocess.run(["timeout", "-k", "10", "600", sys.executable, script, ds, ck, "--k", "10", "--out", "c.tsv", "--npz", "c.npz"], cwd=cwd,
-                       capture_output=True, text=True, timeout=700)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    f = summary(r.stdout)
+    f = summary(run_cli("companions.py", [ds, ck, "--k", "10", "--out", "c.tsv", "--npz", "c.npz"], cwd))
     z = np.load(os.path.join(cwd, "c.npz"))
     assert np.array_equal(z["items"], q) and np.array_equal(z["ids"], want_i) and _eq(z["scores"], want_s)
     rows = open(os.path.join(cwd, "c.tsv")).read().splitlines()
@@ -523,21 +490,13 @@ def test_companions_cli_equals_the_class(tmp_path):
     assert int(f["items"]) == q.size and abs(float(f["coverage@10"]) - m["coverage"]) < 1e-6 and abs(float(f["mean_prob@1"]) - m["mean_prob"]) < 1e-6
     assert 0.0 < float(f["coverage@10"]) <= 1.0 and 0.0 < float(f["mean_prob@1"]) < 1.0
     # two ranks (gloo, one GPU), candidates sharded by item slab: the same table bit for bit
-    env = dict(os.environ, LTGAN_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = ["timeout", "-k", "10", "900", sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
-           "--master-addr", "127.0.0.1", "--master-port", "29651", script, ds, ck, "--k", "10", "--out", "c2.tsv", "--npz", "c2.npz"]
-    r2 = subprocess.run(cmd, cwd=cwd, capture_output=True, text=True, env=env, timeout=1000)
-    assert r2.returncode == 0, r2.stdout[-2000:] + r2.stderr[-4000:]
+    out2 = run_cli("companions.py", [ds, ck, "--k", "10", "--out", "c2.tsv", "--npz", "c2.npz"], cwd, world=2, limit=900)
     z2 = np.load(os.path.join(cwd, "c2.npz"))
     assert np.array_equal(z2["ids"], want_i) and _eq(z2["scores"], want_s)
     assert open(os.path.join(cwd, "c2.tsv")).read() == open(os.path.join(cwd, "c.tsv")).read()
-    assert summary(r2.stdout) == f
+    assert summary(out2) == f
 
 
 @pytest.mark.parametrize("world", [2])
 def test_sharded_pair_companions(world):
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="2")
-    cmd = ["timeout", "-k", "10", "900", sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
-           "--master-addr", "127.0.0.1", "--master-port", "29653", os.path.join(ROOT, "tests", "dist_companions_worker.py"), "5003"]
-    out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=1000)      # fresh children only
-    assert out.returncode == 0 and ("COMPANIONS_SHARDED_OK world=%d" % world) in out.stdout, out.stdout[-3000:] + out.stderr[-6000:]
+    run_ranks("dist_companions_worker.py", ["5003"], world, "COMPANIONS_SHARDED_OK world=%d" % world)

@@ -6,8 +6,6 @@ Recommender, recommend.py / longtail.py, and the item-sharded run (tests/dist_cr
 import ctypes as C
 import functools
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -16,9 +14,9 @@ import companions_ref as CR
 import critic_ref as KR
 import test_critic_cpu as TK
 import test_gpu_companions as TG
+from serving_harness import askubuntu_run, run_cli, run_ranks
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TINY, CONFIG = (8, 5, 7, 13), (100, 150, 250, 300)       # h3 = 13 is no multiple of 4 (ld = 16); config.ini's sizes
 CASES = [(TINY, False), (CONFIG, False), (TINY, True), (CONFIG, True)]
 CASE_IDS = ["h3-13", "config", "h3-13-trained-range", "config-trained-range"]
@@ -388,52 +386,27 @@ def test_recommender_with_gate():
 # ---------------------------------------------------------------------------------------------- 6. over item shards
 @pytest.mark.parametrize("world", [2, 3])
 def test_sharded_critic_and_gate(world):
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="2")
-    cmd = ["timeout", "-k", "10", "900", sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
-           "--master-addr", "127.0.0.1", "--master-port", "29695", os.path.join(ROOT, "tests", "dist_critic_worker.py"), "1001", "230"]
-    out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=1000)      # fresh children only
-    print(out.stdout[-3000:])
-    assert out.returncode == 0 and ("CRITIC_SHARDED_OK world=%d" % world) in out.stdout, out.stdout[-3000:] + out.stderr[-6000:]
+    run_ranks("dist_critic_worker.py", ["1001", "230"], world, "CRITIC_SHARDED_OK world=%d" % world)
 
 
 # ---------------------------------------------------------------------------------------------- 7. the CLIs
 def test_cli_on_askubuntu(tmp_path):
     import json
     import torch
-    from ltgan import data_processing as dp
     from ltgan import longtail as lt
     from ltgan import recommend as rc
-    from ltgan.dataset import EvalData, count_items, materialize_askubuntu
-    from ltgan.generator import generator_VAECF
-    from ltgan.test import _Counters
-    from ltgan.train import save_checkpoint
+    from ltgan.dataset import EvalData
     from ltgan.trainer import Critic, CriticGate, LongTailReport, Recommender
-    ds = str(tmp_path / "Askubuntu_Sample")
-    materialize_askubuntu(os.path.join(ROOT, "tests", "golden", "askubuntu_raw.npz"), ds)
-    cwd = str(tmp_path / "run")
-    os.makedirs(cwd)
-    open(os.path.join(cwd, "config.ini"), "w").write(TG.CONFIG_INI)
-    n_items = count_items(ds)
-    gen, *_ = generator_VAECF(ds + "/", h_sizes=CONFIG, lr=1e-4, precision="bf16", device="cuda:0")
-    eng = gen.engine
-    ck = os.path.join(cwd, "model_0.pt")
-    save_checkpoint(ck, eng, _Counters(), 0)
-    tr, te, uid0 = dp.load_tr_te_data(os.path.join(ds, "test_tr.csv"), os.path.join(ds, "test_te.csv"), n_items)
+    ds, cwd, n_items, eng, ck, tr, te, uid0 = askubuntu_run(tmp_path)
     niche, valid = lt.critic_sides(ds, n_items)
     ev = EvalData(tr, te, eng.device)
-
-    def run(cmd):
-        r = subprocess.run(["timeout", "-k", "10", "600", sys.executable] + cmd, cwd=cwd, capture_output=True, text=True, timeout=700)
-        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-        return r.stdout.strip().splitlines()
 
     # recommend.py --gate --critic against the classes
     gate, crt = CriticGate(niche, valid, 0.5), Critic(niche, valid, top=30)
     ids, sc = Recommender(eng, ev, k=100, gate=gate, critic=crt).run(rng_step=rc.RNG_STEP)
     tab = crt.table()
     torch.cuda.synchronize()
-    script = os.path.join(ROOT, "long-tail-gan_amd", "recommend.py")
-    out = run([script, ds, ck, "--gate", "0.5", "--critic", "30", "--critic-out", "c.tsv", "--out", "recs.tsv", "--npz", "recs.npz"])
+    out = run_cli("recommend.py", [ds, ck, "--gate", "0.5", "--critic", "30", "--critic-out", "c.tsv", "--out", "recs.tsv", "--npz", "recs.npz"], cwd)
     z = np.load(os.path.join(cwd, "recs.npz"))
     assert np.array_equal(z["ids"], ids) and np.array_equal(_bits(z["scores"]), _bits(sc))
     for key, name in (("crit", "crit"), ("anchor_i", "anchor_ids"), ("anchor_s", "anchor_scores"), ("n_anchor", "n_anchor")):
@@ -453,7 +426,7 @@ def test_cli_on_askubuntu(tmp_path):
         assert int(a) in hist.indices[hist.indptr[u]:hist.indptr[u + 1]] and int(sid) in niche and int(a) not in niche
         assert float(prob) >= 0.5 - 5.1e-7                             # the gate let it in
     # without the flags: the plain lists, no new line, no file
-    plain = run([script, ds, ck, "--out", "plain.tsv", "--npz", "plain.npz"])
+    plain = run_cli("recommend.py", [ds, ck, "--out", "plain.tsv", "--npz", "plain.npz"], cwd)
     p_ids, _ = Recommender(eng, ev, k=100).run(rng_step=rc.RNG_STEP)
     assert np.array_equal(np.load(os.path.join(cwd, "plain.npz"))["ids"], p_ids) and sorted(np.load(os.path.join(cwd, "plain.npz")).files) == ["ids", "scores", "uids"]
     assert plain[-1] == rc.summary_line(rc.long_tail_summary(p_ids, niche, n_items, te), 100) and not os.path.exists(os.path.join(cwd, "critic.tsv"))
@@ -464,7 +437,7 @@ def test_cli_on_askubuntu(tmp_path):
     gate2, crt2 = CriticGate(niche, valid, 0.5, candidates=150), Critic(niche, valid)
     ids2, _ = Recommender(eng, ev, k=100, report=report, gate=gate2, critic=crt2).run(rng_step=lt.RNG_STEP)
     rep = lt.aggregate(*report.table(), labels, names, 100)
-    out = run([os.path.join(ROOT, "long-tail-gan_amd", "longtail.py"), ds, ck, "--gate", "0.5", "--gate-candidates", "150", "--critic", "--json", "r.json"])
+    out = run_cli("longtail.py", [ds, ck, "--gate", "0.5", "--gate-candidates", "150", "--critic", "--json", "r.json"], cwd)
     assert out[-6:-2] == lt.report_lines(rep) and out[-2] == lt.gate_line(gate2.stats(), 0.5, 100) and out[-1] == lt.critic_line(crt2.summary(), 100)
     js = json.load(open(os.path.join(cwd, "r.json")))
     assert js["critic"] == dict(crt2.summary(), top=100) and js["all"]["ndcg"] == rep["all"]["ndcg"] and js["all"]["coverage"] == rep["all"]["coverage"]

@@ -5,25 +5,16 @@ reading the diversified lists; the item-sharded recommender (tests/dist_diversif
 child processes.  The reference is tests/diversify_ref.py.
 
 The second test prints its largest pick shortfall and statistic error per case (pytest -s); DESIGN 5.12 records them."""
-import ctypes as C
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import diversify_ref as D
 import neighbors_ref as NR
+from serving_harness import DEV, _pack_dev, _small_engine, _t, askubuntu_run, run_cli, run_ranks
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEV = "cuda:0"
-
-
-def _t(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 def _eq(a, b):
@@ -126,7 +117,6 @@ def real_tables():
     import torch
     import helpers as Hh
     from ltgan.dataset import EvalData
-    from test_gpu_neighbors import _pack_dev, _small_engine
     rng = np.random.default_rng(21)
     eng = _small_engine(I=1001, steps=3)
     img_d = eng.item_pack("decoder", "cosine")
@@ -217,44 +207,18 @@ def test_recommender_with_diversify(I):
 
 @pytest.mark.parametrize("world", [2, 3])
 def test_sharded_recommender_with_diversify(world):
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="2")
-    cmd = ["timeout", "-k", "10", "900", sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
-           "--master-addr", "127.0.0.1", "--master-port", "29671", os.path.join(ROOT, "tests", "dist_diversify_worker.py"), "1001", "230"]
-    out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=1000)      # fresh children only
-    print(out.stdout[-3000:])
-    assert out.returncode == 0 and ("DIVERSIFY_SHARDED_OK world=%d" % world) in out.stdout, out.stdout[-3000:] + out.stderr[-6000:]
+    run_ranks("dist_diversify_worker.py", ["1001", "230"], world, "DIVERSIFY_SHARDED_OK world=%d" % world)
 
 
 def test_clis_on_askubuntu(tmp_path):
     import torch
     from ltgan import data_processing as dp
     from ltgan import recommend as rc
-    from ltgan.dataset import EvalData, count_items, materialize_askubuntu
-    from ltgan.generator import generator_VAECF
-    from ltgan.test import _Counters
-    from ltgan.train import save_checkpoint
+    from ltgan.dataset import EvalData
     from ltgan.trainer import Recommender
-    from test_gpu_neighbors import CONFIG
-    ds = str(tmp_path / "Askubuntu_Sample")
-    materialize_askubuntu(os.path.join(ROOT, "tests", "golden", "askubuntu_raw.npz"), ds)
-    cwd = str(tmp_path / "run")
-    os.makedirs(cwd)
-    open(os.path.join(cwd, "config.ini"), "w").write(CONFIG)
-    n_items = count_items(ds)
-    gen, *_ = generator_VAECF(ds + "/", h_sizes=(100, 150, 250, 300), lr=1e-4, precision="bf16", device=DEV)
-    eng = gen.engine
-    ck = os.path.join(cwd, "model_0.pt")
-    save_checkpoint(ck, eng, _Counters(), 0)
-    tr, te, uid0 = dp.load_tr_te_data(os.path.join(ds, "test_tr.csv"), os.path.join(ds, "test_te.csv"), n_items)
+    ds, cwd, n_items, eng, ck, tr, te, uid0 = askubuntu_run(tmp_path)
 
-    def run(cmd):
-        r = subprocess.run(["timeout", "-k", "10", "600", sys.executable] + cmd, cwd=cwd, capture_output=True, text=True, timeout=700)
-        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-        return r.stdout.strip().splitlines()
-
-    rscript = os.path.join(ROOT, "long-tail-gan_amd", "recommend.py")
-    lscript = os.path.join(ROOT, "long-tail-gan_amd", "longtail.py")
-    out = run([rscript, ds, ck, "--diversify", "0.5", "--out", "div.tsv"])
+    out = run_cli("recommend.py", [ds, ck, "--diversify", "0.5", "--out", "div.tsv"], cwd)
     assert out[-2].startswith("users: %d\tniche_share@100: " % tr.shape[0]) and out[-1].startswith("ils@100: ") and " -> " in out[-1]
     before, after = (float(x) for x in out[-1][len("ils@100: "):].split(" -> "))
     print(out[-1])
@@ -265,10 +229,10 @@ def test_clis_on_askubuntu(tmp_path):
         u, items = line.split("\t")
         items = [int(x) for x in items.split(",")]
         assert int(u) == uid0 + n and len(items) == 100 == len(set(items)) and min(items) >= 0 and max(items) < n_items
-    out = run([lscript, ds, ck, "--diversify", "0.5", "--candidates", "150", "--div-space", "encoder"])
+    out = run_cli("longtail.py", [ds, ck, "--diversify", "0.5", "--candidates", "150", "--div-space", "encoder"], cwd)
     assert out[-1].startswith("ils@100: ") and out[-2].startswith("all\t") and len(out[-2].split("\t")) == 9
     # without the option: the summary of the plain Recommender as the last line, and no other
-    plain = run([rscript, ds, ck, "--out", "plain.tsv"])
+    plain = run_cli("recommend.py", [ds, ck, "--out", "plain.tsv"], cwd)
     ids, _ = Recommender(eng, EvalData(tr, te, eng.device), k=100).run(rng_step=rc.RNG_STEP)
     _, _, niche, _, _ = dp.load_pop_niche_tags(os.path.join(ds, "item2id.txt"), os.path.join(ds, "item_list.txt"),
                                                os.path.join(ds, "niche_items.txt"), n_items)

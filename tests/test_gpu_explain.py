@@ -5,23 +5,15 @@ Recommender(explain=) against ltg_topk + the entry point called by hand, with an
 (tests/dist_explain_worker.py) and recommend.py on Askubuntu_Sample in fresh child processes.  The reference is tests/explain_ref.py."""
 import ctypes as C
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import explain_ref as E
 import neighbors_ref as NR
+from serving_harness import DEV, _nbr_dev, _small_engine, _t, askubuntu_run, run_cli, run_ranks
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEV = "cuda:0"
-
-
-def _t(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 def _eq(a, b):
@@ -82,7 +74,6 @@ def real_lists():
     import torch
     import helpers as Hh
     from ltgan.dataset import EvalData
-    from test_gpu_neighbors import _small_engine
     rng = np.random.default_rng(21)
     eng = _small_engine(I=1001, steps=3)
     img_d = eng.item_pack("decoder", "cosine")
@@ -100,7 +91,6 @@ def real_lists():
 
 
 def test_same_scores_as_item_neighbors(real_lists):
-    from test_gpu_neighbors import _nbr_dev
     img, img_d, ids, indptr, indices = real_lists
     top, r = 100, 3
     gS, gI = _why_dev(img_d, 0, ids, indptr, indices, 0, top, r)
@@ -208,12 +198,7 @@ def test_recommender_with_explain(I):
 # ---------------------------------------------------------------------------------------------- 4. over item shards
 @pytest.mark.parametrize("world", [2, 3])
 def test_sharded_recommender_with_explain(world):
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="2")
-    cmd = ["timeout", "-k", "10", "900", sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
-           "--master-addr", "127.0.0.1", "--master-port", "29691", os.path.join(ROOT, "tests", "dist_explain_worker.py"), "1001", "230"]
-    out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=1000)      # fresh children only
-    print(out.stdout[-3000:])
-    assert out.returncode == 0 and ("EXPLAIN_SHARDED_OK world=%d" % world) in out.stdout, out.stdout[-3000:] + out.stderr[-6000:]
+    run_ranks("dist_explain_worker.py", ["1001", "230"], world, "EXPLAIN_SHARDED_OK world=%d" % world)
 
 
 # ---------------------------------------------------------------------------------------------- 5. the CLI
@@ -221,32 +206,12 @@ def test_cli_on_askubuntu(tmp_path):
     import torch
     from ltgan import data_processing as dp
     from ltgan import recommend as rc
-    from ltgan.dataset import EvalData, count_items, materialize_askubuntu
-    from ltgan.generator import generator_VAECF
-    from ltgan.test import _Counters
-    from ltgan.train import save_checkpoint
+    from ltgan.dataset import EvalData
     from ltgan.trainer import Recommender
-    from test_gpu_neighbors import CONFIG
-    ds = str(tmp_path / "Askubuntu_Sample")
-    materialize_askubuntu(os.path.join(ROOT, "tests", "golden", "askubuntu_raw.npz"), ds)
-    cwd = str(tmp_path / "run")
-    os.makedirs(cwd)
-    open(os.path.join(cwd, "config.ini"), "w").write(CONFIG)
-    n_items = count_items(ds)
-    gen, *_ = generator_VAECF(ds + "/", h_sizes=(100, 150, 250, 300), lr=1e-4, precision="bf16", device=DEV)
-    eng = gen.engine
-    ck = os.path.join(cwd, "model_0.pt")
-    save_checkpoint(ck, eng, _Counters(), 0)
-    tr, te, uid0 = dp.load_tr_te_data(os.path.join(ds, "test_tr.csv"), os.path.join(ds, "test_te.csv"), n_items)
+    ds, cwd, n_items, eng, ck, tr, te, uid0 = askubuntu_run(tmp_path)
     tr = tr.tocsr()
 
-    def run(cmd):
-        r = subprocess.run(["timeout", "-k", "10", "600", sys.executable] + cmd, cwd=cwd, capture_output=True, text=True, timeout=700)
-        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-        return r.stdout.strip().splitlines()
-
-    script = os.path.join(ROOT, "long-tail-gan_amd", "recommend.py")
-    out = run([script, ds, ck, "--explain", "3", "--explain-top", "10", "--why", "why.tsv", "--out", "recs.tsv", "--npz", "recs.npz"])
+    out = run_cli("recommend.py", [ds, ck, "--explain", "3", "--explain-top", "10", "--why", "why.tsv", "--out", "recs.tsv", "--npz", "recs.npz"], cwd)
     assert out[-2].startswith("users: %d\tniche_share@100: " % tr.shape[0]) and out[-1].startswith("why@10: %d entries, " % (10 * tr.shape[0]))
     recs = [line.split("\t")[1].split(",") for line in open(os.path.join(cwd, "recs.tsv")).read().splitlines()]
     lines = open(os.path.join(cwd, "why.tsv")).read().splitlines()
@@ -268,7 +233,7 @@ def test_cli_on_askubuntu(tmp_path):
     assert out[-1] == "why@10: %d entries, %d reasons" % (len(lines), n_reasons)
     # without the option: the summary of the plain Recommender as the last line, the same lists, and no why-file
     os.remove(os.path.join(cwd, "why.tsv"))
-    plain = run([script, ds, ck, "--out", "plain.tsv"])
+    plain = run_cli("recommend.py", [ds, ck, "--out", "plain.tsv"], cwd)
     ids, _ = Recommender(eng, EvalData(tr, te, eng.device), k=100).run(rng_step=rc.RNG_STEP)
     _, _, niche, _, _ = dp.load_pop_niche_tags(os.path.join(ds, "item2id.txt"), os.path.join(ds, "item_list.txt"),
                                                os.path.join(ds, "niche_items.txt"), n_items)

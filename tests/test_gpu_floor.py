@@ -8,17 +8,14 @@ called by hand, with a LongTailReport and an Explain reading the final lists; th
 and both CLIs on Askubuntu_Sample in fresh child processes."""
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import floor_ref as F
+from serving_harness import DEV, _bits, _t, askubuntu_run, run_cli, run_ranks
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEV = "cuda:0"
 
 #         n,    I,    c,    k,  R,  M,  quant, pad_rows | what the reference gives with lse: rounds, lowerings, rows that differ, items short
 SHAPES = [(64, 24, 24, 5, 2, 6, None, 3),                 # a row shorter than a wave                      4,  10, 0.53,  0
@@ -29,15 +26,6 @@ SHAPES = [(64, 24, 24, 5, 2, 6, None, 3),                 # a row shorter than a
           (777, 129, 129, 10, 3, 30, 0.5, 0),             # quantised scores: ties broken by row          11, 472, 0.94,  0
           (3000, 1000, 256, 100, 10, 50, None, 0)]        # a larger split                                 4, 482, 0.92,  0
 BATCH = 4
-
-
-def _t(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 _CASES, _REFS = {}, {}
@@ -321,39 +309,14 @@ def test_recommender_with_floor():
 
 @pytest.mark.parametrize("world", [2, 3])
 def test_sharded_recommender_with_floor(world):
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="2")
-    cmd = ["timeout", "-k", "10", "900", sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
-           "--master-addr", "127.0.0.1", "--master-port", "29676", os.path.join(ROOT, "tests", "dist_floor_worker.py"), "1001", "230"]
-    out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=1000)      # fresh children only
-    print(out.stdout[-3000:])
-    assert out.returncode == 0 and ("FLOOR_SHARDED_OK world=%d" % world) in out.stdout, out.stdout[-3000:] + out.stderr[-6000:]
+    run_ranks("dist_floor_worker.py", ["1001", "230"], world, "FLOOR_SHARDED_OK world=%d" % world)
 
 
 def test_clis_on_askubuntu(tmp_path):
     import torch
-    from ltgan import data_processing as dp
-    from ltgan.dataset import count_items, materialize_askubuntu
-    from ltgan.generator import generator_VAECF
-    from ltgan.test import _Counters
-    from ltgan.train import save_checkpoint
-    from test_gpu_neighbors import CONFIG
-    ds = str(tmp_path / "Askubuntu_Sample")
-    materialize_askubuntu(os.path.join(ROOT, "tests", "golden", "askubuntu_raw.npz"), ds)
-    cwd = str(tmp_path / "run")
-    os.makedirs(cwd)
-    open(os.path.join(cwd, "config.ini"), "w").write(CONFIG)
-    n_items = count_items(ds)
-    gen, *_ = generator_VAECF(ds + "/", h_sizes=(100, 150, 250, 300), lr=1e-4, precision="bf16", device=DEV)
-    ck = os.path.join(cwd, "model_0.pt")
-    save_checkpoint(ck, gen.engine, _Counters(), 0)
-    tr, te, uid0 = dp.load_tr_te_data(os.path.join(ds, "test_tr.csv"), os.path.join(ds, "test_te.csv"), n_items)
+    ds, cwd, n_items, _, ck, tr, te, uid0 = askubuntu_run(tmp_path)
     n_users = tr.shape[0]
     M = max(2, n_users * 100 // n_items)                 # the mean exposure of an item: whatever the model, some items lie below it
-
-    def run(cmd):
-        r = subprocess.run(["timeout", "-k", "10", "600", sys.executable] + cmd, cwd=cwd, capture_output=True, text=True, timeout=700)
-        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-        return r.stdout.strip().splitlines()
 
     def floor_line(line):
         m = re.fullmatch(r"floor@100: (\d+) floor items, (\d+) short of their floor, below the floor (\d+) -> (\d+), (\d+) inserted slots, "
@@ -363,9 +326,7 @@ def test_clis_on_askubuntu(tmp_path):
         assert short <= after <= before <= items and rows <= slots and rows <= n_users and rounds >= 1, line
         return items, short, before, after, slots, rows, rounds
 
-    rscript = os.path.join(ROOT, "long-tail-gan_amd", "recommend.py")
-    lscript = os.path.join(ROOT, "long-tail-gan_amd", "longtail.py")
-    out = run([rscript, ds, ck, "--floor", str(M), "--floor-reserve", "10", "--out", "floor.tsv"])
+    out = run_cli("recommend.py", [ds, ck, "--floor", str(M), "--floor-reserve", "10", "--out", "floor.tsv"], cwd)
     assert out[-2].startswith("users: %d\tniche_share@100: " % n_users)
     print(out[-1])
     items, short, before, after, slots, rows, _ = floor_line(out[-1])
@@ -379,8 +340,8 @@ def test_clis_on_askubuntu(tmp_path):
         assert int(u) == uid0 + n and len(listed) == len(set(listed)) <= 100 and (not listed or (min(listed) >= 0 and max(listed) < n_items))
         np.add.at(hits, listed, 1)
     assert (hits < M).sum() == after
-    out = run([lscript, ds, ck, "--floor", "niche:%d" % M, "--floor-reserve", "5", "--floor-score", "logit", "--floor-candidates", "300",
-               "--groups", "niche"])
+    out = run_cli("longtail.py", [ds, ck, "--floor", "niche:%d" % M, "--floor-reserve", "5", "--floor-score", "logit", "--floor-candidates", "300",
+                                  "--groups", "niche"], cwd)
     print(out[-1])
     assert 1 <= floor_line(out[-1])[0] < n_items           # only the niche items get a floor
     assert out[-2].startswith("all\t") and len(out[-2].split("\t")) == 9

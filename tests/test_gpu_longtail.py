@@ -5,39 +5,18 @@ test.py in fresh child processes."""
 import ctypes as C
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from oracle import ltg_oracle as O
+from serving_harness import DEV, _t, askubuntu_run, run_cli, run_ranks
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEV = "cuda:0"
 
-CONFIG = """[Long-Tail-GAN]
-h0_size = 100
-h1_size = 150
-h2_size = 250
-h3_size = 300
-NUM_EPOCH = 8
-BATCH_SIZE = 100
-DISPLAY_ITER = 50
-LEARNING_RATE = 0.0001
-to_restore = 0
-model_name = LT_GAN
-GANLAMBDA = 1.0
-"""
 # users with at least one held-out item of the group, Askubuntu_Sample's test split (tests/test_longtail_cpu.py derives them)
 USERS_NICHE = {"popular": 9081, "niche": 7835, "all": 10000}
 USERS_POP4 = {"pop0": 9737, "pop1": 4172, "pop2": 2563, "pop3": 1823, "all": 10000}
-
-
-def _t(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 def _csr_dev(rows):
@@ -322,27 +301,11 @@ def test_recommender_with_report_is_evaluator_plus_recommender():
 def test_sharded_report(world):
     # differences seen between the sharded and the unsharded report (one MI355X, gloo, custom:1001, 230 users; the worker prints them
     # as SEEN ...): 0 in every column at 2 and at 3 ranks.  A record; the bound is the 3e-3 of test_gpu_cli.py.
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="2")
-    cmd = ["timeout", "-k", "10", "900", sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
-           "--master-addr", "127.0.0.1", "--master-port", "29651", os.path.join(ROOT, "tests", "dist_longtail_worker.py"), "custom:1001", "230"]
-    out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=1000)      # fresh children only
-    print(out.stdout[-3000:])
-    assert out.returncode == 0 and ("LONGTAIL_SHARDED_OK world=%d" % world) in out.stdout, out.stdout[-3000:] + out.stderr[-6000:]
+    run_ranks("dist_longtail_worker.py", ["custom:1001", "230"], world, "LONGTAIL_SHARDED_OK world=%d" % world)
 
 
-def _askubuntu(tmp_path):
-    from ltgan.dataset import materialize_askubuntu
-    ds = str(tmp_path / "Askubuntu_Sample")
-    materialize_askubuntu(os.path.join(ROOT, "tests", "golden", "askubuntu_raw.npz"), ds)
-    cwd = str(tmp_path / "run")
-    os.makedirs(cwd)
-    open(os.path.join(cwd, "config.ini"), "w").write(CONFIG)
-    return ds, cwd
-
-
-def _parse(stdout):
-    """longtail.py's stdout -> (first line, {name: fields}) ; the report lines are the ones after the NDCG line"""
-    lines = stdout.strip().splitlines()
+def _parse(lines):
+    """longtail.py's stdout lines -> (first line, {name: fields}) ; the report lines are the ones after the NDCG line"""
     at = max(i for i, l in enumerate(lines) if len(l.split("\t")) == 3)
     rows = {}
     for l in lines[at + 1:]:
@@ -351,8 +314,8 @@ def _parse(stdout):
     return lines[at], rows
 
 
-def _check_report(stdout, json_path, users, k):
-    first, rows = _parse(stdout)
+def _check_report(lines, json_path, users, k):
+    first, rows = _parse(lines)
     assert list(rows) == list(users), rows.keys()
     rep = json.load(open(json_path))
     assert rep["k"] == k
@@ -378,35 +341,19 @@ def _check_report(stdout, json_path, users, k):
 
 
 def test_cli_against_test_py(tmp_path):
-    from ltgan.generator import generator_VAECF
-    from ltgan.test import _Counters
-    from ltgan.train import save_checkpoint
-    ds, cwd = _askubuntu(tmp_path)
-    gen, *_ = generator_VAECF(ds + "/", h_sizes=(100, 150, 250, 300), lr=1e-4, precision="bf16", device="cuda:0")
-    ck = os.path.join(cwd, "model_0.pt")
-    save_checkpoint(ck, gen.engine, _Counters(), 0)
-    tscript = os.path.join(ROOT, "long-tail-gan_amd", "test.py")
-    lscript = os.path.join(ROOT, "long-tail-gan_amd", "longtail.py")
-
-    def run(cmd, **kw):
-        r = subprocess.run(["timeout", "-k", "10", "600"] + cmd, cwd=cwd, capture_output=True, text=True, timeout=700, **kw)
-        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-        return r.stdout
-
-    t_last = run([sys.executable, tscript, ds, ck]).strip().splitlines()[-1]
-    first, rows, rep = _check_report(run([sys.executable, lscript, ds, ck, "--json", "niche.json"]), os.path.join(cwd, "niche.json"), USERS_NICHE, 100)
+    ds, cwd, n_items, _, ck, _, _, _ = askubuntu_run(tmp_path, split=None)
+    t_last = run_cli("test.py", [ds, ck], cwd)[-1]
+    first, rows, rep = _check_report(run_cli("longtail.py", [ds, ck, "--json", "niche.json"], cwd), os.path.join(cwd, "niche.json"), USERS_NICHE, 100)
     print("test.py    : %r\nlongtail.py: %r" % (t_last, first))
     assert first == t_last                                                # string-equal: one forward, the same bits, from process to process (held on an MI355X)
     assert (int(rows["popular"][1]), int(rows["niche"][1])) == (103, 897)
-    first4, rows4, rep4 = _check_report(run([sys.executable, lscript, ds, ck, "--groups", "pop:4", "--k", "20", "--json", "pop4.json"]),
+    first4, rows4, rep4 = _check_report(run_cli("longtail.py", [ds, ck, "--groups", "pop:4", "--k", "20", "--json", "pop4.json"], cwd),
                                         os.path.join(cwd, "pop4.json"), USERS_POP4, 20)
     assert first4 == t_last and [int(rows4["pop%d" % g][1]) for g in range(4)] == [250] * 4
     # two ranks (gloo, one GPU), items sharded: users exact, the means within what test_gpu_cli.py allows between sharded and unsharded.
     # Seen on one MI355X (a record, not a bound): NDCG@100 differs by 2.1e-7 (popular), 5.7e-8 (niche), 8.5e-8 (all); both recalls by 0.
-    env = dict(os.environ, LTGAN_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", "29653", lscript, ds, ck, "--json", "niche2.json"]
-    _, rows2, rep2 = _check_report(run(cmd, env=env), os.path.join(cwd, "niche2.json"), USERS_NICHE, 100)
+    _, rows2, rep2 = _check_report(run_cli("longtail.py", [ds, ck, "--json", "niche2.json"], cwd, world=2), os.path.join(cwd, "niche2.json"),
+                                   USERS_NICHE, 100)
     for name in rows:
         d = [abs(float(a) - float(b)) for a, b in zip(rows[name][3:6], rows2[name][3:6])]
         print("sharded - unsharded, %s: %s" % (name, d))

@@ -3,78 +3,19 @@ against numpy's order bit for bit on tables whose scores are exact in fp32 (heav
 within the derived accumulation bound on real-valued tables, ragged slabs merged with ltg_topk_merge against the whole table bit for bit,
 run-to-run identity, and the host layer: ItemNeighbors, similar.py and the item-sharded ShardedItemNeighbors
 (tests/dist_neighbors_worker.py).  The reference is tests/neighbors_ref.py."""
-import ctypes as C
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import neighbors_ref as NR
+from serving_harness import _nbr_dev, _pack_dev, _small_engine, askubuntu_run, run_cli, run_ranks
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-CONFIG = """[Long-Tail-GAN]
-h0_size = 100
-h1_size = 150
-h2_size = 250
-h3_size = 300
-NUM_EPOCH = 8
-BATCH_SIZE = 100
-DISPLAY_ITER = 50
-LEARNING_RATE = 0.0001
-to_restore = 0
-model_name = LT_GAN
-GANLAMBDA = 1.0
-"""
-
-
-def _cfg(cabi, n_items, h=600, item_lo=0, n_glob=0):
-    return cabi.ltg_config(n_items, h, 200, n_items, 100, 150, 250, 300, 0, 0, item_lo, n_glob, 1, 0, 1e-4, 0.9, 0.999, 1e-8, 1)
-
-
-def _pack_dev(W, metric, space="decoder"):
-    """ltg_item_pack on a host table [I, H] float32 -> the image as a device int16 tensor [I, 608]"""
-    import torch
-    from ltgan import _cabi as cabi
-    lib = cabi.load()
-    Wd = torch.from_numpy(np.ascontiguousarray(W, dtype=np.float32)).cuda()
-    I, H = W.shape
-    gen = cabi.ltg_gen_state()
-    gen.p[3 if space == "decoder" else 0] = Wd.data_ptr()
-    img = torch.full((I, 608), 0x5555, dtype=torch.int16, device="cuda")      # (the pad columns must be WRITTEN)
-    rc = lib.ltg_item_pack(C.byref(_cfg(cabi, I, H)), C.byref(gen), cabi.LTG_SPACE[space], cabi.LTG_METRIC[metric], img.data_ptr(),
-                           torch.cuda.current_stream().cuda_stream)
-    assert rc == 0
-    torch.cuda.synchronize()
-    return img
 
 
 def _u16(img):
     return img.cpu().numpy().view(np.uint16)
-
-
-def _nbr_dev(table, q_img, q_gid, k, labels=None, mask=0x1FF, item_lo=0, n_glob=0):
-    """ltg_item_neighbors: table / q_img device int16 images, q_gid host int32, labels host uint8 per GLOBAL id -> host (scores, ids)"""
-    import torch
-    from ltgan import _cabi as cabi
-    lib = cabi.load()
-    I, n = int(table.shape[0]), int(q_img.shape[0])
-    cfg = _cfg(cabi, I, 600, item_lo, n_glob)
-    gid = torch.from_numpy(np.ascontiguousarray(q_gid, dtype=np.int32)).cuda()
-    lab = torch.from_numpy(np.ascontiguousarray(labels, dtype=np.uint8)).cuda() if labels is not None else None
-    need = lib.ltg_item_neighbors_ws_bytes(C.byref(cfg), n, k)
-    assert need > 0
-    ws = torch.empty(need, dtype=torch.uint8, device="cuda")
-    s = torch.full((n, k), 7.0, dtype=torch.float32, device="cuda")
-    i = torch.full((n, k), -7, dtype=torch.int32, device="cuda")
-    rc = lib.ltg_item_neighbors(C.byref(cfg), table.data_ptr(), q_img.data_ptr(), gid.data_ptr(), n, lab.data_ptr() if lab is not None else None,
-                                mask, k, s.data_ptr(), i.data_ptr(), ws.data_ptr(), need, torch.cuda.current_stream().cuda_stream)
-    assert rc == 0
-    torch.cuda.synchronize()
-    return s.cpu().numpy(), i.cpu().numpy()
 
 
 def _eq(a, b):
@@ -99,33 +40,6 @@ def test_item_pack_equals_numpy_bit_for_bit(H, metric):
         assert not got[17].any()
         bad = np.nonzero((got != want).any(1))[0]
         assert bad.size == 0, (space, bad[:10], got[bad[:1]], want[bad[:1]])
-
-
-def _small_engine(I=1024, steps=0, seed=1234, **kw):
-    """an Engine with the reference's initialisation, optionally moved by a few G steps (smoke()'s step on random histories)"""
-    import torch
-    import helpers as Hh
-    from ltgan.engine import CsrRows, Engine, Pairs
-    from oracle import ltg_oracle as O
-    B = 16
-    rng = np.random.default_rng(0)
-    eng = Engine(I, h_sizes=(16, 24, 40, 32), lr=1e-3, precision="bf16", seed=seed, **kw)
-    if not eng.sharded:
-        eng.set_generator(Hh.gen_to_engine(O.init_generator(I, seed=1)))
-    dev = eng.device
-    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    for st in range(steps):
-        X = Hh.random_history(rng, B, I, mean_nnz=9)
-        slot, uptr, rowidx, pos, nu = Hh.csc_view(X)
-        batch = CsrRows(t(X.indptr.astype(np.int32)), t(X.indices.astype(np.int32)), 0, B, slot=t(slot), uptr=t(uptr), rowidx=t(rowidx),
-                        csr_pos=t(pos), n_unique=nu)
-        acts = eng.new_acts(B)
-        rows = np.repeat(np.arange(B, dtype=np.int32), 2)
-        fake = Pairs(t(rng.integers(0, I, 2 * B).astype(np.int32)), t(rng.integers(0, I, 2 * B).astype(np.int32)), t(rows))
-        cnt = torch.tensor([2 * B], dtype=torch.int32, device=dev)
-        eng.g_step(batch, fake, acts, cnt, anneal=0.1, rng_step=3 + 2 * st, d_rng_step=4 + 2 * st)
-    torch.cuda.synchronize()
-    return eng
 
 
 def test_item_pack_of_an_engine_equals_its_shadow_and_numpy():
@@ -348,31 +262,12 @@ def test_item_neighbors_class_large_catalogue_ragged_last_chunk():
         assert np.array_equal(ids[sl], want_i) and _eq(scores[sl], want_s)
 
 
-def _askubuntu(tmp_path):
-    from ltgan.dataset import materialize_askubuntu
-    ds = str(tmp_path / "Askubuntu_Sample")
-    materialize_askubuntu(os.path.join(ROOT, "tests", "golden", "askubuntu_raw.npz"), ds)
-    cwd = str(tmp_path / "run")
-    os.makedirs(cwd)
-    open(os.path.join(cwd, "config.ini"), "w").write(CONFIG)
-    return ds, cwd
-
-
 def test_similar_cli_equals_the_class(tmp_path):
     import torch
     from ltgan import data_processing as dp
     from ltgan import longtail as lt
-    from ltgan.dataset import count_items
-    from ltgan.generator import generator_VAECF
-    from ltgan.test import _Counters
-    from ltgan.train import save_checkpoint
     from ltgan.trainer import ItemNeighbors
-    ds, cwd = _askubuntu(tmp_path)
-    n_items = count_items(ds)
-    gen, *_ = generator_VAECF(ds + "/", h_sizes=(100, 150, 250, 300), lr=1e-4, precision="bf16", device="cuda:0")
-    eng = gen.engine
-    ck = os.path.join(cwd, "model_0.pt")
-    save_checkpoint(ck, eng, _Counters(), 0)
+    ds, cwd, n_items, eng, ck, _, _, _ = askubuntu_run(tmp_path, split=None)
     _, _, niche, _, _ = dp.load_pop_niche_tags(os.path.join(ds, "item2id.txt"), os.path.join(ds, "item_list.txt"),
                                                os.path.join(ds, "niche_items.txt"), n_items)
     labels, names = lt.build_groups(ds, "niche", 2, n_items)
@@ -380,13 +275,9 @@ def test_similar_cli_equals_the_class(tmp_path):
     ids_all, sc_all = ItemNeighbors(eng, k=20).run()
     ids_shelf, _ = ItemNeighbors(eng, k=10, labels=labels, n_groups=2, only=[1]).run(popular)
     torch.cuda.synchronize()
-    script = os.path.join(ROOT, "long-tail-gan_amd", "similar.py")
 
     def cli(*extra):
-        r = subprocess.run(["timeout", "-k", "10", "600", sys.executable, script, ds, ck] + list(extra), cwd=cwd, capture_output=True, text=True,
-                           timeout=700)
-        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-        last = [l for l in r.stdout.strip().splitlines() if l.startswith("items: ")][-1]
+        last = [l for l in run_cli("similar.py", [ds, ck] + list(extra), cwd) if l.startswith("items: ")][-1]
         return dict(x.split(": ") for x in last.split("\t"))
 
     def table(path):
@@ -410,11 +301,7 @@ def test_similar_cli_equals_the_class(tmp_path):
     assert all(row == [i for i in ids_shelf[n].tolist() if i >= 0] for n, (_, row) in enumerate(got))
     assert float(f["niche_share@10"]) == 1.0 and int(f["items"]) == popular.size
     # two ranks (gloo, one GPU), items sharded: the same table bit for bit
-    env = dict(os.environ, LTGAN_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = ["timeout", "-k", "10", "900", sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
-           "--master-addr", "127.0.0.1", "--master-port", "29647", script, ds, ck, "--out", "sim2.tsv", "--npz", "sim2.npz"]
-    r2 = subprocess.run(cmd, cwd=cwd, capture_output=True, text=True, env=env, timeout=1000)
-    assert r2.returncode == 0, r2.stdout[-2000:] + r2.stderr[-4000:]
+    run_cli("similar.py", [ds, ck, "--out", "sim2.tsv", "--npz", "sim2.npz"], cwd, world=2, limit=900)
     z2 = np.load(os.path.join(cwd, "sim2.npz"))
     assert np.array_equal(z2["ids"], ids_all) and _eq(z2["scores"], sc_all)
     assert open(os.path.join(cwd, "sim2.tsv")).read() == open(os.path.join(cwd, "sim.tsv")).read()
@@ -422,8 +309,4 @@ def test_similar_cli_equals_the_class(tmp_path):
 
 @pytest.mark.parametrize("world", [2])
 def test_sharded_item_neighbors(world):
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="2")
-    cmd = ["timeout", "-k", "10", "900", sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
-           "--master-addr", "127.0.0.1", "--master-port", "29649", os.path.join(ROOT, "tests", "dist_neighbors_worker.py"), "5003"]
-    out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=1000)      # fresh children only
-    assert out.returncode == 0 and ("NEIGHBORS_SHARDED_OK world=%d" % world) in out.stdout, out.stdout[-3000:] + out.stderr[-6000:]
+    run_ranks("dist_neighbors_worker.py", ["5003"], world, "NEIGHBORS_SHARDED_OK world=%d" % world)

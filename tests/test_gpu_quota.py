@@ -4,23 +4,15 @@ Recommender(rule=) on the logits of a real forward with a LongTailReport reading
 (tests/dist_quota_worker.py) and both CLIs on Askubuntu_Sample in fresh child processes.  Nothing is recomputed, so there is no tolerance."""
 import ctypes as C
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import quota_ref as Q
-from test_gpu_topk import CONFIG, _csr, _eq, _reference, _rows, _topk_dev
+from serving_harness import DEV, _t, askubuntu_run, run_cli, run_ranks
+from topk_ref import _csr, _eq, _reference, _rows, _topk_dev
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEV = "cuda:0"
-
-
-def _t(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 def _groups_dev(logits, indptr, indices, k, labels, mask, item_lo=0):
@@ -224,46 +216,19 @@ def test_recommender_with_rule_on_forward_logits(I):
 
 @pytest.mark.parametrize("world", [2, 3])
 def test_sharded_recommender_with_rule(world):
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="2")
-    cmd = ["timeout", "-k", "10", "900", sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
-           "--master-addr", "127.0.0.1", "--master-port", "29661", os.path.join(ROOT, "tests", "dist_quota_worker.py"), "custom:1001", "230"]
-    out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=1000)      # fresh children only
-    print(out.stdout[-3000:])
-    assert out.returncode == 0 and ("QUOTA_SHARDED_OK world=%d" % world) in out.stdout, out.stdout[-3000:] + out.stderr[-6000:]
+    run_ranks("dist_quota_worker.py", ["custom:1001", "230"], world, "QUOTA_SHARDED_OK world=%d" % world)
 
 
 def test_clis_on_askubuntu(tmp_path):
     import torch
-    from ltgan import data_processing as dp
     from ltgan import longtail as lt
-    from ltgan.dataset import EvalData, count_items, materialize_askubuntu
-    from ltgan.generator import generator_VAECF
-    from ltgan.test import _Counters
-    from ltgan.train import save_checkpoint
+    from ltgan.dataset import EvalData
     from ltgan.trainer import LongTailReport, Recommender
-    ds = str(tmp_path / "Askubuntu_Sample")
-    materialize_askubuntu(os.path.join(ROOT, "tests", "golden", "askubuntu_raw.npz"), ds)
-    cwd = str(tmp_path / "run")
-    os.makedirs(cwd)
-    open(os.path.join(cwd, "config.ini"), "w").write(CONFIG)
-    n_items = count_items(ds)
-    gen, *_ = generator_VAECF(ds + "/", h_sizes=(100, 150, 250, 300), lr=1e-4, precision="bf16", device=DEV)
-    eng = gen.engine
-    ck = os.path.join(cwd, "model_0.pt")
-    save_checkpoint(ck, eng, _Counters(), 0)
-    tr, te, uid0 = dp.load_tr_te_data(os.path.join(ds, "test_tr.csv"), os.path.join(ds, "test_te.csv"), n_items)
+    ds, cwd, n_items, eng, ck, tr, te, uid0 = askubuntu_run(tmp_path)
     labels, names = lt.build_groups(ds, "pop", 4, n_items)
     assert names[3] == "pop3" and _n_eligible(tr.tocsr(), labels, 3).min() >= 30        # the minimum this test relies on
-
-    def run(cmd):
-        r = subprocess.run(["timeout", "-k", "10", "600", sys.executable] + cmd, cwd=cwd, capture_output=True, text=True, timeout=700)
-        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-        return r.stdout
-
-    rscript = os.path.join(ROOT, "long-tail-gan_amd", "recommend.py")
-    lscript = os.path.join(ROOT, "long-tail-gan_amd", "longtail.py")
-    out = run([rscript, ds, ck, "--groups", "pop:4", "--min-slots", "pop3:30", "--out", "ruled.tsv"])
-    assert out.strip().splitlines()[-1].startswith("users: %d\tniche_share@100: " % tr.shape[0])
+    out = run_cli("recommend.py", [ds, ck, "--groups", "pop:4", "--min-slots", "pop3:30", "--out", "ruled.tsv"], cwd)
+    assert out[-1].startswith("users: %d\tniche_share@100: " % tr.shape[0])
     lines = open(os.path.join(cwd, "ruled.tsv")).read().splitlines()
     assert len(lines) == tr.shape[0]
     least = 100
@@ -275,12 +240,12 @@ def test_clis_on_askubuntu(tmp_path):
     print("fewest pop3 items in a list: %d" % least)
     assert least >= 30
     # longtail.py: the pop3 row's share@100 under the rule; without --min-slots today's lines, those of Recommender(report=) without a rule
-    ruled = run([lscript, ds, ck, "--groups", "pop:4", "--min-slots", "pop3:30"]).strip().splitlines()[-6:]
+    ruled = run_cli("longtail.py", [ds, ck, "--groups", "pop:4", "--min-slots", "pop3:30"], cwd)[-6:]
     pop3 = [l.split("\t") for l in ruled if l.startswith("pop3\t")][0]
     print("pop3 under the rule: %s" % pop3)
     assert len(pop3) == 8 and float(pop3[6]) >= 0.30
     assert len(ruled[0].split("\t")) == 3 and ruled[-1].startswith("all\t") and len(ruled[-1].split("\t")) == 9
-    plain = run([lscript, ds, ck, "--groups", "pop:4"]).strip().splitlines()[-6:]
+    plain = run_cli("longtail.py", [ds, ck, "--groups", "pop:4"], cwd)[-6:]
     rep = LongTailReport(labels, 4, k_exp=100)
     Recommender(eng, EvalData(tr, te, eng.device), k=rep.k, report=rep).run(rng_step=2 * 10 ** 9)
     want = lt.report_lines(lt.aggregate(*rep.table(), labels, names, 100))

@@ -6,8 +6,9 @@ import sys
 
 import pytest
 
+from serving_harness import ROOT, run_ranks
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.mark.parametrize("workload,users,precision,mode", [("custom:1000", 250, "fp32", ""), ("ml20m", 200, "fp32", ""), ("ml20m", 200, "bf16", ""),
@@ -23,14 +24,11 @@ def test_two_rank_item_sharding_matches_unsharded(workload, users, precision, mo
     issued from inside it (ltg_g_step_sharded; here through host callbacks over gloo); "cutpoints": the five-call sequence with
     torch.distributed collectives instead.  ("c4", 200 users): BASELINE config 4's 200 000 items, 100 000 per rank.  "tail_own": the Adam tail on the pipe's third stream
     (LTG_PIPE_TAIL_OWN; the default keeps it on the caller's stream)."""
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
+    env = {"OMP_NUM_THREADS": None}                      # (the ranks' thread count as this process has it)
     if mode == "tail_own":
         env["LTGAN_PIPE_FLAGS"] = "128"
         mode = ""
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", "29577", os.path.join(ROOT, "tests", "dist_shard_worker.py"), workload, str(users), precision] + ([mode] if mode else [])
-    out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900)
-    assert out.returncode == 0 and "SHARDED_OK" in out.stdout, out.stdout[-3000:] + out.stderr[-6000:]
+    run_ranks("dist_shard_worker.py", [workload, users, precision] + ([mode] if mode else []), 2, "SHARDED_OK", env=env)
 
 
 @pytest.mark.parametrize("workload,users,precision,mode", [("custom:99904", 200, "bf16", ""), ("custom:99904", 200, "bf16", "wide_fp8_full"),
@@ -43,11 +41,7 @@ def test_four_rank_item_sharding_matches_unsharded(workload, users, precision, m
     slabs, below the one-call step's 8 192 -- every rank agrees on the cut-point sequence (the worker asserts which path ran).
     custom:32896: three slabs of 8 256 items and a last one of 8 128 < 8 192 -- ONE rank's slab is too small for the one-call step, so all
     four must agree on the cut-point sequence (`ShardedTrainer._init_sharded_step`)."""
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="2")
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr", "127.0.0.1",
-           "--master-port", "29587", os.path.join(ROOT, "tests", "dist_shard_worker.py"), workload, str(users), precision] + ([mode] if mode else [])
-    out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=1500)      # fresh children only
-    assert out.returncode == 0 and "SHARDED_OK world=4" in out.stdout, out.stdout[-3000:] + out.stderr[-6000:]
+    run_ranks("dist_shard_worker.py", [workload, users, precision] + ([mode] if mode else []), 4, "SHARDED_OK world=4", limit=1500)
 
 
 @pytest.mark.parametrize("world,workload,users", [(2, "c4", 200), (4, "custom:99904", 200)])
@@ -58,28 +52,22 @@ def test_one_shot_exchange_equals_the_rank_ordered_host_transport(world, workloa
     generator tensor and Adam moment -- at world sizes 2 and 4 (c4: 100 000-item slabs / custom:99904: three slabs of 25 024 items and one of
     24 832, the slabs and message sizes of an 8-rank run of c4).
     Correctness only: RCCL stays the transport of every measurement."""
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="2", LTGAN_ONESHOT_LIMIT_MS="20000")
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
-           "--master-port", "29583", os.path.join(ROOT, "tests", "dist_oneshot_worker.py"), workload, str(users)]
-    out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=1500)      # fresh children only
-    assert out.returncode == 0 and ("ONESHOT_OK world=%d" % world) in out.stdout, out.stdout[-3000:] + out.stderr[-6000:]
+    run_ranks("dist_oneshot_worker.py", [workload, users], world, "ONESHOT_OK world=%d" % world, limit=1500, env={"LTGAN_ONESHOT_LIMIT_MS": "20000"})
 
 
 def test_one_shot_exchange_gives_up_and_raises_when_a_peer_never_sends():
     """The one-shot transport's device-side waits are bounded (ltg_oneshot.limit_ms): with a peer that sits out the G phase every exchange of the
     other rank gives up after its bound, counts it in the stage, and the phase ends in an LtgError (ShardedTrainer.g_phase) -- a forced expiry,
     not a hang."""
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="2", LTGAN_ONESHOT_LIMIT_MS="40")
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", "29585", os.path.join(ROOT, "tests", "dist_oneshot_worker.py"), "c4", "200", "expiry"]
-    out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900)
-    assert out.returncode == 0 and "ONESHOT_EXPIRY_OK world=2" in out.stdout, out.stdout[-3000:] + out.stderr[-6000:]
+    run_ranks("dist_oneshot_worker.py", ["c4", "200", "expiry"], 2, "ONESHOT_EXPIRY_OK world=2", env={"LTGAN_ONESHOT_LIMIT_MS": "40"})
 
 
 def test_direct_rccl_transport_of_the_one_call_step_at_world_size_one():
-    """The transport a GPU node uses: RCCL bound directly, its entry points called by the library in-stream (tests/dist_rccl_worker.py)."""
+    """The transport a GPU node uses: RCCL bound directly, its entry points called by the library in-stream (tests/dist_rccl_worker.py).
+    One process that opens its own one-rank group: not a rank launch, so it stays a plain child."""
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "dist_rccl_worker.py")], capture_output=True, text=True, env=env, timeout=900)
+    out = subprocess.run(["timeout", "-k", "10", "900", sys.executable, os.path.join(ROOT, "tests", "dist_rccl_worker.py")], capture_output=True,
+                         text=True, env=env, timeout=1000)
     assert out.returncode == 0 and "RCCL_DIRECT_OK" in out.stdout, out.stdout[-3000:] + out.stderr[-6000:]
 
 
@@ -92,8 +80,6 @@ def test_two_ranks_on_two_gpus_over_rccl(workload, users, mode):
     import torch
     if torch.cuda.device_count() < 2:
         pytest.skip("needs two GPUs (this box has %d)" % torch.cuda.device_count())
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0", LTGAN_TEST_BACKEND="nccl")
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", "29579", os.path.join(ROOT, "tests", "dist_shard_worker.py"), workload, str(users), "bf16"] + ([mode] if mode else [])
-    out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=1200)      # fresh children: this process never hands its GPU state on
-    assert out.returncode == 0 and "SHARDED_OK" in out.stdout and "transport=rccl-direct" in out.stdout, out.stdout[-3000:] + out.stderr[-6000:]
+    out = run_ranks("dist_shard_worker.py", [workload, users, "bf16"] + ([mode] if mode else []), 2, "SHARDED_OK", limit=1200,
+                    env={"LTGAN_TEST_BACKEND": "nccl", "OMP_NUM_THREADS": None})
+    assert "transport=rccl-direct" in out

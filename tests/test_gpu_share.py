@@ -8,17 +8,14 @@ final lists; the item-sharded recommender (tests/dist_share_worker.py) and both 
 import ctypes
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import share_ref as S
+from serving_harness import DEV, _bits, _t, askubuntu_run, run_cli, run_ranks
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEV = "cuda:0"
 
 #        n,    I,    k,    c,  share, quant
 SHAPES = [(64, 40, 5, 40, 0.3, None),                     # a row shorter than a wave
@@ -28,15 +25,6 @@ SHAPES = [(64, 40, 5, 40, 0.3, None),                     # a row shorter than a
           (130, 70, 33, 70, 0.6, None),                   # k off the wave size
           (1500, 300, 100, 200, 0.4, None),               # 150 000 words over many workgroups
           (3000, 1000, 100, 400, 0.3, None)]              # the largest case
-
-
-def _t(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 _CASES = {}
@@ -308,41 +296,16 @@ def test_recommender_with_share(I):
 
 @pytest.mark.parametrize("world", [2, 3])
 def test_sharded_recommender_with_share(world):
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="2")
-    cmd = ["timeout", "-k", "10", "900", sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
-           "--master-addr", "127.0.0.1", "--master-port", "29675", os.path.join(ROOT, "tests", "dist_share_worker.py"), "1001", "230"]
-    out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=1000)      # fresh children only
-    print(out.stdout[-3000:])
-    assert out.returncode == 0 and ("SHARE_SHARDED_OK world=%d" % world) in out.stdout, out.stdout[-3000:] + out.stderr[-6000:]
+    run_ranks("dist_share_worker.py", ["1001", "230"], world, "SHARE_SHARDED_OK world=%d" % world)
 
 
 def test_clis_on_askubuntu(tmp_path):
     import torch
-    from ltgan import data_processing as dp
     from ltgan import longtail as lt
-    from ltgan.dataset import count_items, materialize_askubuntu
-    from ltgan.generator import generator_VAECF
-    from ltgan.test import _Counters
-    from ltgan.train import save_checkpoint
-    from test_gpu_neighbors import CONFIG
-    ds = str(tmp_path / "Askubuntu_Sample")
-    materialize_askubuntu(os.path.join(ROOT, "tests", "golden", "askubuntu_raw.npz"), ds)
-    cwd = str(tmp_path / "run")
-    os.makedirs(cwd)
-    open(os.path.join(cwd, "config.ini"), "w").write(CONFIG)
-    n_items = count_items(ds)
-    gen, *_ = generator_VAECF(ds + "/", h_sizes=(100, 150, 250, 300), lr=1e-4, precision="bf16", device=DEV)
-    ck = os.path.join(cwd, "model_0.pt")
-    save_checkpoint(ck, gen.engine, _Counters(), 0)
-    tr, te, uid0 = dp.load_tr_te_data(os.path.join(ds, "test_tr.csv"), os.path.join(ds, "test_te.csv"), n_items)
+    ds, cwd, n_items, _, ck, tr, te, uid0 = askubuntu_run(tmp_path)
     n_users = tr.shape[0]
     labels, names = lt.build_groups(ds, "niche", 2, n_items)
     assert names[1] == "niche"
-
-    def run(cmd):
-        r = subprocess.run(["timeout", "-k", "10", "600", sys.executable] + cmd, cwd=cwd, capture_output=True, text=True, timeout=700)
-        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-        return r.stdout.strip().splitlines()
 
     def share_line(line):
         m = re.fullmatch(r"share@100: (\S+) (\d\.\d{6}) -> (\d\.\d{6}) \(target (\d\.\d{6})\), (\d+) rows changed, price (\S+)", line)
@@ -361,15 +324,13 @@ def test_clis_on_askubuntu(tmp_path):
             niche += int((labels[items] == 1).sum())
         return niche / slots
 
-    rscript = os.path.join(ROOT, "long-tail-gan_amd", "recommend.py")
-    lscript = os.path.join(ROOT, "long-tail-gan_amd", "longtail.py")
-    out = run([rscript, ds, ck, "--share", "niche:0", "--out", "plain.tsv"])             # the plain lists: where the share stands
+    out = run_cli("recommend.py", [ds, ck, "--share", "niche:0", "--out", "plain.tsv"], cwd)     # the plain lists: where the share stands
     print(out[-1])
     name, before, after, target, changed, price = share_line(out[-1])
     assert (name, after, target, changed, price) == ("niche", before, 0.0, 0, 0.0)
     assert "%.6f" % tsv_share(os.path.join(cwd, "plain.tsv")) == "%.6f" % before
     goal = min(1.0, round(before + 0.1, 3))              # ten points more of every slot for the niche items
-    out = run([rscript, ds, ck, "--share", "niche:%.3f" % goal, "--out", "share.tsv"])
+    out = run_cli("recommend.py", [ds, ck, "--share", "niche:%.3f" % goal, "--out", "share.tsv"], cwd)
     assert out[-2].startswith("users: %d\tniche_share@100: " % n_users)
     print(out[-1])
     name, before2, after, target, changed, price = share_line(out[-1])
@@ -377,7 +338,7 @@ def test_clis_on_askubuntu(tmp_path):
     reached = "%.6f" % tsv_share(os.path.join(cwd, "share.tsv"))
     assert reached == "%.6f" % after                     # the line reports what the TSV holds
     assert after >= target and changed > 0 and price > 0   # the niche items of this catalogue can fill the target: it is reached
-    out = run([lscript, ds, ck, "--share", "niche:%.3f" % goal, "--groups", "niche"])
+    out = run_cli("longtail.py", [ds, ck, "--share", "niche:%.3f" % goal, "--groups", "niche"], cwd)
     print(out[-1])
     assert share_line(out[-1]) == (name, before, after, target, changed, price)           # the same lists, whichever CLI serves them
     assert out[-2].startswith("all\t") and len(out[-2].split("\t")) == 9

@@ -222,7 +222,7 @@ def test_greedy_walk_and_composition_from_lists_agree():
 
 
 def test_masked_lists_reference_is_the_plain_reference_under_the_full_mask():
-    from test_gpu_topk import _eq, _reference, _rows
+    from topk_ref import _eq, _reference, _rows
     rng = np.random.default_rng(3)
     L, folds = _rows(rng, 300, 40)
     labels = rng.integers(0, 12, 300 + 17).astype(np.uint8)

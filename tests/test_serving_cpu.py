@@ -7,11 +7,7 @@ diversified, calibrated, capped, floored (both by log-probability and by the log
 the lists and alone, k = 0), each without and with a report and / or explanations -- for the rules over the whole split the second pass
 after the match --, item-sharded and not; the full-row lse is combined exactly where something ranks by log-probability.  No two rules
 go together, and k = 0 goes with nothing that needs lists."""
-import os
-import subprocess
-import sys
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from serving_harness import run_ranks
 
 
 def test_unsharded_lists_are_written_directly_and_the_calls_are_the_direct_ones():
@@ -20,9 +16,5 @@ def test_unsharded_lists_are_written_directly_and_the_calls_are_the_direct_ones(
 
 
 def test_world_size_two_lists_and_call_sequences():
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="1")
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", "29641", os.path.join(ROOT, "tests", "serving_cpu_worker.py")]
-    out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600)
-    assert out.returncode == 0 and "SERVING_CPU_OK" in out.stdout, out.stdout[-2000:] + out.stderr[-4000:]
+    run_ranks("serving_cpu_worker.py", [], 2, "SERVING_CPU_OK", limit=600, env={"OMP_NUM_THREADS": "1"})
 

@@ -529,6 +529,62 @@ int ltg_g_step_sharded_plan(const ltg_config* cfg, const ltg_gen_state* gen, con
 int ltg_g_step_sharded(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_disc_state* disc, const ltg_batch* batch,
                        const ltg_pairs* fake, const ltg_g_opts* opts, const ltg_gen_acts* acts, const ltg_comm* comm,
                        const ltg_pipe* pipe, float* loss_out, void* ws, size_t ws_bytes, ltg_stream stream);
+
+/* ---- kernel routes (additive in ABI v14).  Which kernels a call with this configuration, this state and this many rows runs: the library decides it
+ * once per call, in one place (csrc/ltg_kernels.hip: g_route / d_route), and every stage switches on the result.  The two queries below
+ * hand that decision out, so that a test can say which route a shape reaches.  Host-only: they look at the PRESENCE of the pointers in
+ * the structs they are handed (and, for the Adam sweep, at whether the tensors lie back to back) and dereference none of them; 1 = *out
+ * is filled, 0 = the configuration is refused (or an argument is missing). */
+enum { LTG_ENC0_GENERIC = 0, LTG_ENC0_FAST };                   /* k_enc0_fwd | fk_enc0_fwd */
+enum { LTG_MID_DENSE = 0, LTG_MID_FAST };                       /* k_dense_fwd pair (+ k_reparam; backward: five launches) | fk_enc1 / fk_dec0 (backward: fk_g_tail jobs) */
+enum { LTG_DEC_TILE = 0, LTG_DEC_SMALL, LTG_DEC_STREAM1, LTG_DEC_STREAM2 };   /* k_dec1_fwd | fk_dec1 | k_dec1_fwd_stream | k_dec1_fwd_stream2 */
+enum { LTG_STATS_ROW = 0, LTG_STATS_SEGMENT, LTG_STATS_EPILOGUE };            /* k_row_lse / k_row_partial | segment pass | the streaming decoder's epilogue */
+enum { LTG_LOSS_GENERIC = 0, LTG_LOSS_COMBINE, LTG_LOSS_ROW };  /* k_g_combine + k_dlogits | k_dlogits_combine | fk_row_dlogits (small slab) */
+enum { LTG_DH2_PARTIAL = 0, LTG_DH2_SMALL, LTG_DH2_STREAM };    /* k_dh2_partial | fk_dh2 | k_dh2_stream */
+enum { LTG_DW_TILE = 0, LTG_DW_TAIL_JOB, LTG_DW_STREAM };       /* k_dec1_bwd_adam | a job of fk_g_tail (small slab) | k_dec1_bwd_adam_stream */
+enum { LTG_Q0_DENSE = 0, LTG_Q0_SWEEP, LTG_Q0_LAZY };           /* dense product in the tail | slot-map sweep | lazy clock */
+typedef struct ltg_g_route_info {
+    int32_t enc0;        /* LTG_ENC0_* */
+    int32_t small;       /* 1: the small-slab step (one launch per stage, dense enc-0 operand rows) */
+    int32_t mid;         /* LTG_MID_*: middle layers forward, and the backward chain behind dh2 */
+    int32_t mid_vec;     /* LTG_MID_DENSE: 16-byte loaders */
+    int32_t dec;         /* LTG_DEC_* */
+    int32_t dec_tile;    /* LTG_DEC_TILE: 128 = 64 x 128 tiles, 32 = 32 x 32 */
+    int32_t stats;       /* LTG_STATS_*, given scratch for them (without: LTG_STATS_ROW) */
+    int32_t seg_pass;    /* 1: the slab is long enough for the segment pass (forward-only calls ask for scratch only then) */
+    int32_t loss;        /* LTG_LOSS_* */
+    int32_t dlog_bf16;   /* 1: dlogits stored as bf16 (producer and both consumers read this one field) */
+    int32_t dh2;         /* LTG_DH2_* */
+    int32_t dh2_tile;    /* LTG_DH2_PARTIAL: 128 = 64 x 128 tiles, -32 = 32 x 32 with 16-byte loads, 32 = 32 x 32 */
+    int32_t dh2_chunk;   /* items per partial slab, and how many of them */
+    int32_t dh2_nsplit;
+    int32_t dw;          /* LTG_DW_* */
+    int32_t dw_tile;     /* LTG_DW_TILE: 64, -32 (16-byte loads), 32 */
+    int32_t dw_ragged;   /* 1: LTG_DW_STREAM with the generic tile kernel on the last n_items % 32 rows */
+    int32_t q0;          /* LTG_Q0_* */
+    int32_t q0_own_launch; /* 1: the W_q0 update is a launch of its own, not a job of the tail */
+    int32_t grad_rows;   /* 1: the sparse W_q0 gradient one wave per row (0: column-blocked) */
+    int32_t sharded_ok;  /* 1: ltg_g_step_sharded serves this (= ltg_g_step_sharded_ok) */
+} ltg_g_route_info;
+int ltg_g_route(const ltg_config* cfg, const ltg_gen_state* gen, int32_t n_rows, ltg_g_route_info* out);
+
+enum { LTG_D_GENERIC = 0,    /* k_d_*<mode> */
+       LTG_D_TOWER,          /* forward only: the one-kernel tower */
+       LTG_D_STAGED_FWD,     /* forward only: fks_d_l1 -> fks_d_l2 -> fk_d_y */
+       LTG_D_FAST,           /* fk_d_* */
+       LTG_D_FP8_OPFMT,      /* fp8, every operand in operand format (the step) */
+       LTG_D_FP8_STAGED,     /* fp8 LDS-staged forward (+ generic backward) */
+       LTG_D_FP8_REG };      /* fp8 register-block forward (+ generic backward) */
+enum { LTG_D_ADAM_TENSORS = 0, LTG_D_ADAM_FLAT, LTG_D_ADAM_FP8 };   /* k_d_adam | fk_d_adam | k8_d_adam */
+typedef struct ltg_d_route_info {
+    int32_t kind;        /* LTG_D_* */
+    int32_t mode;        /* template mode of the generic kernels: 0 fp32, 1 bf16, 2 fp8 */
+    int32_t tile[4];     /* generic kernels l1, l2, bwd1, bwd2: 128 / 64 / -32 (32 x 32, 16-byte loads) / -33 (on operand A only) / 32 */
+    int32_t spl[4];      /* LTG_D_FAST: bf16 terms per product of fk_d_l1, fk_d_l2, fk_d_bwd1, fk_d_bwd2 (0 = fp32 MFMA) */
+    int32_t adam;        /* LTG_D_ADAM_*: the step's sweep */
+    int32_t fork;        /* 1: jobs B / C of the backward run on the aux stream */
+} ltg_d_route_info;
+int ltg_d_route(const ltg_config* cfg, const ltg_disc_state* disc, int32_t n_pairs, int32_t with_bwd, int32_t has_aux, ltg_d_route_info* out);
 /* 1: `stream` and pipe->side_stream (and pipe->tail_stream, and those two with each other) run concurrently (a waiter on one does not hold
  * up the other), as the device-word hand-over needs;
  * 0: they share a hardware queue (HIP maps streams onto a few of them) -- use another side stream, or LTG_PIPE_EVENTS; < 0: error.

@@ -118,6 +118,28 @@ class ltg_pipe(C.Structure):
                 ("q0_mark", vp), ("next_uitem", vp), ("next_nu", C.c_int32), ("caught_up", C.c_int32), ("shadow_out", vp)]
 
 
+# kernel routes (include/ltg.h: ltg_g_route / ltg_d_route); the enumerators in the header's order
+LTG_ENC0_GENERIC, LTG_ENC0_FAST = 0, 1
+LTG_MID_DENSE, LTG_MID_FAST = 0, 1
+LTG_DEC_TILE, LTG_DEC_SMALL, LTG_DEC_STREAM1, LTG_DEC_STREAM2 = 0, 1, 2, 3
+LTG_STATS_ROW, LTG_STATS_SEGMENT, LTG_STATS_EPILOGUE = 0, 1, 2
+LTG_LOSS_GENERIC, LTG_LOSS_COMBINE, LTG_LOSS_ROW = 0, 1, 2
+LTG_DH2_PARTIAL, LTG_DH2_SMALL, LTG_DH2_STREAM = 0, 1, 2
+LTG_DW_TILE, LTG_DW_TAIL_JOB, LTG_DW_STREAM = 0, 1, 2
+LTG_Q0_DENSE, LTG_Q0_SWEEP, LTG_Q0_LAZY = 0, 1, 2
+LTG_D_GENERIC, LTG_D_TOWER, LTG_D_STAGED_FWD, LTG_D_FAST, LTG_D_FP8_OPFMT, LTG_D_FP8_STAGED, LTG_D_FP8_REG = 0, 1, 2, 3, 4, 5, 6
+LTG_D_ADAM_TENSORS, LTG_D_ADAM_FLAT, LTG_D_ADAM_FP8 = 0, 1, 2
+
+
+class ltg_g_route_info(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("enc0", "small", "mid", "mid_vec", "dec", "dec_tile", "stats", "seg_pass", "loss", "dlog_bf16", "dh2", "dh2_tile",
+                                         "dh2_chunk", "dh2_nsplit", "dw", "dw_tile", "dw_ragged", "q0", "q0_own_launch", "grad_rows", "sharded_ok")]
+
+
+class ltg_d_route_info(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("mode", C.c_int32), ("tile", C.c_int32 * 4), ("spl", C.c_int32 * 4), ("adam", C.c_int32), ("fork", C.c_int32)]
+
+
 LTG_ONESHOT_MAX_RANKS = 16
 
 
@@ -134,6 +156,8 @@ SYMBOLS = {
     "ltg_oneshot_all_gather": (C.c_int, [vp, vp, C.c_size_t, C.c_int, vp, vp]),
     "ltg_g_step_sharded_ok": (C.c_int, [C.POINTER(ltg_config), C.POINTER(ltg_gen_state), C.c_int32]),
     "ltg_g_step_sharded_plan": (C.c_int, [C.POINTER(ltg_config), C.POINTER(ltg_gen_state), C.POINTER(ltg_batch), C.POINTER(ltg_pipe)]),
+    "ltg_g_route": (C.c_int, [C.POINTER(ltg_config), C.POINTER(ltg_gen_state), C.c_int32, C.POINTER(ltg_g_route_info)]),
+    "ltg_d_route": (C.c_int, [C.POINTER(ltg_config), C.POINTER(ltg_disc_state), C.c_int32, C.c_int32, C.c_int32, C.POINTER(ltg_d_route_info)]),
     "ltg_g_step_sharded": (C.c_int, [C.POINTER(ltg_config), C.POINTER(ltg_gen_state), C.POINTER(ltg_disc_state), C.POINTER(ltg_batch),
                                      C.POINTER(ltg_pairs), C.POINTER(ltg_g_opts), C.POINTER(ltg_gen_acts), C.POINTER(ltg_comm),
                                      C.POINTER(ltg_pipe), vp, vp, C.c_size_t, vp]),

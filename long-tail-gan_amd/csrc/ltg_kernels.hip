@@ -2,6 +2,7 @@
 // gfx950 only.  Reference citations are relative to /root/reference/.
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <algorithm>
 #include <stdint.h>
 
 #include "../../include/ltg.h"
@@ -189,30 +190,33 @@ __global__ __launch_bounds__(64) void k_gate_set(LtgGate g, LtgGate g2 = LTG_NO_
 // ---------------------------------------------------------------------------------------------
 inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 
-// the streaming decoder kernels: bf16, large item slab, a training batch (<= 128 rows), H <= 608, 16-B aligned rows
-inline bool stream_ok(const ltg_config* cfg, const ltg_gen_state* gen, int rows) {
-    return gen->wp1t_bf16 && cfg->precision == LTG_PREC_BF16 && cfg->n_items >= 8192 && (cfg->n_items % 8) == 0 && rows <= 128 && cfg->h_enc <= ST_KP &&
-           (cfg->h_enc % 4) == 0;
-}
-// k_dec1_bwd_adam_stream walks the 4 H/4 float4 a wave owns per tile as exactly ten 64-lane accesses
-inline bool dw_stream_ok(int H) { return (H % 4) == 0 && H > 576 && H <= 640; }
-constexpr int DH2_NH = 2;   // column halves of the streaming dh2 product (k_dh2_stream<.., NH>)
-inline int dh2_stream_chunk1(int I);
-inline int dh2_stream_chunk(int I) { return DH2_NH * dh2_stream_chunk1(I); }
-inline int dh2_stream_chunk1(int I) {
-    // items per workgroup of k_dh2_stream = one partial [B][H] slab each: up to 256 workgroups, but at least 4 tiles per
-    // workgroup -- at 20 000 items 157 slabs instead of 209 (each slab is 240 KB written and read once more by k_da2)
-    int c = (I + 255) / 256;
-    c = (c + ST_BN - 1) / ST_BN * ST_BN;
-    return c < 4 * ST_BN ? 4 * ST_BN : c;
-}
+// Which of the round-2 latency-path kernels (ltg_fast.h) apply.  Tuning-knob bit 18 of ltg_config.tuning switches all of
+// them off (the round-1 kernels compute the same function; kept for A/B measurements and as the path of unusual sizes).
+inline bool fast_on(const ltg_config* c) { return (c->tuning & (1 << 18)) == 0; }
+// the wide discriminator (BASELINE config 5's shape): its GEMMs are throughput-bound, the generic kernels' large tiles serve it
+inline bool d_wide(const ltg_config* c) { return c->d_h0 >= 512 && c->d_h1 + c->d_h2 >= 512 && c->d_h3 >= 128; }
 
-inline int dh2_kchunk(int I) {
-    // split the item dimension so that ~128 workgroups x (H/64) share the reduction
-    int chunk = (I + 63) / 64;
-    chunk = (chunk + 31) / 32 * 32;
-    if (chunk < 256) chunk = 256;
-    return chunk;
+constexpr int DH2_NH = 2;   // column halves of the streaming dh2 product (k_dh2_stream<.., NH>)
+// The item dimension of the dh2 product cut into partial [B][H] slabs (summed by k_da2): items per slab and their number.  The route of
+// a step (g_route) and the workspace (carve) both take it from here.
+struct Dh2Split {
+    int chunk, nsplit;
+};
+inline Dh2Split dh2_split(int I, bool stream) {
+    int c;
+    if (stream) {
+        // items per workgroup of k_dh2_stream = one partial [B][H] slab each: up to 256 workgroups, but at least 4 tiles per
+        // workgroup -- at 20 000 items 157 slabs instead of 209 (each slab is 240 KB written and read once more by k_da2)
+        c = (I + 255) / 256;
+        c = (c + ST_BN - 1) / ST_BN * ST_BN;
+        c = DH2_NH * (c < 4 * ST_BN ? 4 * ST_BN : c);
+    } else {
+        // split the item dimension so that ~128 workgroups x (H/64) share the reduction
+        c = (I + 63) / 64;
+        c = (c + 31) / 32 * 32;
+        if (c < 256) c = 256;
+    }
+    return Dh2Split{c, (I + c - 1) / c};
 }
 
 // rows of the sparse W_q0 gradient = distinct items of a batch <= min(n_items, nnz of the batch).  The workspace is sized
@@ -254,7 +258,7 @@ inline size_t ft_wsp_bytes(int h0, int h1, int h2, int h3) { return ft_wsp_tripl
 // registers), h3 <= 320 (five 16-column tiles per wave column) and A1 [64][h1 + h2] within the LDS.  The choice depends on the layer sizes and
 // d_arith only, so the tower inside a step and the batched tower run the same kernel and produce the same bits.
 inline bool ft_wsp_capable(const ltg_config* c) {
-    return (c->tuning & 262144) == 0 && c->d_precision == LTG_PREC_FP32 && !(c->d_h0 >= 512 && c->d_h1 + c->d_h2 >= 512 && c->d_h3 >= 128) && c->d_h0 >= 4 &&
+    return fast_on(c) && c->d_precision == LTG_PREC_FP32 && !d_wide(c) && c->d_h0 >= 4 &&
            c->d_h0 <= 32 * FT_KP1_MAX && (c->d_h0 % 4) == 0 && c->d_h1 >= 1 && c->d_h2 >= 1 && c->d_h3 >= 1 && c->d_h3 <= 320 &&
            ft_lds_bytes(c->d_h1 + c->d_h2) <= (size_t)160 * 1024;
 }
@@ -268,12 +272,8 @@ Workspace carve(const ltg_config* cfg, int max_rows, int max_pairs, char* base) 
     };
     const size_t R = (size_t)max_rows, I = (size_t)cfg->n_items, H = (size_t)cfg->h_enc, Z = (size_t)cfg->z_dim;
     const size_t P = (size_t)max_pairs, h12 = (size_t)cfg->d_h1 + cfg->d_h2, h3 = (size_t)cfg->d_h3;
-    const int kchunk = dh2_kchunk(cfg->n_items);
-    size_t nsplit = (I + kchunk - 1) / kchunk;
-    {
-        const size_t ns2 = (I + dh2_stream_chunk(cfg->n_items) - 1) / dh2_stream_chunk(cfg->n_items);
-        if (ns2 > nsplit) nsplit = ns2;
-    }
+    // (sized without a generator state: whichever form of the dh2 product the step's route takes)
+    const size_t nsplit = (size_t)std::max(dh2_split(cfg->n_items, false).nsplit, dh2_split(cfg->n_items, true).nsplit);
     w.rowpart = take(R * RP);
     w.segpart = take(segpart_floats(I, R));
     w.nb = take(R);
@@ -353,6 +353,8 @@ inline int check_launch() { return hipGetLastError() == hipSuccess ? LTG_OK : LT
 inline void clear_errors() { (void)hipGetLastError(); }
 
 inline dim3 grid2(int N, int M, int bn = 64, int bm = 64, int z = 1) { return dim3((N + bn - 1) / bn, (M + bm - 1) / bm, z); }
+// workgroups of NT threads for n elements, at most `cap` of them (grid-stride kernels)
+inline dim3 grid1(int n, int cap) { return dim3((n + NT - 1) / NT < cap ? (n + NT - 1) / NT : cap); }
 
 }  // namespace
 namespace {
@@ -363,43 +365,12 @@ namespace {
 }
 namespace {
 
-// Which of the round-2 latency-path kernels (ltg_fast.h) apply.  Tuning-knob bit 18 of ltg_config.tuning switches all of
-// them off (the round-1 kernels compute the same function; kept for A/B measurements and as the path of unusual sizes).
-inline bool fast_on(const ltg_config* c) { return (c->tuning & 262144) == 0; }
-inline bool mid_fast(const ltg_config* c, int rows) { return fast_on(c) && (c->z_dim % 4) == 0 && rows <= 256; }
-inline bool d_wide(const ltg_config* c) { return c->d_h0 >= 512 && c->d_h1 + c->d_h2 >= 512 && c->d_h3 >= 128; }
-// fp8 discriminator with EVERY GEMM operand in operand format (ltg_fp8bwd.h).  Tuning-knob bit 19 (backward converts on the fly, the
-// round-2 path) switches it off.
-inline bool d_fp8_opfmt(const ltg_config* c, const ltg_disc_state* d) {
-    return fast_on(c) && c->d_precision == LTG_PREC_FP8 && d->emb_fp8 && d->w1t_fp8 && d->w2t_fp8 && d->w3t_fp8 && d->w3_fp8 && (c->d_h0 % 128) == 0 &&
-           ((c->d_h1 + c->d_h2) % 128) == 0 && (c->d_h3 % 128) == 0 && (c->d_h1 % 64) == 0 && (c->d_h2 % 64) == 0 && c->d_h3 <= 64 * D8_OUT_CM &&
-           (c->tuning & (1 << 19)) == 0;
-}
-inline bool d_fast(const ltg_config* c) {
-    return fast_on(c) && c->d_precision == LTG_PREC_FP32 && !d_wide(c) && c->d_h3 <= 512 && (c->d_h0 % 4) == 0 && ((c->d_h1 + c->d_h2) % 4) == 0 && (c->d_h3 % 4) == 0;
-}
-// ltg_config.d_arith: SPL of kernel `which` (0 fk_d_l1, 1 fk_d_l2, 2 fk_d_bwd1, 3 fk_d_bwd2) of the config.ini-sized fp32 discriminator step --
-// 0 = v_mfma_f32_16x16x4_f32, 6 / 4 = bf16 cross terms of the split operands (ltg_rgemm.h).  Bits 4-7 choose the kernels (measurements);
-// 0 = the library's set LTG_D_SPLIT_SET.
-#ifndef LTG_D_SPLIT_SET
-#define LTG_D_SPLIT_SET 0xE      // l2, bwd1, bwd2 (l1: one 16 x 16 output per wave -- the split's 36 vector instructions per block buy 4 MFMAs of 32 cycles)
-#endif
-inline int d_spl(const ltg_config* c, int which) {
-    // (the four-term form is cheap enough to pay in fk_d_l1 too: D phase 45.5 against 45.9 ms, profiles/r6_ab_d_arith.txt)
-    const int mode = c->d_arith & 3, set = ((c->d_arith >> 4) & 15) ? ((c->d_arith >> 4) & 15) : (mode == LTG_DARITH_BF16X4 ? 0xF : LTG_D_SPLIT_SET);
-    if (mode == LTG_DARITH_FP32 || !((set >> which) & 1)) return 0;
-    return mode == LTG_DARITH_BF16X4 ? 4 : 6;
-}
 #define LTG_D_SPL_LAUNCH(SPLV, KERNEL, ...)                                       \
     do {                                                                          \
         if ((SPLV) == 6) hipLaunchKernelGGL((KERNEL<6>), __VA_ARGS__);            \
         else if ((SPLV) == 4) hipLaunchKernelGGL((KERNEL<4>), __VA_ARGS__);       \
         else hipLaunchKernelGGL((KERNEL<0>), __VA_ARGS__);                        \
     } while (0)
-inline bool unsharded(const ltg_config* c) { return c->item_lo == 0 && (c->n_items_global == 0 || c->n_items_global == c->n_items); }
-inline bool small_fast(const ltg_config* c, int rows) {
-    return fast_on(c) && unsharded(c) && c->n_items <= RD_MAXI && (c->n_items % 4) == 0 && (c->z_dim % 4) == 0 && rows <= 256;
-}
 
 // ltg_config.tuning: the selection bits include/ltg.h lists; a configuration with any other bit is refused
 constexpr int32_t TUNING_BITS = (1 << 14) | (1 << 17) | (1 << 18) | (1 << 19) | (1 << 20) | (1 << 21) | (1 << 22) | (1 << 26);
@@ -417,10 +388,74 @@ inline bool q0_lazy(const ltg_config* cfg, const ltg_gen_state* gen) {
     return gen->q0_last && gen->q0_lr_hist && gen->q0_period >= 1 && gen->q0_period <= LTG_Q0_HIST / 2 && gen->q0_ord >= 0 && (cfg->h_enc % 4) == 0 &&
            cfg->n_items >= 8192;   // smaller slabs update W_q0 as a dense product: nothing to defer
 }
+
+// ---- the generator's route: which kernel every stage of a step over `rows` batch rows runs.  A pure function of its arguments, computed
+// once per call; the stages switch on the fields and test nothing themselves.  (ltg_g_route hands it out: include/ltg.h has the fields.)
+// staged: the step cut at its exchange points (ltg_g_fwd_* / ltg_g_bwd_*), which has no small-slab form.
+ltg_g_route_info g_route(const ltg_config* c, const ltg_gen_state* gen, int rows, bool staged = false) {
+    ltg_g_route_info r = {};
+    const int I = c->n_items, H = c->h_enc;
+    const bool fast = fast_on(c), bf = c->precision == LTG_PREC_BF16, big = I >= 8192;
+    const bool vz = (c->z_dim % 4) == 0;   // 16-B loaders of the middle layers (H % 4 == 0 always)
+    const bool unsharded = c->item_lo == 0 && (c->n_items_global == 0 || c->n_items_global == I);
+    r.enc0 = fast ? LTG_ENC0_FAST : LTG_ENC0_GENERIC;
+    // small item slab: a row's softmax statistics, loss terms and dlogits need no other row -> one launch per stage
+    r.small = !staged && fast && unsharded && I <= RD_MAXI && (I % 4) == 0 && vz && rows <= 256;
+    r.mid = (fast && vz && rows <= 256) ? LTG_MID_FAST : LTG_MID_DENSE;
+    r.mid_vec = vz;
+    // the streaming decoder kernels: bf16, large item slab, a training batch (<= 128 rows), H <= 608, 16-B aligned rows
+    const bool stream = gen->wp1t_bf16 && bf && big && (I % 8) == 0 && rows <= 128 && H <= ST_KP && (H % 4) == 0;
+    // k_dec1_bwd_adam_stream walks the 4 H/4 float4 a wave owns per tile as exactly ten 64-lane accesses
+    const bool dw_stream = stream && (H % 4) == 0 && H > 576 && H <= 640;
+    if (fast && I <= RD_MAXI && rows <= 256) r.dec = LTG_DEC_SMALL;
+    else if (stream) {
+        // the second form for the HBM-bound slabs (see k_dec1_fwd_stream2); tuning-knob bit 26: the first form at every size, bit 17: the second
+        // form from 8 192 items (A/B measurements)
+        const int st2_min = (c->tuning & (1 << 17)) ? 8192 : ST2_MIN_ITEMS;
+        // (the second form addresses the logits AND the shadow rows with 32-bit byte offsets from a uniform base: R * I * 4 and I * ST_KP * 2 must both
+        // stay below 2^32 -- 3 532 110 items of one slab for the shadow; beyond either limit the first form, which has none)
+        const bool form2 = (c->tuning & (1 << 26)) == 0 && I >= st2_min && (size_t)rows * (size_t)I < ((size_t)1 << 30) &&
+                           (size_t)I * (size_t)(ST_KP * 2) < ((size_t)1 << 32);
+        r.dec = form2 ? LTG_DEC_STREAM2 : LTG_DEC_STREAM1;
+    } else {
+        r.dec = LTG_DEC_TILE;
+        r.dec_tile = big ? 128 : 32;
+    }
+    // (tuning-knob bit 21: statistics from a second pass over the logits)
+    r.seg_pass = I > 2 * RS_SEG;
+    r.stats = (stream && (c->tuning & (1 << 21)) == 0) ? LTG_STATS_EPILOGUE : (r.seg_pass ? LTG_STATS_SEGMENT : LTG_STATS_ROW);
+    r.loss = r.small ? LTG_LOSS_ROW : (fast ? LTG_LOSS_COMBINE : LTG_LOSS_GENERIC);
+    // dlog as bf16: when BOTH its consumers are the streaming kernels (k_dh2_stream, k_dec1_bwd_adam_stream + ragged tail); tuning-knob bit 22: fp32
+    r.dlog_bf16 = fast && dw_stream && (c->tuning & (1 << 22)) == 0;
+    if (r.small) r.dh2 = LTG_DH2_SMALL;
+    else {
+        r.dh2 = stream ? LTG_DH2_STREAM : LTG_DH2_PARTIAL;
+        if (!stream) r.dh2_tile = big ? 128 : ((bf && (I % 4) == 0) ? -32 : 32);
+        const Dh2Split s = dh2_split(I, stream);
+        r.dh2_chunk = s.chunk;
+        r.dh2_nsplit = s.nsplit;
+    }
+    if (r.small) r.dw = LTG_DW_TAIL_JOB;
+    else if (dw_stream) {
+        r.dw = LTG_DW_STREAM;
+        r.dw_ragged = (I % 32) != 0;   // ragged tail: the generic tile kernel on the last I % 32 item rows
+    } else {
+        r.dw = LTG_DW_TILE;
+        r.dw_tile = big ? 64 : ((bf && (I % 4) == 0) ? -32 : 32);
+    }
+    r.q0 = r.small ? LTG_Q0_DENSE : (q0_lazy(c, gen) ? LTG_Q0_LAZY : LTG_Q0_SWEEP);
+    // HBM-bound sweep: its own launch at full occupancy (measured 490 vs 525 us at 200 000 items when it rode in the 118-register job
+    // kernel); the generic chain's sweep always is one
+    r.q0_own_launch = r.q0 == LTG_Q0_LAZY || (r.q0 == LTG_Q0_SWEEP && (big || r.mid == LTG_MID_DENSE));
+    r.grad_rows = (c->tuning & (1 << 14)) == 0;   // tuning-knob bit 14: the column-blocked shape of the sparse gradient
+    r.sharded_ok = r.mid == LTG_MID_FAST && r.dlog_bf16 && r.q0 == LTG_Q0_LAZY;
+    return r;
+}
+
 // the item rows this batch reads, up to the caller's clock (no-ops for rows that are current)
-void q0_touch(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_batch* bt, hipStream_t st, const unsigned* poison = nullptr,
+void q0_touch(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_g_route_info& r, const ltg_batch* bt, hipStream_t st, const unsigned* poison = nullptr,
               int32_t* mark = nullptr, unsigned seq = 0u) {
-    if (!q0_lazy(cfg, gen) || bt->n_rows <= 0) return;
+    if (r.q0 != LTG_Q0_LAZY || bt->n_rows <= 0) return;
     const AdamC ad = make_adam(cfg, 1);   // b1, b2, eps; the learning rates come from the history ring
     if (bt->uptr && bt->csr_pos) {
         if (bt->n_unique > 0)
@@ -432,13 +467,13 @@ void q0_touch(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_batch* 
 }
 
 // stage 1: enc-0 over this rank's item slab.  pre_only: leave the partial pre-activation in acts->h1.
-void fwd_stage_enc(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_batch* bt, const ltg_fwd_opts* o,
+void fwd_stage_enc(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_g_route_info& r, const ltg_batch* bt, const ltg_fwd_opts* o,
                    const ltg_gen_acts* acts, int pre_only, hipStream_t st, float* xd = nullptr, bool touched = false,
                    LtgGate started = LTG_NO_GATE, LtgGate end_wait = LTG_NO_GATE) {
     const int R = bt->n_rows, I = cfg->n_items, H = cfg->h_enc;
     const Probe pr{o->probe, st};
-    if (!touched) q0_touch(cfg, gen, bt, st);
-    if (fast_on(cfg)) {
+    if (!touched) q0_touch(cfg, gen, r, bt, st);
+    if (r.enc0 == LTG_ENC0_FAST) {
         LTG_PROBED(pr, LTG_K_ENC0_FWD,
                    hipLaunchKernelGGL(fk_enc0_fwd, dim3((H / 4 + 63) / 64, R + (end_wait.word ? 1 : 0)), dim3(ENC_NT), xd ? (size_t)I * sizeof(float) : 0, st, H, I, bt->indptr,
                                       bt->indices, bt->values, o->drop_keep, o->keep_prob, cfg->seed, o->rng_step, gen->p[0], gen->p[4], acts->h1,
@@ -451,8 +486,8 @@ void fwd_stage_enc(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_ba
                                   acts->row_scale, bt->row_norm2, cfg->item_lo, Ig_of(cfg), pre_only, o->rows_per_step));
 }
 
-// the streaming decoder forward (stream_ok): logits of R <= 128 rows over the local slab; stat != NULL: per-group softmax statistics
-// as well.  Returns the number of statistic groups.
+// the streaming decoder forward (LTG_DEC_STREAM1 / LTG_DEC_STREAM2): logits of R <= 128 rows over the local slab; stat != NULL: per-group
+// softmax statistics as well.  Returns the number of statistic groups.
 // (Round 4, built and not run: 64-item tiles with the eight waves as 4 row groups x 2 item halves -- a wave then owns 32 batch rows, so
 // every B fragment it reads from LDS feeds two MFMAs: half the LDS bytes per FLOP, the untested suspect for this kernel's 0.46 of the
 // HBM rate -- needs two stationary fragment sets = 152 registers per lane: hipcc allocates 256 VGPRs + 776 bytes of scratch per lane for
@@ -460,15 +495,9 @@ void fwd_stage_enc(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_ba
 // (Measured and not kept, round 3: the same loop as TWO independent 4-wave workgroups per CU -- half the batch rows each, 2 x 77 KB of
 // LDS, 244 VGPRs, bit-identical outputs -- so that one half's loads overlap the other's MFMAs and stores: 110.4 vs 107.9 us per launch
 // at 200 000 items on one box, min 81.8 vs 78.6; whole step 968-970 vs 965-968 us.  The serialisation is not inside the workgroup.)
-int launch_dec1_fwd_stream(const ltg_config* cfg, const ltg_gen_state* gen, int R, const ltg_gen_acts* acts, float* stat, hipStream_t st) {
+int launch_dec1_fwd_stream(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_g_route_info& r, int R, const ltg_gen_acts* acts, float* stat, hipStream_t st) {
     const int I = cfg->n_items, H = cfg->h_enc;
-    // the second form for the HBM-bound slabs (see k_dec1_fwd_stream2); tuning-knob bit 26: the first form at every size, bit 17: the second
-    // form from 8 192 items (A/B measurements)
-    const int st2_min = (cfg->tuning & (1 << 17)) ? 8192 : ST2_MIN_ITEMS;
-    // (the second form addresses the logits AND the shadow rows with 32-bit byte offsets from a uniform base: R * I * 4 and I * ST_KP * 2 must both
-    // stay below 2^32 -- 3 532 110 items of one slab for the shadow; beyond either limit the first form, which has none)
-    if ((cfg->tuning & (1 << 26)) == 0 && I >= st2_min && (size_t)R * (size_t)I < ((size_t)1 << 30) &&
-        (size_t)I * (size_t)(ST_KP * 2) < ((size_t)1 << 32)) {
+    if (r.dec == LTG_DEC_STREAM2) {
         const int nt2 = (I + 31) / 32, G2 = nt2 < 256 ? nt2 : 256;
 #define LTG_ST2(STATS, NTB) hipLaunchKernelGGL((k_dec1_fwd_stream2<STATS, NTB>), dim3(G2), dim3(ST_NT), (size_t)ST_KS * NTB * 64 * 16, st, R, I, H, acts->h2, gen->wp1t_bf16, gen->p[7], acts->logits, stat)
         if (stat) { if (R <= 112) LTG_ST2(true, 7); else LTG_ST2(true, 8); }
@@ -486,17 +515,16 @@ int launch_dec1_fwd_stream(const ltg_config* cfg, const ltg_gen_state* gen, int 
 // stage 2: (bias + tanh of the all-reduced pre-activation,) enc-1, reparameterisation, dec-0, dec-1 over the local slab
 // stat (optional scratch of segpart_floats()): the streaming decoder kernel leaves its per-workgroup softmax statistics there;
 // returns the number of workgroups that wrote them (0: the caller reads the logits for the statistics)
-int fwd_stage_rest(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_batch* bt, const ltg_fwd_opts* o,
+int fwd_stage_rest(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_g_route_info& r, const ltg_batch* bt, const ltg_fwd_opts* o,
                    const ltg_gen_acts* acts, int apply_bias_tanh, hipStream_t st, float* stat = nullptr) {
     int stat_groups = 0;
     const int R = bt->n_rows, I = cfg->n_items, H = cfg->h_enc, Z = cfg->z_dim;
     const Probe pr{o->probe, st};
-    const bool vz = (Z % 4) == 0;   // 16-B loaders of the middle layers (H % 4 == 0 always)
+    const bool vz = r.mid_vec != 0;
     if (apply_bias_tanh) {
-        const int n = R * H;
-        hipLaunchKernelGGL(k_bias_tanh, dim3((n + NT - 1) / NT < 1024 ? (n + NT - 1) / NT : 1024), dim3(NT), 0, st, n, H, gen->p[4], acts->h1);
+        hipLaunchKernelGGL(k_bias_tanh, grid1(R * H, 1024), dim3(NT), 0, st, R * H, H, gen->p[4], acts->h1);
     }
-    if (mid_fast(cfg, R)) {
+    if (r.mid == LTG_MID_FAST) {
         LTG_PROBED(pr, LTG_K_ENC1, hipLaunchKernelGGL(fk_enc1<false>, grid2(Z, R, 16, 16), dim3(ENC1_NT), 0, st, R, H, Z, acts->h1, gen->p[1], gen->p[5], o->eps, o->is_training,
                                                       cfg->seed, o->rng_step, acts->mulv, acts->z));
         LTG_PROBED(pr, LTG_K_DEC0, hipLaunchKernelGGL(fk_dec0, grid2(H, R, 16, 16), dim3(NT), 0, st, R, H, Z, acts->z, acts->mulv, gen->p[2], gen->p[6],
@@ -514,16 +542,14 @@ int fwd_stage_rest(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_ba
     pr.after(LTG_K_DEC0);
     }
     {
-        const bool bf = cfg->precision == LTG_PREC_BF16, big = I >= 8192;
+        const bool bf = cfg->precision == LTG_PREC_BF16, big = r.dec_tile == 128;
         pr.before(LTG_K_DEC1_FWD);
-        if (fast_on(cfg) && I <= RD_MAXI && R <= 256) {
+        if (r.dec == LTG_DEC_SMALL) {
             if (bf) hipLaunchKernelGGL(fk_dec1<true>, grid2(I, R, 16, 16), dim3(NT), 0, st, R, I, H, acts->h2, gen->p[3], gen->p[7], acts->logits);
             else hipLaunchKernelGGL(fk_dec1<false>, grid2(I, R, 16, 16), dim3(NT), 0, st, R, I, H, acts->h2, gen->p[3], gen->p[7], acts->logits);
-        } else if (stream_ok(cfg, gen, R)) {
-            if (stat && (cfg->tuning & (1 << 21)) == 0)   // (tuning-knob bit 21: statistics from a second pass over the logits)
-                stat_groups = launch_dec1_fwd_stream(cfg, gen, R, acts, stat, st);
-            else
-                launch_dec1_fwd_stream(cfg, gen, R, acts, nullptr, st);
+        } else if (r.dec != LTG_DEC_TILE) {
+            if (stat && r.stats == LTG_STATS_EPILOGUE) stat_groups = launch_dec1_fwd_stream(cfg, gen, r, R, acts, stat, st);
+            else launch_dec1_fwd_stream(cfg, gen, r, R, acts, nullptr, st);
         } else if (bf && big) hipLaunchKernelGGL((k_dec1_fwd<true, true>), grid2(I, R, 64, 128), dim3(NT), 0, st, R, I, H, acts->h2, gen->p[3], gen->p[7], acts->logits);
         else if (bf) hipLaunchKernelGGL((k_dec1_fwd<true, false, true>), grid2(I, R, 32, 32), dim3(NT), 0, st, R, I, H, acts->h2, gen->p[3], gen->p[7], acts->logits);
         else if (big) hipLaunchKernelGGL((k_dec1_fwd<false, true>), grid2(I, R, 64, 128), dim3(NT), 0, st, R, I, H, acts->h2, gen->p[3], gen->p[7], acts->logits);
@@ -531,6 +557,29 @@ int fwd_stage_rest(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_ba
         pr.after(LTG_K_DEC1_FWD);
     }
     return stat_groups;
+}
+
+// softmax statistics of the local logits into rowpart (the G step: with the batch's loss terms, RP floats per row) and / or lse: from the
+// decoder kernel's epilogue (stat_groups > 0), by the segment pass, or row by row
+void g_row_partial(const ltg_config* cfg, const ltg_g_route_info& r, const ltg_batch* bt, const ltg_pairs* fake, const ltg_gen_acts* acts,
+                          float* rowpart, hipStream_t st, float* segpart = nullptr, float* lse = nullptr, int stat_groups = 0) {
+    const int I = cfg->n_items, B = bt->n_rows;
+    if (stat_groups > 0) {   // the decoder kernel left its statistics in segpart
+        hipLaunchKernelGGL(k_row_stats_merge, dim3(B), dim3(NT), 0, st, B, stat_groups, I, cfg->item_lo, segpart, bt->indptr, bt->indices, bt->values,
+                           acts->logits, fake ? fake->n : 0, fake ? fake->row : nullptr, fake ? fake->niche : nullptr, fake ? fake->pop : nullptr,
+                           rowpart, lse);
+        return;
+    }
+    if (segpart && r.seg_pass) {
+        const int nseg = (I + RS_SEG - 1) / RS_SEG;
+        hipLaunchKernelGGL(k_row_partial_seg, dim3(nseg, B), dim3(NT), 0, st, I, cfg->item_lo, bt->indptr, bt->indices, bt->values, acts->logits,
+                           fake ? fake->n : 0, fake ? fake->row : nullptr, fake ? fake->niche : nullptr, fake ? fake->pop : nullptr, segpart);
+        hipLaunchKernelGGL(k_row_partial_merge, dim3(B), dim3(64), 0, st, B, nseg, segpart, rowpart, lse);
+        return;
+    }
+    hipLaunchKernelGGL(k_row_partial, dim3(bt->n_rows), dim3(NT), 0, st, cfg->n_items, cfg->item_lo, bt->indptr, bt->indices, bt->values,
+                       acts->logits, fake ? fake->n : 0, fake ? fake->row : nullptr, fake ? fake->niche : nullptr,
+                       fake ? fake->pop : nullptr, rowpart);
 }
 
 // bytes of the segment-partial scratch for `rows` rows (the first two carve entries of the workspace)
@@ -542,21 +591,13 @@ int vae_forward_impl(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_
                      const ltg_gen_acts* acts, float* probs_out, hipStream_t st, void* ws = nullptr, size_t ws_bytes = 0) {
     const int R = bt->n_rows, I = cfg->n_items;
     if (R <= 0) return LTG_OK;
-    fwd_stage_enc(cfg, gen, bt, o, acts, 0, st);
-    const bool have_scratch = ws && I > 2 * RS_SEG && ws_bytes >= segpart_bytes(cfg, R);
+    const ltg_g_route_info r = g_route(cfg, gen, R, true);
+    fwd_stage_enc(cfg, gen, r, bt, o, acts, 0, st);
+    const bool have_scratch = ws && r.seg_pass && ws_bytes >= segpart_bytes(cfg, R);
     float* segpart = have_scratch ? reinterpret_cast<float*>((char*)ws + align_up((size_t)R * RP * sizeof(float))) : nullptr;
-    const int sg = fwd_stage_rest(cfg, gen, bt, o, acts, 0, st, segpart);
-    if (sg > 0) {
-        hipLaunchKernelGGL(k_row_stats_merge, dim3(R), dim3(NT), 0, st, R, sg, I, cfg->item_lo, segpart, bt->indptr, bt->indices, bt->values, acts->logits, 0,
-                           (const int32_t*)nullptr, (const int32_t*)nullptr, (const int32_t*)nullptr, (float*)nullptr, acts->lse);
-    } else if (have_scratch) {
-        // large item slab: one pass over the logits in (segment, row) blocks, then a per-row merge
-        const int nseg = (I + RS_SEG - 1) / RS_SEG;
-        hipLaunchKernelGGL(k_row_partial_seg, dim3(nseg, R), dim3(NT), 0, st, I, cfg->item_lo, bt->indptr, bt->indices, bt->values, acts->logits,
-                           0, (const int32_t*)nullptr, (const int32_t*)nullptr, (const int32_t*)nullptr, segpart);
-        hipLaunchKernelGGL(k_row_partial_merge, dim3(R), dim3(64), 0, st, R, nseg, segpart, (float*)nullptr, acts->lse);
-    } else
-    hipLaunchKernelGGL(k_row_lse, dim3(R), dim3(NT), 0, st, I, acts->logits, acts->lse);
+    const int sg = fwd_stage_rest(cfg, gen, r, bt, o, acts, 0, st, segpart);
+    if (segpart) g_row_partial(cfg, r, bt, nullptr, acts, nullptr, st, segpart, acts->lse, sg);
+    else hipLaunchKernelGGL(k_row_lse, dim3(R), dim3(NT), 0, st, I, acts->logits, acts->lse);
     if (probs_out) {
         const int gx = (I + NT - 1) / NT < 64 ? (I + NT - 1) / NT : 64;
         hipLaunchKernelGGL(k_softmax_write, dim3(gx, R), dim3(NT), 0, st, I, acts->logits, acts->lse, probs_out);
@@ -564,25 +605,93 @@ int vae_forward_impl(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_
     return check_launch();
 }
 
-// forward of one or both towers into ws (A1, A3, y, ds, lrow)
-// (precision mode, tile size) -> template instance of a discriminator GEMM kernel
-inline int d_mode(const ltg_config* cfg) { return cfg->d_precision == LTG_PREC_BF16 ? 1 : (cfg->d_precision == LTG_PREC_FP8 ? 2 : 0); }
-// tile of discriminator GEMM kernel `which` (0 l1, 1 l2, 2 bwd1, 3 bwd2): 32 = scalar loaders (latency-bound default
-// sizes); 64 / 128 = 16-B vector loaders for a wide discriminator (every dimension a multiple of 4), sized so that each
-// launch still fills the 256 CUs
-inline int d_tile(const ltg_config* cfg, int which) {
-    const bool wide = cfg->d_h0 >= 512 && cfg->d_h1 + cfg->d_h2 >= 512 && cfg->d_h3 >= 128;
-    const bool vec = (cfg->d_h0 % 4) == 0 && (cfg->d_h1 % 4) == 0 && (cfg->d_h2 % 4) == 0 && (cfg->d_h3 % 4) == 0;
-    if (!(wide && vec)) {
+#ifndef LTG_D_FORK_MIN_ROWS
+#define LTG_D_FORK_MIN_ROWS 1024
+#endif
+#ifndef LTG_D_SPLIT_SET
+#define LTG_D_SPLIT_SET 0xE      // l2, bwd1, bwd2 (l1: one 16 x 16 output per wave -- the split's 36 vector instructions per block buy 4 MFMAs of 32 cycles)
+#endif
+// fp8 discriminator with EVERY GEMM operand in operand format (ltg_fp8bwd.h).  Tuning-knob bit 19 (backward converts on the fly, the
+// round-2 path) switches it off.
+inline bool d_fp8_opfmt(const ltg_config* c, const ltg_disc_state* d) {
+    return fast_on(c) && c->d_precision == LTG_PREC_FP8 && d->emb_fp8 && d->w1t_fp8 && d->w2t_fp8 && d->w3t_fp8 && d->w3_fp8 && (c->d_h0 % 128) == 0 &&
+           ((c->d_h1 + c->d_h2) % 128) == 0 && (c->d_h3 % 128) == 0 && (c->d_h1 % 64) == 0 && (c->d_h2 % 64) == 0 && c->d_h3 <= 64 * D8_OUT_CM &&
+           (c->tuning & (1 << 19)) == 0;
+}
+// The Adam sweep over `slab` (gradient slabs of stride `stride`; lrow: the per-row loss terms of the generic kernels, else the loss sits in
+// slot P of the slabs): tile-wise with the operand-format shadows following the weights (k8_d_adam), or one flat float4 sweep (fk_d_adam)
+// when the eight tensors (and moments) lie back to back -- and no operand-format shadows have to follow the weights (fp8 mode: k_d_adam
+// rewrites the e4m3 copies of the three matrices it updates) --, else tensor by tensor (k_d_adam)
+int d_adam_kind(const ltg_config* cfg, const ltg_disc_state* disc, int stride, const float* slab, bool lrow) {
+    if (d_fp8_opfmt(cfg, disc)) return LTG_D_ADAM_FP8;
+    const DLayout L = d_layout(cfg->d_h0, cfg->d_h1, cfg->d_h2, cfg->d_h3);
+    bool flat = !lrow && (stride % 4) == 0 && !(cfg->d_precision == LTG_PREC_FP8 && disc->w1t_fp8);
+    for (int i = 0; i < 7; ++i) {
+        const size_t sz = (size_t)(L.off[i + 1] - L.off[i]);
+        flat = flat && disc->p[i + 1] == disc->p[i] + sz && disc->m[i + 1] == disc->m[i] + sz && disc->v[i + 1] == disc->v[i] + sz;
+    }
+    flat = flat && ((uintptr_t)disc->p[0] % 16) == 0 && ((uintptr_t)disc->m[0] % 16) == 0 && ((uintptr_t)disc->v[0] % 16) == 0 && ((uintptr_t)slab % 16) == 0;
+    return flat ? LTG_D_ADAM_FLAT : LTG_D_ADAM_TENSORS;
+}
+
+// ---- the discriminator's route: the kernels of a forward (with_bwd = false) or a step over n pair rows.  A pure function of its arguments,
+// computed once per call (ltg_d_route hands it out: include/ltg.h has the fields).  has_aux: the caller gave an aux stream and device words;
+// slab: where the step's gradient slabs will lie (the flat sweep needs them 16-byte aligned).
+ltg_d_route_info d_route(const ltg_config* c, const ltg_disc_state* d, int n, bool with_bwd, bool has_aux = false, const float* slab = nullptr) {
+    ltg_d_route_info r = {};
+    const int h0 = c->d_h0, h1 = c->d_h1, h2 = c->d_h2, h3 = c->d_h3, h12 = h1 + h2, arith = c->d_arith & 3;
+    const bool fast = fast_on(c), fp8 = c->d_precision == LTG_PREC_FP8;
+    const bool fk = fast && c->d_precision == LTG_PREC_FP32 && !d_wide(c) && h3 <= 512 && (h0 % 4) == 0 && (h12 % 4) == 0 && (h3 % 4) == 0;
+    r.mode = c->d_precision == LTG_PREC_BF16 ? 1 : (fp8 ? 2 : 0);
+    if (!with_bwd && ft_wsp_capable(c) && arith != LTG_DARITH_FP32 && (c->tuning & (1 << 20)) == 0)
+        r.kind = LTG_D_TOWER;   // forward only, split arithmetic (tuning-knob bit 20: the three launches of LTG_D_STAGED_FWD instead)
+    else if (fk && !with_bwd && h0 >= 32 && h12 >= 32)
+        r.kind = LTG_D_STAGED_FWD;   // (d_arith = fp32, tuning bit 20, or sizes the one-kernel tower does not take)
+    else if (fk) r.kind = LTG_D_FAST;
+    else if (fp8 && fast && d->emb_fp8 && d->w1t_fp8 && d->w2t_fp8 && d->w3t_fp8 && (h0 % 64) == 0 && (h12 % 64) == 0) {
+        // operand-format storage: both forward layers read e4m3 bytes (embedding table, transposed weight shadows, A1 in e4m3);
+        // LDS-staged tiles for 128-multiples, the register-resident block for 64- but not 128-multiples
+        if (with_bwd && d_fp8_opfmt(c, d)) r.kind = LTG_D_FP8_OPFMT;
+        else r.kind = ((h0 % 128) == 0 && (h12 % 128) == 0) ? LTG_D_FP8_STAGED : LTG_D_FP8_REG;
+    } else r.kind = LTG_D_GENERIC;
+    // tiles of the generic GEMM kernels: 32 = scalar loaders (latency-bound default sizes); 64 / 128 = 16-B vector loaders for a wide
+    // discriminator (every dimension a multiple of 4), sized so that each launch still fills the 256 CUs
+    if (d_wide(c) && (h0 % 4) == 0 && (h1 % 4) == 0 && (h2 % 4) == 0 && (h3 % 4) == 0) {
+        r.tile[0] = r.tile[2] = 64;
+        r.tile[1] = fp8 ? 64 : -32;   // l2 (N = h3 = 256): too few 64-tiles to fill the chip unless the loads are the bottleneck
+        r.tile[3] = 128;
+    } else {
         // default sizes (100/150/250/300): l2 and backward stage 1 only touch h12 = 400 and h3 = 300 wide rows -> 16-B
         // loaders on the 32 x 32 tiles; l1 / stage 2 index columns of width h1 = 150 (8-B aligned only) -> scalar
-        const bool v12 = ((cfg->d_h1 + cfg->d_h2) % 4) == 0 && (cfg->d_h3 % 4) == 0;
-        if (which == 1 || which == 2) return v12 ? -32 : 32;
-        return (cfg->d_h0 % 4) == 0 ? -33 : 32;   // embedding rows (operand A) in 16-B pieces
+        r.tile[1] = r.tile[2] = ((h12 % 4) == 0 && (h3 % 4) == 0) ? -32 : 32;
+        r.tile[0] = r.tile[3] = (h0 % 4) == 0 ? -33 : 32;   // embedding rows (operand A) in 16-B pieces
     }
-    if (which == 1) return d_mode(cfg) == 2 ? 64 : -32;   // l2 (N = h3 = 256): too few 64-tiles to fill the chip unless the loads are the bottleneck
-    return which == 3 ? 128 : 64;
+    {   // backward stage 1 with > 1024 32 x 32 tiles is throughput-bound, not latency-bound: 64 x 64 tiles (measured -5 %)
+        const int ks = (n + D_KCHUNK - 1) / D_KCHUNK;
+        const long t32 = (long)((n + 31) / 32) * ((h12 + 31) / 32) + (long)ks * ((h12 + 32) / 32) * ((h3 + 31) / 32);
+        if (r.tile[2] == -32 && t32 > 1024) r.tile[2] = 64;
+    }
+    // ltg_config.d_arith: SPL of fk_d_l1, fk_d_l2, fk_d_bwd1, fk_d_bwd2 of the config.ini-sized fp32 discriminator step -- 0 =
+    // v_mfma_f32_16x16x4_f32, 6 / 4 = bf16 cross terms of the split operands (ltg_rgemm.h).  Bits 4-7 choose the kernels (measurements);
+    // 0 = the library's set LTG_D_SPLIT_SET.
+    // (the four-term form is cheap enough to pay in fk_d_l1 too: D phase 45.5 against 45.9 ms, profiles/r6_ab_d_arith.txt)
+    const int set = ((c->d_arith >> 4) & 15) ? ((c->d_arith >> 4) & 15) : (arith == LTG_DARITH_BF16X4 ? 0xF : LTG_D_SPLIT_SET);
+    for (int i = 0; i < 4; ++i) r.spl[i] = (arith == LTG_DARITH_FP32 || !((set >> i) & 1)) ? 0 : (arith == LTG_DARITH_BF16X4 ? 4 : 6);
+    const bool padded = r.kind == LTG_D_FAST || r.kind == LTG_D_FP8_OPFMT;
+    const int P = d_layout(h0, h1, h2, h3).off[8];
+    r.adam = d_adam_kind(c, d, padded ? d_slab_stride(P) : P, slab, r.kind != LTG_D_FAST);
+    // Jobs B / C on the aux stream (d_step_impl has the mechanism and its measurements):
+    // (only with the FLAT tensor layout: the poison word reaches fk_d_adam alone -- separate tensors take k_d_adam, which has no early
+    // return, so a direct C-ABI caller with that layout keeps the whole step on one stream)
+    // (Round 6: only from LTG_D_FORK_MIN_ROWS pair rows.  At the ~300 rows per step of the synthetic tables the two jobs are one or two slabs of work and
+    // the fork's two gate kernels and its poll cost more than they hide -- and not steadily: D step 32.6-38.9 us with the fork against 34.1 +- 0.1
+    // without at 20 000 items, 34.1-38.2 against 32.4 at 200 000 -- profiles/r6_ab_d_fork_small.txt.  Either way the same kernels write the same slab
+    // entries: same bits.)
+    r.fork = has_aux && with_bwd && r.kind == LTG_D_FAST && n >= LTG_D_FORK_MIN_ROWS && r.adam == LTG_D_ADAM_FLAT;
+    return r;
 }
+
+// forward of one or both towers into ws (A1, A3, y, ds, lrow)
 #define LTG_D_DISPATCH3(KERNEL, MODE, TS, V, GRID, ST, ...)                                                          \
     do {                                                                                                             \
         if ((MODE) == 1) hipLaunchKernelGGL((KERNEL<1, TS, V>), GRID, dim3(NT), 0, ST, __VA_ARGS__);                 \
@@ -599,16 +708,15 @@ inline int d_tile(const ltg_config* cfg, int which) {
         else LTG_D_DISPATCH3(KERNEL, MODE, 32, 0, GRID, ST, __VA_ARGS__);                                            \
     } while (0)
 
-void disc_forward(const ltg_config* cfg, const ltg_disc_state* d, PairView pv, DropView dA, DropView dB, DropView dC,
+void disc_forward(const ltg_config* cfg, const ltg_disc_state* d, const ltg_d_route_info& r, PairView pv, DropView dA, DropView dB, DropView dC,
                   float keep, uint64_t step, const Workspace& w0, bool with_bwd, const ltg_probe* probe, hipStream_t st, float* y_dst = nullptr) {
     Workspace w = w0;
     if (y_dst) w.y = y_dst;   // y straight into the caller's buffer
     const Probe pr{probe, st};
     const int n = pv.nr + pv.nf, h0 = cfg->d_h0, h1 = cfg->d_h1, h2 = cfg->d_h2, h3 = cfg->d_h3, h12 = h1 + h2;
     const int nmax = h1 > h2 ? h1 : h2;
-    if (!with_bwd && ft_wsp_capable(cfg) && (cfg->d_arith & 3) != LTG_DARITH_FP32 && (cfg->tuning & (1 << 20)) == 0) {
-        // forward only, split arithmetic: ONE kernel from the id lists to y, A1 stays in LDS (ltg_tower.h).  (Tuning-knob bit 20: the three
-        // launches below instead.)  The weights are split first: 1 MB at config.ini's sizes, ~3 us, once per call.
+    if (r.kind == LTG_D_TOWER) {
+        // forward only, split arithmetic: ONE kernel from the id lists to y, A1 stays in LDS (ltg_tower.h).  The weights are split first: 1 MB at config.ini's sizes, ~3 us, once per call.
         ltg_ft_u32x4* wsp = reinterpret_cast<ltg_ft_u32x4*>(w.wsp);
         const int nwv = (int)ft_wsp_triples(h0, h1, h2, h3);
         hipLaunchKernelGGL(fkt_split_weights, dim3((nwv + NT / 64 - 1) / (NT / 64)), dim3(NT), 0, st, h0, h1, h2, h3, d->p[0], d->p[2], d->p[4], wsp);
@@ -625,10 +733,10 @@ void disc_forward(const ltg_config* cfg, const ltg_disc_state* d, PairView pv, D
         pr.after(LTG_K_D_L1);
         return;
     }
-    if (d_fast(cfg) && !with_bwd && h0 >= 32 && h12 >= 32 && (h0 % 4) == 0 && (h12 % 4) == 0) {
+    if (r.kind == LTG_D_STAGED_FWD) {
         // forward only (the fake tower of the G steps, one batch or -- ltg_fake_tower_batched -- 10^5 pair rows): LDS-staged 64 x 64
         // tiles.  The choice depends on the layer sizes only, so the tower inside a step and the batched tower run the same
-        // kernels and produce the same bits.  (d_arith = fp32, tuning bit 20, or sizes the one-kernel tower does not take.)
+        // kernels and produce the same bits.
         LTG_PROBED(pr, LTG_K_D_L1, hipLaunchKernelGGL(fks_d_l1, dim3((h1 + 63) / 64 + (h2 + 63) / 64, (n + 63) / 64), dim3(NT), 0, st, pv, h0, h1, h2, d->emb, d->p[0],
                                                       d->p[1], d->p[2], d->p[3], dA, dB, keep, cfg->seed, step, w.A1));
         LTG_PROBED(pr, LTG_K_D_L2, hipLaunchKernelGGL(fks_d_l2, dim3((h3 + 63) / 64, (n + 63) / 64), dim3(NT), 0, st, n, h12, h3, w.A1, d->p[4], d->p[5], d->p[6], dC, keep,
@@ -636,57 +744,50 @@ void disc_forward(const ltg_config* cfg, const ltg_disc_state* d, PairView pv, D
         hipLaunchKernelGGL(fk_d_y, dim3((n + NT - 1) / NT), dim3(NT), 0, st, pv, 2 * ((h3 + 63) / 64), w.spart, d->p[7], w.y);
         return;
     }
-    if (d_fast(cfg)) {
+    if (r.kind == LTG_D_FAST) {
         // A3, G3 (backward only) and the per-tile partial dot products of the output unit; y only when nothing else follows
-        LTG_PROBED(pr, LTG_K_D_L1, LTG_D_SPL_LAUNCH(d_spl(cfg, 0), fk_d_l1, grid2(nmax, n, 32, 32, 2), dim3(NT), 0, st, pv, h0, h1, h2, d->emb, d->p[0], d->p[1], d->p[2],
+        LTG_PROBED(pr, LTG_K_D_L1, LTG_D_SPL_LAUNCH(r.spl[0], fk_d_l1, grid2(nmax, n, 32, 32, 2), dim3(NT), 0, st, pv, h0, h1, h2, d->emb, d->p[0], d->p[1], d->p[2],
                                                     d->p[3], dA, dB, keep, cfg->seed, step, w.A1));
-        LTG_PROBED(pr, LTG_K_D_L2, LTG_D_SPL_LAUNCH(d_spl(cfg, 1), fk_d_l2, dim3(((h3 + 31) / 32) * ((n + 31) / 32)), dim3(DL2_NT), 0, st, n, h12, h3, w.A1, d->p[4], d->p[5], d->p[6], dC, keep,
+        LTG_PROBED(pr, LTG_K_D_L2, LTG_D_SPL_LAUNCH(r.spl[1], fk_d_l2, dim3(((h3 + 31) / 32) * ((n + 31) / 32)), dim3(DL2_NT), 0, st, n, h12, h3, w.A1, d->p[4], d->p[5], d->p[6], dC, keep,
                                                     cfg->seed, step, w.A3, with_bwd ? w.G3 : (float*)nullptr, w.spart));
         if (!with_bwd) hipLaunchKernelGGL(fk_d_y, dim3((n + NT - 1) / NT), dim3(NT), 0, st, pv, (h3 + 31) / 32, w.spart, d->p[7], w.y);
         return;
     }
-    const int md = d_mode(cfg), ts = d_tile(cfg, 0), ts2 = d_tile(cfg, 1), t1 = ts < 0 ? 32 : ts, t2 = ts2 < 0 ? 32 : ts2;
-    if (md == 2 && fast_on(cfg) && d->emb_fp8 && d->w1t_fp8 && d->w2t_fp8 && d->w3t_fp8 && (h0 % 64) == 0 && (h12 % 64) == 0) {
-        // operand-format storage: both forward layers read e4m3 bytes (embedding table, transposed weight shadows, A1 in e4m3)
-        const bool staged = (h0 % 128) == 0 && (h12 % 128) == 0;   // LDS-staged tiles (64- but not 128-multiples: the register-resident block)
-        if (with_bwd && d_fp8_opfmt(cfg, d)) {
-            // the step's own forward: the same products, and every activation the backward multiplies is left behind in e4m3 in the
-            // orientation its GEMM contracts over (ltg_fp8bwd.h)
-            const int NP = d8_np(n);
-            hipLaunchKernelGGL(k8_gather_t, dim3(h0 / 64, NP / 64, 2), dim3(NT), 0, st, pv, h0, NP, d->emb_fp8, w.ET_8);
-            // (Round 5, measured and removed: the branch layers' product on 128 x 64 / 128 x 128 tiles -- half the operand bytes through the L1s per
-            // output -- ran 38.3 / 72.1 us against the 64 x 64 tiles' 30.1 us on the same box: the loop is bound by the latency of its staged K
-            // blocks, which 720 small workgroups hide better than 360 / 180 large ones, not by L2 bandwidth.)
-            LTG_PROBED(pr, LTG_K_D_L1, hipLaunchKernelGGL((fk8t_d_l1<64, 64>), dim3((h1 + 63) / 64 + (h2 + 63) / 64, NP / 64), dim3(NT), 0, st, pv, h0, h1, h2, NP,
-                                                          d->emb_fp8, d->w1t_fp8, d->p[1], d->w2t_fp8, d->p[3], dA, dB, keep, cfg->seed, step, w.dA1T_16, w.A1_8, w.A1T_8));
-            LTG_PROBED(pr, LTG_K_D_L2, hipLaunchKernelGGL((fk8s_d_l2<64, 64>), grid2(h3, n, 64, 64), dim3(NT), 0, st, n, h12, h3, w.A1_8, d->w3t_fp8, d->p[5], dC, keep,
-                                                          cfg->seed, step, w.A3));
-            hipLaunchKernelGGL(k8_d_out, dim3(NP / 16), dim3(NT), 0, st, pv, h3, NP, w.A3, d->p[6], d->p[7], keep, w.y, w.ds, w.lrow, w.dpre3_8, w.dpre3T_8);
-            return;
-        }
-        if (staged) {
-            // 64 x 64 tiles: 696 workgroups of 37 KB LDS, three or four per CU hide each other's load latency (measured at 1 820 pair
-            // rows: 30-32 us; 128 x 128 tiles = 180 workgroups, one per CU, 54 us; 128 x 64: 60 us; register-resident block: 52 us)
-            LTG_PROBED(pr, LTG_K_D_L1, hipLaunchKernelGGL((fk8s_d_l1<64, 64>), dim3((h1 + 63) / 64 + (h2 + 63) / 64, (n + 63) / 64), dim3(NT), 0, st, pv, h0, h1, h2,
-                                                          d->emb_fp8, d->w1t_fp8, d->p[1], d->w2t_fp8, d->p[3], dA, dB, keep, cfg->seed, step, w.A1, w.A1_8));
-            LTG_PROBED(pr, LTG_K_D_L2, hipLaunchKernelGGL((fk8s_d_l2<64, 64>), grid2(h3, n, 64, 64), dim3(NT), 0, st, n, h12, h3, w.A1_8, d->w3t_fp8, d->p[5], dC, keep,
-                                                          cfg->seed, step, w.A3));
-        } else {
-        LTG_PROBED(pr, LTG_K_D_L1, hipLaunchKernelGGL(fk8_d_l1, dim3(8 * (((h1 + 63) / 64 + (h2 + 63) / 64 + 7) / 8) * ((n + 63) / 64)), dim3(NT), 0, st, pv, h0, h1, h2, d->emb_fp8, d->w1t_fp8, d->p[1],
+    // fp8 with operand-format storage: both forward layers read e4m3 bytes (embedding table, transposed weight shadows, A1 in e4m3)
+    const dim3 g8l1((h1 + 63) / 64 + (h2 + 63) / 64, (n + 63) / 64);
+    if (r.kind == LTG_D_FP8_OPFMT) {
+        // the step's own forward: the same products, and every activation the backward multiplies is left behind in e4m3 in the
+        // orientation its GEMM contracts over (ltg_fp8bwd.h)
+        const int NP = d8_np(n);
+        hipLaunchKernelGGL(k8_gather_t, dim3(h0 / 64, NP / 64, 2), dim3(NT), 0, st, pv, h0, NP, d->emb_fp8, w.ET_8);
+        // (Round 5, measured and removed: the branch layers' product on 128 x 64 / 128 x 128 tiles -- half the operand bytes through the L1s per
+        // output -- ran 38.3 / 72.1 us against the 64 x 64 tiles' 30.1 us on the same box: the loop is bound by the latency of its staged K
+        // blocks, which 720 small workgroups hide better than 360 / 180 large ones, not by L2 bandwidth.)
+        LTG_PROBED(pr, LTG_K_D_L1, hipLaunchKernelGGL((fk8t_d_l1<64, 64>), dim3(g8l1.x, NP / 64), dim3(NT), 0, st, pv, h0, h1, h2, NP,
+                                                      d->emb_fp8, d->w1t_fp8, d->p[1], d->w2t_fp8, d->p[3], dA, dB, keep, cfg->seed, step, w.dA1T_16, w.A1_8, w.A1T_8));
+    } else if (r.kind == LTG_D_FP8_STAGED) {
+        // 64 x 64 tiles: 696 workgroups of 37 KB LDS, three or four per CU hide each other's load latency (measured at 1 820 pair
+        // rows: 30-32 us; 128 x 128 tiles = 180 workgroups, one per CU, 54 us; 128 x 64: 60 us; register-resident block: 52 us)
+        LTG_PROBED(pr, LTG_K_D_L1, hipLaunchKernelGGL((fk8s_d_l1<64, 64>), g8l1, dim3(NT), 0, st, pv, h0, h1, h2,
+                                                      d->emb_fp8, d->w1t_fp8, d->p[1], d->w2t_fp8, d->p[3], dA, dB, keep, cfg->seed, step, w.A1, w.A1_8));
+    } else if (r.kind == LTG_D_FP8_REG) {
+        LTG_PROBED(pr, LTG_K_D_L1, hipLaunchKernelGGL(fk8_d_l1, dim3(8 * ((g8l1.x + 7) / 8) * g8l1.y), dim3(NT), 0, st, pv, h0, h1, h2, d->emb_fp8, d->w1t_fp8, d->p[1],
                                                       d->w2t_fp8, d->p[3], dA, dB, keep, cfg->seed, step, w.A1, w.A1_8));
         LTG_PROBED(pr, LTG_K_D_L2, hipLaunchKernelGGL(fk8_d_l2, grid2(h3, n, 64, 64), dim3(NT), 0, st, n, h12, h3, w.A1_8, d->w3t_fp8, d->p[5], dC, keep,
                                                       cfg->seed, step, w.A3));
-        }
-        const dim3 go8((n + NT / 64 - 1) / (NT / 64));
-        if (with_bwd) hipLaunchKernelGGL(k_d_out<true>, go8, dim3(NT), 0, st, pv, h3, w.A3, d->p[6], d->p[7], keep, w.y, w.ds, w.lrow, w.dpre3);
-        else hipLaunchKernelGGL(k_d_out<false>, go8, dim3(NT), 0, st, pv, h3, w.A3, d->p[6], d->p[7], keep, w.y, w.ds, w.lrow, w.dpre3);
-        return;
+    } else {
+        const int md = r.mode, ts = r.tile[0], ts2 = r.tile[1], t1 = ts < 0 ? 32 : ts, t2 = ts2 < 0 ? 32 : ts2;
+        LTG_PROBED(pr, LTG_K_D_L1, LTG_D_DISPATCH(k_d_l1, md, ts, grid2(nmax, n, t1, t1, 2), st, pv, h0, h1, h2, d->emb, d->p[0], d->p[1], d->p[2],
+                                                  d->p[3], dA, dB, keep, cfg->seed, step, w.A1));
+        LTG_PROBED(pr, LTG_K_D_L2, LTG_D_DISPATCH(k_d_l2, md, ts2, grid2(h3, n, t2, t2), st, n, h12, h3, w.A1, d->p[4], d->p[5], dC, keep, cfg->seed, step, w.A3));
     }
-    LTG_PROBED(pr, LTG_K_D_L1, LTG_D_DISPATCH(k_d_l1, md, ts, grid2(nmax, n, t1, t1, 2), st, pv, h0, h1, h2, d->emb, d->p[0], d->p[1], d->p[2],
-                                              d->p[3], dA, dB, keep, cfg->seed, step, w.A1));
-    LTG_PROBED(pr, LTG_K_D_L2, LTG_D_DISPATCH(k_d_l2, md, ts2, grid2(h3, n, t2, t2), st, n, h12, h3, w.A1, d->p[4], d->p[5], dC, keep, cfg->seed, step, w.A3));
+    if (r.kind == LTG_D_FP8_OPFMT || r.kind == LTG_D_FP8_STAGED)
+        LTG_PROBED(pr, LTG_K_D_L2, hipLaunchKernelGGL((fk8s_d_l2<64, 64>), grid2(h3, n, 64, 64), dim3(NT), 0, st, n, h12, h3, w.A1_8, d->w3t_fp8, d->p[5], dC, keep,
+                                                      cfg->seed, step, w.A3));
     const dim3 go((n + NT / 64 - 1) / (NT / 64));
-    if (with_bwd) hipLaunchKernelGGL(k_d_out<true>, go, dim3(NT), 0, st, pv, h3, w.A3, d->p[6], d->p[7], keep, w.y, w.ds, w.lrow, w.dpre3);
+    if (r.kind == LTG_D_FP8_OPFMT)
+        hipLaunchKernelGGL(k8_d_out, dim3(d8_np(n) / 16), dim3(NT), 0, st, pv, h3, d8_np(n), w.A3, d->p[6], d->p[7], keep, w.y, w.ds, w.lrow, w.dpre3_8, w.dpre3T_8);
+    else if (with_bwd) hipLaunchKernelGGL(k_d_out<true>, go, dim3(NT), 0, st, pv, h3, w.A3, d->p[6], d->p[7], keep, w.y, w.ds, w.lrow, w.dpre3);
     else hipLaunchKernelGGL(k_d_out<false>, go, dim3(NT), 0, st, pv, h3, w.A3, d->p[6], d->p[7], keep, w.y, w.ds, w.lrow, w.dpre3);
 }
 
@@ -699,6 +800,12 @@ int32_t ltg_abi_version(void) { return LTG_ABI_VERSION; }
 size_t ltg_workspace_bytes(const ltg_config* cfg, int32_t max_rows, int32_t max_pairs) {
     if (!cfg_ok(cfg) || max_rows < 0 || max_pairs < 0) return 0;
     return carve(cfg, max_rows < 1 ? 1 : max_rows, max_pairs < 1 ? 1 : max_pairs, nullptr).bytes;
+}
+// The workspace of a call with `rows` batch rows and `pairs` pair rows in the caller's buffer, or LTG_EWORKSPACE when that is too small
+static int carve_checked(const ltg_config* cfg, int rows, int pairs, void* ws, size_t ws_bytes, Workspace* w) {
+    if (ltg_workspace_bytes(cfg, rows, pairs) > ws_bytes) return LTG_EWORKSPACE;
+    *w = carve(cfg, rows, pairs, (char*)ws);
+    return LTG_OK;
 }
 
 int ltg_vae_forward(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_batch* batch, const ltg_fwd_opts* opts,
@@ -736,27 +843,16 @@ int ltg_sample_pairs(const ltg_config* cfg, const ltg_sample_inputs* in, const f
     return check_launch();
 }
 
-// One Adam sweep of the discriminator from `ks` gradient slabs of stride `stride` (lrow: the per-row loss terms of the
-// round-1 kernels, else the loss sits in slot P of the slabs)
-// one flat float4 sweep (fk_d_adam) when the eight tensors (and moments) lie back to back -- and no operand-format shadows have to follow
-// the weights (fp8 mode: k_d_adam rewrites the e4m3 copies of the three matrices it updates)
-static bool d_adam_flat(const ltg_config* cfg, const ltg_disc_state* disc, const DLayout& L, int stride, const float* slab, const float* lrow) {
-    bool flat = lrow == nullptr && (stride % 4) == 0 && !(cfg->d_precision == LTG_PREC_FP8 && disc->w1t_fp8);
-    for (int i = 0; i < 7; ++i) {
-        const size_t sz = (size_t)(L.off[i + 1] - L.off[i]);
-        flat = flat && disc->p[i + 1] == disc->p[i] + sz && disc->m[i + 1] == disc->m[i] + sz && disc->v[i + 1] == disc->v[i] + sz;
-    }
-    return flat && ((uintptr_t)disc->p[0] % 16) == 0 && ((uintptr_t)disc->m[0] % 16) == 0 && ((uintptr_t)disc->v[0] % 16) == 0 &&
-           ((uintptr_t)slab % 16) == 0;
-}
-static void d_apply(const ltg_config* cfg, const ltg_disc_state* disc, const DLayout& L, int ks, int stride, const float* slab, int n,
+// One Adam sweep of the discriminator (adam: LTG_D_ADAM_*, see d_adam_kind) from `ks` gradient slabs of stride `stride` (lrow: the
+// per-row loss terms of the round-1 kernels, else the loss sits in slot P of the slabs)
+static void d_apply(const ltg_config* cfg, const ltg_disc_state* disc, int adam, const DLayout& L, int ks, int stride, const float* slab, int n,
                     const float* lrow, const AdamC& ad, float* loss_out, const Probe& pr, hipStream_t st, const unsigned* poison = nullptr) {
     const int P = L.off[8];
-    const bool flat = d_adam_flat(cfg, disc, L, stride, slab, lrow);
+    const bool flat = adam == LTG_D_ADAM_FLAT;
     int ga = ((flat ? P / 4 : P) + NT - 1) / NT;
     if (ga > 1024) ga = 1024;
     if (ga < 1) ga = 1;
-    if (d_fp8_opfmt(cfg, disc)) {
+    if (adam == LTG_D_ADAM_FP8) {
         // operand-format shadows follow the weights: tile-wise sweep with the transposed e4m3 copies written through LDS
         const int h0 = cfg->d_h0, h1 = cfg->d_h1, h2 = cfg->d_h2, h3 = cfg->d_h3;
         const int nt1 = (h0 / 64) * (h1 / 64), nt2 = (h0 / 64) * (h2 / 64), nt3 = ((h1 + h2) / 64) * (h3 / 64);
@@ -773,20 +869,22 @@ static void d_apply(const ltg_config* cfg, const ltg_disc_state* disc, const DLa
 
 // forward + backward of the pair rows in `pv` into gradient slabs; then either the Adam sweep (grad_out == NULL: the
 // whole step, train.py:300) or one summed gradient vector in grad_out (this rank's share: ltg_d_grad)
-#ifndef LTG_D_FORK_MIN_ROWS
-#define LTG_D_FORK_MIN_ROWS 1024
-#endif
 static int d_step_impl(const ltg_config* cfg, const ltg_disc_state* disc, PairView pv, DropView dA, DropView dB, DropView dC,
                        const ltg_d_opts* o, float* grad_out, float* loss_out, const Workspace& w, hipStream_t st) {
     const int n = pv.nr + pv.nf;
     const int h0 = cfg->d_h0, h1 = cfg->d_h1, h2 = cfg->d_h2, h3 = cfg->d_h3, h12 = h1 + h2;
-    disc_forward(cfg, disc, pv, dA, dB, dC, o->keep_prob, o->rng_step, w, true, o->probe, st);
+    const ltg_d_route_info r = d_route(cfg, disc, n, true, o->aux_stream && o->sync && !grad_out, w.slab);
+    disc_forward(cfg, disc, r, pv, dA, dB, dC, o->keep_prob, o->rng_step, w, true, o->probe, st);
     const Probe pr{o->probe, st};
     const AdamC ad = make_adam(cfg, o->adam_t > 0 ? o->adam_t : 1);
     const DLayout L = d_layout(h0, h1, h2, h3);
-    const int ks = (n + D_KCHUNK - 1) / D_KCHUNK;
-    if (d_fast(cfg)) {
-        const int P = L.off[8], SP = d_slab_stride(P), ntile = (h3 + 31) / 32;
+    const int ks = (n + D_KCHUNK - 1) / D_KCHUNK, P = L.off[8], SP = d_slab_stride(P);
+    // what the sweep (or the gradient sum) behind the two backward stages reads: slabs, their stride, the per-row loss terms of n rows
+    int n_slabs = ks, stride = SP, n_lrow = n;
+    const float* lrow = w.lrow;
+    const unsigned* poison = nullptr;
+    if (r.kind == LTG_D_FAST) {
+        const int ntile = (h3 + 31) / 32;
         const int nA = (((n + 31) / 32) * ((h12 + 31) / 32) + 7) & ~7;      // padded: job B starts on a multiple of 8 (XCD chunk map)
         const int nB = ks * ((h12 + 1 + 31) / 32) * ((h3 + 31) / 32);
         const int nC = ks * ((h3 + 2 + 31) / 32);
@@ -797,15 +895,10 @@ static int d_step_impl(const ltg_config* cfg, const ltg_disc_state* disc, PairVi
         // gave up = poison, the sweep then returns at once).  (Measured and not kept, same round: the same jobs riding in stage 2's OWN
         // launch instead of beside job A: 59.5-59.6 -> 61.3-61.6 us per step; profiles/r4_d_step_floor.txt, which also has the step's
         // launch structure: the five grids returning at once take 18 us.)
-        // (only with the FLAT tensor layout: the poison word reaches fk_d_adam alone -- separate tensors take k_d_adam, which has no early
-        // return, so a direct C-ABI caller with that layout keeps the whole step on one stream)
-        // (Round 6: only from LTG_D_FORK_MIN_ROWS pair rows.  At the ~300 rows per step of the synthetic tables the two jobs are one or two slabs of work and
-        // the fork's two gate kernels and its poll cost more than they hide -- and not steadily: D step 32.6-38.9 us with the fork against 34.1 +- 0.1
-        // without at 20 000 items, 34.1-38.2 against 32.4 at 200 000 -- profiles/r6_ab_d_fork_small.txt.  Either way the same kernels write the same slab
-        // entries: same bits.)
-        const bool fork = o->aux_stream && o->sync && !grad_out && n >= LTG_D_FORK_MIN_ROWS && d_adam_flat(cfg, disc, L, SP, w.slab, nullptr);
-        const unsigned* poison = fork ? o->sync + 2 : nullptr;
-        const int spl1 = d_spl(cfg, 2), spl2 = d_spl(cfg, 3);
+        // (when it is taken: d_route)
+        const bool fork = r.fork != 0;
+        if (fork) poison = o->sync + 2;
+        const int spl1 = r.spl[2], spl2 = r.spl[3];
         LTG_PROBED(pr, LTG_K_D_BWD1, LTG_D_SPL_LAUNCH(spl1, fk_d_bwd1, dim3(fork ? nA : nA + nB + nC), dim3(NT), 0, st, pv, h12, h3, nA, nB, ntile, L, SP, w.A1, w.A3, w.G3,
                                                       w.spart, disc->p[7], disc->p[4], o->keep_prob, w.dpre1, w.slab,
                                                       fork ? LtgGate{o->sync, o->seq, nullptr, 0} : LTG_NO_GATE));
@@ -819,13 +912,11 @@ static int d_step_impl(const ltg_config* cfg, const ltg_disc_state* disc, PairVi
         const int n2 = ks * ((h0 + 1 + 15) / 16) * ((h1 + 31) / 32 + (h2 + 31) / 32);
         LTG_PROBED(pr, LTG_K_D_BWD2, LTG_D_SPL_LAUNCH(spl2, fk_d_bwd2, dim3(n2 + (fork ? 1 : 0)), dim3(DB2_NT), 0, st, pv, h0, h1, h2, L, SP, disc->emb, w.dpre1, w.slab,
                                                       fork ? LtgGate{o->sync + 1, o->seq, o->sync + 2, 0} : LTG_NO_GATE));
-        if (grad_out) hipLaunchKernelGGL(k_d_grad_sum, dim3(64), dim3(NT), 0, st, ks, P, SP, w.slab, 0, (const float*)nullptr, grad_out);
-        else d_apply(cfg, disc, L, ks, SP, w.slab, 0, nullptr, ad, loss_out, pr, st, poison);
-        return check_launch();
-    }
-    if (d_fp8_opfmt(cfg, disc)) {
+        n_lrow = 0;      // (the loss sits in slot P of the slabs)
+        lrow = nullptr;
+    } else if (r.kind == LTG_D_FP8_OPFMT) {
         // fp8 operands in operand format (ltg_fp8bwd.h): the forward left A1^T, dpre3, dpre3^T and the gathered embeddings^T behind
-        const int NP = d8_np(n), P = L.off[8], SP = d_slab_stride(P), ks8 = (NP + D8_KCHUNK - 1) / D8_KCHUNK;
+        const int NP = d8_np(n), ks8 = (NP + D8_KCHUNK - 1) / D8_KCHUNK;
         const int nA = (NP / 64) * ((h12 + 63) / 64);
         const int nB = ks8 * ((h12 + 1 + 63) / 64) * ((h3 + 63) / 64);
         const int nC = ks8 * ((h3 + 1 + 31) / 32);
@@ -833,28 +924,23 @@ static int d_step_impl(const ltg_config* cfg, const ltg_disc_state* disc, PairVi
                                                         w.A1T_8, disc->w3_fp8, o->keep_prob, w.dpre1T_8, w.slab));
         const int n2 = ks8 * ((h0 + 1 + 63) / 64) * (h1 / 64 + h2 / 64);
         LTG_PROBED(pr, LTG_K_D_BWD2, hipLaunchKernelGGL(k8_d_bwd2, dim3(n2), dim3(NT), 0, st, NP, h0, h1, h2, L, SP, w.ET_8, w.dpre1T_8, w.slab));
-        if (grad_out) hipLaunchKernelGGL(k_d_grad_sum, dim3(64), dim3(NT), 0, st, ks8, P, SP, w.slab, n, w.lrow, grad_out);
-        else d_apply(cfg, disc, L, ks8, SP, w.slab, n, w.lrow, ad, loss_out, pr, st);
-        return check_launch();
+        n_slabs = ks8;
+    } else {
+        // stage 1 (products with the OLD w3) and stage 2 only write gradient slabs; the single Adam sweep runs last
+        const int md = r.mode, ts = r.tile[2], tsb = r.tile[3], ta = ts < 0 ? 32 : ts, tb = tsb < 0 ? 32 : tsb;
+        auto tiles = [ta](int x) { return (x + ta - 1) / ta; };
+        auto tilesb = [tb](int x) { return (x + tb - 1) / tb; };
+        const int nA = tiles(n) * tiles(h12);
+        const int nB = ks * tiles(h12 + 1) * tiles(h3);
+        const int nC = ks * ((h3 + 1 + 31) / 32);
+        LTG_PROBED(pr, LTG_K_D_BWD1, LTG_D_DISPATCH(k_d_bwd1, md, ts, dim3(nA + nB + nC), st, n, h12, h3, nA, nB, ks, L, w.A1, w.A3, w.ds, w.dpre3, disc->p[4],
+                                                    o->keep_prob, w.dpre1, w.slab));
+        const int n2 = ks * tilesb(h0 + 1) * (tilesb(h1) + tilesb(h2));
+        LTG_PROBED(pr, LTG_K_D_BWD2, LTG_D_DISPATCH(k_d_bwd2, md, tsb, dim3(n2), st, pv, h0, h1, h2, ks, L, disc->emb, w.dpre1, w.slab));
+        stride = P;      // (these kernels do not pad their slabs)
     }
-    // stage 1 (products with the OLD w3) and stage 2 only write gradient slabs; the single Adam sweep runs last
-    int ts = d_tile(cfg, 2);
-    {   // backward stage 1 with > 1024 32 x 32 tiles is throughput-bound, not latency-bound: 64 x 64 tiles (measured -5 %)
-        const long t32 = (long)((n + 31) / 32) * ((h12 + 31) / 32) + (long)ks * ((h12 + 32) / 32) * ((h3 + 31) / 32);
-        if (ts == -32 && t32 > 1024) ts = 64;
-    }
-    const int md = d_mode(cfg), tsb = d_tile(cfg, 3), ta = ts < 0 ? 32 : ts, tb = tsb < 0 ? 32 : tsb;
-    auto tiles = [ta](int x) { return (x + ta - 1) / ta; };
-    auto tilesb = [tb](int x) { return (x + tb - 1) / tb; };
-    const int nA = tiles(n) * tiles(h12);
-    const int nB = ks * tiles(h12 + 1) * tiles(h3);
-    const int nC = ks * ((h3 + 1 + 31) / 32);
-    LTG_PROBED(pr, LTG_K_D_BWD1, LTG_D_DISPATCH(k_d_bwd1, md, ts, dim3(nA + nB + nC), st, n, h12, h3, nA, nB, ks, L, w.A1, w.A3, w.ds, w.dpre3, disc->p[4],
-                                                o->keep_prob, w.dpre1, w.slab));
-    const int n2 = ks * tilesb(h0 + 1) * (tilesb(h1) + tilesb(h2));
-    LTG_PROBED(pr, LTG_K_D_BWD2, LTG_D_DISPATCH(k_d_bwd2, md, tsb, dim3(n2), st, pv, h0, h1, h2, ks, L, disc->emb, w.dpre1, w.slab));
-    if (grad_out) hipLaunchKernelGGL(k_d_grad_sum, dim3(64), dim3(NT), 0, st, ks, L.off[8], L.off[8], w.slab, n, w.lrow, grad_out);
-    else d_apply(cfg, disc, L, ks, L.off[8], w.slab, n, w.lrow, ad, loss_out, pr, st);
+    if (grad_out) hipLaunchKernelGGL(k_d_grad_sum, dim3(64), dim3(NT), 0, st, n_slabs, P, stride, w.slab, n_lrow, lrow, grad_out);
+    else d_apply(cfg, disc, r.adam, L, n_slabs, stride, w.slab, n_lrow, lrow, ad, loss_out, pr, st, poison);
     return check_launch();
 }
 
@@ -865,10 +951,10 @@ int ltg_d_step(const ltg_config* cfg, const ltg_disc_state* disc, const ltg_pair
     if (!cfg_ok(cfg) || !disc || !real || !fake || !o || !loss_out || !ws || o->adam_t < 1) return LTG_EINVAL;
     const int n = real->n + fake->n;
     if (real->n < 0 || fake->n < 0) return LTG_EINVAL;
-    if (ltg_workspace_bytes(cfg, 1, n) > ws_bytes) return LTG_EWORKSPACE;
+    Workspace w;
+    if (carve_checked(cfg, 1, n, ws, ws_bytes, &w) != LTG_OK) return LTG_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     if (n == 0) return hipMemsetAsync(loss_out, 0, sizeof(float), st) == hipSuccess ? LTG_OK : LTG_ELAUNCH;
-    const Workspace w = carve(cfg, 1, n, (char*)ws);
     PairView pv{real->n, fake->n, real->pop, real->niche, fake->pop, fake->niche};
     DropView dA{o->drop_real[0], o->drop_fake[0], real->n, 0}, dB{o->drop_real[1], o->drop_fake[1], real->n, 0},
         dC{o->drop_real[2], o->drop_fake[2], real->n, 0};
@@ -890,8 +976,8 @@ int ltg_d_grad(const ltg_config* cfg, const ltg_disc_state* disc, const ltg_pair
     const size_t gf = ltg_d_grad_floats(cfg);
     const int m = row_hi - row_lo;
     if (m == 0) return hipMemsetAsync(grad_out, 0, gf * sizeof(float), st) == hipSuccess ? LTG_OK : LTG_ELAUNCH;
-    if (ltg_workspace_bytes(cfg, 1, m) > ws_bytes) return LTG_EWORKSPACE;
-    const Workspace w = carve(cfg, 1, m, (char*)ws);
+    Workspace w;
+    if (carve_checked(cfg, 1, m, ws, ws_bytes, &w) != LTG_OK) return LTG_EWORKSPACE;
     // the sub-range [row_lo, row_hi) of the logical concatenation real | fake is again a (real, fake) pair of ranges
     const int r0 = row_lo < real->n ? row_lo : real->n, r1 = row_hi < real->n ? row_hi : real->n;
     const int f0 = (row_lo > real->n ? row_lo : real->n) - real->n, f1 = (row_hi > real->n ? row_hi : real->n) - real->n;
@@ -912,7 +998,8 @@ int ltg_d_apply(const ltg_config* cfg, const ltg_disc_state* disc, const float* 
     if (!cfg_ok(cfg) || !disc || !grad || !loss_out || adam_t < 1) return LTG_EINVAL;
     const DLayout L = d_layout(cfg->d_h0, cfg->d_h1, cfg->d_h2, cfg->d_h3);
     const Probe pr{nullptr, (hipStream_t)stream};
-    d_apply(cfg, disc, L, 1, d_slab_stride(L.off[8]), grad, 0, nullptr, make_adam(cfg, adam_t), loss_out, pr, (hipStream_t)stream);
+    const int stride = d_slab_stride(L.off[8]);
+    d_apply(cfg, disc, d_adam_kind(cfg, disc, stride, grad, false), L, 1, stride, grad, 0, nullptr, make_adam(cfg, adam_t), loss_out, pr, (hipStream_t)stream);
     return check_launch();
 }
 
@@ -920,51 +1007,32 @@ int ltg_d_apply(const ltg_config* cfg, const ltg_disc_state* disc, const float* 
 // pre-activation [B,H] (all-reduce), (2) the row partials [B,5] (all-gather), (3) dh2 [B,H] (all-reduce).
 // ltg_g_step runs the same stages back to back with one "rank".
 
-static void g_row_partial(const ltg_config* cfg, const ltg_batch* bt, const ltg_pairs* fake, const ltg_gen_acts* acts,
-                          float* rowpart, hipStream_t st, float* segpart = nullptr, float* lse = nullptr, int stat_groups = 0) {
-    const int I = cfg->n_items, B = bt->n_rows;
-    if (stat_groups > 0) {   // the decoder kernel left its statistics in segpart
-        hipLaunchKernelGGL(k_row_stats_merge, dim3(B), dim3(NT), 0, st, B, stat_groups, I, cfg->item_lo, segpart, bt->indptr, bt->indices, bt->values,
-                           acts->logits, fake ? fake->n : 0, fake ? fake->row : nullptr, fake ? fake->niche : nullptr, fake ? fake->pop : nullptr,
-                           rowpart, lse);
-        return;
-    }
-    if (segpart && I > 2 * RS_SEG) {
-        const int nseg = (I + RS_SEG - 1) / RS_SEG;
-        hipLaunchKernelGGL(k_row_partial_seg, dim3(nseg, B), dim3(NT), 0, st, I, cfg->item_lo, bt->indptr, bt->indices, bt->values, acts->logits,
-                           fake ? fake->n : 0, fake ? fake->row : nullptr, fake ? fake->niche : nullptr, fake ? fake->pop : nullptr, segpart);
-        hipLaunchKernelGGL(k_row_partial_merge, dim3(B), dim3(64), 0, st, B, nseg, segpart, rowpart, lse);
-        return;
-    }
-    hipLaunchKernelGGL(k_row_partial, dim3(bt->n_rows), dim3(NT), 0, st, cfg->n_items, cfg->item_lo, bt->indptr, bt->indices, bt->values,
-                       acts->logits, fake ? fake->n : 0, fake ? fake->row : nullptr, fake ? fake->niche : nullptr,
-                       fake ? fake->pop : nullptr, rowpart);
+// The forward-only fake tower (y_data is pruned from the g_trainer fetch, train.py:326): y of the fake pairs into w.y, or y_dst
+static void fake_tower(const ltg_config* cfg, const ltg_disc_state* disc, const ltg_pairs* fake, DropView dA, DropView dB, DropView dC, float keep,
+                       uint64_t step, const Workspace& w, const ltg_probe* probe, hipStream_t st, float* y_dst = nullptr) {
+    const PairView pv{0, fake->n, nullptr, nullptr, fake->pop, fake->niche};
+    disc_forward(cfg, disc, d_route(cfg, disc, fake->n, false), pv, dA, dB, dC, keep, step, w, false, probe, st, y_dst);
+}
+// ... of one G step: its masks (or injected keep flags) and its counter
+static void fake_tower(const ltg_config* cfg, const ltg_disc_state* disc, const ltg_pairs* fake, const ltg_g_opts* o, const Workspace& w,
+                       const ltg_probe* probe, hipStream_t st) {
+    fake_tower(cfg, disc, fake, DropView{nullptr, o->drop_fake[0], 0, 0}, DropView{nullptr, o->drop_fake[1], 0, 0}, DropView{nullptr, o->drop_fake[2], 0, 0},
+               o->d_keep_prob, o->d_rng_step, w, probe, st);
 }
 
-// dlog as bf16: when BOTH its consumers are the streaming kernels (k_dh2_stream, k_dec1_bwd_adam_stream + ragged tail)
-static bool dlog16_ok(const ltg_config* cfg, const ltg_gen_state* gen, int B) {
-    return fast_on(cfg) && stream_ok(cfg, gen, B) && dw_stream_ok(cfg->h_enc) && (cfg->tuning & (1 << 22)) == 0;
-}
-
-static int g_stage_bwd_dec(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_disc_state* disc, const ltg_batch* bt,
+static int g_stage_bwd_dec(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_disc_state* disc, const ltg_g_route_info& r, const ltg_batch* bt,
                            const ltg_pairs* fake, const ltg_g_opts* o, const ltg_gen_acts* acts, const float* rowpart_all,
                            int n_ranks, float* loss_out, const Workspace& w, float* dh2_out, hipStream_t st,
                            bool disc_done = false, const float* h2_for_da2 = nullptr) {
     const int B = bt->n_rows, I = cfg->n_items, H = cfg->h_enc, nf = fake->n;
     const Probe pr{o->probe, st};
-    // fake tower forward only (y_data is pruned from the g_trainer fetch, train.py:326); replicated on every rank
-    if (nf > 0 && !disc_done) {
-        PairView pv{0, nf, nullptr, nullptr, fake->pop, fake->niche};
-        DropView dA{nullptr, o->drop_fake[0], 0, 0}, dB{nullptr, o->drop_fake[1], 0, 0}, dC{nullptr, o->drop_fake[2], 0, 0};
-        disc_forward(cfg, disc, pv, dA, dB, dC, o->d_keep_prob, o->d_rng_step, w, false, o->probe, st);
-    }
-    const bool d16 = dlog16_ok(cfg, gen, B);
-    if (fast_on(cfg)) {
+    if (nf > 0 && !disc_done) fake_tower(cfg, disc, fake, o, w, o->probe, st);   // replicated on every rank
+    if (r.loss != LTG_LOSS_GENERIC) {
 #define LTG_DLC(D16)                                                                                                                                \
     hipLaunchKernelGGL(k_dlogits_combine<D16>, dim3((I + DL_SEG - 1) / DL_SEG, B), dim3(NT), 0, st, B, I, n_ranks, bt->indptr, bt->indices, bt->values, \
                        acts->logits, rowpart_all, acts->kl_rows, nf > 0 ? w.y : (const float*)nullptr, o->cnt, o->anneal, o->gan_lambda, nf,       \
                        fake->row, fake->niche, fake->pop, w.dlog, acts->lse, w.scal, loss_out, cfg->item_lo)
-        if (d16) LTG_DLC(true);
+        if (r.dlog_bf16) LTG_DLC(true);
         else LTG_DLC(false);
 #undef LTG_DLC
     } else {
@@ -973,46 +1041,47 @@ static int g_stage_bwd_dec(const ltg_config* cfg, const ltg_gen_state* gen, cons
     hipLaunchKernelGGL(k_dlogits, dim3((I + DL_SEG - 1) / DL_SEG, B), dim3(NT), 0, st, B, I, bt->indptr, bt->indices, bt->values,
                        acts->logits, acts->lse, w.nb, w.Pb, w.scal, nf, fake->row, fake->niche, fake->pop, w.dlog, cfg->item_lo);
     }
-    const bool stream = stream_ok(cfg, gen, B);
-    const int kchunk = stream ? dh2_stream_chunk(I) : dh2_kchunk(I);
-    const int nsplit = (I + kchunk - 1) / kchunk;
+    const int kchunk = r.dh2_chunk, nsplit = r.dh2_nsplit;
     const bool bf = cfg->precision == LTG_PREC_BF16;
-    const bool big = I >= 8192;
     pr.before(LTG_K_DH2);
-    if (stream && d16) hipLaunchKernelGGL((k_dh2_stream<true, DH2_NH>), dim3(nsplit, DH2_NH), dim3(ST_NT), (size_t)2 * ST_BN * ST_LDW * 2, st, B, I, H, kchunk, w.dlog, gen->wp1t_bf16, w.part);
-    else if (stream) hipLaunchKernelGGL((k_dh2_stream<false, DH2_NH>), dim3(nsplit, DH2_NH), dim3(ST_NT), (size_t)2 * ST_BN * ST_LDW * 2, st, B, I, H, kchunk, w.dlog, gen->wp1t_bf16, w.part);
-    else if (bf && big) hipLaunchKernelGGL((k_dh2_partial<true, true>), grid2(H, B, 64, 128, nsplit), dim3(NT), 0, st, B, I, H, kchunk, w.dlog, gen->p[3], w.part);
-    else if (bf && (I % 4) == 0) hipLaunchKernelGGL((k_dh2_partial<true, false, true>), grid2(H, B, 32, 32, nsplit), dim3(NT), 0, st, B, I, H, kchunk, w.dlog, gen->p[3], w.part);
+    if (r.dh2 == LTG_DH2_STREAM) {
+        if (r.dlog_bf16) hipLaunchKernelGGL((k_dh2_stream<true, DH2_NH>), dim3(nsplit, DH2_NH), dim3(ST_NT), (size_t)2 * ST_BN * ST_LDW * 2, st, B, I, H, kchunk, w.dlog, gen->wp1t_bf16, w.part);
+        else hipLaunchKernelGGL((k_dh2_stream<false, DH2_NH>), dim3(nsplit, DH2_NH), dim3(ST_NT), (size_t)2 * ST_BN * ST_LDW * 2, st, B, I, H, kchunk, w.dlog, gen->wp1t_bf16, w.part);
+    } else if (r.dh2_tile == 128) {
+        if (bf) hipLaunchKernelGGL((k_dh2_partial<true, true>), grid2(H, B, 64, 128, nsplit), dim3(NT), 0, st, B, I, H, kchunk, w.dlog, gen->p[3], w.part);
+        else hipLaunchKernelGGL((k_dh2_partial<false, true>), grid2(H, B, 64, 128, nsplit), dim3(NT), 0, st, B, I, H, kchunk, w.dlog, gen->p[3], w.part);
+    } else if (r.dh2_tile == -32) hipLaunchKernelGGL((k_dh2_partial<true, false, true>), grid2(H, B, 32, 32, nsplit), dim3(NT), 0, st, B, I, H, kchunk, w.dlog, gen->p[3], w.part);
     else if (bf) hipLaunchKernelGGL((k_dh2_partial<true, false>), grid2(H, B, 32, 32, nsplit), dim3(NT), 0, st, B, I, H, kchunk, w.dlog, gen->p[3], w.part);
-    else if (big) hipLaunchKernelGGL((k_dh2_partial<false, true>), grid2(H, B, 64, 128, nsplit), dim3(NT), 0, st, B, I, H, kchunk, w.dlog, gen->p[3], w.part);
     else hipLaunchKernelGGL((k_dh2_partial<false, false>), grid2(H, B, 32, 32, nsplit), dim3(NT), 0, st, B, I, H, kchunk, w.dlog, gen->p[3], w.part);
     pr.after(LTG_K_DH2);
-    {
-        const int n = B * H;
-        const int gx = (n + NT - 1) / NT < 2048 ? (n + NT - 1) / NT : 2048;
-        // slab sum; the single-GPU path folds the tanh derivative in (dh2_out is then already da2)
-        hipLaunchKernelGGL(k_da2, dim3(gx), dim3(NT), 0, st, n, nsplit, w.part, h2_for_da2, dh2_out);
-    }
+    // slab sum; the single-GPU path folds the tanh derivative in (dh2_out is then already da2)
+    hipLaunchKernelGGL(k_da2, grid1(B * H, 2048), dim3(NT), 0, st, B * H, nsplit, w.part, h2_for_da2, dh2_out);
     return check_launch();
 }
 
-// item -> gradient-row map of the batch: the caller's cache, or rebuilt in the workspace (ltg_batch.slot == NULL)
+// item -> gradient-row map of the batch: the caller's cache, or rebuilt in the workspace (ltg_batch.slot == NULL: no per-batch cache --
+// n_batches x I ints at full scale)
 static const int32_t* g_slot_map(const ltg_config* cfg, const ltg_batch* bt, const Workspace& w, hipStream_t st) {
     if (bt->slot) return bt->slot;
     const int I = cfg->n_items, nu = bt->n_unique;
-    hipLaunchKernelGGL(k_fill_i32, dim3((I + NT - 1) / NT < 512 ? (I + NT - 1) / NT : 512), dim3(NT), 0, st, I, -1, w.slotmap);
+    hipLaunchKernelGGL(k_fill_i32, grid1(I, 512), dim3(NT), 0, st, I, -1, w.slotmap);
     if (nu > 0) hipLaunchKernelGGL(k_slot_scatter, dim3((nu + NT - 1) / NT), dim3(NT), 0, st, nu, bt->uptr, bt->csr_pos, bt->indices, w.slotmap);
     return w.slotmap;
 }
+// grid of the sweep over W_q0 and its bias row (k_enc0_bwd_adam, or that job of fk_g_tail): a thread per float4, capped
+static unsigned q0_sweep_grid(int I, int H) {
+    const size_t total = (size_t)(I + 1) * (H / 4), gx = (total + NT - 1) / NT;
+    return (unsigned)(gx > 262144 ? 262144 : gx);
+}
 
-// sparse gradient rows of W_q0 (+ partial bias rows) into w.gq0
+// sparse gradient rows of W_q0 (+ partial bias rows) into w.gq0 (the latency path's kernels: LTG_MID_FAST chains only)
 static void g_enc0_grad(const ltg_config* cfg, const ltg_batch* bt, const ltg_g_opts* o, const ltg_gen_acts* acts, const Workspace& w,
                         hipStream_t st, const ltg_gen_state* gen = nullptr, const AdamC* ad = nullptr, bool row_waves = true,
                         const unsigned* poison = nullptr, LtgGate started = LTG_NO_GATE, LtgGate end_wait = LTG_NO_GATE, float* lr_slot = nullptr) {   // gen + ad: fused lazy Adam step
     const int B = bt->n_rows, I = cfg->n_items, H = cfg->h_enc, nu = bt->n_unique;
     const Probe pe{o->probe, st};
     pe.before(LTG_K_ENC0_GRAD);
-    if (fast_on(cfg) && row_waves) {   // one wave per row over all columns: a third of the waves (see fk_enc0_grad_rows)
+    if (row_waves) {   // one wave per row over all columns: a third of the waves (see fk_enc0_grad_rows)
         const int ncb = (H / 4 + 63) / 64;
         const dim3 g((nu + ENC0_BIAS_PARTS + G0_NW - 1) / G0_NW + (end_wait.word ? 1 : 0));
 #define LTG_G0_ROWS(N)                                                                                                                                   \
@@ -1023,47 +1092,34 @@ static void g_enc0_grad(const ltg_config* cfg, const ltg_batch* bt, const ltg_g_
         else if (ncb == 2) LTG_G0_ROWS(2);
         else LTG_G0_ROWS(3);
 #undef LTG_G0_ROWS
-    } else if (fast_on(cfg))
+    } else
         hipLaunchKernelGGL(fk_enc0_grad, dim3((H / 4 + 63) / 64, (nu + ENC0_BIAS_PARTS + G0_NW - 1) / G0_NW), dim3(G0_NT), 0, st, B, I, H, nu, bt->uptr, bt->rowidx, bt->csr_pos,
                            bt->indices, bt->values, o->fwd.drop_keep, o->fwd.keep_prob, cfg->seed, o->fwd.rng_step, acts->row_scale, w.da1, w.gq0,
                            cfg->item_lo, Ig_of(cfg), gen ? *gen : ltg_gen_state{}, ad ? *ad : AdamC{}, (gen && ad) ? gen->q0_ord + 1 : 0, bt->uitem);
-    else
-        hipLaunchKernelGGL(k_enc0_grad, dim3(nu + ENC0_BIAS_PARTS), dim3(NT), (size_t)4 * H * sizeof(float), st, B, I, H, nu, bt->uptr, bt->rowidx,
-                           bt->csr_pos, bt->indices, bt->values, o->fwd.drop_keep, o->fwd.keep_prob, cfg->seed, o->fwd.rng_step,
-                           acts->row_scale, w.da1, w.gq0, cfg->item_lo, Ig_of(cfg));
     pe.after(LTG_K_ENC0_GRAD);
 }
 
-// The backward chain dz -> dh1 and the Adam updates of the step as jobs of three launches of fk_g_tail (see there):
-//   stage 0: dz tiles + W_p1t (with_dec1: small item slabs; large ones ran the streaming kernel before)
-//   stage 1: dh1 tiles + W_p0        stage 2: W_q1, W_q0 (dense product when slot == NULL, else sweep + sparse rows), scalars
-static void g_jobs(int stage, const ltg_config* cfg, const ltg_gen_state* gen, const ltg_batch* bt, const ltg_g_opts* o, const ltg_gen_acts* acts,
+// Every Adam update of the step behind dz -> dh1 as jobs of ONE launch of fk_g_tail (see there): W_p1t (with_dec1: small item slabs; large
+// ones ran the streaming kernel before), W_p0, W_q1, W_q0 (dense product when slot == NULL, else sweep + sparse rows; no_q0: a launch of
+// its own follows; q0_bias: only the bias row, the lazy clock has the item rows), scalars
+static void g_jobs(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_batch* bt, const ltg_g_opts* o, const ltg_gen_acts* acts,
                    const Workspace& w, const AdamC& ad, const int32_t* slot, bool with_dec1, float* loss_out, hipStream_t st,
                    bool no_q0 = false, bool q0_bias = false, const unsigned* poison = nullptr, LtgGate end_wait = LTG_NO_GATE, bool bias_from_da1 = false) {
     const int B = bt->n_rows, I = cfg->n_items, H = cfg->h_enc, Z = cfg->z_dim;
     TailArgs a;
     a.B = B; a.I = I; a.H = H; a.Z = Z; a.nu = bt->n_unique;
-    const bool all = stage < 0;     // stage -1: every Adam job in ONE launch (dz / dh1 were launched on their own)
-    a.nz = a.nh = 0;
-    a.n1 = ((stage == 0 || all) && with_dec1) ? ((I + 31) / 32) * ((H + 1 + LTG_TAIL_BN - 1) / LTG_TAIL_BN) : 0;
-    a.n2 = (stage == 1 || all) ? ((Z + 1 + 31) / 32) * ((H + LTG_TAIL_BN - 1) / LTG_TAIL_BN) : 0;
-    a.n3 = (stage == 2 || all) ? ((H + 1 + 31) / 32) * ((2 * Z + LTG_TAIL_BN - 1) / LTG_TAIL_BN) : 0;
+    a.nz = a.nh = 0;     // (dz / dh1 were launched on their own)
+    a.n1 = with_dec1 ? ((I + 31) / 32) * ((H + 1 + LTG_TAIL_BN - 1) / LTG_TAIL_BN) : 0;
+    a.n2 = ((Z + 1 + 31) / 32) * ((H + LTG_TAIL_BN - 1) / LTG_TAIL_BN);
+    a.n3 = ((H + 1 + 31) / 32) * ((2 * Z + LTG_TAIL_BN - 1) / LTG_TAIL_BN);
     a.n4 = 0;
-    if ((stage == 2 || all) && !no_q0) {
-        if (!slot) a.n4 = ((I + 1 + 31) / 32) * ((H + LTG_TAIL_BN - 1) / LTG_TAIL_BN);
-        else {
-            const size_t total = (size_t)(I + 1) * (H / 4);
-            size_t gx = (total + NT - 1) / NT;
-            if (gx > 262144) gx = 262144;
-            a.n4 = (int)gx;
-        }
-    }
+    if (!no_q0) a.n4 = slot ? (int)q0_sweep_grid(I, H) : ((I + 1 + 31) / 32) * ((H + LTG_TAIL_BN - 1) / LTG_TAIL_BN);
     a.q0_bias = 0;
-    if ((stage == 2 || all) && q0_bias) {   // lazy Adam clock: fk_enc0_grad updated the item rows, one block finishes the bias row
+    if (q0_bias) {   // lazy Adam clock: fk_enc0_grad updated the item rows, one block finishes the bias row
         a.n4 = bias_from_da1 ? 0 : 1;      // (bias_from_da1: fk_q0_bias_from_da1 follows on the same stream)
         a.q0_bias = bias_from_da1 ? 0 : 1;
     }
-    a.n5 = ((stage == 2 || all) && with_dec1) ? 1 : 0;
+    a.n5 = with_dec1 ? 1 : 0;
     a.Wp0 = gen->p[2]; a.Wq1 = gen->p[1]; a.mulv = acts->mulv; a.eps = o->fwd.eps; a.is_training = o->fwd.is_training;
     a.seed = cfg->seed; a.step = o->fwd.rng_step; a.dmlv_out = w.dmlv; a.da1_out = w.da1;
     a.dlog = w.dlog; a.h2 = acts->h2; a.z = acts->z; a.da2 = w.da2; a.h1 = acts->h1; a.dmlv = w.dmlv; a.G = w.gq0;
@@ -1073,17 +1129,15 @@ static void g_jobs(int stage, const ltg_config* cfg, const ltg_gen_state* gen, c
     a.loss_out = w.scal; a.loss_out2 = loss_out;
     a.poison = poison; a.n_wait = end_wait.word ? 1 : 0; a.end_wait = end_wait;
     const Probe pr{o->probe, st};
-    const int kid = stage == 0 ? LTG_K_DZ : (stage == 1 ? LTG_K_DH1 : LTG_K_G_TAIL);
-    pr.before(kid);
+    pr.before(LTG_K_G_TAIL);
     const dim3 g(a.nz + a.nh + a.n1 + a.n2 + a.n3 + a.n4 + a.n5 + a.n_wait);
     if (cfg->precision == LTG_PREC_BF16) hipLaunchKernelGGL(fk_g_tail<true>, g, dim3(NT), 0, st, a, *gen, ad);
     else hipLaunchKernelGGL(fk_g_tail<false>, g, dim3(NT), 0, st, a, *gen, ad);
-    if ((stage == 2 || all) && q0_bias && bias_from_da1)
+    if (q0_bias && bias_from_da1)
         hipLaunchKernelGGL(fk_q0_bias_from_da1, dim3(((H >> 2) + Q0B_COLS - 1) / Q0B_COLS), dim3(NT), 0, st, B, H, w.da1, *gen, ad, poison);
-    pr.after(kid);
+    pr.after(LTG_K_G_TAIL);
 }
 
-// dz -> dh1 -> (sparse W_q0 gradient) -> Adam updates as one tail launch.
 // Adam step gen->q0_ord + 1 of W_q0 / b_q0 on the lazy clock: the batch's rows with their gradient rows (w.gq0), the bias
 // row, then the rotating slice of untouched rows
 constexpr int G_AUX_SWEEP = 0x40000000;   // library-internal bit of ltg_g_opts.fake_done: ltg_g_step runs the slice on its aux stream
@@ -1092,93 +1146,81 @@ static void q0_slice_sweep(const ltg_config* cfg, const ltg_gen_state* gen, int 
     const int I = cfg->n_items, P = gen->q0_period, start = (gen->q0_ord + 1) % P;
     if (start < I) hipLaunchKernelGGL(k_q0_sweep, dim3((I - start + P - 1) / P), dim3(Q0_NT), 0, st, I, cfg->h_enc, start, P, target, *gen, make_adam(cfg, 1));
 }
-static void q0_lazy_update(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_batch* bt, const ltg_g_opts* o, const Workspace& w, const AdamC& ad,
-                           hipStream_t st, bool rows_done = false) {
-    const int I = cfg->n_items, H = cfg->h_enc, nu = bt->n_unique, ord = gen->q0_ord + 1;
-    // (rows_done: fk_enc0_grad applied the step to the batch's rows and fk_g_tail to the bias row)
-    if (!rows_done) hipLaunchKernelGGL(k_q0_step_touched, dim3(nu + 1), dim3(Q0_NT), 0, st, I, H, nu, bt->uptr, bt->csr_pos, bt->indices, w.gq0, ord, *gen, ad);
-    if (!(o->fake_done & G_AUX_SWEEP)) q0_slice_sweep(cfg, gen, ord, st);   // (else: ltg_g_step has the slice on its aux stream, up to ord - 1)
+// ... of this step, behind the clock's update of the batch's rows and the bias row (unless ltg_g_step has the slice on its aux stream, up to ord - 1)
+static void q0_slice_of_step(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_g_opts* o, hipStream_t st) {
+    if (!(o->fake_done & G_AUX_SWEEP)) q0_slice_sweep(cfg, gen, gen->q0_ord + 1, st);
 }
 
-static void g_chain(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_batch* bt, const ltg_g_opts* o, const ltg_gen_acts* acts,
-                    const Workspace& w, const AdamC& ad, const int32_t* slot, bool with_dec1, float* loss_out, hipStream_t st, bool lazy = false) {
+// The LTG_MID_FAST backward chain behind da2: dz -> dh1 -> (sparse W_q0 gradient) -> every remaining Adam update as one tail launch ->
+// the W_q0 update where it is a launch of its own.  r.small: W_p1t and the step's scalars (loss_out) are jobs of the tail as well.
+static void g_chain(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_g_route_info& r, const ltg_batch* bt, const ltg_g_opts* o,
+                    const ltg_gen_acts* acts, const Workspace& w, const AdamC& ad, float* loss_out, hipStream_t st) {
     const int B = bt->n_rows, H = cfg->h_enc, Z = cfg->z_dim;
     const Probe pr{o->probe, st};
+    // (the lazy clock needs no item -> gradient-row map: its update walks the batch's distinct items)
+    const bool lazy = r.q0 == LTG_Q0_LAZY;
+    const int32_t* slot = r.q0 == LTG_Q0_SWEEP ? g_slot_map(cfg, bt, w, st) : nullptr;
     LTG_PROBED(pr, LTG_K_DZ, hipLaunchKernelGGL(fk_dz, grid2(Z, B, 16, 16), dim3(NT), 0, st, B, Z, H, w.da2, gen->p[2], acts->mulv, o->fwd.eps,
                                                 o->fwd.is_training, o->anneal, cfg->seed, o->fwd.rng_step, w.dmlv));
     LTG_PROBED(pr, LTG_K_DH1, hipLaunchKernelGGL(fk_dh1, grid2(H, B, 16, 16), dim3(NT), 0, st, B, H, 2 * Z, w.dmlv, gen->p[1], acts->h1, w.da1));
-    const bool fused = lazy && fast_on(cfg);   // Adam on the batch's rows inside the gradient kernel
-    const bool row_waves = (cfg->tuning & (1 << 14)) == 0;   // tuning-knob bit 14: the column-blocked shape of the sparse gradient
-    if (fused) g_enc0_grad(cfg, bt, o, acts, w, st, gen, &ad, row_waves);
-    else if (slot || lazy) g_enc0_grad(cfg, bt, o, acts, w, st, nullptr, nullptr, row_waves);
-    const bool own_sweep = (slot && cfg->n_items >= 8192) || lazy;   // HBM-bound sweep: its own launch at full occupancy (measured 490 vs
-                                                                     // 525 us at 200 000 items when it rode in the 118-register job kernel)
-    g_jobs(-1, cfg, gen, bt, o, acts, w, ad, slot, with_dec1, loss_out, st, own_sweep, fused);
-    if (lazy) {
-        LTG_PROBED(pr, LTG_K_ENC0_BWD_ADAM, q0_lazy_update(cfg, gen, bt, o, w, ad, st, fused));
-    } else if (own_sweep) {
-        const int I = cfg->n_items;
-        const size_t total = (size_t)(I + 1) * (H / 4);
-        size_t gx = (total + NT - 1) / NT;
-        if (gx > 262144) gx = 262144;
-        LTG_PROBED(pr, LTG_K_ENC0_BWD_ADAM, hipLaunchKernelGGL(k_enc0_bwd_adam, dim3((unsigned)gx), dim3(NT), 0, st, I, H, bt->n_unique, slot, w.gq0, *gen, ad));
+    if (lazy) g_enc0_grad(cfg, bt, o, acts, w, st, gen, &ad, r.grad_rows);   // Adam on the batch's rows inside the gradient kernel
+    else if (slot) g_enc0_grad(cfg, bt, o, acts, w, st, nullptr, nullptr, r.grad_rows);
+    g_jobs(cfg, gen, bt, o, acts, w, ad, slot, r.small, loss_out, st, r.q0_own_launch, lazy);
+    if (lazy) {   // (fk_enc0_grad applied the step to the batch's rows and fk_g_tail to the bias row)
+        LTG_PROBED(pr, LTG_K_ENC0_BWD_ADAM, q0_slice_of_step(cfg, gen, o, st));
+    } else if (r.q0_own_launch) {
+        LTG_PROBED(pr, LTG_K_ENC0_BWD_ADAM, hipLaunchKernelGGL(k_enc0_bwd_adam, dim3(q0_sweep_grid(cfg->n_items, H)), dim3(NT), 0, st, cfg->n_items, H, bt->n_unique, slot, w.gq0, *gen, ad));
     }
 }
 
-static int g_stage_bwd_rest(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_batch* bt, const ltg_g_opts* o,
+static int g_stage_bwd_rest(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_g_route_info& r, const ltg_batch* bt, const ltg_g_opts* o,
                             const ltg_gen_acts* acts, const float* dh2, const Workspace& w, hipStream_t st, bool da2_ready = false,
                             bool only_dec1 = false, LtgH2Done hd = LtgH2Done{nullptr, nullptr, 0u, nullptr}) {
     const int B = bt->n_rows, I = cfg->n_items, H = cfg->h_enc, Z = cfg->z_dim;
     const AdamC ad = make_adam(cfg, o->adam_t);
     const bool bf = cfg->precision == LTG_PREC_BF16;
-    const bool big = I >= 8192;
-    const bool vz = (Z % 4) == 0;   // 16-B loaders of the middle layers (H % 4 == 0 always)
+    const bool aux_sweep = (o->fake_done & G_AUX_SWEEP) && r.q0 == LTG_Q0_LAZY;   // ltg_g_step: the lazy clock's work on the aux stream
     // Everything on `st` unless the lazy clock's chain runs beside the weight update (below).  (Measured and removed: small item slabs,
     // the three weight-gradient + Adam kernels on the aux stream beside da2 -> dz -> dh1 -> sweep -- the event pairs cost more than the
     // overlap saves once the chain's kernels take 6-18 us; I = 200 000, the two HBM sweeps side by side: they only contend.)
     hipStream_t aux = (hipStream_t)o->aux_stream;
     hipEvent_t evf = (hipEvent_t)o->ev_fork;
-    hipStream_t s_dw = st;
-    if (!da2_ready && !only_dec1) {
-        const int n = B * H;
-        const int gx = (n + NT - 1) / NT < 1024 ? (n + NT - 1) / NT : 1024;
-        hipLaunchKernelGGL(k_da2, dim3(gx), dim3(NT), 0, st, n, 1, dh2, acts->h2, w.da2);  // da2 = dh2 * (1 - h2^2)
-    }
+    if (!da2_ready && !only_dec1) hipLaunchKernelGGL(k_da2, grid1(B * H, 1024), dim3(NT), 0, st, B * H, 1, dh2, acts->h2, w.da2);  // da2 = dh2 * (1 - h2^2)
     // persistent workgroups of the streaming decoder weight update (see launch_dw).  Slabs below 65 536 items: 160 -- the rest of the
     // step runs beside the update, and what a kernel of that chain costs there is mostly how many CUs the update leaves it (round 4,
     // same box, per-rank proxy at 25 024 items: 196 workgroups 173.3-174.1 us per step, 160: 170.1-170.5, 128: 184, 96: 205;
     // 20 000 items: 166.3 / 161.6 / 161.3-162.4 / 179; the update alone takes 89 / 92 / 110 / 122 us with 196 / 160 / 128 / 98)
     int dw_gmax = I / 32 < 2048 ? 160 : 224;
     auto launch_dw = [&]() {
-        const Probe prs{o->probe, s_dw};
+        const Probe prs{o->probe, st};
         prs.before(LTG_K_DEC1_BWD_ADAM);
-        if (stream_ok(cfg, gen, B) && dw_stream_ok(H)) {
+        if (r.dw == LTG_DW_STREAM) {
             const int ntl = I / 32;
-            if (dlog16_ok(cfg, gen, B)) {   // (the producer, g_stage_bwd_dec, stored dlog as bf16 under the same predicate)
+            if (r.dlog_bf16) {   // (the field the producer, g_stage_bwd_dec, stored dlog under)
                 // persistent workgroups: 224 = 28 per XCD (measured 657 us at 200 000 items; 256: 678, 240: 669, 192: 671) -- and 32 CUs
                 // stay free for whatever runs beside it ...
                 int gmax = dw_gmax;
                 // ... and no more workgroups than the same number of rounds needs (782 tiles of a 25 024-item slab: 4 rounds with
                 // 224 or with 196 workgroups -- 60 CUs left to the chain and the collective running beside it)
                 if (ntl > gmax) gmax = (ntl + (ntl + gmax - 1) / gmax - 1) / ((ntl + gmax - 1) / gmax);
-                hipLaunchKernelGGL(k_dec1_bwd_adam_stream<true>, dim3(ntl < gmax ? ntl : gmax), dim3(ST_NT), 0, s_dw, B, I, H, w.dlog, acts->h2, *gen, ad, hd);
-                if (I % 32)   // ragged tail: the generic tile kernel on the last I % 32 item rows
-                    hipLaunchKernelGGL((k_dec1_bwd_adam<true, 2, false, true>), grid2(H + 1, I - ntl * 32, 64, 64), dim3(NT), 0, s_dw, B, I, H, w.dlog, acts->h2, *gen, ad, ntl * 32,
+                hipLaunchKernelGGL(k_dec1_bwd_adam_stream<true>, dim3(ntl < gmax ? ntl : gmax), dim3(ST_NT), 0, st, B, I, H, w.dlog, acts->h2, *gen, ad, hd);
+                if (r.dw_ragged)
+                    hipLaunchKernelGGL((k_dec1_bwd_adam<true, 2, false, true>), grid2(H + 1, I - ntl * 32, 64, 64), dim3(NT), 0, st, B, I, H, w.dlog, acts->h2, *gen, ad, ntl * 32,
                                        hd.poison);
             } else {
-                hipLaunchKernelGGL(k_dec1_bwd_adam_stream<false>, dim3(ntl < 256 ? ntl : 256), dim3(ST_NT), 0, s_dw, B, I, H, w.dlog, acts->h2, *gen, ad);
-                if (I % 32)
-                    hipLaunchKernelGGL((k_dec1_bwd_adam<true, 2>), grid2(H + 1, I - ntl * 32, 64, 64), dim3(NT), 0, s_dw, B, I, H, w.dlog, acts->h2, *gen, ad, ntl * 32);
+                hipLaunchKernelGGL(k_dec1_bwd_adam_stream<false>, dim3(ntl < 256 ? ntl : 256), dim3(ST_NT), 0, st, B, I, H, w.dlog, acts->h2, *gen, ad);
+                if (r.dw_ragged)
+                    hipLaunchKernelGGL((k_dec1_bwd_adam<true, 2>), grid2(H + 1, I - ntl * 32, 64, 64), dim3(NT), 0, st, B, I, H, w.dlog, acts->h2, *gen, ad, ntl * 32);
             }
-        } else if (!bf) {
-            if (big) hipLaunchKernelGGL((k_dec1_bwd_adam<false, 2>), grid2(H + 1, I, 64, 64), dim3(NT), 0, s_dw, B, I, H, w.dlog, acts->h2, *gen, ad, 0);
-            else hipLaunchKernelGGL((k_dec1_bwd_adam<false, 0>), grid2(H + 1, I, 32, 32), dim3(NT), 0, s_dw, B, I, H, w.dlog, acts->h2, *gen, ad, 0);
-        } else if (big) hipLaunchKernelGGL((k_dec1_bwd_adam<true, 2>), grid2(H + 1, I, 64, 64), dim3(NT), 0, s_dw, B, I, H, w.dlog, acts->h2, *gen, ad, 0);
-        else if ((I % 4) == 0) hipLaunchKernelGGL((k_dec1_bwd_adam<true, 0, true>), grid2(H + 1, I, 32, 32), dim3(NT), 0, s_dw, B, I, H, w.dlog, acts->h2, *gen, ad, 0);
-        else hipLaunchKernelGGL((k_dec1_bwd_adam<true, 0>), grid2(H + 1, I, 32, 32), dim3(NT), 0, s_dw, B, I, H, w.dlog, acts->h2, *gen, ad, 0);
+        } else if (r.dw_tile == 64) {
+            if (bf) hipLaunchKernelGGL((k_dec1_bwd_adam<true, 2>), grid2(H + 1, I, 64, 64), dim3(NT), 0, st, B, I, H, w.dlog, acts->h2, *gen, ad, 0);
+            else hipLaunchKernelGGL((k_dec1_bwd_adam<false, 2>), grid2(H + 1, I, 64, 64), dim3(NT), 0, st, B, I, H, w.dlog, acts->h2, *gen, ad, 0);
+        } else if (r.dw_tile == -32) hipLaunchKernelGGL((k_dec1_bwd_adam<true, 0, true>), grid2(H + 1, I, 32, 32), dim3(NT), 0, st, B, I, H, w.dlog, acts->h2, *gen, ad, 0);
+        else if (bf) hipLaunchKernelGGL((k_dec1_bwd_adam<true, 0>), grid2(H + 1, I, 32, 32), dim3(NT), 0, st, B, I, H, w.dlog, acts->h2, *gen, ad, 0);
+        else hipLaunchKernelGGL((k_dec1_bwd_adam<false, 0>), grid2(H + 1, I, 32, 32), dim3(NT), 0, st, B, I, H, w.dlog, acts->h2, *gen, ad, 0);
         prs.after(LTG_K_DEC1_BWD_ADAM);
     };
-    if ((o->fake_done & G_AUX_SWEEP) && q0_lazy(cfg, gen) && mid_fast(cfg, B) && !only_dec1) {
+    if (aux_sweep && r.mid == LTG_MID_FAST && !only_dec1) {
         // ltg_g_step, large item slab, lazy Adam clock of W_q0.  The decoder weight update (HBM-bound, the largest kernel of the
         // step) needs only dlog and h2; everything else that is left -- dz -> dh1 -> sparse W_q0 gradient -> the other Adam
         // updates -> the clock's step and its rotating slice -- needs only da2.  The two run side by side: the weight update on
@@ -1194,11 +1236,11 @@ static int g_stage_bwd_rest(const ltg_config* cfg, const ltg_gen_state* gen, con
         if (!o->dec1_done) launch_dw();
         ltg_g_opts oc = *o;
         oc.fake_done &= ~G_AUX_SWEEP;   // the slice runs in the chain's own stream order, behind the clock's step
-        g_chain(cfg, gen, bt, &oc, acts, w, ad, nullptr, false, nullptr, aux, true);
+        g_chain(cfg, gen, r, bt, &oc, acts, w, ad, nullptr, aux);
         (void)hipEventRecord((hipEvent_t)o->ev_sweep, aux);
         return check_launch();
     }
-    if ((o->fake_done & G_AUX_SWEEP) && q0_lazy(cfg, gen)) {
+    if (aux_sweep) {
         // (batches the middle-layer fast path does not serve) only the rotating slice on the aux stream, eligible together with the decoder weight update
         (void)hipEventRecord(evf, st);
         (void)hipStreamWaitEvent(aux, evf, 0);
@@ -1207,13 +1249,11 @@ static int g_stage_bwd_rest(const ltg_config* cfg, const ltg_gen_state* gen, con
         (void)hipEventRecord((hipEvent_t)o->ev_sweep, aux);
     } else if (!o->dec1_done) launch_dw();
     if (only_dec1) return check_launch();
-    if (mid_fast(cfg, B)) {
-        // dz -> dh1 -> sparse W_q0 gradient, then every remaining Adam update (W_p0, W_q1, W_q0 + biases) in ONE launch
-        const bool lazy = q0_lazy(cfg, gen);   // no item -> gradient-row map needed: the update walks the batch's distinct items
-        const int32_t* slot = lazy ? nullptr : g_slot_map(cfg, bt, w, st);
-        g_chain(cfg, gen, bt, o, acts, w, ad, slot, false, nullptr, st, lazy);
+    if (r.mid == LTG_MID_FAST) {
+        g_chain(cfg, gen, r, bt, o, acts, w, ad, nullptr, st);
         return check_launch();
     }
+    const bool vz = r.mid_vec != 0;
     const Probe pc{o->probe, st};
     pc.before(LTG_K_DZ);
 #define LTG_V2(KERNEL, ...)                                       \
@@ -1242,18 +1282,12 @@ static int g_stage_bwd_rest(const ltg_config* cfg, const ltg_gen_state* gen, con
     hipLaunchKernelGGL(k_enc0_grad, dim3(nu + ENC0_BIAS_PARTS), dim3(NT), (size_t)4 * H * sizeof(float), st, B, I, H, nu, bt->uptr, bt->rowidx,
                        bt->csr_pos, bt->indices, bt->values, o->fwd.drop_keep, o->fwd.keep_prob, cfg->seed, o->fwd.rng_step,
                        acts->row_scale, w.da1, w.gq0, cfg->item_lo, Ig_of(cfg));
-    if (q0_lazy(cfg, gen)) q0_lazy_update(cfg, gen, bt, o, w, ad, st);
-    else {
-        const size_t total = (size_t)(I + 1) * (H / 4);
-        size_t gx = (total + NT - 1) / NT;
-        if (gx > 262144) gx = 262144;
-        const int32_t* slot = bt->slot;
-        if (!slot) {   // no per-batch cache (n_batches x I ints at full scale): build the map of this batch in the workspace
-            hipLaunchKernelGGL(k_fill_i32, dim3((I + NT - 1) / NT < 512 ? (I + NT - 1) / NT : 512), dim3(NT), 0, st, I, -1, w.slotmap);
-            if (nu > 0) hipLaunchKernelGGL(k_slot_scatter, dim3((nu + NT - 1) / NT), dim3(NT), 0, st, nu, bt->uptr, bt->csr_pos, bt->indices, w.slotmap);
-            slot = w.slotmap;
-        }
-        hipLaunchKernelGGL(k_enc0_bwd_adam, dim3((unsigned)gx), dim3(NT), 0, st, I, H, nu, slot, w.gq0, *gen, ad);
+    if (r.q0 == LTG_Q0_LAZY) {
+        hipLaunchKernelGGL(k_q0_step_touched, dim3(nu + 1), dim3(Q0_NT), 0, st, I, H, nu, bt->uptr, bt->csr_pos, bt->indices, w.gq0, gen->q0_ord + 1, *gen, ad);
+        q0_slice_of_step(cfg, gen, o, st);
+    } else {
+        const int32_t* slot = g_slot_map(cfg, bt, w, st);
+        hipLaunchKernelGGL(k_enc0_bwd_adam, dim3(q0_sweep_grid(I, H)), dim3(NT), 0, st, I, H, nu, slot, w.gq0, *gen, ad);
     }
     pe.after(LTG_K_ENC0_BWD_ADAM);
     return check_launch();
@@ -1271,15 +1305,16 @@ int ltg_g_step(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_disc_s
     if (!bt->uptr || !bt->rowidx || !bt->csr_pos || !o->cnt || !fake->row || bt->n_rows <= 0 || fake->n < 0) return LTG_EINVAL;
     if (bt->n_unique < 0 || (size_t)bt->n_unique > gq0_rows(cfg, bt->n_rows)) return LTG_EINVAL;
     const int B = bt->n_rows, nf = fake->n;
-    if (ltg_workspace_bytes(cfg, B, nf) > ws_bytes) return LTG_EWORKSPACE;
+    Workspace w;
+    if (carve_checked(cfg, B, nf, ws, ws_bytes, &w) != LTG_OK) return LTG_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    Workspace w = carve(cfg, B, nf, (char*)ws);
+    const ltg_g_route_info r = g_route(cfg, gen, B);
     const bool have_y = o->y_pre != nullptr;   // y_generated of this batch came from ltg_fake_tower_batched: no tower in this step
     if (have_y) w.y = const_cast<float*>(o->y_pre);
     // lazy Adam clock of W_q0: the batch's rows up to date first; its rotating slice (rows NOT of this batch: arithmetic-bound,
     // 48 registers -- it fits beside the 2 x 232-register waves of the HBM-bound decoder kernels) then runs on the aux stream
-    q0_touch(cfg, gen, bt, st);
-    const bool aux_sweep = q0_lazy(cfg, gen) && o->aux_stream && o->ev_fork && o->ev_sweep;
+    q0_touch(cfg, gen, r, bt, st);
+    const bool aux_sweep = r.q0 == LTG_Q0_LAZY && o->aux_stream && o->ev_fork && o->ev_sweep;
     // fork: the fake tower (independent of the generator forward) runs on the caller's aux stream
     const bool fork = o->aux_stream && o->ev_fork && o->ev_join && nf > 0 && !have_y;
     if (fork || aux_sweep) {
@@ -1287,28 +1322,20 @@ int ltg_g_step(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_disc_s
         if (hipEventRecord((hipEvent_t)o->ev_fork, st) != hipSuccess || hipStreamWaitEvent(aux, (hipEvent_t)o->ev_fork, 0) != hipSuccess)
             return LTG_ELAUNCH;
         if (fork) {
-            PairView pv{0, nf, nullptr, nullptr, fake->pop, fake->niche};
-            DropView dA{nullptr, o->drop_fake[0], 0, 0}, dB{nullptr, o->drop_fake[1], 0, 0}, dC{nullptr, o->drop_fake[2], 0, 0};
-            disc_forward(cfg, disc, pv, dA, dB, dC, o->d_keep_prob, o->d_rng_step, w, false, nullptr, aux);
+            fake_tower(cfg, disc, fake, o, w, nullptr, aux);
             if (hipEventRecord((hipEvent_t)o->ev_join, aux) != hipSuccess) return LTG_ELAUNCH;
         }
     }
     ltg_g_opts o_local = *o;
     o_local.fake_done = (o->fake_done & 1) | (aux_sweep ? G_AUX_SWEEP : 0);
     o = &o_local;
-    const bool small = small_fast(cfg, B);
-    fwd_stage_enc(cfg, gen, bt, &o->fwd, acts, 0, st, small ? w.xd : nullptr, true);
-    const int sgroups = fwd_stage_rest(cfg, gen, bt, &o->fwd, acts, 0, st, small ? nullptr : w.segpart);
-    if (small) {
-        // small item slab: a row's softmax statistics, loss terms and dlogits need no other row -> one launch per stage,
-        // nine launches per step: enc0, enc1, dec0, dec1 | row softmax + dlogits, dh2, dz, dh1, Adam tail (dW_q0 = xd^T . da1 dense)
+    fwd_stage_enc(cfg, gen, r, bt, &o->fwd, acts, 0, st, r.small ? w.xd : nullptr, true);
+    const int sgroups = fwd_stage_rest(cfg, gen, r, bt, &o->fwd, acts, 0, st, r.small ? nullptr : w.segpart);
+    if (r.small) {
+        // small item slab: nine launches per step: enc0, enc1, dec0, dec1 | row softmax + dlogits, dh2, dz, dh1, Adam tail (dW_q0 = xd^T . da1 dense)
         const int I = cfg->n_items, H = cfg->h_enc;
         const Probe pr{o->probe, st};
-        if (nf > 0 && !fork && !have_y) {
-            PairView pv{0, nf, nullptr, nullptr, fake->pop, fake->niche};
-            DropView dA{nullptr, o->drop_fake[0], 0, 0}, dB{nullptr, o->drop_fake[1], 0, 0}, dC{nullptr, o->drop_fake[2], 0, 0};
-            disc_forward(cfg, disc, pv, dA, dB, dC, o->d_keep_prob, o->d_rng_step, w, false, o->probe, st);
-        }
+        if (nf > 0 && !fork && !have_y) fake_tower(cfg, disc, fake, o, w, o->probe, st);
         if (fork && hipStreamWaitEvent(st, (hipEvent_t)o->ev_join, 0) != hipSuccess) return LTG_ELAUNCH;
         LTG_PROBED(pr, LTG_K_ROW_DLOGITS, hipLaunchKernelGGL(fk_row_dlogits, dim3(B), dim3(NT), 0, st, B, I, bt->indptr, bt->indices, bt->values, acts->logits,
                                                              acts->kl_rows, w.y, nf, o->cnt, o->gan_lambda, fake->row, fake->niche, fake->pop, w.dlog,
@@ -1317,15 +1344,15 @@ int ltg_g_step(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_disc_s
         if (cfg->precision == LTG_PREC_BF16) hipLaunchKernelGGL(fk_dh2<true>, grid2(H, B, 16, 16), dim3(DH2_NT), 0, st, B, I, H, w.dlog, gen->p[3], acts->h2, w.da2);
         else hipLaunchKernelGGL(fk_dh2<false>, grid2(H, B, 16, 16), dim3(DH2_NT), 0, st, B, I, H, w.dlog, gen->p[3], acts->h2, w.da2);
         pr.after(LTG_K_DH2);
-        g_chain(cfg, gen, bt, o, acts, w, make_adam(cfg, o->adam_t), nullptr, true, loss_out, st);
+        g_chain(cfg, gen, r, bt, o, acts, w, make_adam(cfg, o->adam_t), loss_out, st);
         return check_launch();
     }
-    g_row_partial(cfg, bt, fake, acts, w.rowpart, st, w.segpart, nullptr, sgroups);
+    g_row_partial(cfg, r, bt, fake, acts, w.rowpart, st, w.segpart, nullptr, sgroups);
     if (fork && hipStreamWaitEvent(st, (hipEvent_t)o->ev_join, 0) != hipSuccess) return LTG_ELAUNCH;
     // single GPU: the slab sum writes da2 directly (one launch less than the sharded stage pair)
-    int rc = g_stage_bwd_dec(cfg, gen, disc, bt, fake, o, acts, w.rowpart, 1, loss_out, w, w.da2, st, fork || have_y, acts->h2);
+    int rc = g_stage_bwd_dec(cfg, gen, disc, r, bt, fake, o, acts, w.rowpart, 1, loss_out, w, w.da2, st, fork || have_y, acts->h2);
     if (rc != LTG_OK) return rc;
-    rc = g_stage_bwd_rest(cfg, gen, bt, o, acts, w.da2, w, st, true);
+    rc = g_stage_bwd_rest(cfg, gen, r, bt, o, acts, w.da2, w, st, true);
     if (aux_sweep && hipStreamWaitEvent(st, (hipEvent_t)o->ev_sweep, 0) != hipSuccess) return LTG_ELAUNCH;   // join
     return rc;
 }
@@ -1335,7 +1362,7 @@ int ltg_g_fwd_enc(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_bat
                   const ltg_gen_acts* acts, ltg_stream stream) {
     clear_errors();
     if (!g_args_ok(cfg, gen, bt, acts) || !opts) return LTG_EINVAL;
-    fwd_stage_enc(cfg, gen, bt, opts, acts, 1, (hipStream_t)stream);
+    fwd_stage_enc(cfg, gen, g_route(cfg, gen, bt->n_rows, true), bt, opts, acts, 1, (hipStream_t)stream);
     return check_launch();
 }
 
@@ -1347,8 +1374,9 @@ int ltg_g_fwd_rest(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_ba
     hipStream_t st = (hipStream_t)stream;
     float* segpart = (ws && ws_bytes >= segpart_bytes(cfg, bt->n_rows))
                          ? reinterpret_cast<float*>((char*)ws + align_up((size_t)bt->n_rows * RP * sizeof(float))) : nullptr;
-    const int sgroups = fwd_stage_rest(cfg, gen, bt, opts, acts, 1, st, segpart);
-    g_row_partial(cfg, bt, (fake && fake->n > 0) ? fake : nullptr, acts, rowpart_out, st, segpart, nullptr, sgroups);
+    const ltg_g_route_info r = g_route(cfg, gen, bt->n_rows, true);
+    const int sgroups = fwd_stage_rest(cfg, gen, r, bt, opts, acts, 1, st, segpart);
+    g_row_partial(cfg, r, bt, (fake && fake->n > 0) ? fake : nullptr, acts, rowpart_out, st, segpart, nullptr, sgroups);
     return check_launch();
 }
 
@@ -1356,8 +1384,8 @@ int ltg_rowstats_combine(const ltg_config* cfg, const float* rowpart_all, int32_
                          void* ws, size_t ws_bytes, ltg_stream stream) {
     clear_errors();
     if (!cfg_ok(cfg) || !rowpart_all || !lse_out || n_ranks < 1 || n_rows < 1 || !ws) return LTG_EINVAL;
-    if (ltg_workspace_bytes(cfg, n_rows, 1) > ws_bytes) return LTG_EWORKSPACE;
-    const Workspace w = carve(cfg, n_rows, 1, (char*)ws);
+    Workspace w;
+    if (carve_checked(cfg, n_rows, 1, ws, ws_bytes, &w) != LTG_OK) return LTG_EWORKSPACE;
     hipLaunchKernelGGL(k_g_combine, dim3(1), dim3(NT), 0, (hipStream_t)stream, n_rows, n_ranks, rowpart_all, 0, (const float*)nullptr,
                        (const float*)nullptr, (const int32_t*)nullptr, 0.f, 0.f, lse_out, w.nb, w.Pb, (float*)nullptr, (float*)nullptr);
     return check_launch();
@@ -1369,10 +1397,10 @@ int ltg_g_bwd_dec(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_dis
     clear_errors();
     if (!g_args_ok(cfg, gen, bt, acts) || !disc || !fake || !o || !rowpart_all || n_ranks < 1 || !loss_out || !dh2_out || !ws) return LTG_EINVAL;
     if (!o->cnt || !fake->row || fake->n < 0) return LTG_EINVAL;
-    if (ltg_workspace_bytes(cfg, bt->n_rows, fake->n) > ws_bytes) return LTG_EWORKSPACE;
-    Workspace w = carve(cfg, bt->n_rows, fake->n, (char*)ws);
+    Workspace w;
+    if (carve_checked(cfg, bt->n_rows, fake->n, ws, ws_bytes, &w) != LTG_OK) return LTG_EWORKSPACE;
     if (o->y_pre) w.y = const_cast<float*>(o->y_pre);   // y_generated from ltg_fake_tower_batched
-    return g_stage_bwd_dec(cfg, gen, disc, bt, fake, o, acts, rowpart_all, n_ranks, loss_out, w, dh2_out, (hipStream_t)stream,
+    return g_stage_bwd_dec(cfg, gen, disc, g_route(cfg, gen, bt->n_rows, true), bt, fake, o, acts, rowpart_all, n_ranks, loss_out, w, dh2_out, (hipStream_t)stream,
                            (o->fake_done & 1) != 0 || o->y_pre != nullptr);
 }
 
@@ -1380,12 +1408,10 @@ int ltg_g_fake_tower(const ltg_config* cfg, const ltg_disc_state* disc, const lt
                      size_t ws_bytes, ltg_stream stream) {
     clear_errors();
     if (!cfg_ok(cfg) || !disc || !fake || !o || !ws || n_rows <= 0 || fake->n < 0) return LTG_EINVAL;
-    if (ltg_workspace_bytes(cfg, n_rows, fake->n) > ws_bytes) return LTG_EWORKSPACE;
+    Workspace w;   // same carve as ltg_g_bwd_dec: y lives there
+    if (carve_checked(cfg, n_rows, fake->n, ws, ws_bytes, &w) != LTG_OK) return LTG_EWORKSPACE;
     if (fake->n == 0) return LTG_OK;
-    const Workspace w = carve(cfg, n_rows, fake->n, (char*)ws);   // same carve as ltg_g_bwd_dec: y lives there
-    PairView pv{0, fake->n, nullptr, nullptr, fake->pop, fake->niche};
-    DropView dA{nullptr, o->drop_fake[0], 0, 0}, dB{nullptr, o->drop_fake[1], 0, 0}, dC{nullptr, o->drop_fake[2], 0, 0};
-    disc_forward(cfg, disc, pv, dA, dB, dC, o->d_keep_prob, o->d_rng_step, w, false, nullptr, (hipStream_t)stream);
+    fake_tower(cfg, disc, fake, o, w, nullptr, (hipStream_t)stream);
     return check_launch();
 }
 
@@ -1431,14 +1457,13 @@ int ltg_fake_tower_batched(const ltg_config* cfg, const ltg_disc_state* disc, co
     clear_errors();
     if (!cfg_ok(cfg) || !disc || !fake || !seg_of || !seg_row0 || !seg_step || !y_out || !ws || fake->n < 0 || !fake->pop || !fake->niche) return LTG_EINVAL;
     if (fake->n == 0) return LTG_OK;
-    if (ltg_workspace_bytes(cfg, 1, fake->n) > ws_bytes) return LTG_EWORKSPACE;
-    const Workspace w = carve(cfg, 1, fake->n, (char*)ws);
-    PairView pv{0, fake->n, nullptr, nullptr, fake->pop, fake->niche};
+    Workspace w;
+    if (carve_checked(cfg, 1, fake->n, ws, ws_bytes, &w) != LTG_OK) return LTG_EWORKSPACE;
     DropView dv{nullptr, nullptr, 0, 0};
     dv.seg_of = seg_of;
     dv.seg_row0 = seg_row0;
     dv.seg_step = seg_step;
-    disc_forward(cfg, disc, pv, dv, dv, dv, d_keep_prob, 0, w, false, nullptr, (hipStream_t)stream, y_out);
+    fake_tower(cfg, disc, fake, dv, dv, dv, d_keep_prob, 0, w, nullptr, (hipStream_t)stream, y_out);
     return check_launch();
 }
 
@@ -1448,25 +1473,35 @@ int ltg_g_bwd_rest(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_ba
     if (!g_args_ok(cfg, gen, bt, acts) || !fake || !o || !dh2 || !ws || o->adam_t < 1) return LTG_EINVAL;
     if (!bt->uptr || !bt->rowidx || !bt->csr_pos) return LTG_EINVAL;
     if (bt->n_unique < 0 || (size_t)bt->n_unique > gq0_rows(cfg, bt->n_rows)) return LTG_EINVAL;
-    if (ltg_workspace_bytes(cfg, bt->n_rows, fake->n) > ws_bytes) return LTG_EWORKSPACE;
-    const Workspace w = carve(cfg, bt->n_rows, fake->n, (char*)ws);   // same carve as ltg_g_bwd_dec: dlog lives there
-    return g_stage_bwd_rest(cfg, gen, bt, o, acts, dh2, w, (hipStream_t)stream);
+    Workspace w;   // same carve as ltg_g_bwd_dec: dlog lives there
+    if (carve_checked(cfg, bt->n_rows, fake->n, ws, ws_bytes, &w) != LTG_OK) return LTG_EWORKSPACE;
+    return g_stage_bwd_rest(cfg, gen, g_route(cfg, gen, bt->n_rows, true), bt, o, acts, dh2, w, (hipStream_t)stream);
 }
 
 int ltg_g_bwd_dec1(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_batch* bt, const ltg_pairs* fake,
                    const ltg_g_opts* o, const ltg_gen_acts* acts, void* ws, size_t ws_bytes, ltg_stream stream) {
     clear_errors();
     if (!g_args_ok(cfg, gen, bt, acts) || !fake || !o || !ws || o->adam_t < 1 || o->dec1_done) return LTG_EINVAL;
-    if (ltg_workspace_bytes(cfg, bt->n_rows, fake->n) > ws_bytes) return LTG_EWORKSPACE;
-    const Workspace w = carve(cfg, bt->n_rows, fake->n, (char*)ws);   // same carve as ltg_g_bwd_dec: dlog lives there
-    return g_stage_bwd_rest(cfg, gen, bt, o, acts, nullptr, w, (hipStream_t)stream, true, true);
+    Workspace w;   // same carve as ltg_g_bwd_dec: dlog lives there
+    if (carve_checked(cfg, bt->n_rows, fake->n, ws, ws_bytes, &w) != LTG_OK) return LTG_EWORKSPACE;
+    return g_stage_bwd_rest(cfg, gen, g_route(cfg, gen, bt->n_rows, true), bt, o, acts, nullptr, w, (hipStream_t)stream, true, true);
 }
 
 /* ---- the item-sharded step as ONE call, exchanges in-stream, weight update and clock slice beside the next step (include/ltg.h) ---- */
 int ltg_g_step_sharded_ok(const ltg_config* cfg, const ltg_gen_state* gen, int32_t n_rows) {
     if (!cfg_ok(cfg) || !gen || n_rows <= 0) return 0;
-    return (fast_on(cfg) && mid_fast(cfg, n_rows) && stream_ok(cfg, gen, n_rows) && dw_stream_ok(cfg->h_enc) && dlog16_ok(cfg, gen, n_rows) &&
-            q0_lazy(cfg, gen)) ? 1 : 0;
+    return g_route(cfg, gen, n_rows).sharded_ok;
+}
+/* ---- the routes themselves, for callers and tests (host-only; include/ltg.h) ---- */
+int ltg_g_route(const ltg_config* cfg, const ltg_gen_state* gen, int32_t n_rows, ltg_g_route_info* out) {
+    if (!cfg_ok(cfg) || !gen || n_rows <= 0 || !out) return 0;
+    *out = g_route(cfg, gen, n_rows);
+    return 1;
+}
+int ltg_d_route(const ltg_config* cfg, const ltg_disc_state* disc, int32_t n_pairs, int32_t with_bwd, int32_t has_aux, ltg_d_route_info* out) {
+    if (!cfg_ok(cfg) || !disc || n_pairs < 0 || !out) return 0;
+    *out = d_route(cfg, disc, n_pairs, with_bwd != 0, has_aux != 0);
+    return 1;
 }
 
 // the catch-up ahead (include/ltg.h): device words with the slice on the side stream, marks, batches with their distinct-item lists
@@ -1537,12 +1572,14 @@ int ltg_g_step_sharded(const ltg_config* cfg, const ltg_gen_state* gen, const lt
     if (!g_args_ok(cfg, gen, bt, acts) || !disc || !fake || !o || !pp || !loss_out || !ws || o->adam_t < 1) return LTG_EINVAL;
     if (!bt->uptr || !bt->rowidx || !bt->csr_pos || !o->cnt || !fake->row || fake->n < 0) return LTG_EINVAL;
     if (bt->n_unique < 0 || (size_t)bt->n_unique > gq0_rows(cfg, bt->n_rows)) return LTG_EINVAL;
-    if (!ltg_g_step_sharded_ok(cfg, gen, bt->n_rows)) return LTG_EINVAL;
+    const ltg_g_route_info r = g_route(cfg, gen, bt->n_rows);
+    if (!r.sharded_ok) return LTG_EINVAL;
     if (!pp->side_stream || !pp->ev_fork || !pp->ev_dec1 || !pp->h1pre || !pp->rowpart_all || !pp->dh2 || (pp->flags & ~PIPE_FLAGS) != 0) return LTG_EINVAL;
     const int R = comm ? comm->n_ranks : 1, rank = comm ? comm->rank : 0;
     if (R < 1 || rank < 0 || rank >= R || (comm && (!comm->all_reduce || !comm->all_gather))) return LTG_EINVAL;
     const int B = bt->n_rows, I = cfg->n_items, H = cfg->h_enc, Z = cfg->z_dim, nf = fake->n;
-    if (ltg_workspace_bytes(cfg, B, nf) > ws_bytes) return LTG_EWORKSPACE;
+    Workspace w;
+    if (carve_checked(cfg, B, nf, ws, ws_bytes, &w) != LTG_OK) return LTG_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream, sd = (hipStream_t)pp->side_stream;
     hipEvent_t ev_fork = (hipEvent_t)pp->ev_fork, ev_dec1 = (hipEvent_t)pp->ev_dec1;
     const bool fork_dec1 = (pp->flags & LTG_PIPE_NO_DEC1_FORK) == 0;
@@ -1555,7 +1592,6 @@ int ltg_g_step_sharded(const ltg_config* cfg, const ltg_gen_state* gen, const lt
     const bool side_slice = gates && defer_slice && (pp->flags & LTG_PIPE_SLICE_IN_TOUCH) == 0;
     const bool merge_slice = defer_slice && !side_slice;   // (events, or LTG_PIPE_SLICE_IN_TOUCH: the slice rides in the catch-up launch)
     const bool ahead = side_slice && q0_ahead_capable(cfg, gen, bt, pp);   // catch-up of the NEXT batch's rows during this call (include/ltg.h)
-    Workspace w = carve(cfg, B, nf, (char*)ws);
     if (o->y_pre) w.y = const_cast<float*>(o->y_pre);   // y_generated from ltg_fake_tower_batched
     const Probe pr{o->probe, st};
     const AdamC ad = make_adam(cfg, o->adam_t);
@@ -1604,16 +1640,16 @@ int ltg_g_step_sharded(const ltg_config* cfg, const ltg_gen_state* gen, const lt
         // stream's next kernel (the waiter in front of the weight update) when it starts, and the NEXT call's catch-up polls for it
         // (issued in the order the device needs them: the critical stream's kernels first)
         // (the previous call's last kernel waited for word 6 before it ended: ltg_gate_wait_tail in fk_g_tail)
-        q0_touch(cfg, gen, bt, st, poison, ahead ? pp->q0_mark : nullptr, pp->seq);
+        q0_touch(cfg, gen, r, bt, st, poison, ahead ? pp->q0_mark : nullptr, pp->seq);
     } else
-        q0_touch(cfg, gen, bt, st, poison);
+        q0_touch(cfg, gen, r, bt, st, poison);
     // ---- forward: enc-0 over the local slab -> exchange 1 -> enc-1 (bias + tanh in its loader), dec-0, local logits + statistics
     // (Round 4, measured and removed: without a communicator, bias + tanh in enc-0 and the plain enc-1 behind it, h1 alternating between
     // two buffers: 143.5-147.2 against 145.2-148.1 us per step at 20 000 items, equal at 200 000 -- within the noise, one mode fewer.)
     {
         ltg_gen_acts a1 = *acts;
         a1.h1 = pp->h1pre;
-        fwd_stage_enc(cfg, gen, bt, &o->fwd, &a1, 1, st, nullptr, true, side_slice ? LtgGate{pp->sync + 5, pp->seq, nullptr, 0} : LTG_NO_GATE,
+        fwd_stage_enc(cfg, gen, r, bt, &o->fwd, &a1, 1, st, nullptr, true, side_slice ? LtgGate{pp->sync + 5, pp->seq, nullptr, 0} : LTG_NO_GATE,
                       tail_own ? LtgGate{pp->sync + 10, pp->seq - 1u, pp->sync + 2, 0} : LTG_NO_GATE);
     }
     // (Round 4, measured and removed: the clock's kernels on the pipe's THIRD stream instead of between two weight updates on the side
@@ -1655,21 +1691,17 @@ int ltg_g_step_sharded(const ltg_config* cfg, const ltg_gen_state* gen, const lt
     // 143 against 139.5 us per step at 20 000 items, 102 against 101 at 25 024 -- the redundancy costs what the launch saved.)
     {
         int G = 0;
-        LTG_PROBED(pr, LTG_K_DEC1_FWD, G = launch_dec1_fwd_stream(cfg, gen, B, acts, w.segpart, st));
-        g_row_partial(cfg, bt, nf > 0 ? fake : nullptr, acts, rowpart, st, w.segpart, nullptr, G);
+        LTG_PROBED(pr, LTG_K_DEC1_FWD, G = launch_dec1_fwd_stream(cfg, gen, r, B, acts, w.segpart, st));
+        g_row_partial(cfg, r, bt, nf > 0 ? fake : nullptr, acts, rowpart, st, w.segpart, nullptr, G);
     }
     if (comm) LTG_PROBED(pr, LTG_K_EXCH_ROWPART, LTG_COMM(comm->all_gather(rowpart, pp->rowpart_all, (size_t)B * RP, LTG_NCCL_FLOAT32, comm->comm, stream)));
     // ---- backward: (fake tower when it was not evaluated ahead,) losses + dlogits
-    if (nf > 0 && !o->y_pre && !(o->fake_done & 1)) {
-        PairView pv{0, nf, nullptr, nullptr, fake->pop, fake->niche};
-        DropView dA{nullptr, o->drop_fake[0], 0, 0}, dB{nullptr, o->drop_fake[1], 0, 0}, dC{nullptr, o->drop_fake[2], 0, 0};
-        disc_forward(cfg, disc, pv, dA, dB, dC, o->d_keep_prob, o->d_rng_step, w, false, o->probe, st);
-    }
+    if (nf > 0 && !o->y_pre && !(o->fake_done & 1)) fake_tower(cfg, disc, fake, o, w, o->probe, st);
     hipLaunchKernelGGL(k_dlogits_combine<true>, dim3((I + DL_SEG - 1) / DL_SEG, B), dim3(NT), 0, st, B, I, R, bt->indptr, bt->indices, bt->values, acts->logits,
                        pp->rowpart_all, acts->kl_rows, nf > 0 ? w.y : (const float*)nullptr, o->cnt, o->anneal, o->gan_lambda, nf, fake->row, fake->niche, fake->pop,
                        w.dlog, acts->lse, w.scal, loss_out, cfg->item_lo);
     {
-        const int kchunk = dh2_stream_chunk(I), nsplit = (I + kchunk - 1) / kchunk;
+        const int kchunk = r.dh2_chunk, nsplit = r.dh2_nsplit;
         // Two shadow buffers (ltg_pipe.shadow_out): the update of this call writes the OTHER buffer, so the dh2 product -- the last reader of
         // this call's shadow -- leaves the cycle update -> streaming forward -> dlogits -> [dh2 product] -> update that bounds the step at
         // 20 000 - 25 000 items: the update's gate (word 0) opens when the product STARTS (dlogits is complete), not when it has ended.
@@ -1687,7 +1719,7 @@ int ltg_g_step_sharded(const ltg_config* cfg, const ltg_gen_state* gen, const lt
         hipStream_t sdw = st;
         const int n_da2 = B * H;
         if (gates)   // the slab sum first: it is the next kernel of the critical stream, the side stream's launches take the host ~30 us
-            hipLaunchKernelGGL(k_da2, dim3((n_da2 + NT - 1) / NT < 2048 ? (n_da2 + NT - 1) / NT : 2048), dim3(NT), 0, st, n_da2, nsplit, w.part, (const float*)nullptr,
+            hipLaunchKernelGGL(k_da2, grid1(n_da2, 2048), dim3(NT), 0, st, n_da2, nsplit, w.part, (const float*)nullptr,
                                pp->dh2, pingpong ? LTG_NO_GATE : LtgGate{pp->sync, pp->seq, nullptr, 0});
         if (gates) {   // the side stream's work starts behind a one-wave kernel that polls the word the slab sum (below) sets when it starts
             hipLaunchKernelGGL(k_gate_wait, dim3(1), dim3(64), 0, sd, LtgGate{pp->sync, pp->seq, pp->sync + 2, 0},
@@ -1707,7 +1739,7 @@ int ltg_g_step_sharded(const ltg_config* cfg, const ltg_gen_state* gen, const lt
         const LtgH2Done hd_last = h2_early ? LtgH2Done{pp->sync + 8, pp->sync + 1, pp->seq, poison} : LtgH2Done{nullptr, nullptr, 0u, poison};
         ltg_gen_state gen_dw = *gen;
         if (pingpong) gen_dw.wp1t_bf16 = pp->shadow_out;   // (the caller exchanges the two pointers after the call)
-        const int rc = g_stage_bwd_rest(cfg, &gen_dw, bt, &od, acts, nullptr, w, sdw, true, true, hd_last);
+        const int rc = g_stage_bwd_rest(cfg, &gen_dw, r, bt, &od, acts, nullptr, w, sdw, true, true, hd_last);
         if (rc != LTG_OK) return rc;
         // (Round 4, measured and removed: word 7 stored by the NEXT call's first waiter on the side stream when it starts, instead of by one
         // wave behind the update: 149.8 against 146.8 us per step at 20 000 items, 165.7 against 161.5 at 25 024 -- slower; and a host that is
@@ -1717,7 +1749,7 @@ int ltg_g_step_sharded(const ltg_config* cfg, const ltg_gen_state* gen, const lt
                                h2_early ? LTG_NO_GATE : LtgGate{pp->sync + 1, pp->seq, nullptr, 0});
         else if (fork_dec1) LTG_HIP(hipEventRecord(ev_dec1, sd));
         if (!gates)
-            hipLaunchKernelGGL(k_da2, dim3((n_da2 + NT - 1) / NT < 2048 ? (n_da2 + NT - 1) / NT : 2048), dim3(NT), 0, st, n_da2, nsplit, w.part, (const float*)nullptr,
+            hipLaunchKernelGGL(k_da2, grid1(n_da2, 2048), dim3(NT), 0, st, n_da2, nsplit, w.part, (const float*)nullptr,
                                pp->dh2);
     }
     if (comm) LTG_PROBED(pr, LTG_K_EXCH_DH2, LTG_COMM(comm->all_reduce(pp->dh2, pp->dh2, (size_t)B * H, LTG_NCCL_FLOAT32, LTG_NCCL_SUM, comm->comm, stream)));
@@ -1730,11 +1762,11 @@ int ltg_g_step_sharded(const ltg_config* cfg, const ltg_gen_state* gen, const lt
         g_enc0_grad(cfg, bt, o, acts, w, st, gen, &ad, true, poison, LtgGate{pp->sync + 9, pp->seq, nullptr, 0}, slice_done,
                     gen->q0_lr_hist + ((gen->q0_ord + 1) & (LTG_Q0_HIST - 1)));
         hipLaunchKernelGGL(k_gate_wait, dim3(1), dim3(64), 0, stl, LtgGate{pp->sync + 9, pp->seq, pp->sync + 2, 0}, LTG_NO_GATE);
-        g_jobs(-1, cfg, gen, bt, o, acts, w, ad, nullptr, false, nullptr, stl, true, true, poison, LTG_NO_GATE, true);
+        g_jobs(cfg, gen, bt, o, acts, w, ad, nullptr, false, nullptr, stl, true, true, poison, LTG_NO_GATE, true);
         hipLaunchKernelGGL(k_gate_set, dim3(1), dim3(64), 0, stl, LtgGate{pp->sync + 10, pp->seq, nullptr, 0}, LTG_NO_GATE);
     } else {
         g_enc0_grad(cfg, bt, o, acts, w, st, gen, &ad, (pp->flags & LTG_PIPE_WIDE_GRAD) == 0, poison);
-        g_jobs(-1, cfg, gen, bt, o, acts, w, ad, nullptr, false, nullptr, st, true, true, poison, slice_done);
+        g_jobs(cfg, gen, bt, o, acts, w, ad, nullptr, false, nullptr, st, true, true, poison, slice_done);
     }
     if (!defer_slice) {   // the slice of THIS step at its end, in program order (the cut-point schedule)
         const int ord = gen->q0_ord + 1, start = ord % qP;

@@ -588,6 +588,21 @@ class Engine:
             return False
         return bool(self.lib.ltg_g_step_sharded_ok(C.byref(self.cfg), C.byref(self.gen_c), int(rows)))
 
+    def g_route(self, rows):
+        """the kernels a G step (or a forward) over `rows` batch rows runs with this engine's configuration (include/ltg.h: ltg_g_route)"""
+        out = cabi.ltg_g_route_info()
+        if not self.lib.ltg_g_route(C.byref(self.cfg), C.byref(self.gen_c), int(rows), C.byref(out)):
+            raise cabi.LtgError("ltg_g_route refused the configuration")
+        return out
+
+    def d_route(self, n, with_bwd=True):
+        """the kernels a D step (with_bwd) or a forward-only tower over n pair rows runs (include/ltg.h: ltg_d_route)"""
+        out = cabi.ltg_d_route_info()
+        has_aux = bool(with_bwd and self.d_fork and self.d_precision == cabi.LTG_PREC_FP32)
+        if not self.lib.ltg_d_route(C.byref(self.cfg), C.byref(self.disc_c), int(n), int(bool(with_bwd)), int(has_aux), C.byref(out)):
+            raise cabi.LtgError("ltg_d_route refused the configuration")
+        return out
+
     def g_step_sharded(self, batch, fake, acts, gopts, pipe, comm=None, loss_out=None, next_batch=None):
         """every launch of the step and its exchanges from one call (comm: _rccl.RcclComm / HostComm; None = one rank).
         next_batch: the batch of the NEXT call on this pipe when the caller knows it -- its rows of W_q0 are brought up to the lazy clock

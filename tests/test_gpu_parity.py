@@ -272,7 +272,8 @@ G_CASES = [(1000, 100, "step", G_D), (333, 17, "step", G_D), (6000, 100, "step",
            (1000, 100, "step-generic", G_D), (333, 17, "step-generic", G_D), (8200, 100, "step-generic", G_D),
            # the fake tower at unaligned sizes (generic kernels) and past the one-kernel tower's h0 / h3 limits (fks_d_*)
            (1000, 100, "step", (99, 151, 250, 301)), (1000, 100, "step", (132, 150, 250, 324)),
-           # either side of small_fast / mid_fast (rows <= 256), and 300 rows: generic middle layers beside the streaming decoder
+           # either side of the small-slab / middle-fast row limit (256), and 300 rows of a large slab: generic middle layers and, past the
+           # streaming kernels' 128 rows, the tiled decoder (tests/test_routes_cpu.py has each route)
            (1000, 256, "step", G_D), (1000, 257, "step", G_D), (8200, 300, "step", G_D)]
 
 
@@ -358,7 +359,7 @@ def _g_step_case(precision, I, B, path, warm, hs=G_D, history="uniform", P=None,
         # ltg_g_step_sharded serves the bf16 decoder path only: an fp32 engine is refused before any launch (a trainer then takes
         # ltg_g_step), and that step is held to the same oracle below
         from ltgan._cabi import LtgError
-        assert not eng.sharded_step_ok(B)
+        assert not eng.sharded_step_ok(B) and eng.g_route(B).sharded_ok == 0
         before = [t.clone() for t in eng.g_p]
         with pytest.raises(LtgError, match="ltg_g_step_sharded"):
             eng.g_step_sharded(batch, fake, acts, eng.g_opts(cnt_t, anneal, lam, keep, 1.0, dkeep, step, dstep), Pipe(eng, B))
@@ -367,7 +368,7 @@ def _g_step_case(precision, I, B, path, warm, hs=G_D, history="uniform", P=None,
         eng.adam_t = t0                      # (g_opts drew the shared counter for a step that never ran)
         path = "step"
     if path.startswith("one-call"):
-        assert eng.sharded_step_ok(B)
+        assert eng.sharded_step_ok(B) and eng.g_route(B).sharded_ok == 1
         pipe = Pipe(eng, B)
         go = eng.g_opts(cnt_t, anneal, lam, keep, 1.0, dkeep, step, dstep)
         loss = eng.g_step_sharded(batch, fake, acts, go, pipe)
@@ -451,7 +452,7 @@ def test_g_step_adam_quotient_from_warm_moments(precision, I, B, path, history):
 
 
 # Discriminator layer sizes (config.ini h0_size..h3_size) against the routes the library picks from them alone (csrc/ltg_kernels.hip:
-# d_fast, d_wide, d_tile; the bwd1 tile promotion above 1 024 32 x 32 tiles).  witness "generic": the step equals its tuning-bit-18 twin
+# d_route -- kind, tile codes, the bwd1 tile promotion above 1 024 32 x 32 tiles; tests/test_routes_cpu.py pins each line's route).  witness "generic": the step equals its tuning-bit-18 twin
 # (the generic kernels forced) bit for bit, and d_arith, which only reaches the latency-path kernels, changes no bit; "fast": the fk_d_*
 # kernels run, so the twin differs somewhere; None: too small for either statement.
 D_SIZES = [((99, 150, 250, 300), "generic"),     # generic; l1 / bwd2 scalar 32, l2 / bwd1 -32 (64 above 1 024 tiles)
@@ -578,6 +579,8 @@ def _d_step_case(nr, nf, warm, knob=0, d_arith=None, loosen=1.0, hs=None, witnes
         def same(a, b):
             return np.array_equal(a[0].view(np.uint32), b[0].view(np.uint32)) and all(
                 np.array_equal(x.view(np.uint32), y.view(np.uint32)) for sa, sb in zip(a[1], b[1]) for x, y in zip(sa, sb))
+        from ltgan import _cabi as cabi
+        assert eng.d_route(n).kind == {"generic": cabi.LTG_D_GENERIC, "fast": cabi.LTG_D_FAST}[witness], (hs, "the library names another route")
         twin = device_step(1 << 18, d_arith)[1:]
         if witness == "generic":
             assert same((loss_bits, state), twin), (hs, "not the generic kernels: the bit-18 twin differs")

@@ -240,7 +240,7 @@ typedef struct ltg_d_opts {
     const ltg_probe* probe; /* optional */
     /* optional (ABI v12; ltg_d_step at the fp32 default sizes): jobs B / C of the backward's first stage -- dw3, db3, dw4, db4, d_loss: they
      * need the forward only -- run on `aux_stream` beside the critical chain job A -> stage 2, handed over through device words like
-     * ltg_pipe's: sync = 4 zeroed words owned by the caller (0: forward complete, 1: jobs B / C ended, 2: polls that gave up = poison:
+     * ltg_pipe's: sync = 4 zeroed words owned by the caller (LTG_WORD_D_FWD_DONE: forward complete, LTG_WORD_D_JOBS_DONE: jobs B / C ended, LTG_WORD_POISON: polls that gave up:
      * the Adam sweep then returns at once and the caller must treat it as fatal), seq = the call's ordinal on these words (+ 1 per
      * call, starting at 1).  The two streams must run concurrently (ltg_g_pipe_probe tests a pair).  NULL: one stream, five launches. */
     ltg_stream aux_stream;
@@ -417,23 +417,12 @@ int ltg_gather_cand_logits(const ltg_config* cfg, const ltg_sample_inputs* in, c
  * Hand-over between the two streams: a cross-stream event pair costs ~12 us per direction on this hardware and ~6 us of bubble on the
  * recording stream (scripts/micro/sync_cost.hip), so the streams meet through words of device memory (ltg_pipe.sync; `seq` = the
  * call's ordinal) -- no packet waits on the caller's stream at all:
- *   word 0  the dh2 product of call seq is complete (stored by the slab sum when it starts; a one-wave kernel in front of the weight
- *           update polls for it)
- *   word 1  the weight update of call seq has READ h2 -- it reads h2 in its prologue only: its workgroups count themselves in word 8
- *           behind it and the last one stores the ordinal (ragged slabs: stored when the update ends).  dec-0 of call seq + 1 overwrites h2.
- *   word 7  the weight update of call seq has ENDED (one wave behind it): the streaming forward of call seq + 1 reads the shadow rows
- *           and the bias it writes
- *   word 5  enc-0 of call seq has started = the catch-up of the batch's rows is complete (a one-wave kernel in front of the slice polls)
- *   word 6  the clock's work beside call seq -- its slice and, ABI v13, the catch-up of the next batch's rows -- has ended (stored by the
- *           next kernel of the side stream when it starts): the catch-up of call seq + 1 must not meet it on a row
- *   word 9  dh1 of call seq is complete (stored by the sparse gradient kernel when it starts; a one-wave kernel in front of the Adam
- *           tail on ltg_pipe.tail_stream polls);  word 10  that tail has ended (one wave behind it): enc-1 of call seq + 1 reads what it updates
- *   word 2  polls that gave up (each is bounded: 30 s) = the pipe's POISON
+ *   (enum ltg_word below names every word and says who stores it and who polls for it)
  * Every poll is made by ONE thread: a one-wave kernel of the side stream, or -- on the caller's stream -- the last thread of the kernel
- * IN FRONT of the one that needs the word (enc-1 for word 1, dec-0 for word 7, enc-0 for word 10, the step's last kernel for word 6): stream order then
+ * IN FRONT of the one that needs the word (enc-1 for H2_READ, dec-0 for UPDATE_END, enc-0 for TAIL_END, the step's last kernel for SLICE_DONE): stream order then
  * gates the consumer whatever its size, and no workgroup of a large launch holds a CU while it waits for a producer that may still
- * need one.  Once word 2 is non-zero every kernel of the step that writes h2 or the model returns at once, so the model stays what it
- * was when the wait expired; the caller checks word 2 before it reads the model out (end of a phase, checkpoint) and treats it as fatal.
+ * need one.  Once LTG_WORD_POISON is non-zero every kernel of the step that writes h2 or the model returns at once, so the model stays what it
+ * was when the wait expired; the caller checks that word before it reads the model out (end of a phase, checkpoint) and treats it as fatal.
  * LTG_PIPE_SLICE_IN_TOUCH keeps the slice in the catch-up launch of call t (one launch over the batch's rows and the slice's rows; a
  * row in both sets goes to whichever workgroup's atomic max on its clock comes first).  LTG_PIPE_EVENTS (or sync == NULL) selects event
  * pairs instead of words: stream waits on events recorded by the PREVIOUS call (a never-recorded event does not block), the slice in
@@ -446,7 +435,7 @@ int ltg_gather_cand_logits(const ltg_config* cfg, const ltg_sample_inputs* in, c
  * Catch-up AHEAD (ABI v13; device-word mode with the slice on the side stream, batches that carry `uitem`, h_enc <= 768): the catch-up
  * of the lazy clock -- the rows of W_q0 the batch reads, brought up to the caller's clock before enc-0 -- is the FIRST kernel of the
  * step's critical chain and moves 24 B per parameter of every distinct row.  A caller that knows the NEXT batch sets
- * ltg_pipe.next_uitem / next_nu: call t then brings those rows up to ordinal t ON THE SIDE STREAM, behind its slice (so word 6 covers
+ * ltg_pipe.next_uitem / next_nu: call t then brings those rows up to ordinal t ON THE SIDE STREAM, behind its slice (so LTG_WORD_SLICE_DONE covers
  * it), beside its own forward -- every row except the ones batch t itself holds (those get step t's gradient from the sparse gradient
  * kernel and are at t with it).  Which rows batch t holds is read from ltg_pipe.q0_mark (one int32 per local item, zeroed once by the
  * caller and with every reset of seq): the catch-up -- or the ahead kernel of the call before -- stores the call's ordinal there.  The
@@ -484,6 +473,36 @@ size_t ltg_oneshot_expired_offset(int32_t n_ranks);
 int ltg_oneshot_all_reduce(const void* sendbuf, void* recvbuf, size_t count, int dtype, int op, void* comm, ltg_stream stream);
 int ltg_oneshot_all_gather(const void* sendbuf, void* recvbuf, size_t sendcount, int dtype, void* comm, ltg_stream stream);
 
+/* The device words of a pipe (indices into ltg_pipe.sync; `seq` = the ordinal of the call that stores the word).  THE description of each:
+ * who stores it, who polls for it.  ltg_d_step's fork (ltg_d_opts.sync) has two words of its own and the same poison index. */
+enum ltg_word {
+    LTG_WORD_DH2_DONE = 0,   /* the dh2 product of call seq is complete (stored by the slab sum when it starts -- with two shadow buffers by the
+                              * product itself when it starts: dlogits is complete; a one-wave kernel in front of the weight update polls) */
+    LTG_WORD_H2_READ = 1,    /* the weight update of call seq has READ h2 -- it reads h2 in its prologue only: its workgroups count themselves
+                              * in LTG_WORD_H2_COUNT behind it and the last one stores the ordinal (ragged slabs: the generic tile kernel on the
+                              * last n_items % 32 rows reads h2 throughout, the word is stored with LTG_WORD_UPDATE_END).  Polled by the last
+                              * thread of call seq + 1's enc-1, in front of dec-0, which overwrites h2 */
+    LTG_WORD_POISON = 2,     /* polls that gave up (each is bounded: 30 s) = the pipe's POISON: every kernel of the step that writes h2 or the
+                              * model returns at once when it is set */
+    LTG_WORD_PROBE = 3,      /* ltg_g_pipe_probe's gate, and in the word behind it (4) its own count of polls that gave up */
+    LTG_WORD_CATCHUP = 5,    /* enc-0 of call seq has started = the catch-up of the batch's rows is complete (a one-wave kernel in front of the
+                              * clock slice on the side stream polls) */
+    LTG_WORD_SLICE_DONE = 6, /* the clock's work beside call seq -- its slice and, ABI v13, the catch-up of the next batch's rows -- has ended
+                              * (stored by the next kernel of the side stream, the waiter in front of the weight update, when it starts).  Polled
+                              * by the last thread of call seq's OWN last kernel on the caller's stream: the catch-up of call seq + 1 must not
+                              * meet the slice on a row */
+    LTG_WORD_UPDATE_END = 7, /* the weight update of call seq has ENDED (one wave behind it).  Polled by the last thread of call seq + 1's dec-0,
+                              * in front of the streaming forward, which reads the shadow rows and the bias the update writes */
+    LTG_WORD_H2_COUNT = 8,   /* the update's workgroups that are past their prologue (see LTG_WORD_H2_READ) */
+    LTG_WORD_DH1_DONE = 9,   /* dh1 of call seq is complete (stored by the sparse gradient kernel when it starts; a one-wave kernel in front of
+                              * the Adam tail on ltg_pipe.tail_stream polls) */
+    LTG_WORD_TAIL_END = 10,  /* that tail has ended (one wave behind it).  Polled by the last thread of call seq + 1's enc-0, in front of enc-1,
+                              * which reads what the tail updates */
+    /* ltg_d_opts.sync */
+    LTG_WORD_D_FWD_DONE = 0, /* the forward is complete (stored by job A's launch when it starts, polled by one wave in front of jobs B / C) */
+    LTG_WORD_D_JOBS_DONE = 1 /* jobs B / C have ended (one wave behind them; polled by an extra block of stage 2 in front of the Adam sweep) */
+};
+
 typedef struct ltg_pipe {
     ltg_stream side_stream;
     void* ev_fork; /* hipEvent_t x 2, timing disabled (LTG_PIPE_EVENTS and ltg_g_pipe_join) */
@@ -494,11 +513,11 @@ typedef struct ltg_pipe {
     float* dh2;         /* [n_rows][H]  exchange 3: local dh2, all-reduced in place */
     int32_t flags;      /* LTG_PIPE_* measurement switches, 0 = the shipped schedule */
     uint32_t seq;       /* ordinal of this call on this pipe: the caller adds 1 before every ltg_g_step_sharded call (starting at 1) */
-    uint32_t* sync;     /* [16] device words, zeroed once by the caller: the hand-overs listed above (words 0-2, 5-8; 3-4: ltg_g_pipe_probe).
+    uint32_t* sync;     /* [16] device words, zeroed once by the caller: the hand-overs of enum ltg_word.
                          * NULL: the hand-overs are events (ev_fork / ev_dec1), as with LTG_PIPE_EVENTS */
     ltg_stream tail_stream; /* optional THIRD stream (ABI v12; device-word mode only): the step's Adam tail -- W_p0, W_q1 and the biases; it needs
                              * the backward's dh1 only -- runs there beside the sparse W_q0 gradient, the next call's catch-up and enc-0
-                             * (words 9 / 10); used with LTG_PIPE_TAIL_OWN only.  NULL: the tail is the step's last kernel on the caller's stream */
+                             * (LTG_WORD_DH1_DONE / LTG_WORD_TAIL_END); used with LTG_PIPE_TAIL_OWN only.  NULL: the tail is the step's last kernel on the caller's stream */
     /* catch-up ahead (ABI v13; all optional, see above) */
     int32_t* q0_mark;           /* [n_items] int32, zeroed by the caller (and again whenever seq restarts): ordinal of the last call whose batch holds the row */
     const int32_t* next_uitem;  /* the NEXT call's ltg_batch.uitem (its distinct local items) or NULL */
@@ -515,11 +534,12 @@ typedef struct ltg_pipe {
                                       side stream between the catch-up of call t and that of call t + 1 */
 #define LTG_PIPE_EVENTS 16       /* fork and join of the weight update as hipEventRecord / hipStreamWaitEvent pairs instead of device words */
 #define LTG_PIPE_WIDE_GRAD 8     /* the sparse W_q0 gradient in its column-blocked shape (three times the waves) although it runs beside the update */
-#define LTG_PIPE_TAIL_OWN 128    /* the Adam tail on ltg_pipe.tail_stream (default: the step's last kernel on the caller's stream -- measured, see ltg_g_step_sharded) */
+#define LTG_PIPE_TAIL_OWN 128    /* the Adam tail on ltg_pipe.tail_stream (default: the step's last kernel on the caller's stream -- measured, see csrc: pipe_plan) */
 /* a flags bit outside these: ltg_g_step_sharded returns LTG_EINVAL */
 
 int ltg_g_step_sharded_ok(const ltg_config* cfg, const ltg_gen_state* gen, int32_t n_rows);
-/* What ltg_g_step_sharded will do with this batch and this pipe (the caller's bookkeeping depends on it), bits:
+/* What ltg_g_step_sharded will do with this batch and this pipe (the caller's bookkeeping depends on it): two fields of
+ * ltg_g_pipe_plan's struct (below) as bits:
  *   LTG_PLAN_AHEAD   it brings the rows announced in next_uitem up to date and honours caught_up
  *   LTG_PLAN_SHADOW  its weight update writes pipe->shadow_out (the caller exchanges it with gen->wp1t_bf16 after the call)
  * 0 also when the call would be refused. */
@@ -568,6 +588,28 @@ typedef struct ltg_g_route_info {
 } ltg_g_route_info;
 int ltg_g_route(const ltg_config* cfg, const ltg_gen_state* gen, int32_t n_rows, ltg_g_route_info* out);
 
+/* ---- the pipe's schedule (additive in ABI v14).  Where each stage of ltg_g_step_sharded runs and what it waits for, decided once per call in
+ * one place (csrc/ltg_kernels.hip: pipe_plan) from ltg_pipe.flags and the PRESENCE of pointers; every stage, ltg_g_step_sharded_plan and
+ * ltg_g_pipe_join read the result.  Host-only like the routes: nothing is dereferenced on the device; 1 = *out is filled, 0 = the call
+ * would be refused (a flags bit outside LTG_PIPE_*, a configuration ltg_g_step_sharded_ok refuses, a missing argument). */
+enum { LTG_HAND_ORDER = 0,   /* LTG_PIPE_NO_DEC1_FORK: one stream, program order */
+       LTG_HAND_EVENTS,      /* fork and join of the weight update are event pairs (LTG_PIPE_EVENTS, or no sync words) */
+       LTG_HAND_WORDS };     /* ... device words (enum ltg_word) */
+enum { LTG_SLICE_OWN_END = 0, /* the lazy clock's slice of step t at the end of step t, on the caller's stream */
+       LTG_SLICE_IN_TOUCH,    /* the slice step t - 1 owes in the catch-up launch of call t */
+       LTG_SLICE_SIDE };      /* ... on the side stream, between the catch-up of call t and that of call t + 1 */
+typedef struct ltg_pipe_plan_info {
+    int32_t handover;    /* LTG_HAND_* */
+    int32_t slice;       /* LTG_SLICE_* */
+    int32_t ahead;       /* 1: the call brings the rows announced in next_uitem up to date and honours caught_up (LTG_PLAN_AHEAD) */
+    int32_t shadow;      /* 1: the weight update writes pipe->shadow_out (LTG_PLAN_SHADOW) */
+    int32_t tail_own;    /* 1: the Adam tail runs on pipe->tail_stream */
+    int32_t h2_early;    /* 1: LTG_WORD_H2_READ opens behind the update's prologue (0: with its end) */
+    int32_t grad_rows;   /* 1: the sparse W_q0 gradient one wave per row (0: column-blocked, LTG_PIPE_WIDE_GRAD) */
+    int32_t poisonable;  /* 1: the step's kernels look at LTG_WORD_POISON */
+} ltg_pipe_plan_info;
+int ltg_g_pipe_plan(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_batch* batch, const ltg_pipe* pipe, ltg_pipe_plan_info* out);
+
 enum { LTG_D_GENERIC = 0,    /* k_d_*<mode> */
        LTG_D_TOWER,          /* forward only: the one-kernel tower */
        LTG_D_STAGED_FWD,     /* forward only: fks_d_l1 -> fks_d_l2 -> fk_d_y */
@@ -588,7 +630,7 @@ int ltg_d_route(const ltg_config* cfg, const ltg_disc_state* disc, int32_t n_pai
 /* 1: `stream` and pipe->side_stream (and pipe->tail_stream, and those two with each other) run concurrently (a waiter on one does not hold
  * up the other), as the device-word hand-over needs;
  * 0: they share a hardware queue (HIP maps streams onto a few of them) -- use another side stream, or LTG_PIPE_EVENTS; < 0: error.
- * Synchronises both streams; uses sync[3..4].  Call it once per (stream, side stream) pair before the first step. */
+ * Synchronises both streams; uses LTG_WORD_PROBE and the word behind it.  Call it once per (stream, side stream) pair before the first step. */
 int ltg_g_pipe_probe(const ltg_pipe* pipe, ltg_stream stream);
 /* `stream` waits for the forked pieces of the last ltg_g_step_sharded call (dec1_stream, q0_stream). */
 int ltg_g_pipe_join(const ltg_pipe* pipe, ltg_stream stream);

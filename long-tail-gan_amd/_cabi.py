@@ -140,6 +140,18 @@ class ltg_d_route_info(C.Structure):
     _fields_ = [("kind", C.c_int32), ("mode", C.c_int32), ("tile", C.c_int32 * 4), ("spl", C.c_int32 * 4), ("adam", C.c_int32), ("fork", C.c_int32)]
 
 
+# the pipe's schedule (include/ltg.h: ltg_g_pipe_plan) and the device words of ltg_pipe.sync / ltg_d_opts.sync (enum ltg_word)
+LTG_HAND_ORDER, LTG_HAND_EVENTS, LTG_HAND_WORDS = 0, 1, 2
+LTG_SLICE_OWN_END, LTG_SLICE_IN_TOUCH, LTG_SLICE_SIDE = 0, 1, 2
+(LTG_WORD_DH2_DONE, LTG_WORD_H2_READ, LTG_WORD_POISON, LTG_WORD_PROBE, LTG_WORD_CATCHUP, LTG_WORD_SLICE_DONE, LTG_WORD_UPDATE_END, LTG_WORD_H2_COUNT,
+ LTG_WORD_DH1_DONE, LTG_WORD_TAIL_END) = 0, 1, 2, 3, 5, 6, 7, 8, 9, 10
+LTG_WORD_D_FWD_DONE, LTG_WORD_D_JOBS_DONE = 0, 1
+
+
+class ltg_pipe_plan_info(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("handover", "slice", "ahead", "shadow", "tail_own", "h2_early", "grad_rows", "poisonable")]
+
+
 LTG_ONESHOT_MAX_RANKS = 16
 
 
@@ -156,6 +168,7 @@ SYMBOLS = {
     "ltg_oneshot_all_gather": (C.c_int, [vp, vp, C.c_size_t, C.c_int, vp, vp]),
     "ltg_g_step_sharded_ok": (C.c_int, [C.POINTER(ltg_config), C.POINTER(ltg_gen_state), C.c_int32]),
     "ltg_g_step_sharded_plan": (C.c_int, [C.POINTER(ltg_config), C.POINTER(ltg_gen_state), C.POINTER(ltg_batch), C.POINTER(ltg_pipe)]),
+    "ltg_g_pipe_plan": (C.c_int, [C.POINTER(ltg_config), C.POINTER(ltg_gen_state), C.POINTER(ltg_batch), C.POINTER(ltg_pipe), C.POINTER(ltg_pipe_plan_info)]),
     "ltg_g_route": (C.c_int, [C.POINTER(ltg_config), C.POINTER(ltg_gen_state), C.c_int32, C.POINTER(ltg_g_route_info)]),
     "ltg_d_route": (C.c_int, [C.POINTER(ltg_config), C.POINTER(ltg_disc_state), C.c_int32, C.c_int32, C.c_int32, C.POINTER(ltg_d_route_info)]),
     "ltg_g_step_sharded": (C.c_int, [C.POINTER(ltg_config), C.POINTER(ltg_gen_state), C.POINTER(ltg_disc_state), C.POINTER(ltg_batch),

@@ -190,6 +190,11 @@ __global__ __launch_bounds__(64) void k_gate_set(LtgGate g, LtgGate g2 = LTG_NO_
 // ---------------------------------------------------------------------------------------------
 inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 
+// a hand-over word of ltg_pipe.sync / ltg_d_opts.sync (include/ltg.h: enum ltg_word) as the gate a kernel stores `seq` to ...
+inline LtgGate gate_store(uint32_t* sync, int word, unsigned seq) { return LtgGate{sync + word, seq, nullptr, 0}; }
+// ... or polls for `seq` in (a poll that gives up counts in the poison word)
+inline LtgGate gate_poll(uint32_t* sync, int word, unsigned seq) { return LtgGate{sync + word, seq, sync + LTG_WORD_POISON, 0}; }
+
 // Which of the round-2 latency-path kernels (ltg_fast.h) apply.  Tuning-knob bit 18 of ltg_config.tuning switches all of
 // them off (the round-1 kernels compute the same function; kept for A/B measurements and as the path of unusual sizes).
 inline bool fast_on(const ltg_config* c) { return (c->tuning & (1 << 18)) == 0; }
@@ -467,17 +472,24 @@ void q0_touch(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_g_route
 }
 
 // stage 1: enc-0 over this rank's item slab.  pre_only: leave the partial pre-activation in acts->h1.
+struct Enc0Fwd {
+    float* xd = nullptr;              // small slabs: the dense operand rows for the backward's W_q0 product as well
+    bool touched = false;             // the caller ran the lazy clock's catch-up itself
+    LtgGate started = LTG_NO_GATE;    // stored when the kernel starts
+    LtgGate end_wait = LTG_NO_GATE;   // polled by one more block row, as the last thing the launch does
+};
 void fwd_stage_enc(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_g_route_info& r, const ltg_batch* bt, const ltg_fwd_opts* o,
-                   const ltg_gen_acts* acts, int pre_only, hipStream_t st, float* xd = nullptr, bool touched = false,
-                   LtgGate started = LTG_NO_GATE, LtgGate end_wait = LTG_NO_GATE) {
+                   const ltg_gen_acts* acts, int pre_only, hipStream_t st, const Enc0Fwd& a = {}) {
     const int R = bt->n_rows, I = cfg->n_items, H = cfg->h_enc;
     const Probe pr{o->probe, st};
-    if (!touched) q0_touch(cfg, gen, r, bt, st);
+    float* const xd = a.xd;
+    const LtgGate end_wait = a.end_wait;
+    if (!a.touched) q0_touch(cfg, gen, r, bt, st);
     if (r.enc0 == LTG_ENC0_FAST) {
         LTG_PROBED(pr, LTG_K_ENC0_FWD,
                    hipLaunchKernelGGL(fk_enc0_fwd, dim3((H / 4 + 63) / 64, R + (end_wait.word ? 1 : 0)), dim3(ENC_NT), xd ? (size_t)I * sizeof(float) : 0, st, H, I, bt->indptr,
                                       bt->indices, bt->values, o->drop_keep, o->keep_prob, cfg->seed, o->rng_step, gen->p[0], gen->p[4], acts->h1,
-                                      acts->row_scale, bt->row_norm2, cfg->item_lo, Ig_of(cfg), pre_only, xd, o->rows_per_step, started, end_wait));
+                                      acts->row_scale, bt->row_norm2, cfg->item_lo, Ig_of(cfg), pre_only, xd, o->rows_per_step, a.started, end_wait));
         return;
     }
     LTG_PROBED(pr, LTG_K_ENC0_FWD,
@@ -890,28 +902,25 @@ static int d_step_impl(const ltg_config* cfg, const ltg_disc_state* disc, PairVi
         const int nC = ks * ((h3 + 2 + 31) / 32);
         // Jobs B / C (dw3, db3, dw4, db4, d_loss) need the forward only, not dpre1; job A -> stage 2 -> Adam is the critical chain.  With
         // ltg_d_opts.aux_stream + sync they run on the caller's AUX stream beside job A and stage 2, handed over through two device
-        // words like the G step's forks (word 0: the forward is complete, stored by job A's launch when it starts, polled by one wave
-        // in front of jobs B / C; word 1: they have ended, polled by an extra block of stage 2 in front of the Adam sweep; word 2: a poll
-        // gave up = poison, the sweep then returns at once).  (Measured and not kept, same round: the same jobs riding in stage 2's OWN
-        // launch instead of beside job A: 59.5-59.6 -> 61.3-61.6 us per step; profiles/r4_d_step_floor.txt, which also has the step's
-        // launch structure: the five grids returning at once take 18 us.)
+        // words like the G step's forks (LTG_WORD_D_FWD_DONE, LTG_WORD_D_JOBS_DONE and the poison: include/ltg.h, enum ltg_word; once
+        // poisoned the sweep returns at once).  (The jobs inside stage 2's launch: DESIGN.md 5.4, "Tried and not kept".)
         // (when it is taken: d_route)
         const bool fork = r.fork != 0;
-        if (fork) poison = o->sync + 2;
+        if (fork) poison = o->sync + LTG_WORD_POISON;
         const int spl1 = r.spl[2], spl2 = r.spl[3];
         LTG_PROBED(pr, LTG_K_D_BWD1, LTG_D_SPL_LAUNCH(spl1, fk_d_bwd1, dim3(fork ? nA : nA + nB + nC), dim3(NT), 0, st, pv, h12, h3, nA, nB, ntile, L, SP, w.A1, w.A3, w.G3,
                                                       w.spart, disc->p[7], disc->p[4], o->keep_prob, w.dpre1, w.slab,
-                                                      fork ? LtgGate{o->sync, o->seq, nullptr, 0} : LTG_NO_GATE));
+                                                      fork ? gate_store(o->sync, LTG_WORD_D_FWD_DONE, o->seq) : LTG_NO_GATE));
         if (fork) {
             hipStream_t ax = (hipStream_t)o->aux_stream;
-            hipLaunchKernelGGL(k_gate_wait, dim3(1), dim3(64), 0, ax, LtgGate{o->sync, o->seq, o->sync + 2, 0}, LTG_NO_GATE);
+            hipLaunchKernelGGL(k_gate_wait, dim3(1), dim3(64), 0, ax, gate_poll(o->sync, LTG_WORD_D_FWD_DONE, o->seq), LTG_NO_GATE);
             LTG_D_SPL_LAUNCH(spl1, fk_d_bwd1, dim3(nB + nC), dim3(NT), 0, ax, pv, h12, h3, 0, nB, ntile, L, SP, w.A1, w.A3, w.G3, w.spart, disc->p[7], disc->p[4],
                              o->keep_prob, w.dpre1, w.slab, LTG_NO_GATE);
-            hipLaunchKernelGGL(k_gate_set, dim3(1), dim3(64), 0, ax, LtgGate{o->sync + 1, o->seq, nullptr, 0}, LTG_NO_GATE);
+            hipLaunchKernelGGL(k_gate_set, dim3(1), dim3(64), 0, ax, gate_store(o->sync, LTG_WORD_D_JOBS_DONE, o->seq), LTG_NO_GATE);
         }
         const int n2 = ks * ((h0 + 1 + 15) / 16) * ((h1 + 31) / 32 + (h2 + 31) / 32);
         LTG_PROBED(pr, LTG_K_D_BWD2, LTG_D_SPL_LAUNCH(spl2, fk_d_bwd2, dim3(n2 + (fork ? 1 : 0)), dim3(DB2_NT), 0, st, pv, h0, h1, h2, L, SP, disc->emb, w.dpre1, w.slab,
-                                                      fork ? LtgGate{o->sync + 1, o->seq, o->sync + 2, 0} : LTG_NO_GATE));
+                                                      fork ? gate_poll(o->sync, LTG_WORD_D_JOBS_DONE, o->seq) : LTG_NO_GATE));
         n_lrow = 0;      // (the loss sits in slot P of the slabs)
         lrow = nullptr;
     } else if (r.kind == LTG_D_FP8_OPFMT) {
@@ -1075,19 +1084,30 @@ static unsigned q0_sweep_grid(int I, int H) {
 }
 
 // sparse gradient rows of W_q0 (+ partial bias rows) into w.gq0 (the latency path's kernels: LTG_MID_FAST chains only)
+struct Enc0Grad {
+    const ltg_gen_state* gen = nullptr;   // gen + ad: the lazy clock's Adam step on the batch's rows, fused
+    const AdamC* ad = nullptr;
+    bool row_waves = true;                // one wave per row (false: column-blocked)
+    const unsigned* poison = nullptr;
+    LtgGate started = LTG_NO_GATE;        // stored when the kernel starts
+    LtgGate end_wait = LTG_NO_GATE;       // polled by one more block, as the last thing the launch does
+    float* lr_slot = nullptr;             // the step's learning rate into the clock's ring here (the tail runs elsewhere)
+};
 static void g_enc0_grad(const ltg_config* cfg, const ltg_batch* bt, const ltg_g_opts* o, const ltg_gen_acts* acts, const Workspace& w,
-                        hipStream_t st, const ltg_gen_state* gen = nullptr, const AdamC* ad = nullptr, bool row_waves = true,
-                        const unsigned* poison = nullptr, LtgGate started = LTG_NO_GATE, LtgGate end_wait = LTG_NO_GATE, float* lr_slot = nullptr) {   // gen + ad: fused lazy Adam step
+                        hipStream_t st, const Enc0Grad& a) {
     const int B = bt->n_rows, I = cfg->n_items, H = cfg->h_enc, nu = bt->n_unique;
+    const ltg_gen_state* gen = a.gen;
+    const AdamC* ad = a.ad;
+    const LtgGate end_wait = a.end_wait;
     const Probe pe{o->probe, st};
     pe.before(LTG_K_ENC0_GRAD);
-    if (row_waves) {   // one wave per row over all columns: a third of the waves (see fk_enc0_grad_rows)
+    if (a.row_waves) {   // one wave per row over all columns: a third of the waves (see fk_enc0_grad_rows)
         const int ncb = (H / 4 + 63) / 64;
         const dim3 g((nu + ENC0_BIAS_PARTS + G0_NW - 1) / G0_NW + (end_wait.word ? 1 : 0));
 #define LTG_G0_ROWS(N)                                                                                                                                   \
     hipLaunchKernelGGL(fk_enc0_grad_rows<N>, g, dim3(G0_NT), 0, st, B, I, H, nu, bt->uptr, bt->rowidx, bt->csr_pos, bt->indices, bt->values, o->fwd.drop_keep, \
                        o->fwd.keep_prob, cfg->seed, o->fwd.rng_step, acts->row_scale, w.da1, w.gq0, cfg->item_lo, Ig_of(cfg), gen ? *gen : ltg_gen_state{},     \
-                       ad ? *ad : AdamC{}, (gen && ad) ? gen->q0_ord + 1 : 0, bt->uitem, poison, started, end_wait, lr_slot)
+                       ad ? *ad : AdamC{}, (gen && ad) ? gen->q0_ord + 1 : 0, bt->uitem, a.poison, a.started, end_wait, a.lr_slot)
         if (ncb == 1) LTG_G0_ROWS(1);
         else if (ncb == 2) LTG_G0_ROWS(2);
         else LTG_G0_ROWS(3);
@@ -1099,13 +1119,22 @@ static void g_enc0_grad(const ltg_config* cfg, const ltg_batch* bt, const ltg_g_
     pe.after(LTG_K_ENC0_GRAD);
 }
 
-// Every Adam update of the step behind dz -> dh1 as jobs of ONE launch of fk_g_tail (see there): W_p1t (with_dec1: small item slabs; large
-// ones ran the streaming kernel before), W_p0, W_q1, W_q0 (dense product when slot == NULL, else sweep + sparse rows; no_q0: a launch of
-// its own follows; q0_bias: only the bias row, the lazy clock has the item rows), scalars
+// Every Adam update of the step behind dz -> dh1 as jobs of ONE launch of fk_g_tail (see there): W_p0, W_q1, the scalars, and
+struct TailJobs {
+    const int32_t* slot = nullptr;    // W_q0: sweep + sparse rows through this map (NULL: the dense product)
+    bool with_dec1 = false;           // W_p1t as well (small item slabs; large ones ran the streaming kernel before)
+    float* loss_out = nullptr;
+    bool no_q0 = false;               // no W_q0 job: a launch of its own follows
+    bool q0_bias = false;             // only the bias row of W_q0: the lazy clock has the item rows
+    const unsigned* poison = nullptr;
+    LtgGate end_wait = LTG_NO_GATE;   // polled by one more block, as the last thing the launch does
+    bool bias_from_da1 = false;       // q0_bias: the bias row by fk_q0_bias_from_da1 behind the tail instead
+};
 static void g_jobs(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_batch* bt, const ltg_g_opts* o, const ltg_gen_acts* acts,
-                   const Workspace& w, const AdamC& ad, const int32_t* slot, bool with_dec1, float* loss_out, hipStream_t st,
-                   bool no_q0 = false, bool q0_bias = false, const unsigned* poison = nullptr, LtgGate end_wait = LTG_NO_GATE, bool bias_from_da1 = false) {
+                   const Workspace& w, const AdamC& ad, hipStream_t st, const TailJobs& j) {
     const int B = bt->n_rows, I = cfg->n_items, H = cfg->h_enc, Z = cfg->z_dim;
+    const int32_t* slot = j.slot;
+    const bool with_dec1 = j.with_dec1, q0_bias = j.q0_bias, bias_from_da1 = j.bias_from_da1;
     TailArgs a;
     a.B = B; a.I = I; a.H = H; a.Z = Z; a.nu = bt->n_unique;
     a.nz = a.nh = 0;     // (dz / dh1 were launched on their own)
@@ -1113,7 +1142,7 @@ static void g_jobs(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_ba
     a.n2 = ((Z + 1 + 31) / 32) * ((H + LTG_TAIL_BN - 1) / LTG_TAIL_BN);
     a.n3 = ((H + 1 + 31) / 32) * ((2 * Z + LTG_TAIL_BN - 1) / LTG_TAIL_BN);
     a.n4 = 0;
-    if (!no_q0) a.n4 = slot ? (int)q0_sweep_grid(I, H) : ((I + 1 + 31) / 32) * ((H + LTG_TAIL_BN - 1) / LTG_TAIL_BN);
+    if (!j.no_q0) a.n4 = slot ? (int)q0_sweep_grid(I, H) : ((I + 1 + 31) / 32) * ((H + LTG_TAIL_BN - 1) / LTG_TAIL_BN);
     a.q0_bias = 0;
     if (q0_bias) {   // lazy Adam clock: fk_enc0_grad updated the item rows, one block finishes the bias row
         a.n4 = bias_from_da1 ? 0 : 1;      // (bias_from_da1: fk_q0_bias_from_da1 follows on the same stream)
@@ -1126,35 +1155,39 @@ static void g_jobs(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_ba
     a.xd = (slot || q0_bias) ? nullptr : w.xd;
     a.da1 = w.da1;
     a.slot = slot; a.rowout = w.rowout; a.cnt = o->cnt; a.anneal = o->anneal; a.lam = o->gan_lambda;
-    a.loss_out = w.scal; a.loss_out2 = loss_out;
-    a.poison = poison; a.n_wait = end_wait.word ? 1 : 0; a.end_wait = end_wait;
+    a.loss_out = w.scal; a.loss_out2 = j.loss_out;
+    a.poison = j.poison; a.n_wait = j.end_wait.word ? 1 : 0; a.end_wait = j.end_wait;
     const Probe pr{o->probe, st};
     pr.before(LTG_K_G_TAIL);
     const dim3 g(a.nz + a.nh + a.n1 + a.n2 + a.n3 + a.n4 + a.n5 + a.n_wait);
     if (cfg->precision == LTG_PREC_BF16) hipLaunchKernelGGL(fk_g_tail<true>, g, dim3(NT), 0, st, a, *gen, ad);
     else hipLaunchKernelGGL(fk_g_tail<false>, g, dim3(NT), 0, st, a, *gen, ad);
     if (q0_bias && bias_from_da1)
-        hipLaunchKernelGGL(fk_q0_bias_from_da1, dim3(((H >> 2) + Q0B_COLS - 1) / Q0B_COLS), dim3(NT), 0, st, B, H, w.da1, *gen, ad, poison);
+        hipLaunchKernelGGL(fk_q0_bias_from_da1, dim3(((H >> 2) + Q0B_COLS - 1) / Q0B_COLS), dim3(NT), 0, st, B, H, w.da1, *gen, ad, j.poison);
     pr.after(LTG_K_G_TAIL);
 }
 
 // Adam step gen->q0_ord + 1 of W_q0 / b_q0 on the lazy clock: the batch's rows with their gradient rows (w.gq0), the bias
-// row, then the rotating slice of untouched rows
-constexpr int G_AUX_SWEEP = 0x40000000;   // library-internal bit of ltg_g_opts.fake_done: ltg_g_step runs the slice on its aux stream
+// row, then the rotating slice of untouched rows.
+// Where the clock's work of a step runs: ltg_g_step with an aux stream sets on_aux (g_stage_bwd_rest then runs it there); everyone else
+// leaves it in stream order behind the clock's step
+struct ClockSched {
+    bool on_aux = false;
+};
 // the rotating slice of G step gen->q0_ord + 1: rows i = ord (mod period) up to `target`
 static void q0_slice_sweep(const ltg_config* cfg, const ltg_gen_state* gen, int target, hipStream_t st) {
     const int I = cfg->n_items, P = gen->q0_period, start = (gen->q0_ord + 1) % P;
     if (start < I) hipLaunchKernelGGL(k_q0_sweep, dim3((I - start + P - 1) / P), dim3(Q0_NT), 0, st, I, cfg->h_enc, start, P, target, *gen, make_adam(cfg, 1));
 }
 // ... of this step, behind the clock's update of the batch's rows and the bias row (unless ltg_g_step has the slice on its aux stream, up to ord - 1)
-static void q0_slice_of_step(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_g_opts* o, hipStream_t st) {
-    if (!(o->fake_done & G_AUX_SWEEP)) q0_slice_sweep(cfg, gen, gen->q0_ord + 1, st);
+static void q0_slice_of_step(const ltg_config* cfg, const ltg_gen_state* gen, ClockSched clock, hipStream_t st) {
+    if (!clock.on_aux) q0_slice_sweep(cfg, gen, gen->q0_ord + 1, st);
 }
 
 // The LTG_MID_FAST backward chain behind da2: dz -> dh1 -> (sparse W_q0 gradient) -> every remaining Adam update as one tail launch ->
 // the W_q0 update where it is a launch of its own.  r.small: W_p1t and the step's scalars (loss_out) are jobs of the tail as well.
 static void g_chain(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_g_route_info& r, const ltg_batch* bt, const ltg_g_opts* o,
-                    const ltg_gen_acts* acts, const Workspace& w, const AdamC& ad, float* loss_out, hipStream_t st) {
+                    const ltg_gen_acts* acts, const Workspace& w, const AdamC& ad, float* loss_out, hipStream_t st, ClockSched clock) {
     const int B = bt->n_rows, H = cfg->h_enc, Z = cfg->z_dim;
     const Probe pr{o->probe, st};
     // (the lazy clock needs no item -> gradient-row map: its update walks the batch's distinct items)
@@ -1163,29 +1196,36 @@ static void g_chain(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_g
     LTG_PROBED(pr, LTG_K_DZ, hipLaunchKernelGGL(fk_dz, grid2(Z, B, 16, 16), dim3(NT), 0, st, B, Z, H, w.da2, gen->p[2], acts->mulv, o->fwd.eps,
                                                 o->fwd.is_training, o->anneal, cfg->seed, o->fwd.rng_step, w.dmlv));
     LTG_PROBED(pr, LTG_K_DH1, hipLaunchKernelGGL(fk_dh1, grid2(H, B, 16, 16), dim3(NT), 0, st, B, H, 2 * Z, w.dmlv, gen->p[1], acts->h1, w.da1));
-    if (lazy) g_enc0_grad(cfg, bt, o, acts, w, st, gen, &ad, r.grad_rows);   // Adam on the batch's rows inside the gradient kernel
-    else if (slot) g_enc0_grad(cfg, bt, o, acts, w, st, nullptr, nullptr, r.grad_rows);
-    g_jobs(cfg, gen, bt, o, acts, w, ad, slot, r.small, loss_out, st, r.q0_own_launch, lazy);
+    if (lazy) g_enc0_grad(cfg, bt, o, acts, w, st, {.gen = gen, .ad = &ad, .row_waves = r.grad_rows != 0});   // Adam on the batch's rows inside the gradient kernel
+    else if (slot) g_enc0_grad(cfg, bt, o, acts, w, st, {.row_waves = r.grad_rows != 0});
+    g_jobs(cfg, gen, bt, o, acts, w, ad, st, {.slot = slot, .with_dec1 = r.small != 0, .loss_out = loss_out, .no_q0 = r.q0_own_launch != 0, .q0_bias = lazy});
     if (lazy) {   // (fk_enc0_grad applied the step to the batch's rows and fk_g_tail to the bias row)
-        LTG_PROBED(pr, LTG_K_ENC0_BWD_ADAM, q0_slice_of_step(cfg, gen, o, st));
+        LTG_PROBED(pr, LTG_K_ENC0_BWD_ADAM, q0_slice_of_step(cfg, gen, clock, st));
     } else if (r.q0_own_launch) {
         LTG_PROBED(pr, LTG_K_ENC0_BWD_ADAM, hipLaunchKernelGGL(k_enc0_bwd_adam, dim3(q0_sweep_grid(cfg->n_items, H)), dim3(NT), 0, st, cfg->n_items, H, bt->n_unique, slot, w.gq0, *gen, ad));
     }
 }
 
+// which part of the backward behind the dh2 exchange a caller asks for, and how it is scheduled
+struct BwdRest {
+    const float* dh2 = nullptr;   // the exchanged dh2; NULL: da2 is ready (the slab sum wrote it)
+    bool only_dec1 = false;       // the decoder weight update alone
+    LtgH2Done hd = LtgH2Done{nullptr, nullptr, 0u, nullptr};   // the streaming update's hand-over words (one-call step)
+    ClockSched clock = {};
+};
 static int g_stage_bwd_rest(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_g_route_info& r, const ltg_batch* bt, const ltg_g_opts* o,
-                            const ltg_gen_acts* acts, const float* dh2, const Workspace& w, hipStream_t st, bool da2_ready = false,
-                            bool only_dec1 = false, LtgH2Done hd = LtgH2Done{nullptr, nullptr, 0u, nullptr}) {
+                            const ltg_gen_acts* acts, const Workspace& w, hipStream_t st, const BwdRest& a) {
     const int B = bt->n_rows, I = cfg->n_items, H = cfg->h_enc, Z = cfg->z_dim;
     const AdamC ad = make_adam(cfg, o->adam_t);
     const bool bf = cfg->precision == LTG_PREC_BF16;
-    const bool aux_sweep = (o->fake_done & G_AUX_SWEEP) && r.q0 == LTG_Q0_LAZY;   // ltg_g_step: the lazy clock's work on the aux stream
-    // Everything on `st` unless the lazy clock's chain runs beside the weight update (below).  (Measured and removed: small item slabs,
-    // the three weight-gradient + Adam kernels on the aux stream beside da2 -> dz -> dh1 -> sweep -- the event pairs cost more than the
-    // overlap saves once the chain's kernels take 6-18 us; I = 200 000, the two HBM sweeps side by side: they only contend.)
+    const bool only_dec1 = a.only_dec1;
+    const LtgH2Done hd = a.hd;
+    const bool aux_sweep = a.clock.on_aux && r.q0 == LTG_Q0_LAZY;   // ltg_g_step: the lazy clock's work on the aux stream
+    // Everything on `st` unless the lazy clock's chain runs beside the weight update (below).  (The other updates on the aux stream:
+    // DESIGN.md 5.4, "Tried and not kept".)
     hipStream_t aux = (hipStream_t)o->aux_stream;
     hipEvent_t evf = (hipEvent_t)o->ev_fork;
-    if (!da2_ready && !only_dec1) hipLaunchKernelGGL(k_da2, grid1(B * H, 1024), dim3(NT), 0, st, B * H, 1, dh2, acts->h2, w.da2);  // da2 = dh2 * (1 - h2^2)
+    if (a.dh2 && !only_dec1) hipLaunchKernelGGL(k_da2, grid1(B * H, 1024), dim3(NT), 0, st, B * H, 1, a.dh2, acts->h2, w.da2);  // da2 = dh2 * (1 - h2^2)
     // persistent workgroups of the streaming decoder weight update (see launch_dw).  Slabs below 65 536 items: 160 -- the rest of the
     // step runs beside the update, and what a kernel of that chain costs there is mostly how many CUs the update leaves it (round 4,
     // same box, per-rank proxy at 25 024 items: 196 workgroups 173.3-174.1 us per step, 160: 170.1-170.5, 128: 184, 96: 205;
@@ -1234,9 +1274,7 @@ static int g_stage_bwd_rest(const ltg_config* cfg, const ltg_gen_state* gen, con
         // steps, 208 -> 666, 192 -> 647, 176 -> 650, 160 -> 659; cold moments 629 vs 632)
         if (I / 32 >= 2048) dw_gmax = 192;
         if (!o->dec1_done) launch_dw();
-        ltg_g_opts oc = *o;
-        oc.fake_done &= ~G_AUX_SWEEP;   // the slice runs in the chain's own stream order, behind the clock's step
-        g_chain(cfg, gen, r, bt, &oc, acts, w, ad, nullptr, aux);
+        g_chain(cfg, gen, r, bt, o, acts, w, ad, nullptr, aux, ClockSched{});   // (the slice in the chain's own stream order, behind the clock's step)
         (void)hipEventRecord((hipEvent_t)o->ev_sweep, aux);
         return check_launch();
     }
@@ -1250,7 +1288,7 @@ static int g_stage_bwd_rest(const ltg_config* cfg, const ltg_gen_state* gen, con
     } else if (!o->dec1_done) launch_dw();
     if (only_dec1) return check_launch();
     if (r.mid == LTG_MID_FAST) {
-        g_chain(cfg, gen, r, bt, o, acts, w, ad, nullptr, st);
+        g_chain(cfg, gen, r, bt, o, acts, w, ad, nullptr, st, a.clock);
         return check_launch();
     }
     const bool vz = r.mid_vec != 0;
@@ -1284,7 +1322,7 @@ static int g_stage_bwd_rest(const ltg_config* cfg, const ltg_gen_state* gen, con
                        acts->row_scale, w.da1, w.gq0, cfg->item_lo, Ig_of(cfg));
     if (r.q0 == LTG_Q0_LAZY) {
         hipLaunchKernelGGL(k_q0_step_touched, dim3(nu + 1), dim3(Q0_NT), 0, st, I, H, nu, bt->uptr, bt->csr_pos, bt->indices, w.gq0, gen->q0_ord + 1, *gen, ad);
-        q0_slice_of_step(cfg, gen, o, st);
+        q0_slice_of_step(cfg, gen, a.clock, st);
     } else {
         const int32_t* slot = g_slot_map(cfg, bt, w, st);
         hipLaunchKernelGGL(k_enc0_bwd_adam, dim3(q0_sweep_grid(I, H)), dim3(NT), 0, st, I, H, nu, slot, w.gq0, *gen, ad);
@@ -1326,10 +1364,7 @@ int ltg_g_step(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_disc_s
             if (hipEventRecord((hipEvent_t)o->ev_join, aux) != hipSuccess) return LTG_ELAUNCH;
         }
     }
-    ltg_g_opts o_local = *o;
-    o_local.fake_done = (o->fake_done & 1) | (aux_sweep ? G_AUX_SWEEP : 0);
-    o = &o_local;
-    fwd_stage_enc(cfg, gen, r, bt, &o->fwd, acts, 0, st, r.small ? w.xd : nullptr, true);
+    fwd_stage_enc(cfg, gen, r, bt, &o->fwd, acts, 0, st, {.xd = r.small ? w.xd : nullptr, .touched = true});
     const int sgroups = fwd_stage_rest(cfg, gen, r, bt, &o->fwd, acts, 0, st, r.small ? nullptr : w.segpart);
     if (r.small) {
         // small item slab: nine launches per step: enc0, enc1, dec0, dec1 | row softmax + dlogits, dh2, dz, dh1, Adam tail (dW_q0 = xd^T . da1 dense)
@@ -1344,7 +1379,7 @@ int ltg_g_step(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_disc_s
         if (cfg->precision == LTG_PREC_BF16) hipLaunchKernelGGL(fk_dh2<true>, grid2(H, B, 16, 16), dim3(DH2_NT), 0, st, B, I, H, w.dlog, gen->p[3], acts->h2, w.da2);
         else hipLaunchKernelGGL(fk_dh2<false>, grid2(H, B, 16, 16), dim3(DH2_NT), 0, st, B, I, H, w.dlog, gen->p[3], acts->h2, w.da2);
         pr.after(LTG_K_DH2);
-        g_chain(cfg, gen, r, bt, o, acts, w, make_adam(cfg, o->adam_t), loss_out, st);
+        g_chain(cfg, gen, r, bt, o, acts, w, make_adam(cfg, o->adam_t), loss_out, st, ClockSched{});
         return check_launch();
     }
     g_row_partial(cfg, r, bt, fake, acts, w.rowpart, st, w.segpart, nullptr, sgroups);
@@ -1352,7 +1387,7 @@ int ltg_g_step(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_disc_s
     // single GPU: the slab sum writes da2 directly (one launch less than the sharded stage pair)
     int rc = g_stage_bwd_dec(cfg, gen, disc, r, bt, fake, o, acts, w.rowpart, 1, loss_out, w, w.da2, st, fork || have_y, acts->h2);
     if (rc != LTG_OK) return rc;
-    rc = g_stage_bwd_rest(cfg, gen, r, bt, o, acts, w.da2, w, st, true);
+    rc = g_stage_bwd_rest(cfg, gen, r, bt, o, acts, w, st, {.clock = {.on_aux = aux_sweep}});
     if (aux_sweep && hipStreamWaitEvent(st, (hipEvent_t)o->ev_sweep, 0) != hipSuccess) return LTG_ELAUNCH;   // join
     return rc;
 }
@@ -1475,7 +1510,7 @@ int ltg_g_bwd_rest(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_ba
     if (bt->n_unique < 0 || (size_t)bt->n_unique > gq0_rows(cfg, bt->n_rows)) return LTG_EINVAL;
     Workspace w;   // same carve as ltg_g_bwd_dec: dlog lives there
     if (carve_checked(cfg, bt->n_rows, fake->n, ws, ws_bytes, &w) != LTG_OK) return LTG_EWORKSPACE;
-    return g_stage_bwd_rest(cfg, gen, g_route(cfg, gen, bt->n_rows, true), bt, o, acts, dh2, w, (hipStream_t)stream);
+    return g_stage_bwd_rest(cfg, gen, g_route(cfg, gen, bt->n_rows, true), bt, o, acts, w, (hipStream_t)stream, {.dh2 = dh2});
 }
 
 int ltg_g_bwd_dec1(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_batch* bt, const ltg_pairs* fake,
@@ -1484,7 +1519,7 @@ int ltg_g_bwd_dec1(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_ba
     if (!g_args_ok(cfg, gen, bt, acts) || !fake || !o || !ws || o->adam_t < 1 || o->dec1_done) return LTG_EINVAL;
     Workspace w;   // same carve as ltg_g_bwd_dec: dlog lives there
     if (carve_checked(cfg, bt->n_rows, fake->n, ws, ws_bytes, &w) != LTG_OK) return LTG_EWORKSPACE;
-    return g_stage_bwd_rest(cfg, gen, g_route(cfg, gen, bt->n_rows, true), bt, o, acts, nullptr, w, (hipStream_t)stream, true, true);
+    return g_stage_bwd_rest(cfg, gen, g_route(cfg, gen, bt->n_rows, true), bt, o, acts, w, (hipStream_t)stream, {.only_dec1 = true});
 }
 
 /* ---- the item-sharded step as ONE call, exchanges in-stream, weight update and clock slice beside the next step (include/ltg.h) ---- */
@@ -1504,30 +1539,70 @@ int ltg_d_route(const ltg_config* cfg, const ltg_disc_state* disc, int32_t n_pai
     return 1;
 }
 
-// the catch-up ahead (include/ltg.h): device words with the slice on the side stream, marks, batches with their distinct-item lists
-static bool q0_ahead_capable(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_batch* bt, const ltg_pipe* pp) {
-    if (!cfg || !gen || !bt || !pp || !pp->q0_mark || !pp->sync || !bt->uitem || !bt->uptr || !bt->csr_pos) return false;
-    const int fl = pp->flags;
-    if (fl & (LTG_PIPE_NO_DEC1_FORK | LTG_PIPE_NO_SLICE_FORK | LTG_PIPE_EVENTS | LTG_PIPE_SLICE_IN_TOUCH)) return false;
-    return q0_lazy(cfg, gen) && (cfg->h_enc >> 2) <= Q0_NT;
-}
 // ltg_pipe.flags: the LTG_PIPE_* switches of include/ltg.h; a pipe with any other bit is refused
 constexpr int32_t PIPE_FLAGS = LTG_PIPE_NO_DEC1_FORK | LTG_PIPE_NO_SLICE_FORK | LTG_PIPE_WIDE_GRAD | LTG_PIPE_EVENTS | LTG_PIPE_SLICE_IN_TOUCH | LTG_PIPE_TAIL_OWN;
-// the pipe's hand-overs are device words (not events, not program order)
-static bool pipe_gates(const ltg_pipe* pp) { return pp->sync && (pp->flags & (LTG_PIPE_NO_DEC1_FORK | LTG_PIPE_EVENTS)) == 0; }
-// the weight update writes the pipe's second shadow buffer
-static bool shadow_pingpong(const ltg_gen_state* gen, const ltg_pipe* pp) {
-    return pipe_gates(pp) && pp->shadow_out && gen->wp1t_bf16 && pp->shadow_out != gen->wp1t_bf16;
+static bool pipe_ok(const ltg_g_route_info& r, const ltg_pipe* pp) { return r.sharded_ok && (pp->flags & ~PIPE_FLAGS) == 0; }
+// the catch-up ahead (include/ltg.h) beyond what the plan implies (device words, the slice on the side stream, the lazy clock): marks, batches
+// with their distinct-item lists, a row per workgroup
+static bool q0_ahead_capable(const ltg_config* cfg, const ltg_batch* bt, const ltg_pipe* pp) {
+    return pp->q0_mark && bt->uitem && bt->uptr && bt->csr_pos && (cfg->h_enc >> 2) <= Q0_NT;
+}
+// how the pipe's streams meet: a function of the pipe alone (ltg_g_pipe_join has nothing else)
+static int pipe_handover(const ltg_pipe* pp) {
+    if (pp->flags & LTG_PIPE_NO_DEC1_FORK) return LTG_HAND_ORDER;
+    return (pp->sync && (pp->flags & LTG_PIPE_EVENTS) == 0) ? LTG_HAND_WORDS : LTG_HAND_EVENTS;
+}
+// THE schedule of one ltg_g_step_sharded call (include/ltg.h: ltg_pipe_plan_info): where each stage runs and what it waits for.  Every stage
+// below, ltg_g_step_sharded_plan and ltg_g_pipe_plan read this.  Besides it only pipe_ok (the refusal), pipe_handover (a term of it) and
+// ltg_g_pipe_join (which has the pipe alone) look at ltg_pipe.flags.  For calls pipe_ok accepts.
+static ltg_pipe_plan_info pipe_plan(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_batch* bt, const ltg_pipe* pp) {
+    const int fl = pp->flags;
+    ltg_pipe_plan_info p{};
+    p.handover = pipe_handover(pp);
+    const bool words = p.handover == LTG_HAND_WORDS;
+    // the lazy clock's slice of the previous step: on the side stream between this call's catch-up and the next one's (device words: two
+    // more of them; beside enc-1 / dec-0 instead of inside the catch-up launch on the critical stream), in this call's catch-up launch
+    // (events, or LTG_PIPE_SLICE_IN_TOUCH), or not deferred at all: at the end of its own step
+    if (p.handover == LTG_HAND_ORDER || (fl & LTG_PIPE_NO_SLICE_FORK)) p.slice = LTG_SLICE_OWN_END;
+    else p.slice = (words && (fl & LTG_PIPE_SLICE_IN_TOUCH) == 0) ? LTG_SLICE_SIDE : LTG_SLICE_IN_TOUCH;
+    const bool side = p.slice == LTG_SLICE_SIDE;
+    p.ahead = side && q0_ahead_capable(cfg, bt, pp);   // catch-up of the NEXT batch's rows during this call
+    p.shadow = words && pp->shadow_out && gen->wp1t_bf16 && pp->shadow_out != gen->wp1t_bf16;   // the update writes the pipe's second shadow buffer
+    // the Adam tail (W_p0, W_q1, the biases: it needs dh1's outputs only) on its OWN stream beside the sparse gradient kernel, the next
+    // call's catch-up and enc-0; needs <= G0_LIGHT batch rows per partial bias row (its bias job then re-sums them in the same order).
+    // OPT-IN (LTG_PIPE_TAIL_OWN).  It was the default without a communicator while the catch-up launch led the critical stream (20 000 items:
+    // 146.0-147.1 against 150.9-151.9 us per step).  With the catch-up ahead and two shadow buffers the tail's own chain -- waiter, tail, bias
+    // kernel, LTG_WORD_TAIL_END -- is what the next enc-0 then waits for: 20 000 items 142.0-143.6 on its own stream against 139.1-139.5 inline
+    // (equal, 138.7-140.4 / 138.1-140.6, once the bias kernel was spread over 8 x as many threads), 200 000 items 802-825 against 745-767; with
+    // the three RCCL calls in the stream (per-rank proxy) 154.4-157.0 against 154.6-155.1.
+    // (The row bound is 128 rows, which is also the most the one-call step serves (g_route: sharded_ok): true for every accepted call today.)
+    p.tail_own = side && pp->tail_stream && pp->ev_tail && (fl & LTG_PIPE_TAIL_OWN) != 0 && (fl & LTG_PIPE_WIDE_GRAD) == 0 &&
+                 (bt->n_rows + ENC0_BIAS_PARTS - 1) / ENC0_BIAS_PARTS <= G0_LIGHT;
+    // (a ragged slab's last I % 32 rows go through the generic tile kernel behind the streaming one, and that reads h2 throughout:
+    // LTG_WORD_H2_READ then opens with LTG_WORD_UPDATE_END)
+    p.h2_early = words && (cfg->n_items % 32) == 0;
+    p.grad_rows = (fl & LTG_PIPE_WIDE_GRAD) == 0;
+    p.poisonable = words;
+    return p;
+}
+int ltg_g_pipe_plan(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_batch* bt, const ltg_pipe* pp, ltg_pipe_plan_info* out) {
+    if (!cfg_ok(cfg) || !gen || !bt || !pp || !out || bt->n_rows <= 0) return 0;
+    const ltg_g_route_info r = g_route(cfg, gen, bt->n_rows);
+    if (!pipe_ok(r, pp)) return 0;
+    *out = pipe_plan(cfg, gen, bt, pp);
+    return 1;
 }
 int ltg_g_step_sharded_plan(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_batch* bt, const ltg_pipe* pp) {
-    if (!cfg_ok(cfg) || !gen || !bt || !pp || (pp->flags & ~PIPE_FLAGS) != 0 || !ltg_g_step_sharded_ok(cfg, gen, bt->n_rows)) return 0;
-    return (q0_ahead_capable(cfg, gen, bt, pp) ? LTG_PLAN_AHEAD : 0) | (shadow_pingpong(gen, pp) ? LTG_PLAN_SHADOW : 0);
+    ltg_pipe_plan_info p;
+    if (!ltg_g_pipe_plan(cfg, gen, bt, pp, &p)) return 0;
+    return (p.ahead ? LTG_PLAN_AHEAD : 0) | (p.shadow ? LTG_PLAN_SHADOW : 0);
 }
 
 int ltg_g_pipe_probe(const ltg_pipe* pipe, ltg_stream stream) {
     clear_errors();
     if (!pipe || !pipe->sync || !pipe->side_stream) return LTG_EINVAL;
     hipStream_t st = (hipStream_t)stream;
+    uint32_t* const probe = pipe->sync + LTG_WORD_PROBE;
     // a waiter on the side stream FIRST, then its producer on `stream`: with one hardware queue under both, the producer cannot start
     // before the waiter has given up (5 ms).  The same for the tail stream when the pipe has one.
     // Pairs (waiter's stream, setter's stream): the caller's stream against each side stream, and -- when the pipe has both -- the tail
@@ -1540,11 +1615,11 @@ int ltg_g_pipe_probe(const ltg_pipe* pipe, ltg_stream stream) {
         if (!sd || (which == 2 && !pipe->side_stream)) continue;     // (`stream` itself may be the null stream: handle 0)
         unsigned zero[2] = {0u, 0u}, got[2] = {0u, 0u};
         if (hipStreamSynchronize(sd) != hipSuccess || hipStreamSynchronize(sp) != hipSuccess) return LTG_ELAUNCH;
-        if (hipMemcpy(pipe->sync + 3, zero, sizeof(zero), hipMemcpyHostToDevice) != hipSuccess) return LTG_ELAUNCH;
-        hipLaunchKernelGGL(k_gate_wait, dim3(1), dim3(64), 0, sd, LtgGate{pipe->sync + 3, 1u, pipe->sync + 4, 5});
-        hipLaunchKernelGGL(k_gate_set, dim3(1), dim3(64), 0, sp, LtgGate{pipe->sync + 3, 1u, nullptr, 0});
+        if (hipMemcpy(probe, zero, sizeof(zero), hipMemcpyHostToDevice) != hipSuccess) return LTG_ELAUNCH;
+        hipLaunchKernelGGL(k_gate_wait, dim3(1), dim3(64), 0, sd, LtgGate{probe, 1u, probe + 1, 5});   // (gives up after 5 ms, counted in the word behind)
+        hipLaunchKernelGGL(k_gate_set, dim3(1), dim3(64), 0, sp, LtgGate{probe, 1u, nullptr, 0});
         if (hipStreamSynchronize(sd) != hipSuccess || hipStreamSynchronize(sp) != hipSuccess) return LTG_ELAUNCH;
-        if (hipMemcpy(got, pipe->sync + 3, sizeof(got), hipMemcpyDeviceToHost) != hipSuccess) return LTG_ELAUNCH;
+        if (hipMemcpy(got, probe, sizeof(got), hipMemcpyDeviceToHost) != hipSuccess) return LTG_ELAUNCH;
         if (check_launch() != LTG_OK) return LTG_ELAUNCH;
         if (!(got[0] == 1u && got[1] == 0u)) return 0;
     }
@@ -1554,7 +1629,9 @@ int ltg_g_pipe_probe(const ltg_pipe* pipe, ltg_stream stream) {
 int ltg_g_pipe_join(const ltg_pipe* pipe, ltg_stream stream) {
     clear_errors();
     if (!pipe || !pipe->ev_dec1 || !pipe->side_stream) return LTG_EINVAL;
-    if (pipe->sync && (pipe->flags & LTG_PIPE_EVENTS) == 0) {   // gates: nothing was recorded per call -- everything on the side stream so far
+    // device words: nothing was recorded per call -- everything on the side stream so far.  (Not pipe_handover() == LTG_HAND_WORDS: a pipe with
+    // words under LTG_PIPE_NO_DEC1_FORK, LTG_HAND_ORDER, has always had this record on its idle side stream, and keeps it.)
+    if (pipe->sync && (pipe->flags & LTG_PIPE_EVENTS) == 0) {
         if (hipEventRecord((hipEvent_t)pipe->ev_dec1, (hipStream_t)pipe->side_stream) != hipSuccess) return LTG_ELAUNCH;
     }
     if (hipStreamWaitEvent((hipStream_t)stream, (hipEvent_t)pipe->ev_dec1, 0) != hipSuccess) return LTG_ELAUNCH;
@@ -1565,6 +1642,195 @@ int ltg_g_pipe_join(const ltg_pipe* pipe, ltg_stream stream) {
     return LTG_OK;
 }
 
+// ---- ltg_g_step_sharded, stage by stage.  A stage reads the call (GSharded) and what it needs of the route and the plan; the entry point runs them in this
+// order, which IS the host's issue order of the launches.  What each device word means: include/ltg.h, enum ltg_word.  Every poll is made by
+// ONE thread, either a one-wave kernel of the side stream or the last thread of the kernel in front of the one that needs the gate: no
+// workgroup of a large launch ever holds a CU while it waits for a producer that still needs one.  Schedules that were measured and
+// removed: DESIGN.md 5.4, "Tried and not kept".
+struct GSharded {
+    const ltg_config* cfg;
+    const ltg_gen_state* gen;
+    const ltg_disc_state* disc;
+    const ltg_batch* bt;
+    const ltg_pairs* fake;
+    const ltg_g_opts* o;
+    const ltg_gen_acts* acts;
+    const ltg_comm* comm;
+    const ltg_pipe* pp;
+    float* loss_out;
+    ltg_stream stream;         // the caller's stream as the collectives take it ...
+    hipStream_t st, sd, stl;   // ... as HIP does; the side stream; the tail stream
+    int R;                     // ranks
+    Workspace w;
+    float* rowpart;            // this rank's block of the all-gather buffer: the exchange is in place
+    AdamC ad;
+    const unsigned* poison;    // plan.poisonable: LTG_WORD_POISON
+    Probe pr;
+    // the pipe's words as gates of THIS call's ordinal (prev: the call before)
+    LtgGate store(int word) const { return gate_store(pp->sync, word, pp->seq); }
+    LtgGate poll(int word) const { return gate_poll(pp->sync, word, pp->seq); }
+    LtgGate poll_prev(int word) const { return gate_poll(pp->sync, word, pp->seq - 1u); }
+};
+#define LTG_HIP(x) do { if ((x) != hipSuccess) return LTG_ELAUNCH; } while (0)
+#define LTG_COMM(x) do { if ((x) != 0) return LTG_ELAUNCH; } while (0)
+
+// the clock slice forked by the PREVIOUS call is done (it must not meet the catch-up on a row); the rows this batch reads
+static void gs_catch_up(const GSharded& c, const ltg_g_route_info& r, const ltg_pipe_plan_info& p) {
+    const ltg_gen_state* gen = c.gen;
+    const ltg_batch* bt = c.bt;
+    const int I = c.cfg->n_items, qP = gen->q0_period;
+    if (p.slice == LTG_SLICE_IN_TOUCH && gen->q0_ord > 0 && gen->q0_ord % qP < I) {
+        const int start = gen->q0_ord % qP, ns = (I - start + qP - 1) / qP;
+        hipLaunchKernelGGL(k_q0_touch_slice, dim3(bt->n_unique + ns), dim3(Q0_NT), 0, c.st, I, c.cfg->h_enc, bt->n_unique, bt->uptr, bt->csr_pos, bt->indices, bt->uitem,
+                           gen->q0_ord, start, qP, *gen, make_adam(c.cfg, 1));
+    } else if (p.ahead && c.pp->caught_up) {
+        // the previous call brought this batch's rows up to q0_ord on the side stream (k_q0_touch_ahead; its end is behind
+        // LTG_WORD_SLICE_DONE, which that call's last kernel on this stream waited for) and marked them: no catch-up launch
+    } else if (p.slice == LTG_SLICE_SIDE) {
+        // (the previous call's last kernel waited for LTG_WORD_SLICE_DONE before it ended: ltg_gate_wait_tail in fk_g_tail)
+        q0_touch(c.cfg, gen, r, bt, c.st, c.poison, p.ahead ? c.pp->q0_mark : nullptr, c.pp->seq);
+    } else
+        q0_touch(c.cfg, gen, r, bt, c.st, c.poison);
+}
+
+// forward, encoder half: enc-0 over the local slab (exchange 1 follows the side stream's launches: gs_forward)
+static void gs_enc0(const GSharded& c, const ltg_g_route_info& r, const ltg_pipe_plan_info& p) {
+    ltg_gen_acts a1 = *c.acts;
+    a1.h1 = c.pp->h1pre;
+    fwd_stage_enc(c.cfg, c.gen, r, c.bt, &c.o->fwd, &a1, 1, c.st, {.touched = true, .started = p.slice == LTG_SLICE_SIDE ? c.store(LTG_WORD_CATCHUP) : LTG_NO_GATE,
+                                                                  .end_wait = p.tail_own ? c.poll_prev(LTG_WORD_TAIL_END) : LTG_NO_GATE});
+}
+
+// the side stream's clock work: the slice step t - 1 owes (rows i = ord (mod period) up to ord) between this call's catch-up and the next
+// call's, then the catch-up ahead.  LTG_WORD_CATCHUP is opened by enc-0 when it starts (the catch-up in front of it is complete: the rows of
+// this batch are at ord, the slice skips them whatever happens to them later), a one-wave kernel in front of the sweep polls for it;
+// LTG_WORD_SLICE_DONE is opened by the side stream's next kernel (the waiter in front of the weight update) when it starts.  (Issued in the
+// order the device needs them: the critical stream's kernels first.)
+static void gs_side_clock(const GSharded& c, const ltg_pipe_plan_info& p) {
+    if (p.slice != LTG_SLICE_SIDE) return;
+    const ltg_gen_state* gen = c.gen;
+    const ltg_pipe* pp = c.pp;
+    const int I = c.cfg->n_items, H = c.cfg->h_enc, qP = gen->q0_period, start = gen->q0_ord % qP;
+    hipLaunchKernelGGL(k_gate_wait, dim3(1), dim3(64), 0, c.sd, c.poll(LTG_WORD_CATCHUP), LTG_NO_GATE);
+    if (gen->q0_ord > 0 && start < I)
+        hipLaunchKernelGGL(k_q0_sweep, dim3((I - start + qP - 1) / qP), dim3(Q0_NT), 0, c.sd, I, H, start, qP, gen->q0_ord, *gen, make_adam(c.cfg, 1), c.poison);
+    if (p.ahead && pp->next_uitem && pp->next_nu > 0)
+        hipLaunchKernelGGL(k_q0_touch_ahead, dim3(pp->next_nu), dim3(Q0_NT), 0, c.sd, H, pp->next_nu, pp->next_uitem, gen->q0_ord + 1, *gen, c.ad, pp->q0_mark,
+                           pp->seq, c.poison);
+}
+
+// forward: exchange 1 -> enc-1 (bias + tanh in its loader), dec-0, local logits + statistics -> exchange 2
+static int gs_forward(const GSharded& c, const ltg_g_route_info& r, const ltg_pipe_plan_info& p) {
+    const ltg_config* cfg = c.cfg;
+    const ltg_gen_state* gen = c.gen;
+    const ltg_g_opts* o = c.o;
+    const ltg_gen_acts* acts = c.acts;
+    const ltg_comm* comm = c.comm;
+    const ltg_pipe* pp = c.pp;
+    const Probe& pr = c.pr;
+    hipStream_t st = c.st;
+    const int B = c.bt->n_rows, H = cfg->h_enc, Z = cfg->z_dim;
+    const bool words = p.handover == LTG_HAND_WORDS;
+    if (comm) LTG_PROBED(pr, LTG_K_EXCH_H1, LTG_COMM(comm->all_reduce(pp->h1pre, pp->h1pre, (size_t)B * H, LTG_NCCL_FLOAT32, LTG_NCCL_SUM, comm->comm, c.stream)));
+    LTG_PROBED(pr, LTG_K_ENC1, hipLaunchKernelGGL(fk_enc1<true>, grid2(Z, B, 16, 16), dim3(ENC1_NT), 0, st, B, H, Z, pp->h1pre, gen->p[1], gen->p[5], o->fwd.eps,
+                                                  o->fwd.is_training, cfg->seed, o->fwd.rng_step, acts->mulv, acts->z, gen->p[4], acts->h1,
+                                                  words ? c.poll_prev(LTG_WORD_H2_READ) : LTG_NO_GATE));
+    // (dec-0 overwrites h2, which the previous step's weight update reads in its prologue: enc-1's last thread polled for LTG_WORD_H2_READ --
+    // or, with events, the stream waits for the whole update; the streaming forward behind dec-0 needs the update's END: LTG_WORD_UPDATE_END)
+    if (p.handover == LTG_HAND_EVENTS) LTG_HIP(hipStreamWaitEvent(st, (hipEvent_t)pp->ev_dec1, 0));
+    LTG_PROBED(pr, LTG_K_DEC0, hipLaunchKernelGGL(fk_dec0, grid2(H, B, 16, 16), dim3(NT), 0, st, B, H, Z, acts->z, acts->mulv, gen->p[2], gen->p[6], acts->kl_rows,
+                                                  acts->h2, words ? c.poll_prev(LTG_WORD_UPDATE_END) : LTG_NO_GATE, c.poison));
+    int G = 0;
+    LTG_PROBED(pr, LTG_K_DEC1_FWD, G = launch_dec1_fwd_stream(cfg, gen, r, B, acts, c.w.segpart, st));
+    g_row_partial(cfg, r, c.bt, c.fake->n > 0 ? c.fake : nullptr, acts, c.rowpart, st, c.w.segpart, nullptr, G);
+    if (comm) LTG_PROBED(pr, LTG_K_EXCH_ROWPART, LTG_COMM(comm->all_gather(c.rowpart, pp->rowpart_all, (size_t)B * RP, LTG_NCCL_FLOAT32, comm->comm, c.stream)));
+    return LTG_OK;
+}
+
+// backward: (fake tower when it was not evaluated ahead,) losses + dlogits
+static void gs_losses(const GSharded& c) {
+    const ltg_batch* bt = c.bt;
+    const ltg_pairs* fake = c.fake;
+    const ltg_g_opts* o = c.o;
+    const Workspace& w = c.w;
+    const int B = bt->n_rows, I = c.cfg->n_items, nf = fake->n;
+    if (nf > 0 && !o->y_pre && !(o->fake_done & 1)) fake_tower(c.cfg, c.disc, fake, o, w, o->probe, c.st);
+    hipLaunchKernelGGL(k_dlogits_combine<true>, dim3((I + DL_SEG - 1) / DL_SEG, B), dim3(NT), 0, c.st, B, I, c.R, bt->indptr, bt->indices, bt->values, c.acts->logits,
+                       c.pp->rowpart_all, c.acts->kl_rows, nf > 0 ? w.y : (const float*)nullptr, o->cnt, o->anneal, o->gan_lambda, nf, fake->row, fake->niche, fake->pop,
+                       w.dlog, c.acts->lse, w.scal, c.loss_out, c.cfg->item_lo);
+}
+
+// the dh2 product, then ONE fork behind it (the last reader of this step's W_p1t shadow) onto the side stream: the decoder weight update
+// (needs dlogits and h2 only; joined before the NEXT step's dec-0), then the slab sum + exchange 3.
+// Two shadow buffers (plan.shadow): the update of this call writes the OTHER buffer, so the dh2 product leaves the cycle update -> streaming
+// forward -> dlogits -> [dh2 product] -> update that bounds the step at 20 000 - 25 000 items: LTG_WORD_DH2_DONE opens when the product
+// STARTS (dlogits is complete), not when it has ended.
+static int gs_dh2_update(const GSharded& c, const ltg_g_route_info& r, const ltg_pipe_plan_info& p) {
+    const ltg_config* cfg = c.cfg;
+    const ltg_gen_state* gen = c.gen;
+    const ltg_pipe* pp = c.pp;
+    const Workspace& w = c.w;
+    hipStream_t st = c.st, sd = c.sd;
+    const int B = c.bt->n_rows, I = cfg->n_items, H = cfg->h_enc, nsplit = r.dh2_nsplit, n_da2 = B * H;
+    const bool words = p.handover == LTG_HAND_WORDS, events = p.handover == LTG_HAND_EVENTS;
+    LTG_PROBED(c.pr, LTG_K_DH2, hipLaunchKernelGGL((k_dh2_stream<true, DH2_NH>), dim3(nsplit, DH2_NH), dim3(ST_NT), (size_t)2 * ST_BN * ST_LDW * 2, st, B, I, H, r.dh2_chunk,
+                                                   w.dlog, gen->wp1t_bf16, w.part, p.shadow ? c.store(LTG_WORD_DH2_DONE) : LTG_NO_GATE));
+    if (words) {
+        // the slab sum first: it is the next kernel of the critical stream, the side stream's launches take the host ~30 us
+        hipLaunchKernelGGL(k_da2, grid1(n_da2, 2048), dim3(NT), 0, st, n_da2, nsplit, w.part, (const float*)nullptr,
+                           pp->dh2, p.shadow ? LTG_NO_GATE : c.store(LTG_WORD_DH2_DONE));
+        // the side stream's work starts behind a one-wave kernel that polls the word the slab sum (or the product) sets when it starts
+        hipLaunchKernelGGL(k_gate_wait, dim3(1), dim3(64), 0, sd, c.poll(LTG_WORD_DH2_DONE), p.slice == LTG_SLICE_SIDE ? c.store(LTG_WORD_SLICE_DONE) : LTG_NO_GATE);
+    } else if (events) {
+        LTG_HIP(hipEventRecord((hipEvent_t)pp->ev_fork, st));
+        LTG_HIP(hipStreamWaitEvent(sd, (hipEvent_t)pp->ev_fork, 0));
+    }
+    const LtgH2Done hd_last = p.h2_early ? LtgH2Done{pp->sync + LTG_WORD_H2_COUNT, pp->sync + LTG_WORD_H2_READ, pp->seq, c.poison} : LtgH2Done{nullptr, nullptr, 0u, c.poison};
+    ltg_g_opts od = *c.o;
+    od.dec1_done = 0;   // the one call always runs the update itself, whatever cut-point options the caller reuses say
+    ltg_gen_state gen_dw = *gen;
+    if (p.shadow) gen_dw.wp1t_bf16 = pp->shadow_out;   // (the caller exchanges the two pointers after the call)
+    const int rc = g_stage_bwd_rest(cfg, &gen_dw, r, c.bt, &od, c.acts, w, p.handover == LTG_HAND_ORDER ? st : sd, {.only_dec1 = true, .hd = hd_last});
+    if (rc != LTG_OK) return rc;
+    if (words) hipLaunchKernelGGL(k_gate_set, dim3(1), dim3(64), 0, sd, c.store(LTG_WORD_UPDATE_END), p.h2_early ? LTG_NO_GATE : c.store(LTG_WORD_H2_READ));
+    else if (events) LTG_HIP(hipEventRecord((hipEvent_t)pp->ev_dec1, sd));
+    if (!words) hipLaunchKernelGGL(k_da2, grid1(n_da2, 2048), dim3(NT), 0, st, n_da2, nsplit, w.part, (const float*)nullptr, pp->dh2);
+    if (c.comm) LTG_PROBED(c.pr, LTG_K_EXCH_DH2, LTG_COMM(c.comm->all_reduce(pp->dh2, pp->dh2, (size_t)B * H, LTG_NCCL_FLOAT32, LTG_NCCL_SUM, c.comm->comm, c.stream)));
+    return LTG_OK;
+}
+
+// the replicated rest: dz (tanh derivative in its loader) -> dh1 -> sparse W_q0 gradient + its Adam step -> the other updates (the tail)
+static void gs_rest(const GSharded& c, const ltg_pipe_plan_info& p) {
+    const ltg_config* cfg = c.cfg;
+    const ltg_gen_state* gen = c.gen;
+    const ltg_g_opts* o = c.o;
+    const ltg_gen_acts* acts = c.acts;
+    const Workspace& w = c.w;
+    hipStream_t st = c.st;
+    const int B = c.bt->n_rows, I = cfg->n_items, H = cfg->h_enc, Z = cfg->z_dim;
+    LTG_PROBED(c.pr, LTG_K_DZ, hipLaunchKernelGGL(fk_dz_dh2, grid2(Z, B, 16, 16), dim3(NT), 0, st, B, Z, H, c.pp->dh2, acts->h2, gen->p[2], acts->mulv, o->fwd.eps,
+                                                  o->fwd.is_training, o->anneal, cfg->seed, o->fwd.rng_step, w.dmlv, w.da2));
+    LTG_PROBED(c.pr, LTG_K_DH1, hipLaunchKernelGGL(fk_dh1, grid2(H, B, 16, 16), dim3(NT), 0, st, B, H, 2 * Z, w.dmlv, gen->p[1], acts->h1, w.da1));
+    // the step's last kernel on the caller's stream waits for the clock's work on the side stream
+    const LtgGate slice_done = p.slice == LTG_SLICE_SIDE ? c.poll(LTG_WORD_SLICE_DONE) : LTG_NO_GATE;
+    if (p.tail_own) {
+        g_enc0_grad(cfg, c.bt, o, acts, w, st, {.gen = gen, .ad = &c.ad, .row_waves = true, .poison = c.poison, .started = c.store(LTG_WORD_DH1_DONE),
+                                               .end_wait = slice_done, .lr_slot = gen->q0_lr_hist + ((gen->q0_ord + 1) & (LTG_Q0_HIST - 1))});
+        hipLaunchKernelGGL(k_gate_wait, dim3(1), dim3(64), 0, c.stl, c.poll(LTG_WORD_DH1_DONE), LTG_NO_GATE);
+        g_jobs(cfg, gen, c.bt, o, acts, w, c.ad, c.stl, {.no_q0 = true, .q0_bias = true, .poison = c.poison, .bias_from_da1 = true});
+        hipLaunchKernelGGL(k_gate_set, dim3(1), dim3(64), 0, c.stl, c.store(LTG_WORD_TAIL_END), LTG_NO_GATE);
+    } else {
+        g_enc0_grad(cfg, c.bt, o, acts, w, st, {.gen = gen, .ad = &c.ad, .row_waves = p.grad_rows != 0, .poison = c.poison});
+        g_jobs(cfg, gen, c.bt, o, acts, w, c.ad, st, {.no_q0 = true, .q0_bias = true, .poison = c.poison, .end_wait = slice_done});
+    }
+    if (p.slice == LTG_SLICE_OWN_END) {   // the slice of THIS step at its end, in program order (the cut-point schedule)
+        const int qP = gen->q0_period, ord = gen->q0_ord + 1, start = ord % qP;
+        if (start < I) hipLaunchKernelGGL(k_q0_sweep, dim3((I - start + qP - 1) / qP), dim3(Q0_NT), 0, st, I, H, start, qP, ord, *gen, make_adam(cfg, 1));
+    }
+}
+#undef LTG_HIP
+#undef LTG_COMM
+
 int ltg_g_step_sharded(const ltg_config* cfg, const ltg_gen_state* gen, const ltg_disc_state* disc, const ltg_batch* bt,
                        const ltg_pairs* fake, const ltg_g_opts* o, const ltg_gen_acts* acts, const ltg_comm* comm,
                        const ltg_pipe* pp, float* loss_out, void* ws, size_t ws_bytes, ltg_stream stream) {
@@ -1573,207 +1839,25 @@ int ltg_g_step_sharded(const ltg_config* cfg, const ltg_gen_state* gen, const lt
     if (!bt->uptr || !bt->rowidx || !bt->csr_pos || !o->cnt || !fake->row || fake->n < 0) return LTG_EINVAL;
     if (bt->n_unique < 0 || (size_t)bt->n_unique > gq0_rows(cfg, bt->n_rows)) return LTG_EINVAL;
     const ltg_g_route_info r = g_route(cfg, gen, bt->n_rows);
-    if (!r.sharded_ok) return LTG_EINVAL;
-    if (!pp->side_stream || !pp->ev_fork || !pp->ev_dec1 || !pp->h1pre || !pp->rowpart_all || !pp->dh2 || (pp->flags & ~PIPE_FLAGS) != 0) return LTG_EINVAL;
+    if (!pipe_ok(r, pp) || !pp->side_stream || !pp->ev_fork || !pp->ev_dec1 || !pp->h1pre || !pp->rowpart_all || !pp->dh2) return LTG_EINVAL;
     const int R = comm ? comm->n_ranks : 1, rank = comm ? comm->rank : 0;
     if (R < 1 || rank < 0 || rank >= R || (comm && (!comm->all_reduce || !comm->all_gather))) return LTG_EINVAL;
-    const int B = bt->n_rows, I = cfg->n_items, H = cfg->h_enc, Z = cfg->z_dim, nf = fake->n;
-    Workspace w;
-    if (carve_checked(cfg, B, nf, ws, ws_bytes, &w) != LTG_OK) return LTG_EWORKSPACE;
-    hipStream_t st = (hipStream_t)stream, sd = (hipStream_t)pp->side_stream;
-    hipEvent_t ev_fork = (hipEvent_t)pp->ev_fork, ev_dec1 = (hipEvent_t)pp->ev_dec1;
-    const bool fork_dec1 = (pp->flags & LTG_PIPE_NO_DEC1_FORK) == 0;
-    // the lazy clock's slice of the previous step: in this call's catch-up launch (default), on the side stream, or at the end of its own step
-    const bool defer_slice = fork_dec1 && (pp->flags & LTG_PIPE_NO_SLICE_FORK) == 0;
-    // fork / join of the weight update: device words (ltg_pipe.sync) or event pairs
-    const bool gates = fork_dec1 && pp->sync && (pp->flags & LTG_PIPE_EVENTS) == 0;
-    // with device words the slice runs on the side stream between this call's catch-up and the next one's (two more words), beside
-    // enc-1 / dec-0 instead of inside the catch-up launch on the critical stream
-    const bool side_slice = gates && defer_slice && (pp->flags & LTG_PIPE_SLICE_IN_TOUCH) == 0;
-    const bool merge_slice = defer_slice && !side_slice;   // (events, or LTG_PIPE_SLICE_IN_TOUCH: the slice rides in the catch-up launch)
-    const bool ahead = side_slice && q0_ahead_capable(cfg, gen, bt, pp);   // catch-up of the NEXT batch's rows during this call (include/ltg.h)
-    if (o->y_pre) w.y = const_cast<float*>(o->y_pre);   // y_generated from ltg_fake_tower_batched
-    const Probe pr{o->probe, st};
-    const AdamC ad = make_adam(cfg, o->adam_t);
-    float* rowpart = pp->rowpart_all + (size_t)rank * B * RP;   // this rank's block of the all-gather buffer: the exchange is in place
-    // Device words of the pipe (ltg_pipe.sync; `seq` = this call's ordinal):
-    //   0  the dh2 product of call seq is complete (set by the slab sum when it starts; polled by one wave in front of the weight update)
-    //   1  the weight update of call seq has READ h2 (its workgroups count themselves in word 8 behind their prologue; ragged slabs: set
-    //      when the update ends) -- polled by the last thread of the next call's enc-1, in front of dec-0, which overwrites h2
-    //   7  the weight update of call seq has ENDED (one wave behind it) -- polled by the last thread of the next call's dec-0, in front of
-    //      the streaming forward, which reads the shadow rows and the bias the update writes
-    //   5  enc-0 of call seq has started = the catch-up of the batch's rows is complete (polled by one wave in front of the clock slice)
-    //   6  the clock slice of call seq has ended (set by the next kernel of the side stream when it starts) -- polled by the last thread
-    //      of call seq's OWN last kernel (the tail), in front of the next call's catch-up
-    //   2  waits that gave up = the pipe's POISON: every kernel of the step that writes h2 or the model returns at once when it is set
-    // Every poll is made by ONE thread, either a one-wave kernel of the side stream or the last thread of the kernel in front of the
-    // one that needs the gate: no workgroup of a large launch ever holds a CU while it waits for a producer that still needs one.
-    //   9  dh1 of call seq is complete (stored by the sparse gradient kernel when it starts; one wave in front of the Adam tail on the
-    //      tail stream polls for it);  10  the tail of call seq has ended (one wave behind it) -- polled by the last thread of the next
-    //      call's enc-0, in front of enc-1, which reads what the tail updates
-    const unsigned* poison = (fork_dec1 && pp->sync && (pp->flags & LTG_PIPE_EVENTS) == 0) ? pp->sync + 2 : nullptr;
-    // the Adam tail (W_p0, W_q1, the biases: it needs dh1's outputs only) on its OWN stream beside the sparse gradient kernel, the next
-    // call's catch-up and enc-0; needs <= G0_LIGHT batch rows per partial bias row (its bias job then re-sums them in the same order)
-    hipStream_t stl = (hipStream_t)pp->tail_stream;
-    // OPT-IN (LTG_PIPE_TAIL_OWN).  It was the default without a communicator while the catch-up launch led the critical stream (20 000 items:
-    // 146.0-147.1 against 150.9-151.9 us per step).  With the catch-up ahead and two shadow buffers the tail's own chain -- waiter, tail, bias
-    // kernel, word 10 -- is what the next enc-0 then waits for: 20 000 items 142.0-143.6 on its own stream against 139.1-139.5 inline (equal,
-    // 138.7-140.4 / 138.1-140.6, once the bias kernel was spread over 8 x as many threads), 200 000 items 802-825 against 745-767; with the
-    // three RCCL calls in the stream (per-rank proxy) 154.4-157.0 against 154.6-155.1.
-    const bool tail_own = gates && side_slice && stl && pp->ev_tail && (pp->flags & LTG_PIPE_TAIL_OWN) != 0 && (pp->flags & LTG_PIPE_WIDE_GRAD) == 0 &&
-                          (B + ENC0_BIAS_PARTS - 1) / ENC0_BIAS_PARTS <= G0_LIGHT;
-#define LTG_HIP(x) do { if ((x) != hipSuccess) return LTG_ELAUNCH; } while (0)
-#define LTG_COMM(x) do { if ((x) != 0) return LTG_ELAUNCH; } while (0)
-    // ---- the clock slice forked by the PREVIOUS call is done (it must not meet the catch-up below on a row); the rows this batch reads
-    const int qP = gen->q0_period;
-    if (merge_slice && gen->q0_ord > 0 && gen->q0_ord % qP < I) {
-        const int start = gen->q0_ord % qP, ns = (I - start + qP - 1) / qP;
-        hipLaunchKernelGGL(k_q0_touch_slice, dim3(bt->n_unique + ns), dim3(Q0_NT), 0, st, I, H, bt->n_unique, bt->uptr, bt->csr_pos, bt->indices, bt->uitem,
-                           gen->q0_ord, start, qP, *gen, make_adam(cfg, 1));
-    } else if (side_slice && ahead && pp->caught_up) {
-        // the previous call brought this batch's rows up to q0_ord on the side stream (k_q0_touch_ahead; its end is behind word 6, which
-        // that call's last kernel on this stream waited for) and marked them: no catch-up launch
-    } else if (side_slice) {
-        // the slice step t - 1 owes (rows i = ord (mod period) up to ord) on the SIDE stream, between this call's catch-up and the next call's:
-        // word 5 is opened by enc-0 when it starts (the catch-up in front of it is complete: the rows of this batch are at ord, the slice
-        // skips them whatever happens to them later), a one-wave kernel in front of the sweep polls for it; word 6 is opened by the side
-        // stream's next kernel (the waiter in front of the weight update) when it starts, and the NEXT call's catch-up polls for it
-        // (issued in the order the device needs them: the critical stream's kernels first)
-        // (the previous call's last kernel waited for word 6 before it ended: ltg_gate_wait_tail in fk_g_tail)
-        q0_touch(cfg, gen, r, bt, st, poison, ahead ? pp->q0_mark : nullptr, pp->seq);
-    } else
-        q0_touch(cfg, gen, r, bt, st, poison);
-    // ---- forward: enc-0 over the local slab -> exchange 1 -> enc-1 (bias + tanh in its loader), dec-0, local logits + statistics
-    // (Round 4, measured and removed: without a communicator, bias + tanh in enc-0 and the plain enc-1 behind it, h1 alternating between
-    // two buffers: 143.5-147.2 against 145.2-148.1 us per step at 20 000 items, equal at 200 000 -- within the noise, one mode fewer.)
-    {
-        ltg_gen_acts a1 = *acts;
-        a1.h1 = pp->h1pre;
-        fwd_stage_enc(cfg, gen, r, bt, &o->fwd, &a1, 1, st, nullptr, true, side_slice ? LtgGate{pp->sync + 5, pp->seq, nullptr, 0} : LTG_NO_GATE,
-                      tail_own ? LtgGate{pp->sync + 10, pp->seq - 1u, pp->sync + 2, 0} : LTG_NO_GATE);
-    }
-    // (Round 4, measured and removed: the clock's kernels on the pipe's THIRD stream instead of between two weight updates on the side
-    // stream -- 142.8-143.4 against 141.4-142.4 us per step at 20 000 items, 155.3-156.7 against 155.1-157.2 at 25 024: no difference.  What
-    // bounds the step at these sizes is the cycle update -> streaming forward -> dlogits -> dh2 product -> update, not either stream's load.)
-    // (... nor did starting them late, behind word 0 on the third stream -- beside the weight update and the backward chain instead of beside
-    // the streaming forward, the row statistics and dlogits: 142.2-142.7 against 139.2-139.7 us at 20 000 items, 159.2-159.4 against
-    // 157.7-158.8 at 25 024, 831-833 against 823 at 200 000.)
-    // (... and again with two shadow buffers in, when the side stream runs back to back -- update, slice, catch-up ahead, three one-wave
-    // kernels = the step's length: the clock's kernels on the third stream then start earlier, beside the previous update's last third:
-    // 143.1-147.3 against 137.8-138.9 us at 20 000 items, 153.5-154.3 against 152.2-153.5 at 25 024, 746-806 against 762-817 at 200 000.)
-    if (side_slice) {
-        const int start = gen->q0_ord % qP;
-        hipStream_t sc = sd;
-        hipLaunchKernelGGL(k_gate_wait, dim3(1), dim3(64), 0, sc, LtgGate{pp->sync + 5, pp->seq, pp->sync + 2, 0}, LTG_NO_GATE);
-        if (gen->q0_ord > 0 && start < I)
-            hipLaunchKernelGGL(k_q0_sweep, dim3((I - start + qP - 1) / qP), dim3(Q0_NT), 0, sc, I, H, start, qP, gen->q0_ord, *gen, make_adam(cfg, 1), poison);
-        if (ahead && pp->next_uitem && pp->next_nu > 0)
-            hipLaunchKernelGGL(k_q0_touch_ahead, dim3(pp->next_nu), dim3(Q0_NT), 0, sc, H, pp->next_nu, pp->next_uitem, gen->q0_ord + 1, *gen, ad, pp->q0_mark,
-                               pp->seq, poison);
-    }
-    if (comm) LTG_PROBED(pr, LTG_K_EXCH_H1, LTG_COMM(comm->all_reduce(pp->h1pre, pp->h1pre, (size_t)B * H, LTG_NCCL_FLOAT32, LTG_NCCL_SUM, comm->comm, stream)));
-    LTG_PROBED(pr, LTG_K_ENC1, hipLaunchKernelGGL(fk_enc1<true>, grid2(Z, B, 16, 16), dim3(ENC1_NT), 0, st, B, H, Z, pp->h1pre, gen->p[1], gen->p[5], o->fwd.eps,
-                                                  o->fwd.is_training, cfg->seed, o->fwd.rng_step, acts->mulv, acts->z, gen->p[4], acts->h1,
-                                                  gates ? LtgGate{pp->sync + 1, pp->seq - 1u, pp->sync + 2, 0} : LTG_NO_GATE));
-    // (dec-0 overwrites h2, which the previous step's weight update reads in its prologue: enc-1's last thread polled for word 1 -- or,
-    // with events, the stream waits for the whole update; the streaming forward behind dec-0 needs the update's END: word 7)
-    if (fork_dec1 && !gates) LTG_HIP(hipStreamWaitEvent(st, ev_dec1, 0));
-    // (Round 4, measured and removed: slabs of 65 536 items or more with the weight update AND the streaming forward as two launches each
-    // over the halves of the slab, the forward's first half beside the update's second -- bit-identical through carried per-lane softmax
-    // statistics, but slower: 777-813 against 753-792 us per step at 200 000 items, same box.  Beside the update the forward's half takes
-    // 290 us instead of 44 and the update 30 us longer: the step is HBM-bound, overlapping two bandwidth-bound kernels moves no byte
-    // less.  profiles/r4_ab_c4_two_launch_split.txt, r4_c4_timeline_two_launch_split.txt.)
-    LTG_PROBED(pr, LTG_K_DEC0, hipLaunchKernelGGL(fk_dec0, grid2(H, B, 16, 16), dim3(NT), 0, st, B, H, Z, acts->z, acts->mulv, gen->p[2], gen->p[6], acts->kl_rows,
-                                                  acts->h2, gates ? LtgGate{pp->sync + 7, pp->seq - 1u, pp->sync + 2, 0} : LTG_NO_GATE, poison));
-    // (Round 5, measured and removed: with ONE rank no exchange sits between the row statistics and dlogits, so k_row_stats_merge was folded
-    // into k_dlogits_combine -- every (segment, row) workgroup re-folding the 256 (max, sum exp) pairs and the sparse terms of its row, the
-    // step's scalars from the last of B tickets; bit-identical.  The fused kernel took 16.9 us against 10.0 + 5.6 for the two launches:
-    // 143 against 139.5 us per step at 20 000 items, 102 against 101 at 25 024 -- the redundancy costs what the launch saved.)
-    {
-        int G = 0;
-        LTG_PROBED(pr, LTG_K_DEC1_FWD, G = launch_dec1_fwd_stream(cfg, gen, r, B, acts, w.segpart, st));
-        g_row_partial(cfg, r, bt, nf > 0 ? fake : nullptr, acts, rowpart, st, w.segpart, nullptr, G);
-    }
-    if (comm) LTG_PROBED(pr, LTG_K_EXCH_ROWPART, LTG_COMM(comm->all_gather(rowpart, pp->rowpart_all, (size_t)B * RP, LTG_NCCL_FLOAT32, comm->comm, stream)));
-    // ---- backward: (fake tower when it was not evaluated ahead,) losses + dlogits
-    if (nf > 0 && !o->y_pre && !(o->fake_done & 1)) fake_tower(cfg, disc, fake, o, w, o->probe, st);
-    hipLaunchKernelGGL(k_dlogits_combine<true>, dim3((I + DL_SEG - 1) / DL_SEG, B), dim3(NT), 0, st, B, I, R, bt->indptr, bt->indices, bt->values, acts->logits,
-                       pp->rowpart_all, acts->kl_rows, nf > 0 ? w.y : (const float*)nullptr, o->cnt, o->anneal, o->gan_lambda, nf, fake->row, fake->niche, fake->pop,
-                       w.dlog, acts->lse, w.scal, loss_out, cfg->item_lo);
-    {
-        const int kchunk = r.dh2_chunk, nsplit = r.dh2_nsplit;
-        // Two shadow buffers (ltg_pipe.shadow_out): the update of this call writes the OTHER buffer, so the dh2 product -- the last reader of
-        // this call's shadow -- leaves the cycle update -> streaming forward -> dlogits -> [dh2 product] -> update that bounds the step at
-        // 20 000 - 25 000 items: the update's gate (word 0) opens when the product STARTS (dlogits is complete), not when it has ended.
-        const bool pingpong = gates && shadow_pingpong(gen, pp);
-        LTG_PROBED(pr, LTG_K_DH2, hipLaunchKernelGGL((k_dh2_stream<true, DH2_NH>), dim3(nsplit, DH2_NH), dim3(ST_NT), (size_t)2 * ST_BN * ST_LDW * 2, st, B, I, H, kchunk,
-                                                     w.dlog, gen->wp1t_bf16, w.part, pingpong ? LtgGate{pp->sync, pp->seq, nullptr, 0} : LTG_NO_GATE));
-        // ---- ONE fork, behind the dh2 product (the last reader of this step's W_p1t shadow), onto the side stream:
-        //   (1) the clock slice of the PREVIOUS step -- rows i = q0_ord (mod period) up to q0_ord; every row of this batch is at q0_ord
-        //       already (q0_touch), so the slice skips them whatever the rest of this step does to them; joined at the start of the next
-        //       call, before that batch's catch-up;
-        //   (2) the decoder weight update (needs dlogits and h2 only); joined before the NEXT step's dec-0
-        ltg_g_opts od = *o;
-        od.fake_done = 0;
-        od.dec1_done = 0;
-        hipStream_t sdw = st;
-        const int n_da2 = B * H;
-        if (gates)   // the slab sum first: it is the next kernel of the critical stream, the side stream's launches take the host ~30 us
-            hipLaunchKernelGGL(k_da2, grid1(n_da2, 2048), dim3(NT), 0, st, n_da2, nsplit, w.part, (const float*)nullptr,
-                               pp->dh2, pingpong ? LTG_NO_GATE : LtgGate{pp->sync, pp->seq, nullptr, 0});
-        if (gates) {   // the side stream's work starts behind a one-wave kernel that polls the word the slab sum (below) sets when it starts
-            hipLaunchKernelGGL(k_gate_wait, dim3(1), dim3(64), 0, sd, LtgGate{pp->sync, pp->seq, pp->sync + 2, 0},
-                               side_slice ? LtgGate{pp->sync + 6, pp->seq, nullptr, 0} : LTG_NO_GATE);
-            sdw = sd;
-        } else if (fork_dec1) {
-            LTG_HIP(hipEventRecord(ev_fork, st));
-            LTG_HIP(hipStreamWaitEvent(sd, ev_fork, 0));
-            sdw = sd;
-        }
-        // (a ragged slab's last I % 32 rows go through the generic tile kernel behind the streaming one, and that reads h2 throughout:
-        // word 1 then opens with word 7)
-        const bool h2_early = gates && (I % 32) == 0;
-        // (Round 4, measured and removed: word 7 stored by the update's LAST workgroup -- every thread releases its stores at agent scope,
-        // the workgroups count themselves -- instead of by a kernel behind it: 142 -> 184 us per step at 20 000 items, 155 -> 195 at
-        // 25 024, 749 -> 856 at 200 000: 1 256 waves each writing the dirty lines of an L2 back cost far more than the ~4 us the word opens earlier.)
-        const LtgH2Done hd_last = h2_early ? LtgH2Done{pp->sync + 8, pp->sync + 1, pp->seq, poison} : LtgH2Done{nullptr, nullptr, 0u, poison};
-        ltg_gen_state gen_dw = *gen;
-        if (pingpong) gen_dw.wp1t_bf16 = pp->shadow_out;   // (the caller exchanges the two pointers after the call)
-        const int rc = g_stage_bwd_rest(cfg, &gen_dw, r, bt, &od, acts, nullptr, w, sdw, true, true, hd_last);
-        if (rc != LTG_OK) return rc;
-        // (Round 4, measured and removed: word 7 stored by the NEXT call's first waiter on the side stream when it starts, instead of by one
-        // wave behind the update: 149.8 against 146.8 us per step at 20 000 items, 165.7 against 161.5 at 25 024 -- slower; and a host that is
-        // not launches ahead of the device, a two-rank rig with host-side exchanges, stalls dec-0 on it.)
-        if (gates)
-            hipLaunchKernelGGL(k_gate_set, dim3(1), dim3(64), 0, sd, LtgGate{pp->sync + 7, pp->seq, nullptr, 0},
-                               h2_early ? LTG_NO_GATE : LtgGate{pp->sync + 1, pp->seq, nullptr, 0});
-        else if (fork_dec1) LTG_HIP(hipEventRecord(ev_dec1, sd));
-        if (!gates)
-            hipLaunchKernelGGL(k_da2, grid1(n_da2, 2048), dim3(NT), 0, st, n_da2, nsplit, w.part, (const float*)nullptr,
-                               pp->dh2);
-    }
-    if (comm) LTG_PROBED(pr, LTG_K_EXCH_DH2, LTG_COMM(comm->all_reduce(pp->dh2, pp->dh2, (size_t)B * H, LTG_NCCL_FLOAT32, LTG_NCCL_SUM, comm->comm, stream)));
-    // ---- the replicated rest: dz (tanh derivative in its loader) -> dh1 -> sparse W_q0 gradient + its Adam step -> the other updates
-    LTG_PROBED(pr, LTG_K_DZ, hipLaunchKernelGGL(fk_dz_dh2, grid2(Z, B, 16, 16), dim3(NT), 0, st, B, Z, H, pp->dh2, acts->h2, gen->p[2], acts->mulv, o->fwd.eps,
-                                                o->fwd.is_training, o->anneal, cfg->seed, o->fwd.rng_step, w.dmlv, w.da2));
-    LTG_PROBED(pr, LTG_K_DH1, hipLaunchKernelGGL(fk_dh1, grid2(H, B, 16, 16), dim3(NT), 0, st, B, H, 2 * Z, w.dmlv, gen->p[1], acts->h1, w.da1));
-    const LtgGate slice_done = side_slice ? LtgGate{pp->sync + 6, pp->seq, pp->sync + 2, 0} : LTG_NO_GATE;
-    if (tail_own) {
-        g_enc0_grad(cfg, bt, o, acts, w, st, gen, &ad, true, poison, LtgGate{pp->sync + 9, pp->seq, nullptr, 0}, slice_done,
-                    gen->q0_lr_hist + ((gen->q0_ord + 1) & (LTG_Q0_HIST - 1)));
-        hipLaunchKernelGGL(k_gate_wait, dim3(1), dim3(64), 0, stl, LtgGate{pp->sync + 9, pp->seq, pp->sync + 2, 0}, LTG_NO_GATE);
-        g_jobs(cfg, gen, bt, o, acts, w, ad, nullptr, false, nullptr, stl, true, true, poison, LTG_NO_GATE, true);
-        hipLaunchKernelGGL(k_gate_set, dim3(1), dim3(64), 0, stl, LtgGate{pp->sync + 10, pp->seq, nullptr, 0}, LTG_NO_GATE);
-    } else {
-        g_enc0_grad(cfg, bt, o, acts, w, st, gen, &ad, (pp->flags & LTG_PIPE_WIDE_GRAD) == 0, poison);
-        g_jobs(cfg, gen, bt, o, acts, w, ad, nullptr, false, nullptr, st, true, true, poison, slice_done);
-    }
-    if (!defer_slice) {   // the slice of THIS step at its end, in program order (the cut-point schedule)
-        const int ord = gen->q0_ord + 1, start = ord % qP;
-        if (start < I) hipLaunchKernelGGL(k_q0_sweep, dim3((I - start + qP - 1) / qP), dim3(Q0_NT), 0, st, I, H, start, qP, ord, *gen, make_adam(cfg, 1));
-    }
-#undef LTG_HIP
-#undef LTG_COMM
+    const ltg_pipe_plan_info p = pipe_plan(cfg, gen, bt, pp);
+    hipStream_t st = (hipStream_t)stream;
+    GSharded c{cfg, gen, disc, bt, fake, o, acts, comm, pp, loss_out, stream, st, (hipStream_t)pp->side_stream, (hipStream_t)pp->tail_stream, R};
+    if (carve_checked(cfg, bt->n_rows, fake->n, ws, ws_bytes, &c.w) != LTG_OK) return LTG_EWORKSPACE;
+    if (o->y_pre) c.w.y = const_cast<float*>(o->y_pre);   // y_generated from ltg_fake_tower_batched
+    c.rowpart = pp->rowpart_all + (size_t)rank * bt->n_rows * RP;
+    c.ad = make_adam(cfg, o->adam_t);
+    c.poison = p.poisonable ? pp->sync + LTG_WORD_POISON : nullptr;
+    c.pr = Probe{o->probe, st};
+    gs_catch_up(c, r, p);
+    gs_enc0(c, r, p);
+    gs_side_clock(c, p);
+    if (const int rc = gs_forward(c, r, p)) return rc;
+    gs_losses(c);
+    if (const int rc = gs_dh2_update(c, r, p)) return rc;
+    gs_rest(c, p);
     return check_launch();
 }
 

@@ -115,6 +115,21 @@ class Pairs:
         self.c = cabi.ltg_pairs(self.n, 0, _ptr(pop, off), _ptr(niche, off), _ptr(row, off))
 
 
+def _probe_streams(lib, probe_c, st, tries, another):
+    """ltg_g_pipe_probe on the pair (st, the streams of probe_c): True when they run concurrently.  Otherwise another() swaps in a fresh
+    stream (it gets the try's index) and the pair is tested again, `tries` times in all (HIP maps streams onto a few hardware queues)."""
+    if not hasattr(lib, "ltg_g_pipe_probe"):      # (an older build under LTG_AB_COMPAT)
+        return False
+    for k in range(tries):
+        rc = lib.ltg_g_pipe_probe(C.byref(probe_c()), st)
+        if rc < 0:
+            cabi.check(rc, "ltg_g_pipe_probe")
+        if rc == 1:
+            return True
+        another(k)
+    return False
+
+
 class Pipe:
     """Caller-owned side stream, events and exchange buffers of ltg_g_step_sharded (include/ltg.h: ltg_pipe) for batches of up to
     `rows` rows exchanged between `n_ranks` ranks."""
@@ -130,7 +145,7 @@ class Pipe:
         self.h1pre = torch.zeros(rows, engine.H, **f)
         self.rowpart_all = torch.zeros(n_ranks * rows * 5, **f)
         self.dh2 = torch.zeros(rows, engine.H, **f)
-        self.sync = torch.zeros(16, dtype=torch.int32, device=dev)        # words of the device-side hand-overs; [2] = waits that gave up = the pipe's poison
+        self.sync = torch.zeros(16, dtype=torch.int32, device=dev)        # words of the device-side hand-overs (cabi.LTG_WORD_*); LTG_WORD_POISON = waits that gave up
         # catch-up ahead (include/ltg.h, ABI v13): "the current batch holds this row" marks; LTGAN_Q0_AHEAD=0: every call launches its own catch-up
         self.q0_mark = torch.zeros(engine.I, dtype=torch.int32, device=dev) if os.environ.get("LTGAN_Q0_AHEAD", "1") != "0" else None
         self.c = cabi.ltg_pipe(self.side_stream.cuda_stream, self._ev[0].start, self._ev[0].stop, self._ev[1].start, _ptr(self.h1pre),
@@ -162,7 +177,7 @@ class Pipe:
     def expired_waits(self):
         """device-side waits of the hand-overs that gave up (must be 0; synchronises).  Non-zero = the pipe is POISONED: every kernel of the
         one-call step that writes h2 or the model returns at once (csrc: ltg_poisoned), so the model stays what it was when the wait expired."""
-        return int(self.sync[2].item())
+        return int(self.sync[cabi.LTG_WORD_POISON].item())
 
     def reset(self):
         """after a failed call: nothing in flight, every word zero, ordinals restart (a call that stopped between its gate launches would
@@ -191,24 +206,17 @@ class DFork:
 
     def ready(self, engine, st):
         if self.probed_for != st:
-            self.ok = False
-            if hasattr(engine.lib, "ltg_g_pipe_probe"):
-                for _ in range(4):
-                    probe = cabi.ltg_pipe(self.stream.cuda_stream, None, None, None, None, None, None, 0, 0, _ptr(self.sync), None)
-                    rc = engine.lib.ltg_g_pipe_probe(C.byref(probe), st)
-                    if rc < 0:
-                        cabi.check(rc, "ltg_g_pipe_probe")
-                    if rc == 1:
-                        self.ok = True
-                        break
-                    self.stream = torch.cuda.Stream(engine.device)
+            def another(_):
+                self.stream = torch.cuda.Stream(engine.device)
+            self.ok = _probe_streams(engine.lib, lambda: cabi.ltg_pipe(self.stream.cuda_stream, None, None, None, None, None, None, 0, 0, _ptr(self.sync), None),
+                                     st, 4, another)
             self.sync.zero_()
             self.seq = 0
             self.probed_for = st
         return self.ok
 
     def expired_waits(self):
-        return int(self.sync[2].item())
+        return int(self.sync[cabi.LTG_WORD_POISON].item())
 
 
 # arithmetic of the fp32 discriminator's GEMMs (ltg_config.d_arith): the six-term bf16 split is fp32-accurate (every fp32-path parity test passes at
@@ -557,10 +565,10 @@ class Engine:
             pipe.c.next_uitem, pipe.c.next_nu, pipe.c.caught_up = None, 0, 0
 
     def check_pipes(self):
-        """raises if a device-side wait of a one-call G step gave up (ltg_pipe.sync[2]).  The kernels behind such a wait have skipped
+        """raises if a device-side wait of a one-call G step gave up (ltg_pipe.sync[LTG_WORD_POISON]).  The kernels behind such a wait have skipped
         their work, so the model is the one from before that step -- but the run is not the run that was asked for.  ONE device-to-host
         copy and one synchronisation however many pipes the engine has."""
-        words = [pipe.sync[2:3] for pipe in list(self._pipes) + ([self._dfork] if self._dfork is not None else [])]
+        words = [pipe.sync[cabi.LTG_WORD_POISON:cabi.LTG_WORD_POISON + 1] for pipe in list(self._pipes) + ([self._dfork] if self._dfork is not None else [])]
         if not words:
             return
         n = int((words[0] if len(words) == 1 else torch.cat(words)).sum().item())
@@ -603,13 +611,32 @@ class Engine:
             raise cabi.LtgError("ltg_d_route refused the configuration")
         return out
 
+    def pipe_plan(self, batch, pipe):
+        """where each stage of a one-call G step over `batch` on `pipe` runs and what it waits for (include/ltg.h: ltg_g_pipe_plan); None
+        when ltg_g_step_sharded would refuse the call"""
+        out = cabi.ltg_pipe_plan_info()
+        if not hasattr(self.lib, "ltg_g_pipe_plan"):
+            # An older build under LTG_AB_COMPAT (A/B timing against it must find it as fast as it was): the plan from what such a
+            # library can answer -- the two bits of ltg_g_step_sharded_plan (before ABI 13: neither), and for the hand-over the rule it
+            # applies to flags / sync itself.  The fields the host does not read stay 0.  This path only.
+            fl = int(pipe.c.flags)
+            if hasattr(self.lib, "ltg_g_step_sharded_plan"):
+                bits = self.lib.ltg_g_step_sharded_plan(C.byref(self.cfg), C.byref(self.gen_c), C.byref(batch.c), C.byref(pipe.c))
+                out.ahead, out.shadow = int(bool(bits & cabi.LTG_PLAN_AHEAD)), int(bool(bits & cabi.LTG_PLAN_SHADOW))
+            out.handover = (cabi.LTG_HAND_ORDER if fl & cabi.LTG_PIPE_NO_DEC1_FORK else
+                            cabi.LTG_HAND_WORDS if pipe.c.sync and not fl & cabi.LTG_PIPE_EVENTS else cabi.LTG_HAND_EVENTS)
+            out.tail_own = int(out.handover == cabi.LTG_HAND_WORDS and bool(pipe.c.tail_stream) and bool(fl & cabi.LTG_PIPE_TAIL_OWN))
+            return out
+        ok = self.lib.ltg_g_pipe_plan(C.byref(self.cfg), C.byref(self.gen_c), C.byref(batch.c), C.byref(pipe.c), C.byref(out))
+        return out if ok else None
+
     def g_step_sharded(self, batch, fake, acts, gopts, pipe, comm=None, loss_out=None, next_batch=None):
         """every launch of the step and its exchanges from one call (comm: _rccl.RcclComm / HostComm; None = one rank).
         next_batch: the batch of the NEXT call on this pipe when the caller knows it -- its rows of W_q0 are brought up to the lazy clock
         during this call on the side stream, and the next call launches no catch-up (include/ltg.h: catch-up ahead)"""
         loss_out = self.loss_buf if loss_out is None else loss_out
         ws = self.workspace(batch.n_rows, fake.n)
-        self._pipe_ready(pipe)
+        self._pipe_ready(pipe, batch)
         if pipe.c.seq >= 0x7FFFFFF0:                                   # (the marks compare ordinals: restart long before they could repeat)
             self.pipe_join(pipe)
             pipe.reset()
@@ -619,9 +646,8 @@ class Engine:
         pipe.ahead_calls += pipe.c.caught_up
         pipe.ahead = None
         pipe.c.next_uitem, pipe.c.next_nu = None, 0
-        plan = (self.lib.ltg_g_step_sharded_plan(C.byref(self.cfg), C.byref(self.gen_c), C.byref(batch.c), C.byref(pipe.c))
-                if hasattr(self.lib, "ltg_g_step_sharded_plan") else 0)      # (an ABI 11 / 12 build under LTG_AB_COMPAT: no catch-up ahead, one shadow buffer)
-        if next_batch is not None and next_batch.c.uitem and self.q0_defer and (plan & cabi.LTG_PLAN_AHEAD):
+        plan = self.pipe_plan(batch, pipe)     # (None: the call below is refused)
+        if next_batch is not None and next_batch.c.uitem and self.q0_defer and plan is not None and plan.ahead:
             pipe.c.next_uitem, pipe.c.next_nu = next_batch.c.uitem, int(next_batch.c.n_unique)
             pipe.ahead = (next_batch.c.uitem, int(next_batch.c.n_unique), int(self.gen_c.q0_ord) + 1, (int(pipe.c.seq) + 1) & 0xFFFFFFFF)
         rc = self.lib.ltg_g_step_sharded(C.byref(self.cfg), C.byref(self.gen_c), C.byref(self.disc_c), C.byref(batch.c), C.byref(fake.c),
@@ -631,7 +657,7 @@ class Engine:
             pipe.reset()               # (the call may have stopped between its gate launches: words of this ordinal that nobody will set)
             self.refresh_shadow()      # (... or between the update's launch and the exchange below)
         cabi.check(rc, "ltg_g_step_sharded")
-        if plan & cabi.LTG_PLAN_SHADOW:    # the update wrote the pipe's buffer: it is the shadow from now on, the old one the next call's target
+        if plan is not None and plan.shadow:    # the update wrote the pipe's buffer: it is the shadow from now on, the old one the next call's target
             self.g_shadow, pipe.shadow = pipe.shadow, self.g_shadow
             self.gen_c.wp1t_bf16, pipe.c.shadow_out = _ptr(self.g_shadow), _ptr(pipe.shadow)
         if not self.q0_defer:
@@ -644,45 +670,33 @@ class Engine:
         if self.g_shadow is not None:
             cabi.check(self.lib.ltg_refresh_shadow(C.byref(self.cfg), C.byref(self.gen_c), self.stream()), "ltg_refresh_shadow")
 
-    def _pipe_ready(self, pipe):
+    HANDOVER = {cabi.LTG_HAND_ORDER: "none (everything in program order)", cabi.LTG_HAND_EVENTS: "events", cabi.LTG_HAND_WORDS: "device-words"}
+
+    def _pipe_ready(self, pipe, batch):
         """The device-word hand-over of ltg_g_step_sharded needs two CONCURRENT streams; HIP maps streams onto a few hardware queues, so
-        the pair is tested once (ltg_g_pipe_probe; a few other side streams are tried, then the pipe falls back to event pairs)."""
+        the pair is tested once (ltg_g_pipe_probe; a few other side streams are tried, then the pipe falls back to event pairs).
+        pipe.handover then says what the library's plan for this pipe is."""
         st = self.stream()
         if pipe.probed_for == st:
             return
         if pipe.probed_for is not None:
             self.pipe_join(pipe)                     # the mode may change: nothing in flight across the change
             torch.cuda.synchronize(self.device)
-        if pipe.c.flags & cabi.LTG_PIPE_NO_DEC1_FORK:
-            pipe.handover = "none (everything in program order)"
-        elif pipe.c.flags & cabi.LTG_PIPE_EVENTS:
-            pipe.handover = "events"
-        else:
-            pipe.handover = "events"
-
-            def probe():
-                ok = self.lib.ltg_g_pipe_probe(C.byref(pipe.c), st) if hasattr(self.lib, "ltg_g_pipe_probe") else 0   # (an older build under LTG_AB_COMPAT)
-                if ok < 0:
-                    cabi.check(ok, "ltg_g_pipe_probe")
-                return ok == 1
+        plan = self.pipe_plan(batch, pipe)
+        if plan is None:
+            return                                   # (the call will be refused; the streams stay untested for the next one)
+        if plan.handover == cabi.LTG_HAND_WORDS:
             tail = pipe.c.tail_stream
             pipe.c.tail_stream = None                # the side stream first ...
-            for _ in range(6):
-                if probe():
-                    pipe.handover = "device-words"
-                    break
-                pipe.new_side_stream()
-            if pipe.handover == "events":
+            if not _probe_streams(self.lib, lambda: pipe.c, st, 6, lambda k: pipe.new_side_stream()):
                 pipe.c.flags |= cabi.LTG_PIPE_EVENTS
                 pipe.new_tail_stream(drop=True)
             elif tail:                               # ... then the tail's own stream: a third concurrent queue, or the tail stays on the caller's stream
                 pipe.c.tail_stream = tail
-                for k in range(10):     # (a process that has created many streams: the next few may share the side stream's queue)
-                    if probe():
-                        break
-                    pipe.new_tail_stream(drop=(k == 9))
-                if pipe.tail_stream is not None:
-                    pipe.handover = "device-words + tail stream"
+                # (a process that has created many streams: the next few may share the side stream's queue)
+                _probe_streams(self.lib, lambda: pipe.c, st, 10, lambda k: pipe.new_tail_stream(drop=(k == 9)))
+            plan = self.pipe_plan(batch, pipe)
+        pipe.handover = self.HANDOVER[plan.handover] + (" + tail stream" if plan.tail_own else "")
         pipe.probed_for = st
 
     def pipe_join(self, pipe):

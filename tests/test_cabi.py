@@ -53,7 +53,7 @@ def test_struct_layouts_match_the_header_as_gcc_lays_it_out(tmp_path):
     from ltgan import _cabi as cabi
     root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
     names = ["ltg_config", "ltg_gen_state", "ltg_disc_state", "ltg_batch", "ltg_gen_acts", "ltg_probe", "ltg_fwd_opts", "ltg_pairs", "ltg_d_opts",
-             "ltg_g_opts", "ltg_sample_inputs", "ltg_comm", "ltg_pipe", "ltg_oneshot", "ltg_g_route_info", "ltg_d_route_info"]
+             "ltg_g_opts", "ltg_sample_inputs", "ltg_comm", "ltg_pipe", "ltg_oneshot", "ltg_g_route_info", "ltg_d_route_info", "ltg_pipe_plan_info"]
     lines = ["#include <stdio.h>", "#include <stddef.h>", '#include "ltg.h"', "int main(void) {"]
     for n in names:
         st = getattr(cabi, n)
@@ -101,6 +101,9 @@ def test_argument_validation_returns_codes_without_gpu():
     assert lib.ltg_g_step_sharded(C.byref(good), None, None, None, None, None, None, None, None, None, None, 0, None) == -1
     assert lib.ltg_g_step_sharded_ok(C.byref(good), None, 100) == 0 and lib.ltg_g_pipe_join(None, None) == -1
     assert lib.ltg_g_step_sharded_plan(C.byref(good), None, None, None) == 0
+    assert lib.ltg_g_pipe_plan(C.byref(good), None, None, None, None) == 0
+    assert lib.ltg_g_pipe_plan(C.byref(good), C.byref(cabi.ltg_gen_state()), C.byref(cabi.ltg_batch(n_rows=16)), C.byref(cabi.ltg_pipe()), None) == 0   # no *out
+    assert lib.ltg_g_pipe_plan(C.byref(bad), C.byref(cabi.ltg_gen_state()), C.byref(cabi.ltg_batch(n_rows=16)), C.byref(cabi.ltg_pipe()), C.byref(cabi.ltg_pipe_plan_info())) == 0
     assert lib.ltg_g_route(C.byref(good), None, 100, None) == 0 and lib.ltg_g_route(C.byref(bad), C.byref(cabi.ltg_gen_state()), 100, C.byref(cabi.ltg_g_route_info())) == 0
     assert lib.ltg_d_route(C.byref(good), None, 100, 1, 0, None) == 0 and lib.ltg_d_route(C.byref(bad), C.byref(cabi.ltg_disc_state()), 100, 1, 0, C.byref(cabi.ltg_d_route_info())) == 0
     # ltg_config.d_arith (ABI v14): 0 / 1 / 2 + the measurement set in bits 4-7; anything else is rejected

@@ -318,3 +318,152 @@ def hot_forward_inputs(I, B, profile, step=HOT_FWD_STEP, is_training=1.0, seed=N
     _, X, P = hot_problem(I, B, profile, I + B if seed is None else seed)
     eps = eps_dense(HOT_SEED, step, B, O.Z_DIM) if is_training else np.zeros((B, O.Z_DIM))
     return X, P, dropout_mask_dense(HOT_SEED, step, B, I, HOT_KEEP), eps
+
+
+# ---- item slabs in one process (tests/test_gpu_item_slabs.py): every rank of an item-sharded run as an engine of its own on one device, the
+# exchanges done by hand in rank order.  Cut-point G step: (precision, I, B, R, history, warm) -- the smallest shapes that reach each route
+# (tests/test_routes_cpu.py has every slab's)
+SLAB_G = [(p, 1000, 100, 2, "skewed", False) for p in ("fp32", "bf16")] + \
+    [(p, 8200, 100, 2, "uniform", False) for p in ("fp32", "bf16")] + \
+    [("fp32", 1101, 37, 9, "uniform", False),
+     ("bf16", 16520, 100, 2, "uniform", False), ("bf16", 16520, 100, 2, "uniform", True), ("bf16", 25032, 128, 3, "skewed", False)]
+
+
+def slab_cuts(I, R):
+    """[(item_lo, item_hi)] of the R ranks, as ShardedTrainer's callers cut them"""
+    from ltgan.sharded import item_slab
+    return [item_slab(I, r, R) for r in range(R)]
+
+
+def slab_edges(cuts):
+    """the items either side of every rank boundary, and the first and the last item"""
+    I = cuts[-1][1]
+    return sorted({0, I - 1} | {c + d for c, _ in cuts[1:] for d in (-1, 0)})
+
+
+def with_edge_history(X, row, cols, bare=None):
+    """X (binary CSR) with entries at `cols` of `row` as well; bare = (row, lo, hi): and that row without its entries in columns [lo, hi)"""
+    X = X.tolil()
+    for c in cols:
+        X[row, c] = 1.0
+    if bare is not None:
+        X[bare[0], bare[1]:bare[2]] = 0.0
+    X = X.tocsr()
+    X.eliminate_zeros()
+    X.sort_indices()
+    assert X.getnnz(axis=1).min() > 0
+    return X
+
+
+def with_edge_pairs(rows, gen, pop, edges, B, I):
+    """the (row, gen, pop) triples plus a pair on every item of `edges`, the k-th in row (7 k + 1) % B unless that row generates the item
+    already; rows stay sorted, gen distinct and ascending within a row (a row's holes first)"""
+    add = [((7 * k + 1) % B, g) for k, g in enumerate(edges)]
+    add = [(r, g) for r, g in add if not np.any((rows == r) & (gen == g))]
+    rows = np.concatenate([rows, [r for r, _ in add]]).astype(np.int32)
+    gen = np.concatenate([gen, [g for _, g in add]]).astype(np.int32)
+    pop = np.concatenate([pop, [(31 * g + 5) % I for _, g in add]]).astype(np.int32)
+    order = np.lexsort((gen, rows))
+    return rows[order], gen[order], pop[order]
+
+
+def sum_in_rank_order(parts):
+    """((0 + x_0) + x_1) + ... in fp32 on the device: the all-reduce of _rccl.HostComm(ordered=True)"""
+    import torch
+    acc = torch.zeros_like(parts[0])
+    for x in parts:
+        acc += x
+    return acc
+
+
+SLAB_TENSORS = (0, 3, 7)              # W_q0, W_p1t, b_p1: a rank owns its slab's rows; every other tensor is replicated
+
+
+class SlabRig:
+    """The R ranks of an item-sharded run over batch b of X_all as R engines in ONE process: Engine(I, item_lo, item_hi) and DeviceData(idx, B,
+    item_lo, item_hi) per rank over the same IndexData (the batch carries the full row's row_norm2, uitem, the CSC view, non-zero offsets --
+    what training hands over), the same parameters, moments, seed and Adam counter everywhere.  No torch.distributed: the three exchanges
+    are sums / concatenations in rank order on the device."""
+
+    def __init__(self, X_all, B, b, R, engine, P, D=None, m=None, v=None, adam_t=0):
+        """engine(item_lo, item_hi) -> Engine; P / m / v: generator arrays in engine layout over ALL items (set_generator cuts them); D = (emb,
+        arrays) of set_discriminator; b = (b0, b1): the span of batches [b0, b1) as phase C feeds it (forward only)"""
+        from ltgan.dataset import IndexData
+        I = X_all.shape[1]
+        self.I, self.B, self.R, self.cuts = I, B, R, slab_cuts(I, R)
+        self.idx = IndexData(I, X_all, 0, {}, {}, {}, {}, {}, range(I))
+        self.b = b
+        self._start = (engine, P, D, m, v, adam_t)
+        self.ranks = [self.rank(r) for r in range(R)]
+        self.record = None
+
+    def rank(self, r):
+        """(Engine, DeviceData, batch, Acts) of rank r in the start state; a fresh set every call"""
+        from ltgan.dataset import DeviceData
+        engine, P, D, m, v, adam_t = self._start
+        lo, hi = self.cuts[r]
+        eng = engine(lo, hi)
+        eng.set_generator(P, m=m, v=v)
+        if D is not None:
+            eng.set_discriminator(*D)
+        eng.adam_t = adam_t
+        dd = DeviceData(self.idx, self.B, eng.device, item_lo=lo, item_hi=hi)
+        batch = (dd.span(*self.b) if isinstance(self.b, tuple) else dd.view(self.b))["batch"]
+        return eng, dd, batch, eng.new_acts(batch.n_rows)
+
+    def forward(self, fopts, fake=None):
+        """g_fwd_enc on every rank, h1 summed in rank order into every rank's acts, g_fwd_rest: the [R B 5] row partials in rank order"""
+        import torch
+        n = self.ranks[0][2].n_rows
+        for eng, _, batch, acts in self.ranks:
+            eng.g_fwd_enc(batch, acts, fopts(eng))
+        h1 = [acts.h1[:n].clone() for _, _, _, acts in self.ranks]
+        h1_all = sum_in_rank_order(h1)
+        parts = []
+        for eng, _, batch, acts in self.ranks:
+            acts.h1[:n].copy_(h1_all)
+            rp = torch.zeros(n * 5, dtype=torch.float32, device=eng.device)
+            eng.g_fwd_rest(batch, fake, acts, fopts(eng), rp)
+            parts.append(rp)
+        return h1, h1_all, parts, torch.cat(parts)
+
+    def g_step(self, fake, cnt, anneal, lam, keep, dkeep, step, dstep):
+        """ShardedTrainer._g_one's cut-point sequence with the overlaps off, all ranks in lock step.  Leaves self.record = the ranks'
+        contributions to the three exchanges and the three totals; returns every rank's loss_out."""
+        import torch
+        B, R = self.B, self.R
+        gos = {id(eng): eng.g_opts(cnt, anneal, lam, keep, 1.0, dkeep, step, dstep) for eng, _, _, _ in self.ranks}
+        h1, h1_all, parts, rp_all = self.forward(lambda eng: gos[id(eng)].fwd, fake)
+        losses, dh2 = [], []
+        for eng, _, batch, acts in self.ranks:
+            loss = torch.zeros(8, dtype=torch.float32, device=eng.device)
+            d = torch.zeros(B, eng.H, dtype=torch.float32, device=eng.device)
+            eng.g_bwd_dec(batch, fake, acts, gos[id(eng)], rp_all, R, loss, d)
+            losses.append(loss)
+            dh2.append(d)
+        dh2_all = sum_in_rank_order(dh2)
+        for eng, _, batch, acts in self.ranks:
+            eng.g_bwd_dec1(batch, fake, acts, gos[id(eng)])
+            eng.g_bwd_rest(batch, fake, acts, gos[id(eng)], dh2_all)
+        for eng, _, _, _ in self.ranks:
+            eng.g_flush()
+        torch.cuda.synchronize()
+        self.record = dict(h1=h1, rowpart=parts, dh2=dh2, h1_all=h1_all, rowpart_all=rp_all, dh2_all=dh2_all)
+        return losses
+
+    @staticmethod
+    def assemble(engines, losses):
+        """(p, m, v as lists of eight numpy arrays over ALL items, loss) of the model the ranks hold together.  The replica invariant first:
+        every rank's copy of a replicated tensor, of its moments and of loss_out[0:6] equals rank 0's bit for bit."""
+        import torch
+        e0 = engines[0]
+        for r, e in enumerate(engines[1:], 1):
+            for i in range(8):
+                if i not in SLAB_TENSORS:
+                    for what, a, b in (("p", e0.g_p[i], e.g_p[i]), ("m", e0.g_m[i], e.g_m[i]), ("v", e0.g_v[i], e.g_v[i])):
+                        assert torch.equal(a, b), ("replica", what, i, "rank", r, float((a - b).abs().max()))
+            assert torch.equal(losses[0][:6], losses[r][:6]), ("replica loss, rank", r, losses[0][:6].tolist(), losses[r][:6].tolist())
+        out = []
+        for ts in ([e.g_p for e in engines], [e.g_m for e in engines], [e.g_v for e in engines]):
+            out.append([(torch.cat([t[i] for t in ts]) if i in SLAB_TENSORS else ts[0][i]).cpu().numpy() for i in range(8)])
+        return out[0], out[1], out[2], losses[0].cpu().numpy()

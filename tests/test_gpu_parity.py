@@ -282,27 +282,61 @@ def _g_case_ids(cases):
     return ["%d-%d-%s%s" % (I, B, path, "" if hs == G_D else ("-config-d" if hs == CONFIG_D else "-d" + _d_case_id(hs))) for I, B, path, hs in cases]
 
 
-def _g_step_case(precision, I, B, path, warm, hs=G_D, history="uniform", P=None, D=None, pairs=_fake_pairs, tol=None, figures=None, d_precision=None):
+def _g_step_case(precision, I, B, path, warm, hs=G_D, history="uniform", P=None, D=None, pairs=_fake_pairs, tol=None, figures=None, d_precision=None,
+                 ranks=1):
     """history "uniform": Hh.random_history, a hand-built batch 0.  "skewed" / "skewed-values": batch 1 of Hh.long_tail_batch through
     DeviceData (uitem, row_norm2, non-zero offsets, `values` for the second) with Hh.skewed_fake_pairs (> FU * NT pairs, a user past NT).
     P, D: the generator / discriminator parameter sets instead of the initialisers'; pairs(rng, X, I): the fake pairs of a "uniform" batch;
     tol: (first, second) moment bounds of a cold step instead of gtol and 2 gtol; figures: a dict that receives the measured moment errors.
     d_precision "bf16" / "fp8": the discriminator's operand mode -- the oracle's tower quantises alike, and sum_y (all the G step takes from
-    the tower) is held to n x the median bound + the max bound of tests/quantised_ref.py's noise model; everything else as without it."""
-    import torch
-    from ltgan.engine import Pairs, Pipe
+    the tower) is held to n x the median bound + the max bound of tests/quantised_ref.py's noise model; everything else as without it.
+    ranks = R > 1 with path "cut-points": the step over R item slabs in one process (Hh.SlabRig), history and fake pairs on every slab
+    edge, the model the ranks hold together against the SAME oracle on the full I at the SAME bounds.
+    Three halves -- _g_oracle, _g_device, _g_assert; returns (the case, what the device left, the rig or None)."""
+    c = _g_oracle(precision, I, B, warm, hs=hs, history=history, P=P, D=D, pairs=pairs, d_precision=d_precision, ranks=ranks)
+    got, rig = _g_device(c, path, ranks=ranks)
+    _g_assert(c, got, path, tol=tol, figures=figures, tag="%s I=%d B=%d R=%d %s%s" % (precision, I, B, ranks, history, " warm" if warm else "") if ranks > 1 else None)
+    return c, got, rig
+
+
+G_STEP, G_DSTEP, G_KEEP, G_DKEEP, G_ANNEAL, G_LAM = 3, 9, 0.75, 0.7, 0.13, 1.0     # counters and scalars of every G-step case
+
+
+def _g_oracle(precision, I, B, warm, hs=G_D, history="uniform", P=None, D=None, pairs=_fake_pairs, d_precision=None, ranks=1):
+    """The oracle half of a G-step case: the problem (history, fake pairs, parameters, warm moments) and ONE update by O.g_loss_and_grads +
+    O.SharedAdam on the full item range.  ranks > 1: the batch is batch 1 of a two-batch X_all whatever the history, row 2 holds every item
+    of Hh.slab_edges, row 5 nothing of the last slab, and every edge item has a fake pair (Hh.with_edge_pairs)."""
+    from types import SimpleNamespace
+    import scipy.sparse as sp
     rng, X, P0 = _problem(I, B, seed=11 * I + B)
     P = P0 if P is None else P
     D = O.init_discriminator(I, *hs, seed=5) if D is None else D
+    X_all = None
     if history == "uniform":
         rows, gen, pop = pairs(rng, X, I)
     else:
         X_all, X, (rows, gen, pop) = Hh.long_tail_batch(I, B, values=history.endswith("-values"))
+    if ranks > 1:
+        cuts = Hh.slab_cuts(I, ranks)
+        edges = Hh.slab_edges(cuts)
+        if X_all is None:
+            X_all = sp.vstack([Hh.random_history(np.random.default_rng(5 * I + B), B, I), X]).tocsr()
+        X_all = Hh.with_edge_history(X_all, B + 2, edges, bare=(B + 5,) + cuts[-1])      # row 5: nothing in the last slab
+        X = X_all[B:2 * B].tocsr()
+        rows, gen, pop = Hh.with_edge_pairs(rows, gen, pop, edges, B, I)
+        # what the case is for, checked on the host: pairs and history on every edge; lists as the sampler leaves them; a row with no entry in
+        # some slab; a row that has pairs but none in some slab; a row without any pair
+        live = gen >= 0
+        assert all(np.any(gen == g) for g in edges) and set(edges) <= set(X[2].indices.tolist())
+        assert np.all(np.diff(rows) >= 0) and 0 <= rows.min() and rows.max() < B
+        assert len(set(zip(rows[live].tolist(), gen[live].tolist()))) == int(live.sum())
+        assert X[5, cuts[-1][0]:].nnz == 0 and X[5].nnz > 0
+        assert any(np.any(live & (rows == r)) and not np.any(live & (rows == r) & (gen >= lo) & (gen < hi)) for r in range(B) for lo, hi in cuts)
+        assert len(set(rows.tolist())) < B
     valid = (gen >= 0) & (pop >= 0)
     cnt = int(valid.sum())
-    step, dstep, keep, dkeep, anneal, lam = 3, 9, 0.75, 0.7, 0.13, 1.0
+    step, dstep, keep, dkeep, anneal, lam = G_STEP, G_DSTEP, G_KEEP, G_DKEEP, G_ANNEAL, G_LAM
     t0 = 137 if warm else 4                 # the shared counter before this update (t = t0 + 1)
-    # ---- oracle
     q = precision == "bf16"
     mask = Hh.dropout_mask_dense(SEED, step, B, I, keep)
     eps = Hh.eps_dense(SEED, step, B, 200)
@@ -333,26 +367,59 @@ def _g_step_case(precision, I, B, path, warm, hs=G_D, history="uniform", P=None,
             ad.m[k], ad.v[k] = m0[k].astype(np.float64), v0[k].astype(np.float64)
     P64 = {k: np.asarray(v, np.float64) for k, v in P.items()}
     ad.apply(P64, g, O.G_KEYS)
-    # ---- device
+    return SimpleNamespace(precision=precision, I=I, B=B, warm=warm, hs=hs, history=history, d_precision=d_precision, dq=dq, q=q, P=P, D=D, X_all=X_all,
+                           X=X, rows=rows, gen=gen, pop=pop, cnt=cnt, t0=t0, m0=m0, v0=v0, losses=losses, sum_y=sum_y, sum_y_bound=sum_y_bound,
+                           P64=P64, ad=ad, tower_floor=(fmax, fmed) if dq is not None else None)
+
+
+def _g_start(c):
+    """(P, m, v) of the case's start state in engine layout; m, v None from cold moments"""
+    return (Hh.gen_to_engine(c.P), Hh.gen_to_engine(c.m0) if c.warm else None, Hh.gen_to_engine(c.v0) if c.warm else None)
+
+
+def _g_fake(c, dev):
+    """the case's fake pairs and their count on the device"""
+    import torch
+    from ltgan.engine import Pairs
+    return (Pairs(torch.from_numpy(c.pop).to(dev), torch.from_numpy(c.gen).to(dev), torch.from_numpy(c.rows).to(dev)),
+            torch.tensor([c.cnt], dtype=torch.int32, device=dev))
+
+
+def _g_slab_engine(c):
+    """engine(item_lo, item_hi) of Hh.SlabRig for the case"""
+    return lambda lo, hi: _engine(c.I, c.precision, hs=c.hs, lr=1e-3, item_lo=lo, item_hi=hi, **({} if c.d_precision is None else {"d_precision": c.d_precision}))
+
+
+def _g_device(c, path, ranks=1):
+    """The device half: one G step of the case by `path`.  Returns ((loss_out, p, m, v) as numpy -- the tensors over ALL items --, the
+    Hh.SlabRig of a "cut-points" step over `ranks` item slabs or None)."""
+    import torch
+    from ltgan.engine import Pipe
+    precision, I, B, hs, d_precision, q, t0 = c.precision, c.I, c.B, c.hs, c.d_precision, c.q, c.t0
+    step, dstep, keep, dkeep, anneal, lam = G_STEP, G_DSTEP, G_KEEP, G_DKEEP, G_ANNEAL, G_LAM
+    P, m, v = _g_start(c)
+    if ranks > 1:
+        assert path == "cut-points"
+        rig = Hh.SlabRig(c.X_all, B, 1, ranks, _g_slab_engine(c), P, Hh.disc_to_engine(c.D), m=m, v=v, adam_t=t0)
+        fake, cnt_t = _g_fake(c, rig.ranks[0][0].device)
+        losses = rig.g_step(fake, cnt_t, anneal, lam, keep, dkeep, step, dstep)
+        p_got, m_got, v_got, loss = Hh.SlabRig.assemble([r[0] for r in rig.ranks], losses)
+        return (loss, p_got, m_got, v_got), rig
     eng = _engine(I, precision, hs=hs, lr=1e-3, **({} if d_precision is None else {"d_precision": d_precision}))
     assert eng.Z == 200
     if path.endswith("-generic"):
         eng.cfg.tuning = 1 << 18
     if path.endswith("-wide-grad"):
         eng.cfg.tuning = 1 << 14             # the column-blocked fk_enc0_grad (its own heavy-row branch) instead of fk_enc0_grad_rows
-    if warm:
-        eng.set_generator(Hh.gen_to_engine(P), m=Hh.gen_to_engine(m0), v=Hh.gen_to_engine(v0))
-    else:
-        eng.set_generator(Hh.gen_to_engine(P))
-    emb, darr = Hh.disc_to_engine(D)
+    eng.set_generator(P, m=m, v=v)
+    emb, darr = Hh.disc_to_engine(c.D)
     eng.set_discriminator(emb, darr)
     dev = eng.device
-    fake = Pairs(torch.from_numpy(pop).to(dev), torch.from_numpy(gen).to(dev), torch.from_numpy(rows).to(dev))
-    cnt_t = torch.tensor([cnt], dtype=torch.int32, device=dev)
-    if history == "uniform":
-        batch = _upload_batch(eng, X, with_csc=True)
+    fake, cnt_t = _g_fake(c, dev)
+    if c.history == "uniform":
+        batch = _upload_batch(eng, c.X, with_csc=True)
     else:
-        dd, batch = Hh.device_batch(X_all, B, dev)
+        dd, batch = Hh.device_batch(c.X_all, B, dev)
     acts = eng.new_acts(B)
     eng.adam_t = t0  # exercise the shared counter
     if path.startswith("one-call") and not q:
@@ -377,10 +444,18 @@ def _g_step_case(precision, I, B, path, warm, hs=G_D, history="uniform", P=None,
         loss = eng.g_step(batch, fake, acts, cnt_t, anneal, lam, keep, 1.0, dkeep, rng_step=step, d_rng_step=dstep)
     eng.g_flush()
     torch.cuda.synchronize()
-    loss = loss.cpu().numpy()
+    return (loss.cpu().numpy(), *[[t.cpu().numpy() for t in ts] for ts in (eng.g_p, eng.g_m, eng.g_v)]), None
+
+
+def _g_assert(c, got, path, tol=None, figures=None, tag=None):
+    """The assertion half: losses, then every tensor's moments and move against the oracle's update.  tag: print the worst moment errors
+    against their bounds under it."""
+    loss, p_all, m_all, v_all = got
+    precision, I, hs, d_precision, dq, q, warm, t0, P = c.precision, c.I, c.hs, c.d_precision, c.dq, c.q, c.warm, c.t0, c.P
+    losses, sum_y, sum_y_bound, P64, ad, cnt = c.losses, c.sum_y, c.sum_y_bound, c.P64, c.ad, c.cnt
     if dq is not None:
         print("G step %s d_precision %s: sum_y %.6f, device off by %.2e, bound %.2e (floor max / median %.2e / %.2e over %d pairs)" % (
-            hs, d_precision, sum_y, abs(loss[4] - sum_y), sum_y_bound, fmax, fmed, cnt))
+            hs, d_precision, sum_y, abs(loss[4] - sum_y), sum_y_bound, *c.tower_floor, cnt))
     assert abs(loss[4] - sum_y) < sum_y_bound
     assert abs(loss[3] - losses["sum_p"]) < 2e-3 * abs(losses["sum_p"]) + 1e-7
     for i, k in enumerate(("g_loss", "vae_loss", "gan_loss")):
@@ -391,11 +466,10 @@ def _g_step_case(precision, I, B, path, warm, hs=G_D, history="uniform", P=None,
     want_v = Hh.gen_to_engine({k: ad.v[k] for k in O.G_KEYS})
     gtol = 2e-3 if q else 5e-4
     mtol, vtol = (gtol, 2 * gtol) if tol is None else tol
-    worst = 0.0
+    worst, worst_m, worst_v = 0.0, 0.0, 0.0
     for i in range(8):
-        m_got = eng.g_m[i].cpu().numpy()
-        v_got = eng.g_v[i].cpu().numpy()
-        p_got = eng.g_p[i].cpu().numpy()
+        m_got, v_got, p_got = m_all[i], v_all[i], p_all[i]
+        worst_m, worst_v = max(worst_m, Hh.rel_err(m_got, want_m[i])), max(worst_v, Hh.rel_err(v_got, want_v[i]))
         if warm:
             worst = max(worst, _check_warm_adam(p_got, Hh.gen_to_engine(P)[i], want[i], m_got, want_m[i], v_got, want_v[i], 1e-3 if q else 1e-4, ("tensor", i), t0 + 1,
                                                 max_norm=q))
@@ -408,6 +482,9 @@ def _g_step_case(precision, I, B, path, warm, hs=G_D, history="uniform", P=None,
         move_got = p_got - Hh.gen_to_engine(P)[i]
         move_want = want[i] - np.asarray(Hh.gen_to_engine(P)[i], np.float64)
         _check_adam_move(move_got, move_want, want_m[i], ad.lr_t(t0 + 1), ("theta", i))
+    if tag is not None:
+        wm, wv = ((1e-3, 2e-3) if q else (1e-4, 1e-4)) if warm else (mtol, vtol)      # (warm, fp32: element-wise in _check_warm_adam; the figure here is the max norm)
+        print("G step %s (%s): worst m / v relative error %.2e / %.2e against %.0e / %.0e" % (tag, path, worst_m, worst_v, wm, wv))
     if warm:
         print("I=%d %s %s: worst relative error of a theta move from warm moments %.2e" % (I, precision, path, worst))
 
@@ -820,12 +897,33 @@ def test_sampler_matches_oracle_at_20000_items():
     _sampler_case(rng, idx.n_items, 100, prob, False)
 
 
-def _sampler_case(rng, I, B, prob, with_zero_probs):
+def _with_boundary_candidates(prob, cuts, I):
+    """the sampler problem with the items either side of every cut, item 0 and item I - 1 in the candidate list of every third user that
+    has one (lists stay ascending and distinct)"""
+    cand_ptr, cand_idx = prob[0], prob[1]
+    extra = np.array(Hh.slab_edges(cuts), np.int32)
+    ptr, idx = [0], []
+    for b in range(len(cand_ptr) - 1):
+        c = cand_idx[cand_ptr[b]:cand_ptr[b + 1]]
+        if len(c) and b % 3 == 0:
+            c = np.union1d(c, extra).astype(np.int32)
+        idx.append(c)
+        ptr.append(ptr[-1] + len(c))
+    return (np.array(ptr, np.int32), np.concatenate(idx).astype(np.int32)) + tuple(prob[2:])
+
+
+def _sampler_case(rng, I, B, prob, with_zero_probs, cuts=None, rows_per_step=0):
+    """cuts = [(item_lo, item_hi)] of the ranks: the candidate lists get the slab edges, and after the unsharded call the logits go to one
+    engine per slab -- ltg_gather_cand_logits on every rank into a zeroed buffer, the buffers added (the all-reduce), ltg_sample_pairs from
+    ltg_sample_inputs.cand_logit on the first and the last rank: the sum IS logits[b, cand], and gen / pop / cnt are the unsharded call's.
+    rows_per_step: the rows as groups of that many, group k drawing with counter step + k and local rows, a count per group."""
     import ctypes as C
     import torch
     from ltgan import _cabi as cabi
     from ltgan.engine import _ptr
     eng = _engine(I, "fp32")
+    if cuts is not None:
+        prob = _with_boundary_candidates(prob, cuts, I)
     cand_ptr, cand_idx, pop_ptr, pop_idx, n_sample, valid = prob
     slot_ptr = np.concatenate([[0], np.cumsum(n_sample)]).astype(np.int32)
     acts = eng.new_acts(B)
@@ -843,30 +941,57 @@ def _sampler_case(rng, I, B, prob, with_zero_probs):
     t = lambda a: torch.from_numpy(a).to(dev)
     d = [t(x) for x in (cand_ptr, cand_idx, pop_ptr, pop_idx, n_sample, slot_ptr, valid)]
     step = 77
-    samp = cabi.ltg_sample_inputs(B, int(np.diff(cand_ptr).max()), *[_ptr(x) for x in d], step, None, None, None)
+    rps = int(rows_per_step)
+    groups = 1 if rps == 0 else -(-B // rps)
+    inputs = lambda cand_logit: cabi.ltg_sample_inputs(B, int(np.diff(cand_ptr).max()), *[_ptr(x) for x in d], step, None, None, cand_logit, rps, 0)
     ns = int(slot_ptr[-1])
-    gen = torch.full((ns,), -7, dtype=torch.int32, device=dev)
-    pop = torch.full((ns,), -7, dtype=torch.int32, device=dev)
-    cnt = torch.zeros(1, dtype=torch.int32, device=dev)
-    eng.sample_pairs(samp, acts, gen, pop, cnt)
-    torch.cuda.synchronize()
-    gen, pop, cnt = gen.cpu().numpy(), pop.cpu().numpy(), int(cnt.cpu().numpy()[0])
+
+    def draw(e, a, samp):
+        gen = torch.full((ns,), -7, dtype=torch.int32, device=dev)
+        pop = torch.full((ns,), -7, dtype=torch.int32, device=dev)
+        cnt = torch.zeros(groups, dtype=torch.int32, device=dev)
+        e.sample_pairs(samp, a, gen, pop, cnt)
+        torch.cuda.synchronize()
+        return gen.cpu().numpy(), pop.cpu().numpy(), cnt.cpu().numpy()
+
+    samp = inputs(None)
+    gen, pop, cnt_g = draw(eng, acts, samp)
+    if cuts is not None:
+        total = torch.zeros(len(cand_idx), dtype=torch.float32, device=dev)
+        slabs = []
+        for lo, hi in cuts:
+            e = _engine(I, "fp32", item_lo=lo, item_hi=hi)
+            a = e.new_acts(B + 1)           # (a row of NaN behind the batch: a column index one past the slab lands on a value, never outside)
+            a.logits.fill_(float("nan"))
+            a.logits[:B].copy_(torch.from_numpy(np.ascontiguousarray(logits[:, lo:hi])))
+            a.lse[:B].copy_(acts.lse[:B])
+            part = torch.zeros_like(total)
+            e.gather_cand_logits(samp, a, part)
+            total += part
+            slabs.append((e, a))
+        row_of = np.repeat(np.arange(B), np.diff(cand_ptr))
+        assert torch.equal(total, t(logits[row_of, cand_idx]))      # every entry written by exactly one rank, the others add 0
+        for e, a in (slabs[0], slabs[-1]):
+            g2, p2, c2 = draw(e, a, inputs(_ptr(total)))
+            assert np.array_equal(g2, gen) and np.array_equal(p2, pop) and np.array_equal(c2, cnt_g), (e.item_lo, e.item_hi)
+    cnt = int(cnt_g.sum())
     lse32 = lse.astype(np.float32)
     total_ok, flips = 0, 0
     for b in range(B):
         s0, s1 = slot_ptr[b], slot_ptr[b + 1]
         if n_sample[b] == 0:
             continue
+        kstep, row = (step, b) if rps == 0 else (step + b // rps, b % rps)
         c = cand_idx[cand_ptr[b]:cand_ptr[b + 1]]
         lp = (logits[b, c] - lse32[b]).astype(np.float32)
         p = np.exp(lp.astype(np.float64))
         p[np.exp(lp).astype(np.float32) == 0] = 0.0
-        u = O.rng_uniform(SEED, O.STREAM_GUMBEL, step, np.uint64(b) * np.uint64(I) + c.astype(np.uint64))
+        u = O.rng_uniform(SEED, O.STREAM_GUMBEL, kstep, np.uint64(row) * np.uint64(I) + c.astype(np.uint64))
         want = O.sample_user(c, p, int(n_sample[b]), u)
         k_eff = len(want)
         got_slots = gen[s0:s0 + k_eff]
         assert np.all(gen[s0 + k_eff:s1] == -1) and np.all(pop[s0 + k_eff:s1] == -1)     # unused slots are holes
-        up = O.rng_uniform(SEED, O.STREAM_POP_PICK, step, np.uint64(b) * np.uint64(I) + want.astype(np.uint64))
+        up = O.rng_uniform(SEED, O.STREAM_POP_PICK, kstep, np.uint64(row) * np.uint64(I) + want.astype(np.uint64))
         pl = pop_idx[pop_ptr[b]:pop_ptr[b + 1]]
         xg, xp, kept = O.build_fake_pairs(want, pl, up.astype(np.float32), valid)
         exp_gen = np.where(kept, want, -1)

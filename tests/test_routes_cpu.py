@@ -1,7 +1,7 @@
 """The kernel route of every shape the GPU tables claim something about (include/ltg.h: ltg_g_route / ltg_d_route; host-only, no GPU).
 
 The GPU tests name the route a shape is meant to reach in comments -- "small slab", "first streaming form, ragged tail", "d_wide: l1 / bwd1
-64, l2 -32, bwd2 128 tiles".  This module holds the library to those statements: it imports the tables themselves (helpers.HOT_FWD / HOT_G,
+64, l2 -32, bwd2 128 tiles".  This module holds the library to those statements: it imports the tables themselves (helpers.HOT_FWD / HOT_G / SLAB_G -- every rank's slab of the last --,
 test_gpu_parity.G_CASES / G_SKEWED / WARM_CASES / D_SIZES / D_STEP_CASES, test_gpu_quantised_disc.D_Q), and every case of them has to have
 its route written down here.  If a threshold moves, a case no longer exercises the kernel its comment names, and this fails before any GPU
 run.  The expected values are written out from the selection rules of csrc/ltg_kernels.hip as they stood before the routes existed (and
@@ -21,16 +21,19 @@ ARITH = {"fp32": K.LTG_DARITH_FP32, "bf16x6": K.LTG_DARITH_BF16X6, "bf16x4": K.L
 CONFIG_D = (100, 150, 250, 300)
 
 
-def _cfg(I=500, hs=CONFIG_D, precision="bf16", tuning=0, d_precision="fp32", d_arith="bf16x6"):
-    return K.ltg_config(I, 600, 200, I, *hs, PREC[precision], tuning, 0, 0, PREC[d_precision], ARITH[d_arith], 1e-4, 0.9, 0.999, 1e-8, 1)
+def _cfg(I=500, hs=CONFIG_D, precision="bf16", tuning=0, d_precision="fp32", d_arith="bf16x6", item_lo=0, n_items_global=0):
+    """item_lo / n_items_global: an item slab's two fields as Engine(item_lo, item_hi) fills them (0, 0: not sharded; I is then the LOCAL count)"""
+    return K.ltg_config(I, 600, 200, n_items_global or I, *hs, PREC[precision], tuning, item_lo, n_items_global, PREC[d_precision], ARITH[d_arith],
+                        1e-4, 0.9, 0.999, 1e-8, 1)
 
 
-def g_route(precision, I, B, tuning=0):
+def g_route(precision, I, B, tuning=0, item_lo=0, n_items_global=0):
     """H = 600, Z = 200, a shadow of W_p1t, the lazy clock's pointers from 8 192 items on (as Engine hands them over); never dereferenced"""
     clock = I >= 8192
     gen = K.ltg_gen_state(wp1t_bf16=0x1000, q0_last=0x2000 if clock else None, q0_lr_hist=0x3000 if clock else None, q0_ord=0, q0_period=32 if clock else 0)
     out = K.ltg_g_route_info()
-    assert K.load().ltg_g_route(C.byref(_cfg(I, precision=precision, tuning=tuning)), C.byref(gen), B, C.byref(out)) == 1
+    cfg = _cfg(I, precision=precision, tuning=tuning, item_lo=item_lo, n_items_global=n_items_global)
+    assert K.load().ltg_g_route(C.byref(cfg), C.byref(gen), B, C.byref(out)) == 1
     return out
 
 
@@ -124,6 +127,70 @@ G_ROUTES[("bf16", 25024, 128, 1 << 14)] = dict(STREAM(S1, 0), grad_rows=0)      
 G_ROUTES[("bf16", 8200, 100, 1 << 18)] = dict(enc0=K.LTG_ENC0_GENERIC, small=0, mid=K.LTG_MID_DENSE, dec=S1, stats=K.LTG_STATS_EPILOGUE, loss=K.LTG_LOSS_GENERIC,
                                                dlog_bf16=0, dh2=K.LTG_DH2_STREAM, dw=K.LTG_DW_STREAM, dw_ragged=1, sharded_ok=0, **LAZY)
 G_ROUTES[("fp32", 8200, 100, 1 << 18)] = dict(BIG_TILES, enc0=K.LTG_ENC0_GENERIC, mid=K.LTG_MID_DENSE, loss=K.LTG_LOSS_GENERIC)
+
+
+# ---- item slabs (helpers.SLAB_G): the route of a rank is that of its LOCAL item count -- except that a slab is never "small": ltg_config.item_lo
+# != 0 or n_items_global != n_items clears `small`, and with it loss (ROW -> COMBINE), dh2 (SMALL -> PARTIAL, 32-tiles), dw (TAIL_JOB -> TILE)
+# and q0 (DENSE -> the slot-map sweep in the tail) move; dec stays the small decoder kernel (fk_dec1) up to 4 096 items.  Nothing else
+# reads the two fields.  Keyed (precision, slab items): written out from the selection rules, like everything above.
+def SLAB_SMALL_DEC(bf):
+    """a slab of at most 4 096 items: the middle-fast chain around fk_dec1"""
+    return dict(MID(bf), dec=K.LTG_DEC_SMALL, dec_tile=0)
+
+
+SLAB_ROUTES = {}
+for p in ("fp32", "bf16"):
+    for n in (512, 488, 4040, 128):
+        SLAB_ROUTES[(p, n)] = SLAB_SMALL_DEC(p == "bf16")
+    SLAB_ROUTES[(p, 77)] = SLAB_SMALL_DEC(False)                                                 # 77 % 4 != 0: scalar loaders, 32-tiles
+    SLAB_ROUTES[(p, 4160)] = MID(p == "bf16")                                                   # past RD_MAXI: the tiled decoder
+for n in (8320, 8384):
+    SLAB_ROUTES[("bf16", n)] = STREAM(S1, 0)
+for n in (8200, 8264):
+    SLAB_ROUTES[("bf16", n)] = STREAM(S1, 1)                                                    # n % 32 = 8: ragged tail of the weight update
+# Slabs of ONE case that take different routes.  The replicated middle layers run the same kernels on every rank in all of them (mid, loss
+# and the dz -> dh1 -> tail chain depend on the rows alone once no slab is "small"); what differs is slab-local:
+#   8 200 / 2: 4 160 -> k_dec1_fwd 32-tiles, 4 040 -> fk_dec1             1 101 / 9 (fp32): one route; the kernels pick scalar loaders at 77 items
+#   16 520 / 2: 8 320 -> no ragged tail, 8 200 -> ragged                  25 032 / 3: 8 384 x 2 -> none, 8 264 -> ragged
+SLAB_SPLIT_ROUTES = {(8200, 2): ("dec", "dec_tile"), (1101, 9): (), (16520, 2): ("dw_ragged",), (25032, 3): ("dw_ragged",), (1000, 2): ()}
+
+
+def _slab_cases():
+    """(precision, slab items, B, item_lo, I) of every rank of every SLAB_G case"""
+    return sorted({(p, hi - lo, B, lo, I) for p, I, B, R, _, _ in Hh.SLAB_G for lo, hi in Hh.slab_cuts(I, R)})
+
+
+def test_every_slab_of_the_item_slab_cases_has_its_route_written_down():
+    assert sorted({n for _, n, _, _, _ in _slab_cases()}) == [77, 128, 488, 512, 4040, 4160, 8200, 8264, 8320, 8384]
+    for p, n, B, lo, I in _slab_cases():
+        assert (p, n) in SLAB_ROUTES, (p, n)
+        r = g_route(p, n, B, item_lo=lo, n_items_global=I)
+        _holds(r, dict(SLAB_ROUTES[(p, n)], small=0), (p, n, B, lo, I))
+        assert r.sharded_ok == int(n >= 8192)                    # the one-call step's cases: every slab of 16 520 / 2 and 25 032 / 3
+    # the fields that differ between the slabs of one case are the ones named above, and none of them is read by a replicated layer
+    fields = [f for f, _ in K.ltg_g_route_info._fields_]
+    for (I, R), moving in SLAB_SPLIT_ROUTES.items():
+        for p, B in {(p, B) for p, i, B, r, _, _ in Hh.SLAB_G if (i, r) == (I, R)}:
+            routes = [g_route(p, hi - lo, B, item_lo=lo, n_items_global=I) for lo, hi in Hh.slab_cuts(I, R)]
+            differ = {f for f in fields for x in routes[1:] if _field(x, f) != _field(routes[0], f)}
+            assert differ - {"dh2_chunk", "dh2_nsplit"} == set(moving), (I, R, p, differ)
+            assert not differ & {"enc0", "small", "mid", "mid_vec", "loss", "q0", "q0_own_launch", "grad_rows"}
+
+
+def test_a_slab_is_never_small():
+    """the same 512 items unsharded and as either slab of 1 000: item_lo / n_items_global move small, loss, dh2, dw, q0 -- and nothing else"""
+    whole = g_route("bf16", 512, 100)
+    _holds(whole, SMALL, "512 unsharded")
+    for lo, Ig in ((0, 1000), (488, 1000)):
+        r = g_route("bf16", 512, 100, item_lo=lo, n_items_global=Ig)
+        moved = {f for f, _ in K.ltg_g_route_info._fields_ if _field(r, f) != _field(whole, f)}
+        assert moved == {"small", "loss", "dh2", "dh2_tile", "dh2_chunk", "dh2_nsplit", "dw", "dw_tile", "q0"}, moved
+    assert g_route("bf16", 512, 100, item_lo=0, n_items_global=512).small == 1      # the whole range named as a slab is not sharded
+
+
+def _field(r, f):
+    v = getattr(r, f)
+    return v if isinstance(v, (int, float)) else list(v)
 
 
 def _g_table_cases():

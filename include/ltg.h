@@ -1044,6 +1044,39 @@ int ltg_critic_finish(int32_t n_rows, int32_t k_in, const int32_t* id_in, int32_
 int ltg_topk_gate(int32_t n_rows, int32_t c_in, const float* cand_score, const int32_t* cand_id, const float* crit, const int32_t* flag,
                   float tau, int32_t k, float* score_out, int32_t* id_out, int32_t* stat_out, ltg_stream stream);
 
+/* Exploration lists (additive, ABI v14): top-K SAMPLED without replacement under the Plackett-Luce policy at temperature T,
+ * with the conditional log-probability of every pick.  Three calls, cut at the two points where item shards exchange; the unsharded path
+ * makes the same three calls without the exchanges.  inv_temp = (float)(1 / T), formed by the caller.
+ * ltg_topk_sample: the draw is Gumbel-top-k.  Eligible = not a fold-in item of tr and not in excl_id [n_rows][f_in] (a fixed head as
+ * ltg_topk / ltg_topk_merge wrote it: GLOBAL ids; ids outside the slab and padding are skipped and index nothing; NULL with f_in = 0).
+ * key = s * inv_temp + g, one fp32 multiply and one fp32 add, never contracted; g = -logf(-logf(u)), u = the counter RNG's uniform at
+ * (cfg->seed, stream 8, draw, (row_lo + row) * n_items_global + global id) -- a pure function of the seed, the draw, the GLOBAL row and the
+ * GLOBAL id (n_items_global = cfg->n_items_global, or cfg->n_items where that is 0).  u == 0 gives key -inf: eligible, last.  g_noise
+ * (optional) [n_rows][cfg->n_items]: injected Gumbel values aligned with the slab's columns; the RNG is then not called.  key_out / id_out
+ * [n_rows][k]: this slab's k largest keys in ltg_topk's list format with the key in the score's place (key descending, equal keys lower
+ * GLOBAL id first, -0.0 == +0.0, padding id -1 / key -inf), so per-slab outputs go straight into ltg_topk_merge, and the merge of the slabs
+ * of a row equals the call on the whole row bit for bit.  One workgroup per row; the noise is recomputed in every pass, and no [n_rows][n_items]
+ * array is written.  ltg_topk's limits: 1 <= k <= 1024, n_items per slab <= 360 448.  NaN keys are outside the contract.
+ * ltg_topk_sample_mass: id_in [n_rows][k] = the FINAL picks (GLOBAL ids, after the merge).  Over this slab: score_out [n_rows][k] = the raw
+ * logit of every pick the slab owns, -inf elsewhere; max_out [n_rows] = the largest eligible logit (picks included; -inf if there is none);
+ * rest_out [n_rows] = the sum over the eligible items that were NOT picked of exp((s - max_out) * inv_temp), -inf logits adding nothing.  Fixed
+ * per-thread stride and a fixed reduction tree: bit-identical from run to run.  Across slabs the caller forms M = max of max_out, rest = sum of
+ * rest_out * exp((max_out - M) * inv_temp), score = max of score_out.
+ * ltg_topk_sample_finish: logp_out [n_rows][k], logp_j = x_j - log(rest + sum_{m >= j} exp(x_m)) with x_m = (score_m - M) * inv_temp: the log of
+ * the conditional probability of pick j given the earlier ones, from positive terms only.  An entry with score -inf (padding) gets 0.0.  One wave
+ * per row.  Outside the contract: logp where x_j < -80 for a pick, or where every eligible logit is -inf.
+ * No floating-point atomics anywhere.  LTG_EINVAL before any HIP call: a NULL output or input (tr, excl_id with f_in = 0, g_noise and stream
+ * excepted), k outside [1, 1024], f_in < 0, f_in > 0 with excl_id NULL, inv_temp not finite or <= 0, row_lo < 0, item_lo < 0, and whatever
+ * ltg_topk refuses; n_rows = 0 returns LTG_OK and launches nothing. */
+int ltg_topk_sample(const ltg_config* cfg, const float* logits, const ltg_batch* tr, int32_t n_rows, int32_t row_lo, int32_t k, float inv_temp,
+                    uint64_t draw, const int32_t* excl_id, int32_t f_in, const float* g_noise, float* key_out, int32_t* id_out,
+                    ltg_stream stream);
+int ltg_topk_sample_mass(const ltg_config* cfg, const float* logits, const ltg_batch* tr, int32_t n_rows, int32_t k, float inv_temp,
+                         const int32_t* excl_id, int32_t f_in, const int32_t* id_in, float* score_out, float* max_out, float* rest_out,
+                         ltg_stream stream);
+int ltg_topk_sample_finish(int32_t n_rows, int32_t k, const float* score, const float* M, const float* rest, float inv_temp, float* logp_out,
+                           ltg_stream stream);
+
 /* Verification helper of the LTG_PREC_FP8 mode: out[i] = the value the fp8 GEMM operands carry for in[i]
  * (clamp to +-448, round to nearest-even OCP e4m3) -- lets a test pin its CPU model of the rounding to the hardware. */
 int ltg_fp8_roundtrip(const float* in, float* out, int32_t n, ltg_stream stream);

@@ -173,6 +173,7 @@ __global__ __launch_bounds__(64) void k_gate_set(LtgGate g, LtgGate g2 = LTG_NO_
 #include "ltg_clock.h"
 #include "ltg_sampler.h"
 #include "ltg_topk.h"
+#include "ltg_explore.h"
 #include "ltg_audience.h"
 #include "ltg_cap.h"
 #include "ltg_floor.h"
@@ -1951,6 +1952,60 @@ int ltg_topk_merge(int32_t n_parts, int32_t n_rows, int32_t k_in, const float* s
     if (n_rows == 0) return LTG_OK;
     hipLaunchKernelGGL(k_topk_merge, dim3(n_rows), dim3(NT), 0, (hipStream_t)stream, n_parts, n_rows, k_in, score_in, id_in, k, score_out,
                        id_out);
+    return check_launch();
+}
+
+// Exploration lists: the draw, the mass and the log-probabilities, cut where item shards exchange.  What ltg_topk refuses is
+// refused here in the same words, and the dynamic LDS is sized as topk_launch sizes it (cap = 0: the slab is too long).
+static bool explore_args_ok(const ltg_config* cfg, const float* logits, const ltg_batch* tr, int32_t n_rows, int32_t k, float inv_temp,
+                            const int32_t* excl_id, int32_t f_in, size_t* bits, size_t* cap) {
+    if (!cfg || !logits || cfg->n_items <= 0 || cfg->item_lo < 0 || n_rows < 0 || k < 1 || k > 1024) return false;
+    if (tr && (!tr->indptr || !tr->indices || tr->n_rows != n_rows)) return false;
+    if (f_in < 0 || (f_in > 0 && !excl_id) || !std::isfinite(inv_temp) || !(inv_temp > 0.f)) return false;
+    *bits = (size_t)((cfg->n_items + 63) / 64) * 8;
+    *cap = 4096;
+    while (*cap >= 1024 && *bits + *cap * 8 > 60 * 1024) *cap >>= 1;
+    return *cap >= 1024;
+}
+
+int ltg_topk_sample(const ltg_config* cfg, const float* logits, const ltg_batch* tr, int32_t n_rows, int32_t row_lo, int32_t k, float inv_temp,
+                    uint64_t draw, const int32_t* excl_id, int32_t f_in, const float* g_noise, float* key_out, int32_t* id_out,
+                    ltg_stream stream) {
+    size_t bits, cap;
+    if (!key_out || !id_out || row_lo < 0 || !explore_args_ok(cfg, logits, tr, n_rows, k, inv_temp, excl_id, f_in, &bits, &cap)) return LTG_EINVAL;
+    if (n_rows == 0) return LTG_OK;
+    clear_errors();
+    const bool vec = (cfg->n_items % 4) == 0 && ((uintptr_t)logits % 16) == 0;
+    const uint64_t i_glob = (uint64_t)(cfg->n_items_global > 0 ? cfg->n_items_global : cfg->n_items);
+    hipLaunchKernelGGL(vec ? k_topk_sample<true> : k_topk_sample<false>, dim3(n_rows), dim3(TK_NT), bits + cap * 8, (hipStream_t)stream,
+                       cfg->n_items, cfg->item_lo, i_glob, logits, tr ? tr->indptr : (const int32_t*)nullptr,
+                       tr ? tr->indices : (const int32_t*)nullptr, k, (int)cap, inv_temp, cfg->seed, draw, row_lo, excl_id, f_in, g_noise, key_out,
+                       id_out);
+    return check_launch();
+}
+
+int ltg_topk_sample_mass(const ltg_config* cfg, const float* logits, const ltg_batch* tr, int32_t n_rows, int32_t k, float inv_temp,
+                         const int32_t* excl_id, int32_t f_in, const int32_t* id_in, float* score_out, float* max_out, float* rest_out,
+                         ltg_stream stream) {
+    size_t bits, cap;
+    if (!id_in || !score_out || !max_out || !rest_out || !explore_args_ok(cfg, logits, tr, n_rows, k, inv_temp, excl_id, f_in, &bits, &cap))
+        return LTG_EINVAL;
+    if (n_rows == 0) return LTG_OK;
+    clear_errors();
+    const bool vec = (cfg->n_items % 4) == 0 && ((uintptr_t)logits % 16) == 0;
+    hipLaunchKernelGGL(vec ? k_topk_sample_mass<true> : k_topk_sample_mass<false>, dim3(n_rows), dim3(TK_NT), bits, (hipStream_t)stream,
+                       cfg->n_items, cfg->item_lo, logits, tr ? tr->indptr : (const int32_t*)nullptr, tr ? tr->indices : (const int32_t*)nullptr, k,
+                       inv_temp, excl_id, f_in, id_in, score_out, max_out, rest_out);
+    return check_launch();
+}
+
+int ltg_topk_sample_finish(int32_t n_rows, int32_t k, const float* score, const float* M, const float* rest, float inv_temp, float* logp_out,
+                           ltg_stream stream) {
+    if (!score || !M || !rest || !logp_out || n_rows < 0 || k < 1 || k > 1024 || !std::isfinite(inv_temp) || !(inv_temp > 0.f)) return LTG_EINVAL;
+    if (n_rows == 0) return LTG_OK;
+    clear_errors();
+    hipLaunchKernelGGL(k_topk_sample_finish, dim3((n_rows + NT / 64 - 1) / (NT / 64)), dim3(NT), 0, (hipStream_t)stream, n_rows, k, score, M, rest,
+                       inv_temp, logp_out);
     return check_launch();
 }
 

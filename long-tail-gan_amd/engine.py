@@ -800,6 +800,46 @@ class Engine:
                                             _ptr(labels), int(labels.numel()), int(group_mask), _ptr(score_out), _ptr(id_out),
                                             self.stream()), "ltg_topk_groups")
 
+    def topk_sample(self, logits_or_acts, tr, row_lo, k, inv_temp, draw, excl, key_out, id_out, g_noise=None):
+        """the k largest Gumbel keys of each of the key_out.shape[0] rows of this slab's logits: the sampled part of an exploration list
+        (ltg_topk_sample).  row_lo: the GLOBAL row of the first row; inv_temp: float32(1 / T); draw: the counter of the draw; excl: the
+        fixed head [rows, f] int32 GLOBAL ids (as topk / topk_merge wrote it), or None; g_noise: injected Gumbel values [rows, I] (tests).
+        -> key_out [rows, k] float32, id_out [rows, k] int32 GLOBAL ids, ordered and padded as topk writes a list"""
+        logits = logits_or_acts.logits if isinstance(logits_or_acts, Acts) else logits_or_acts
+        n = int(key_out.shape[0])
+        assert logits.dtype == torch.float32 and logits.numel() >= n * self.I and tuple(id_out.shape) == tuple(key_out.shape) == (n, k)
+        assert key_out.is_contiguous() and id_out.is_contiguous() and id_out.dtype == torch.int32
+        f = 0 if excl is None else int(excl.shape[1])
+        assert excl is None or (excl.dtype == torch.int32 and excl.is_contiguous() and int(excl.shape[0]) == n)
+        assert g_noise is None or (g_noise.dtype == torch.float32 and g_noise.is_contiguous() and g_noise.numel() >= n * self.I)
+        cabi.check(self.lib.ltg_topk_sample(C.byref(self.cfg), _ptr(logits), C.byref(tr.c) if tr is not None else None, n, int(row_lo), int(k),
+                                            float(inv_temp), int(draw), _ptr(excl) if f else None, f, _ptr(g_noise), _ptr(key_out),
+                                            _ptr(id_out), self.stream()), "ltg_topk_sample")
+
+    def topk_sample_mass(self, logits_or_acts, tr, inv_temp, excl, ids, score_out, max_out, rest_out):
+        """this slab's part of the mass behind the FINAL picks ids [rows, k] int32 (ltg_topk_sample_mass): score_out [rows, k] the raw logit
+        of every pick the slab owns (-inf elsewhere), max_out [rows] the largest eligible logit, rest_out [rows] the sum over the eligible
+        items that were not picked of exp((s - max_out) * inv_temp); excl as topk_sample takes it"""
+        logits = logits_or_acts.logits if isinstance(logits_or_acts, Acts) else logits_or_acts
+        n, k = (int(x) for x in ids.shape)
+        assert logits.dtype == torch.float32 and logits.numel() >= n * self.I and tuple(score_out.shape) == (n, k)
+        assert ids.is_contiguous() and ids.dtype == torch.int32 and score_out.is_contiguous() and max_out.numel() >= n and rest_out.numel() >= n
+        assert max_out.is_contiguous() and rest_out.is_contiguous() and max_out.dtype == rest_out.dtype == score_out.dtype == torch.float32
+        f = 0 if excl is None else int(excl.shape[1])
+        assert excl is None or (excl.dtype == torch.int32 and excl.is_contiguous() and int(excl.shape[0]) == n)
+        cabi.check(self.lib.ltg_topk_sample_mass(C.byref(self.cfg), _ptr(logits), C.byref(tr.c) if tr is not None else None, n, k,
+                                                 float(inv_temp), _ptr(excl) if f else None, f, _ptr(ids), _ptr(score_out), _ptr(max_out),
+                                                 _ptr(rest_out), self.stream()), "ltg_topk_sample_mass")
+
+    def topk_sample_finish(self, score, M, rest, inv_temp, logp_out):
+        """logp_out [rows, k] <- the conditional log-probability of every pick, from the picks' logits score [rows, k], the largest
+        eligible logit M [rows] and the mass of the unpicked items rest [rows], all over the WHOLE catalogue (ltg_topk_sample_finish)"""
+        n, k = (int(x) for x in score.shape)
+        assert tuple(logp_out.shape) == (n, k) and M.numel() >= n and rest.numel() >= n
+        assert all(t.is_contiguous() and t.dtype == torch.float32 for t in (score, M, rest, logp_out))
+        cabi.check(self.lib.ltg_topk_sample_finish(n, k, _ptr(score), _ptr(M), _ptr(rest), float(inv_temp), _ptr(logp_out), self.stream()),
+                   "ltg_topk_sample_finish")
+
     def topk_quota(self, score_all, id_all, score_grp, id_grp, quota, score_out, id_out):
         """the lists with at least quota[j] entries of reserved list j: score_all / id_all [rows, k_in] plain lists, score_grp / id_grp
         [lists, rows, m_in] reserved lists (topk_groups with one bit each), quota a host sequence of `lists` counts -> [rows, k]

@@ -6,7 +6,7 @@
         [--diversify LAMBDA] [--candidates N] [--div-space decoder|encoder] [--calibrate LAMBDA]
         [--cap C|NAME:C[,NAME:C...]] [--cap-candidates N] [--cap-score logprob|logit] [--share NAME[+NAME...]:S]
         [--floor M|NAME:M[,NAME:M...] --floor-reserve R [--floor-candidates N] [--floor-score logprob|logit]]
-        [--gate P [--gate-candidates N]] [--critic [TOP]]
+        [--gate P [--gate-candidates N]] [--critic [TOP]] [--explore T [--explore-fixed F] [--explore-draw N]]
 
 restores a checkpoint written by train.py, runs test.py's forward over the users of `<split>_tr.csv` ONCE (chunks of 20 000 users,
 dropout on with keep_prob 0.75 by default: Q3, RNG counter 2*10^9 + first row of the chunk), keeps each user's top-K list on the GPU
@@ -73,6 +73,14 @@ ltg_pair_critic / ltg_critic_finish / ltg_topk_gate): the critic of a niche entr
 logit over the user's popular history items with features, an entry passes iff it has no critic or sigmoid(critic) >= P, and the first K
 passing candidates are the list.  N defaults to min(256, 2 K) and must lie in [K, 256], K = max(100, --k).  The table is then what the gate
 costs each group; the last line is `gate@K: <entries> scored candidates, <entries> rejected, <users> short lists (min_prob P)`.
+
+--explore T (T > 0; not together with any rule above) SAMPLES every list before the report reads it (trainer.Explore: ltg_topk_sample,
+ltg_topk_sample_mass, ltg_topk_sample_finish): the first --explore-fixed F entries (default 0, F < K) are the plain top-F, the others are
+drawn without replacement in proportion to exp(logit / T) among the remaining items -- the Plackett-Luce policy -- and every entry carries
+the log of its conditional probability.  --explore-draw N (default 0) numbers the draw: the same N gives the same lists, another N another
+sample.  The table is then what exploration costs in NDCG@100 and gains in tail share / coverage / gini; the last line is
+`explore@K: T <T>, fixed <F>, draw <N>, mean list logp <mean log-propensity of a list>, explored share <share>`, explored share = the part
+of the sampled slots whose item is not in the plain top-K of the same user.
 
 --critic [TOP] scores the first TOP entries (default min(K, 256)) of whatever lists are served the same way without changing them
 (trainer.Critic); the last line is `critic@TOP: <entries> scored entries, <users> users with anchors, mean prob <p>` and --json gets the
@@ -142,12 +150,12 @@ def parse_min_slots(spec, names, k):
     return slots
 
 
-RULE_OPTIONS = ("min_slots", "diversify", "calibrate", "cap", "share", "floor", "gate")     # at most one of them; a refusal names the later first
+RULE_OPTIONS = ("min_slots", "diversify", "calibrate", "cap", "share", "floor", "gate", "explore")     # at most one of them; a refusal names the later first
 
 
 def add_rule_args(ap):
     """the options of the serve-time rules besides --min-slots (trainer.Diversify, Calibrate, ExposureCap, ShareTarget, ExposureFloor,
-    CriticGate) and of the critic (trainer.Critic), shared with recommend.py"""
+    CriticGate, Explore) and of the critic (trainer.Critic), shared with recommend.py"""
     ap.add_argument("--diversify", type=float, default=None, metavar="LAMBDA")
     ap.add_argument("--candidates", type=int, default=None, metavar="N")
     ap.add_argument("--div-space", choices=("decoder", "encoder"), default="decoder")
@@ -162,6 +170,9 @@ def add_rule_args(ap):
     ap.add_argument("--floor-score", choices=("logprob", "logit"), default=None)
     ap.add_argument("--gate", type=float, default=None, metavar="P")
     ap.add_argument("--gate-candidates", type=int, default=None, metavar="N")
+    ap.add_argument("--explore", type=float, default=None, metavar="T")
+    ap.add_argument("--explore-fixed", type=int, default=None, metavar="F")
+    ap.add_argument("--explore-draw", type=int, default=None, metavar="N")
     ap.add_argument("--critic", type=int, nargs="?", const=0, default=None, metavar="TOP")      # (0: the default, min(k, 256))
 
 
@@ -273,6 +284,16 @@ def check_rule_args(ap, a, k):
             ap.error("--gate walks at most 256 candidates: lists of %d entries are too long" % k)
         if a.gate_candidates is not None and not k <= a.gate_candidates <= 256:
             ap.error("--gate-candidates must be in [k, 256] = [%d, 256], got %d" % (k, a.gate_candidates))
+    if a.explore is None:
+        if a.explore_fixed is not None or a.explore_draw is not None:
+            ap.error("--explore-fixed and --explore-draw need --explore")
+    else:
+        if not (a.explore > 0.0 and np.isfinite(a.explore) and np.isfinite(np.float32(1.0 / a.explore))):
+            ap.error("--explore takes a temperature T > 0, finite")
+        if a.explore_fixed is not None and not 0 <= a.explore_fixed < k:
+            ap.error("--explore-fixed must be in [0, k) = [0, %d), got %d" % (k, a.explore_fixed))
+        if a.explore_draw is not None and a.explore_draw < 0:
+            ap.error("--explore-draw takes N >= 0")
     if a.critic is not None and a.critic != 0 and not 1 <= a.critic <= min(k, 256):
         ap.error("--critic takes TOP in [1, min(k, 256)] = [1, %d]" % min(k, 256))
 
@@ -281,7 +302,7 @@ def build_rules(args, dataset_dir, n_items, groups=None):
     """the serve-time rule of the parsed options -> (its keyword for a Recommender: {} or one entry, the stdout lines it adds after
     run(): callables (ids, tr, k) -> str).  groups: (labels, names) of --groups where the caller has built them; else they are built
     here, and only for a rule that refers to them"""
-    from ltgan.serving import Calibrate, CriticGate, Diversify, ExposureCap, ExposureFloor, MinSlots, ShareTarget
+    from ltgan.serving import Calibrate, CriticGate, Diversify, Explore, ExposureCap, ExposureFloor, MinSlots, ShareTarget
 
     def grouped():
         labels, names = groups or build_groups(dataset_dir, args.group_kind, args.n_groups, n_items)
@@ -316,6 +337,9 @@ def build_rules(args, dataset_dir, n_items, groups=None):
     if getattr(args, "gate", None) is not None:
         gate = CriticGate(*critic_sides(dataset_dir, n_items), args.gate, candidates=args.gate_candidates)
         return dict(gate=gate), [lambda ids, tr, k: gate_line(gate.stats(), gate.min_prob, k)]
+    if getattr(args, "explore", None) is not None:
+        exp = Explore(args.explore, fixed=args.explore_fixed or 0, draw=args.explore_draw or 0)
+        return dict(explore=exp), [lambda ids, tr, k: explore_line(exp, k)]
     return {}, []
 
 
@@ -341,6 +365,13 @@ def gate_line(stats, min_prob, k):
     st = np.asarray(stats).astype(np.int64).reshape(-1, 3)
     return "gate@%d: %d scored candidates, %d rejected, %d short lists (min_prob %.6g)" % (
         k, int(st[:, 0].sum()), int(st[:, 1].sum()), int((st[:, 2] < k).sum()), min_prob)
+
+
+def explore_line(exp, k):
+    """the line --explore adds: the mean log-propensity of a list and the explored share (Explore.stats())"""
+    st = exp.stats()
+    return "explore@%d: T %.6g, fixed %d, draw %d, mean list logp %.6f, explored share %.6f" % (
+        k, exp.temperature, exp.fixed, exp.draw, st["mean_logp"], st["explored_share"])
 
 
 def critic_line(summary, top):

@@ -9,6 +9,7 @@
         [--share NAME[+NAME...]:S]
         [--floor M|NAME:M[,NAME:M...] --floor-reserve R [--floor-candidates N] [--floor-score logprob|logit]]
         [--gate P [--gate-candidates N]] [--critic [TOP] [--critic-out critic.tsv]]
+        [--explore T [--explore-fixed F] [--explore-draw N] [--propensities props.tsv]]
 
 restores a checkpoint written by train.py, runs test.py's forward over the users of `<split>_tr.csv` (chunks of 20 000 users,
 dropout on with keep_prob 0.75 by default: Q3, RNG counter 2*10^9 + first row of the chunk) and keeps each user's k best items, the
@@ -74,6 +75,16 @@ score) over the user's popular history items with features; an entry passes iff 
 passing candidates are the list, in score order.  N defaults to min(256, 2 k) and must lie in [k, 256].  P = 0 is the plain list.  The last
 stdout line is `gate@k: <entries> scored candidates, <entries> rejected, <users> short lists (min_prob P)`.
 
+--explore T (T > 0; not together with any rule above) SAMPLES every list on the GPU (trainer.Explore: ltg_topk_sample, ltg_topk_sample_mass,
+ltg_topk_sample_finish): the first --explore-fixed F entries (default 0, F < k) are the plain top-F, the others are drawn without
+replacement in proportion to exp(logit / T) among the remaining items -- the Plackett-Luce policy at temperature T -- so that tail items
+sometimes get slots they would never win on score, and every entry carries the log of the conditional probability with which it was shown,
+for re-weighting the feedback afterwards.  --explore-draw N (default 0) numbers the draw: the same N gives the same lists whatever the
+sharding, another N another sample.  The lists are written in draw order.  --propensities (default props.tsv) gets one line per user,
+`uid<TAB>sid:logp,sid:logp,...` (%.6g; 0 for the fixed head); --npz also stores logp [users, k].  The last stdout line is
+`explore@k: T <T>, fixed <F>, draw <N>, mean list logp <mean log-propensity of a list>, explored share <share>`, explored share = the part
+of the sampled slots whose item is not in the plain top-k of the same user.
+
 --critic [TOP] scores the first TOP entries (default min(k, 256)) of every list, whichever kind it is, the same way without changing it
 (trainer.Critic: one ltg_pair_critic per chunk).  --critic-out (default critic.tsv) gets one line per scored entry,
 `uid<TAB>sid<TAB>prob<TAB>anchor_sid:prob`: prob = sigmoid(critic), then the popular history item that speaks most for the entry with the
@@ -119,6 +130,7 @@ def parse_args(argv):
     ap.add_argument("--explain-metric", choices=("cosine", "dot"), default=None)
     ap.add_argument("--why", default=None)
     ap.add_argument("--critic-out", default=None)
+    ap.add_argument("--propensities", default=None)
     a = ap.parse_args(argv)
     if not 1 <= a.k <= 1024:
         ap.error("--k must be in [1, 1024]")
@@ -141,6 +153,11 @@ def parse_args(argv):
         if a.explain_top is not None and not 1 <= a.explain_top <= min(a.k, 256):
             ap.error("--explain-top must be in [1, min(k, 256)] = [1, %d]" % min(a.k, 256))
         a.why = a.why or "why.tsv"
+    if a.explore is None:
+        if a.propensities is not None:
+            ap.error("--propensities needs --explore")
+    else:
+        a.propensities = a.propensities or "props.tsv"
     if a.critic is None:
         if a.critic_out is not None:
             ap.error("--critic-out needs --critic")
@@ -149,9 +166,9 @@ def parse_args(argv):
     return a
 
 
-def write_recs(ids, scores, uid_start, tsv_path=None, npz_path=None, why=None, critic=None):
+def write_recs(ids, scores, uid_start, tsv_path=None, npz_path=None, why=None, critic=None, logp=None):
     """ids / scores [n_users, k] (padding id -1 dropped from the TSV); row r is uid uid_start + r; the ids are the CSV's sids.
-    why: (why_ids, why_scores) of an Explain, critic: the table() of a Critic, stored in the npz as well."""
+    why: (why_ids, why_scores) of an Explain, critic: the table() of a Critic, logp: the table() of an Explore, stored in the npz as well."""
     ids = np.asarray(ids)
     uids = np.arange(ids.shape[0], dtype=np.int64) + int(uid_start)
     if tsv_path:
@@ -163,6 +180,8 @@ def write_recs(ids, scores, uid_start, tsv_path=None, npz_path=None, why=None, c
         if critic is not None:
             extra.update(crit=np.asarray(critic["crit"], np.float32), anchor_ids=np.asarray(critic["anchor_i"], np.int32),
                          anchor_scores=np.asarray(critic["anchor_s"], np.float32), n_anchor=np.asarray(critic["n_anchor"], np.int32))
+        if logp is not None:
+            extra.update(logp=np.asarray(logp, np.float32))
         np.savez(npz_path, uids=uids, ids=ids.astype(np.int32), scores=np.asarray(scores, np.float32), **extra)
     return uids
 
@@ -185,6 +204,18 @@ def write_why(why_ids, why_scores, ids, uid_start, tsv_path):
                 n_lines += 1
                 n_reasons += int(keep.sum())
     return n_lines, n_reasons
+
+
+def write_propensities(logp, ids, uid_start, tsv_path):
+    """logp [n_users, k] (Explore.table()), ids [n_users, k] the lists it belongs to: one line per user, `uid<TAB>sid:logp,...` in list
+    order, padding left out -> lines written"""
+    logp, ids = np.asarray(logp), np.asarray(ids)
+    with open(tsv_path, "w") as f:
+        for u in range(ids.shape[0]):
+            keep = ids[u] >= 0
+            f.write("%d\t%s\n" % (int(uid_start) + u, ",".join(
+                "%d:%.6g" % (int(i), float(x)) for i, x in zip(ids[u][keep].tolist(), logp[u][keep].tolist()))))
+    return int(ids.shape[0])
 
 
 def write_critic(table, ids, uid_start, tsv_path):
@@ -250,8 +281,11 @@ def recommend(args, h0_size, h1_size, h2_size, h3_size, LEARNING_RATE, precision
     m = long_tail_summary(ids, niche, n_items, te)
     why_tab = why.table() if why is not None else None
     critic_tab = critic.table() if critic is not None else None
+    logp = rule["explore"].table() if "explore" in rule else None
     if rank == 0:
-        write_recs(ids, scores, uid0, args.out, args.npz, why=why_tab, critic=critic_tab)
+        write_recs(ids, scores, uid0, args.out, args.npz, why=why_tab, critic=critic_tab, logp=logp)
+        if logp is not None:
+            write_propensities(logp, ids, uid0, args.propensities)
     print(summary_line(m, args.k))
     ils_first = "diversify" in rule                      # the ils line stands before the why line, every other rule's line after it
     for line in rule_lines if ils_first else []:

@@ -1,6 +1,6 @@
 """Everything that serves a trained model: validation / test scoring, top-K lists (plain, with minimum slots per item group, diversified,
 calibrated to each user's history, capped in how many lists an item may appear, with a set share of all slots for some item groups,
-with a floor under how many lists an item appears in, gated by the discriminator), the long-tail report read off them, the explanation
+with a floor under how many lists an item appears in, gated by the discriminator, sampled for exploration with logged propensities), the long-tail report read off them, the explanation
 of every list entry (the user's history items nearest to it), the discriminator's critic of every niche entry, similar-item lists,
 item audiences (the k likeliest users of an item, gathered over the same chunk walk), and the set-up the CLIs (test.py, recommend.py, longtail.py, similar.py, audience.py) share.
 
@@ -863,6 +863,103 @@ class CriticGate(Rule):
         return self.stat.cpu().numpy()
 
 
+class Explore(Rule):
+    """Exploration lists, passed as `explore=` to a Recommender / ShardedRecommender: randomised exposure with logged propensities.  The
+    first `fixed` entries of a user's list are the plain top-`fixed` (log-probability 0.0); the other k - fixed are drawn without
+    replacement from the remaining eligible items in proportion to exp(logit / temperature) -- the Plackett-Luce policy -- and every entry
+    carries the log of its conditional probability given the earlier picks.  The draw is Gumbel-top-k with the counter RNG at
+    (engine seed, stream 8, draw, global user row * n_items + global item id): the same `draw` gives the same lists whatever the chunk
+    size, the slab or the rank; another `draw` gives another sample.  Per chunk: the plain top-`fixed` (if any), ltg_topk_sample,
+    ltg_topk_sample_mass, ltg_topk_sample_finish, and one plain list of k for the explored share.  Over item shards the per-slab keys
+    are gathered and merged by the SlabLists, and three small all-reduces join the mass (max of the largest eligible logit, sum of the
+    rescaled rest, max of the picks' logits): ids, scores and keys are those of the unsharded run bit for bit, logp up to the rounding of
+    the sum.  The lists keep every pick's raw logit, in draw order, so they are generally not descending; the report, the explanations and
+    the critic read them unchanged.  After run(): logp / keys [n_users, k] on the device (a head entry has key +inf), table(), stats()."""
+
+    def __init__(self, temperature, fixed=0, draw=0):
+        self.temperature = float(temperature)
+        if not (self.temperature > 0.0 and np.isfinite(self.temperature)):     # (NaN fails the comparison)
+            raise ValueError("temperature must be > 0 and finite, got %r" % (temperature,))
+        with np.errstate(over="ignore"):
+            self.inv_temp = np.float32(1.0 / self.temperature)
+        if not (self.inv_temp > 0 and np.isfinite(self.inv_temp)):
+            raise ValueError("1 / temperature is not a positive finite float32, got temperature %r" % (temperature,))
+        self.fixed, self.draw = int(fixed), int(draw)
+        if self.fixed != fixed or self.fixed < 0:
+            raise ValueError("fixed is an integer >= 0, got %r" % (fixed,))
+        if self.draw != draw or not 0 <= self.draw < 2 ** 64:
+            raise ValueError("draw is an integer >= 0, got %r" % (draw,))
+        self.k = self.logp = self.keys = self.explored = self.sampled = None
+
+    def bind(self, engine, rows, k, n_users):
+        if not 0 <= self.fixed < k:
+            raise ValueError("fixed must be in [0, k) = [0, %d), got %d" % (k, self.fixed))
+        if not 1 <= k <= 1024:
+            raise ValueError("k must be in [1, 1024], got %d" % k)
+        dev, F = engine.device, self.fixed
+        self.k = self.longest = int(k)
+        m = k - F
+        f32 = lambda n: torch.empty(n, dtype=torch.float32, device=dev)
+        i32 = lambda n: torch.empty(n, dtype=torch.int32, device=dev)
+        self.head_s, self.head_i = f32(rows * max(1, F)), i32(rows * max(1, F))
+        self.pick_key, self.pick_i, self.pick_s, self.pick_lp = f32(rows * m), i32(rows * m), f32(rows * m), f32(rows * m)
+        self.plain_s, self.plain_i = f32(rows * k), i32(rows * k)
+        self.max, self.top, self.rest = f32(rows), f32(rows), f32(rows)
+        self.logp = torch.zeros(n_users, k, dtype=torch.float32, device=dev)
+        self.keys = torch.full((n_users, k), float("inf"), dtype=torch.float32, device=dev)
+        self.explored = torch.zeros(n_users, dtype=torch.int32, device=dev)
+        self.sampled = torch.zeros(n_users, dtype=torch.int32, device=dev)
+
+    def apply(self, lists, acts, tr, n, k, lo, score_out, id_out):
+        eng, F, m, it = lists.eng, self.fixed, k - self.fixed, float(self.inv_temp)
+        v = lambda t, L: t[: n * L].view(n, L)
+        head_s, head_i = (v(self.head_s, F), v(self.head_i, F)) if F else (None, None)
+        if F:                                            # the fixed head: the plain top-F
+            lists.topk(acts, tr, n, F, head_s, head_i)
+        key, ids, sc, lp = v(self.pick_key, m), v(self.pick_i, m), v(self.pick_s, m), v(self.pick_lp, m)
+        ls, li = lists.local(n, m, key, ids)
+        eng.topk_sample(acts, tr, lo, m, it, self.draw, head_i, ls, li)
+        lists.merge(ls, li, key, ids)                    # (on the keys: a key does not depend on the slab that holds the item)
+        mx, top, rest = self.max[:n], self.top[:n], self.rest[:n]
+        eng.topk_sample_mass(acts, tr, it, head_i, ids, sc, mx, rest)
+        if lists.parts > 1:                              # the mass of the whole row from the slabs' parts
+            top.copy_(mx)
+            dist.all_reduce(top, op=dist.ReduceOp.MAX, group=lists.group)
+            rest.mul_(torch.where(torch.isinf(mx), torch.zeros_like(mx), torch.exp((mx - top) * it)))   # (a slab without an eligible item)
+            dist.all_reduce(rest, op=dist.ReduceOp.SUM, group=lists.group)
+            dist.all_reduce(sc, op=dist.ReduceOp.MAX, group=lists.group)
+        else:
+            top = mx
+        eng.topk_sample_finish(sc, top, rest, it, lp)
+        if F:
+            score_out[:, :F].copy_(head_s)
+            id_out[:, :F].copy_(head_i)
+        score_out[:, F:].copy_(sc)
+        id_out[:, F:].copy_(ids)
+        self.logp[lo:lo + n, F:].copy_(lp)
+        self.keys[lo:lo + n, F:].copy_(key)
+        # the explored share: a sampled entry is outside the plain top-k iff it comes after that list's last entry in ltg_topk's order
+        p_s, p_i = v(self.plain_s, k), v(self.plain_i, k)
+        lists.topk(acts, tr, n, k, p_s, p_i)
+        last_s, last_i = p_s[:, k - 1:k], p_i[:, k - 1:k]
+        real = ids >= 0
+        outside = real & (last_i >= 0) & ((sc < last_s) | ((sc == last_s) & (ids > last_i)))
+        self.explored[lo:lo + n].copy_(outside.sum(1))
+        self.sampled[lo:lo + n].copy_(real.sum(1))
+
+    def table(self):
+        """-> [n_users, k] float32 host array: the conditional log-probability of every entry (0.0 for the fixed head and padding)"""
+        return self.logp.cpu().numpy()
+
+    def stats(self):
+        """-> dict: mean_logp (the mean over the users of a list's log-propensity, the sum of its entries' logp), explored_share (the
+        share of the sampled slots whose item is not in the plain top-k of the same user), sampled (those slots)"""
+        lp = self.logp.sum(1, dtype=torch.float64)
+        n_s = int(self.sampled.sum())
+        return dict(mean_logp=float(lp.mean()) if lp.numel() else float("nan"),
+                    explored_share=int(self.explored.sum()) / n_s if n_s else float("nan"), sampled=n_s)
+
+
 class Audience:
     """The item audiences a Recommender / ShardedRecommender gathers when it is passed as `audience=`: for every query item (GLOBAL ids,
     any order, repeats allowed) the k users of the split with the largest score -- `logprob`: logit - lse, the log-probability the user's
@@ -945,7 +1042,7 @@ class Recommender:
     `chunk` users capped by eval_chunk_rows, the same dropout-on forward (Q3) with counter rng_step + lo per chunk, fold-in
     items excluded.  keep_prob = 1.0 gives dropout-free, deterministic recommendations.  Every list comes out of one SlabLists
     (self.lists).  At most one of rule= (MinSlots), diversify=, calibrate=, cap= (ExposureCap), share= (ShareTarget), floor=
-    (ExposureFloor) and gate= (CriticGate) decides what the lists are: it becomes self.policy, a Rule, and the walk asks it only what Rule's protocol holds;
+    (ExposureFloor), gate= (CriticGate) and explore= (Explore) decides what the lists are: it becomes self.policy, a Rule, and the walk asks it only what Rule's protocol holds;
     without one the lists are the plain top-K.  Per chunk: the forward; audience= (an Audience, audience.table() after run()) gathered
     from the logits; the lists, or with a policy over the whole split only what it gathers; then report= (a LongTailReport, k >= its
     largest cutoff), explain= (an Explain, explain.table() after run()) and critic= (a Critic, critic.table() after run()) read the chunk's
@@ -957,8 +1054,8 @@ class Recommender:
     sharded = False                                  # ShardedRecommender: one rank of `group` per item slab
 
     def __init__(self, engine, ev, k=100, chunk=20000, report=None, rule=None, diversify=None, group=None, audience=None, explain=None,
-                 calibrate=None, cap=None, share=None, floor=None, gate=None, critic=None):
-        rules = dict(rule=rule, diversify=diversify, calibrate=calibrate, cap=cap, share=share, floor=floor, gate=gate)
+                 calibrate=None, cap=None, share=None, floor=None, gate=None, critic=None, explore=None):
+        rules = dict(rule=rule, diversify=diversify, calibrate=calibrate, cap=cap, share=share, floor=floor, gate=gate, explore=explore)
         given = [name for name, r in rules.items() if r is not None]
         if len(given) > 1:
             raise ValueError("%s= cannot be combined with %s=" % (given[-1], "= or ".join(given[:-1])))
@@ -966,7 +1063,7 @@ class Recommender:
         if int(k) == 0 and (self.policy is not None or report is not None or explain is not None or critic is not None):
             raise ValueError("k = 0 serves no user lists: report=, explain= and every rule need k >= 1")
         self.rule, self.diversify, self.calibrate, self.cap, self.share, self.floor = rule, diversify, calibrate, cap, share, floor
-        self.gate, self.critic = gate, critic
+        self.gate, self.critic, self.explore = gate, critic, explore
         self.eng, self.ev, self.k, self.report, self.group, self.audience, self.explain = engine, ev, int(k), report, group, audience, explain
         if report is not None:
             report.bind(engine, ev.n, self.k)

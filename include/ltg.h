@@ -1077,6 +1077,44 @@ int ltg_topk_sample_mass(const ltg_config* cfg, const float* logits, const ltg_b
 int ltg_topk_sample_finish(int32_t n_rows, int32_t k, const float* score, const float* M, const float* rest, float inv_temp, float* logp_out,
                            ltg_stream stream);
 
+/* Replay of an exploration log (additive, ABI v14): off-policy estimates for OTHER Plackett-Luce policies from lists that were
+ * served and logged with their propensities.  A target policy is (T_p, F'): up to LTG_REPLAY_MAX_POLICIES temperatures per call, which share
+ * the fixed head F'.  inv_temp is a HOST array [n_pol] of (float)(1 / T_p); it is read during the call and travels as a kernel argument.
+ * ltg_list_mass: id_in [n_rows][k] = the LOGGED lists (GLOBAL ids, -1 = padding; the ids of a row are distinct and in [0, n_items_global):
+ * the caller's contract, not checked here).  Not eligible under the target = a fold-in item of tr, or in excl_id [n_rows][f_in] (the
+ * target's plain top-F' as ltg_topk / ltg_topk_merge wrote it; NULL with f_in = 0).  Over this slab, for every slot j >= f_in whose id the slab
+ * owns: state_out [n_rows][k] (int32) = 1 if the item is eligible, 2 if not; score_out [n_rows][k] = its raw logit if the state is 1, -inf
+ * otherwise.  Slots j < f_in, padding and ids the slab does not own get state 0 and score -inf.  max_out [n_rows] = the largest eligible
+ * logit, as in ltg_topk_sample_mass.  rest_out [n_pol][n_rows] = the sum over the eligible items that are not a state-1 entry of
+ * exp((s - max_out) * inv_temp[p]), -inf logits adding nothing: an entry without support takes no mass out.  All n_pol sums come from one
+ * walk over the row (two passes: maximum, then sums; fp32 accumulation with ltg_topk_sample_mass's term, stride and tree), so n_pol = 8 in
+ * one call equals eight calls at n_pol = 1 bit for bit, and every call is bit-identical from run to run.  No [n_rows][n_items] array is
+ * written.  Across slabs the caller forms M = max of max_out, rest_p = sum of rest_out[p] * exp((max_out - M) * inv_temp[p]), score = max
+ * of score_out, state = max of state_out.
+ * ltg_replay_rows: takes the merged values of the whole catalogue (score, state [n_rows][k], M [n_rows], rest [n_pol][n_rows]), the target's
+ * head head_id [n_rows][f_in] (NULL with f_in = 0), the log (id_in, logp0 <= 0, reward, each [n_rows][k]) and the group labels item_group
+ * (uint8 per GLOBAL item id, a label >= n_groups is in no group; 1 <= n_groups <= 8 as ltg_topk_metrics takes them).  Everything below in
+ * fp64.  A real slot j < f_in is supported iff id_in[j] == head_id[j], with logp1 = 0; a real slot j >= f_in is supported iff its state is 1,
+ * with logp1_j = x_j - log(rest_p + sum over the supported m >= j, m >= f_in of exp(x_m)), x_m = (score_m - M) * inv_temp[p].  d_j = logp1_j -
+ * logp0_j, c_j = the sum of d_m over the real slots m <= j, w_j = exp(min(c_j, log(clip))) before the first unsupported slot and 0 from it on;
+ * padding is skipped.  row_out [n_rows][n_pol][n_groups + 1][2] = (A, B) = (sum_j w_j reward_j, sum_j w_j) over the slots whose item is
+ * in group g, slot n_groups = all items; w_out [n_rows][n_pol] = w at the last real slot (0 if any slot is unsupported; exp(min(0,
+ * log(clip))) for a row of padding); first_bad_out [n_rows][n_pol] = the first unsupported slot, k if none; logp1_out (optional)
+ * [n_pol][n_rows][k] = logp1 as float, 0.0 for padding and a supported head slot, -inf for an unsupported slot.  One wave per row, no
+ * workspace, no atomics: bit-identical from run to run.  logp1 where x_j < -80 is outside the contract, as for ltg_topk_sample_finish.
+ * Both calls return LTG_EINVAL before any HIP call for: a NULL required pointer (tr, excl_id / head_id with f_in = 0, logp1_out and stream
+ * excepted), k outside [1, 1024], n_pol outside [1, 8], f_in < 0, f_in >= k, f_in > 0 without the head, an inv_temp that is not finite or
+ * <= 0, clip not finite or <= 0, n_groups outside [1, 8], n_items_global <= 0, and whatever ltg_topk refuses; n_rows = 0 returns LTG_OK and
+ * launches nothing. */
+#define LTG_REPLAY_MAX_POLICIES 8
+int ltg_list_mass(const ltg_config* cfg, const float* logits, const ltg_batch* tr, int32_t n_rows, int32_t k, const int32_t* id_in, int32_t f_in,
+                  const int32_t* excl_id, int32_t n_pol, const float* inv_temp, float* score_out, int32_t* state_out, float* max_out,
+                  float* rest_out, ltg_stream stream);
+int ltg_replay_rows(int32_t n_rows, int32_t k, int32_t n_pol, const float* inv_temp, int32_t f_in, const int32_t* head_id, const int32_t* id_in,
+                    const float* logp0, const float* reward, const float* score, const int32_t* state, const float* M, const float* rest,
+                    const uint8_t* item_group, int32_t n_groups, int32_t n_items_global, double clip, double* row_out, double* w_out,
+                    int32_t* first_bad_out, float* logp1_out, ltg_stream stream);
+
 /* Verification helper of the LTG_PREC_FP8 mode: out[i] = the value the fp8 GEMM operands carry for in[i]
  * (clamp to +-448, round to nearest-even OCP e4m3) -- lets a test pin its CPU model of the rounding to the hardware. */
 int ltg_fp8_roundtrip(const float* in, float* out, int32_t n, ltg_stream stream);

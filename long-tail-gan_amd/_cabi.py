@@ -238,6 +238,10 @@ SYMBOLS = {
     "ltg_topk_sample_mass": (C.c_int, [C.POINTER(ltg_config), vp, C.POINTER(ltg_batch), C.c_int32, C.c_int32, C.c_float, vp, C.c_int32, vp, vp,
                                        vp, vp, vp]),
     "ltg_topk_sample_finish": (C.c_int, [C.c_int32, C.c_int32, vp, vp, vp, C.c_float, vp, vp]),
+    "ltg_list_mass": (C.c_int, [C.POINTER(ltg_config), vp, C.POINTER(ltg_batch), C.c_int32, C.c_int32, vp, C.c_int32, vp, C.c_int32,
+                                C.POINTER(C.c_float), vp, vp, vp, vp, vp]),
+    "ltg_replay_rows": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                  C.c_int32, C.c_int32, C.c_double, vp, vp, vp, vp, vp]),
     "ltg_topk_diversify": (C.c_int, [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, C.c_float, C.c_int32, vp, vp, vp, vp]),
     "ltg_topk_explain": (C.c_int, [vp, C.c_int32, C.c_int32, C.POINTER(ltg_batch), C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, vp,
                                    vp, vp]),

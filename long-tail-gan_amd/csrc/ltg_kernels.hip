@@ -174,6 +174,7 @@ __global__ __launch_bounds__(64) void k_gate_set(LtgGate g, LtgGate g2 = LTG_NO_
 #include "ltg_sampler.h"
 #include "ltg_topk.h"
 #include "ltg_explore.h"
+#include "ltg_replay.h"
 #include "ltg_audience.h"
 #include "ltg_cap.h"
 #include "ltg_floor.h"
@@ -2006,6 +2007,54 @@ int ltg_topk_sample_finish(int32_t n_rows, int32_t k, const float* score, const 
     clear_errors();
     hipLaunchKernelGGL(k_topk_sample_finish, dim3((n_rows + NT / 64 - 1) / (NT / 64)), dim3(NT), 0, (hipStream_t)stream, n_rows, k, score, M, rest,
                        inv_temp, logp_out);
+    return check_launch();
+}
+
+// Replay of an exploration log.  The temperatures are a HOST array: they travel as kernel arguments.
+static_assert(RP_MAXG == LT_MAXG, "the replay groups are the report's");
+static bool replay_temps_ok(int32_t n_pol, const float* inv_temp, rp_temps* out) {
+    if (n_pol < 1 || n_pol > RP_MAXP || !inv_temp) return false;
+    for (int p = 0; p < RP_MAXP; ++p) out->v[p] = 1.f;
+    for (int p = 0; p < n_pol; ++p) {
+        if (!std::isfinite(inv_temp[p]) || !(inv_temp[p] > 0.f)) return false;
+        out->v[p] = inv_temp[p];
+    }
+    return true;
+}
+
+int ltg_list_mass(const ltg_config* cfg, const float* logits, const ltg_batch* tr, int32_t n_rows, int32_t k, const int32_t* id_in, int32_t f_in,
+                  const int32_t* excl_id, int32_t n_pol, const float* inv_temp, float* score_out, int32_t* state_out, float* max_out,
+                  float* rest_out, ltg_stream stream) {
+    size_t bits, cap;
+    rp_temps it;
+    if (!id_in || !score_out || !state_out || !max_out || !rest_out || !replay_temps_ok(n_pol, inv_temp, &it) ||
+        !explore_args_ok(cfg, logits, tr, n_rows, k, it.v[0], excl_id, f_in, &bits, &cap) || f_in >= k)
+        return LTG_EINVAL;
+    if (n_rows == 0) return LTG_OK;
+    clear_errors();
+    const bool vec = (cfg->n_items % 4) == 0 && ((uintptr_t)logits % 16) == 0;
+    auto kern = n_pol == 1 ? (vec ? k_list_mass<true, 1> : k_list_mass<false, 1>)
+                           : n_pol <= 4 ? (vec ? k_list_mass<true, 4> : k_list_mass<false, 4>) : (vec ? k_list_mass<true, 8> : k_list_mass<false, 8>);
+    hipLaunchKernelGGL(kern, dim3(n_rows), dim3(TK_NT), bits, (hipStream_t)stream, cfg->n_items, cfg->item_lo, logits,
+                       tr ? tr->indptr : (const int32_t*)nullptr, tr ? tr->indices : (const int32_t*)nullptr, n_rows, k, id_in, f_in, excl_id, n_pol,
+                       it, score_out, state_out, max_out, rest_out);
+    return check_launch();
+}
+
+int ltg_replay_rows(int32_t n_rows, int32_t k, int32_t n_pol, const float* inv_temp, int32_t f_in, const int32_t* head_id, const int32_t* id_in,
+                    const float* logp0, const float* reward, const float* score, const int32_t* state, const float* M, const float* rest,
+                    const uint8_t* item_group, int32_t n_groups, int32_t n_items_global, double clip, double* row_out, double* w_out,
+                    int32_t* first_bad_out, float* logp1_out, ltg_stream stream) {
+    rp_temps it;
+    if (!id_in || !logp0 || !reward || !score || !state || !M || !rest || !item_group || !row_out || !w_out || !first_bad_out || n_rows < 0 ||
+        k < 1 || k > 1024 || !replay_temps_ok(n_pol, inv_temp, &it) || f_in < 0 || f_in >= k || (f_in > 0 && !head_id) || !std::isfinite(clip) ||
+        !(clip > 0.0) || n_groups < 1 || n_groups > RP_MAXG || n_items_global <= 0)
+        return LTG_EINVAL;
+    if (n_rows == 0) return LTG_OK;
+    clear_errors();
+    hipLaunchKernelGGL(k_replay_rows, dim3((n_rows + NT / 64 - 1) / (NT / 64)), dim3(NT), 0, (hipStream_t)stream, n_rows, k, n_pol, it, f_in, head_id,
+                       id_in, logp0, reward, score, state, M, rest, item_group, n_groups, n_items_global, std::log(clip), row_out, w_out,
+                       first_bad_out, logp1_out);
     return check_launch();
 }
 

@@ -840,6 +840,52 @@ class Engine:
         cabi.check(self.lib.ltg_topk_sample_finish(n, k, _ptr(score), _ptr(M), _ptr(rest), float(inv_temp), _ptr(logp_out), self.stream()),
                    "ltg_topk_sample_finish")
 
+    def list_mass(self, logits_or_acts, tr, ids, excl, inv_temps, score_out, state_out, max_out, rest_out):
+        """this slab's part of the mass behind the LOGGED lists ids [rows, k] int32 under the target policies inv_temps (a host sequence of
+        up to 8 float32(1 / T)) that share the head excl [rows, f] (or None) (ltg_list_mass): state_out [rows, k] int32 1 = eligible / 2 =
+        not / 0 = head slot, padding or another slab's id; score_out [rows, k] the raw logit where the state is 1, -inf elsewhere; max_out
+        [rows] the largest eligible logit; rest_out [n_pol, rows] the sum over the eligible items that are not a state-1 entry of
+        exp((s - max_out) * inv_temp)"""
+        logits = logits_or_acts.logits if isinstance(logits_or_acts, Acts) else logits_or_acts
+        n, k = (int(x) for x in ids.shape)
+        n_pol = len(inv_temps)
+        assert logits.dtype == torch.float32 and logits.numel() >= n * self.I and tuple(score_out.shape) == tuple(state_out.shape) == (n, k)
+        assert ids.is_contiguous() and ids.dtype == torch.int32 and score_out.is_contiguous() and state_out.is_contiguous()
+        assert state_out.dtype == torch.int32 and max_out.numel() >= n and tuple(rest_out.shape) == (n_pol, n)
+        assert max_out.is_contiguous() and rest_out.is_contiguous() and max_out.dtype == rest_out.dtype == score_out.dtype == torch.float32
+        f = 0 if excl is None else int(excl.shape[1])
+        assert excl is None or (excl.dtype == torch.int32 and excl.is_contiguous() and int(excl.shape[0]) == n)
+        it = (C.c_float * max(1, n_pol))(*[float(x) for x in inv_temps])
+        cabi.check(self.lib.ltg_list_mass(C.byref(self.cfg), _ptr(logits), C.byref(tr.c) if tr is not None else None, n, k, _ptr(ids), f,
+                                          _ptr(excl) if f else None, n_pol, it, _ptr(score_out), _ptr(state_out), _ptr(max_out),
+                                          _ptr(rest_out), self.stream()), "ltg_list_mass")
+
+    def replay_rows(self, inv_temps, head, ids, logp0, reward, score, state, M, rest, labels, n_groups, clip, row_out, w_out, first_bad_out,
+                    logp1_out=None):
+        """the prefix importance weights of the logged rows ids / logp0 / reward [rows, k] under the target policies, from the merged score /
+        state [rows, k], M [rows] and rest [n_pol, rows] of the whole catalogue and the target's head [rows, f] (or None) (ltg_replay_rows):
+        row_out [rows, n_pol, n_groups + 1, 2] float64 (A, B), w_out [rows, n_pol] float64, first_bad_out [rows, n_pol] int32, logp1_out
+        (optional) [n_pol, rows, k] float32; labels uint8 per GLOBAL item id"""
+        n, k = (int(x) for x in ids.shape)
+        n_pol, g = len(inv_temps), int(n_groups)
+        for t in (ids, state):
+            assert t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == (n, k)
+        for t in (logp0, reward, score):
+            assert t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (n, k)
+        assert M.dtype == rest.dtype == torch.float32 and M.is_contiguous() and rest.is_contiguous() and M.numel() >= n
+        assert tuple(rest.shape) == (n_pol, n) and labels.dtype == torch.uint8 and labels.is_contiguous()
+        assert row_out.dtype == w_out.dtype == torch.float64 and row_out.is_contiguous() and w_out.is_contiguous()
+        assert tuple(row_out.shape) == (n, n_pol, g + 1, 2) and tuple(w_out.shape) == tuple(first_bad_out.shape) == (n, n_pol)
+        assert first_bad_out.dtype == torch.int32 and first_bad_out.is_contiguous()
+        assert logp1_out is None or (logp1_out.dtype == torch.float32 and logp1_out.is_contiguous() and tuple(logp1_out.shape) == (n_pol, n, k))
+        f = 0 if head is None else int(head.shape[1])
+        assert head is None or (head.dtype == torch.int32 and head.is_contiguous() and int(head.shape[0]) == n)
+        it = (C.c_float * max(1, n_pol))(*[float(x) for x in inv_temps])
+        cabi.check(self.lib.ltg_replay_rows(n, k, n_pol, it, f, _ptr(head) if f else None, _ptr(ids), _ptr(logp0), _ptr(reward), _ptr(score),
+                                            _ptr(state), _ptr(M), _ptr(rest), _ptr(labels), g, int(labels.numel()), float(clip),
+                                            _ptr(row_out), _ptr(w_out), _ptr(first_bad_out), _ptr(logp1_out), self.stream()),
+                   "ltg_replay_rows")
+
     def topk_quota(self, score_all, id_all, score_grp, id_grp, quota, score_out, id_out):
         """the lists with at least quota[j] entries of reserved list j: score_all / id_all [rows, k_in] plain lists, score_grp / id_grp
         [lists, rows, m_in] reserved lists (topk_groups with one bit each), quota a host sequence of `lists` counts -> [rows, k]

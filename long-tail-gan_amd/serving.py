@@ -2,7 +2,9 @@
 calibrated to each user's history, capped in how many lists an item may appear, with a set share of all slots for some item groups,
 with a floor under how many lists an item appears in, gated by the discriminator, sampled for exploration with logged propensities), the long-tail report read off them, the explanation
 of every list entry (the user's history items nearest to it), the discriminator's critic of every niche entry, similar-item lists,
-item audiences (the k likeliest users of an item, gathered over the same chunk walk), and the set-up the CLIs (test.py, recommend.py, longtail.py, similar.py, audience.py) share.
+item audiences (the k likeliest users of an item, gathered over the same chunk walk), the replay of a logged exploration run under other
+policies (off-policy estimates, from the same walk), and the set-up the CLIs (test.py, recommend.py, longtail.py, similar.py, audience.py,
+replay.py) share.
 
 One chunk walk (Recommender.run) serves every kind of list, unsharded and over item shards: the forward sits behind one method that
 ShardedRecommender overrides, and every catalogue-wide list comes from one SlabLists, which alone knows whether the catalogue is cut
@@ -960,6 +962,265 @@ class Explore(Rule):
                     explored_share=int(self.explored.sum()) / n_s if n_s else float("nan"), sampled=n_s)
 
 
+def inv_temp_of(temperature):
+    """float32(1 / T) as Explore forms it, refused where T or the result is not positive and finite"""
+    T = float(temperature)
+    if not (T > 0.0 and np.isfinite(T)):                 # (NaN fails the comparison)
+        raise ValueError("temperature must be > 0 and finite, got %r" % (temperature,))
+    with np.errstate(over="ignore"):
+        it = np.float32(1.0 / T)
+    if not (it > 0 and np.isfinite(it)):
+        raise ValueError("1 / temperature is not a positive finite float32, got temperature %r" % (temperature,))
+    return it
+
+
+class ReplayLog:
+    """An exploration log on the host: for user row r of a split the served list ids[r] (GLOBAL item ids, -1 = padding, distinct within a
+    row), logp0[r] (the log of the conditional probability with which every entry was shown, as Explore.table() gives it: <= 0, and 0.0
+    for padding and for the first `fixed` slots, the logging policy's fixed head) and reward[r] (a finite float per entry, e.g. 1.0 =
+    clicked; None until rewards_from / rewards_from_file fills it).  uids: the uid of every row where the log came from a file.  A
+    ValueError names the first row that breaks a rule."""
+
+    def __init__(self, ids, logp0, reward=None, fixed=0, n_items=None, uids=None):
+        ids, logp0 = np.asarray(ids), np.asarray(logp0)
+        if ids.ndim != 2 or logp0.shape != ids.shape:
+            raise ValueError("ids and logp0 must be [n_users, k] arrays of one shape, got %r and %r" % (ids.shape, logp0.shape))
+        self.n, self.k = int(ids.shape[0]), int(ids.shape[1])
+        if not 1 <= self.k <= 1024:
+            raise ValueError("k must be in [1, 1024], got %d" % self.k)
+        self.fixed = int(fixed)
+        if self.fixed != fixed or not 0 <= self.fixed < self.k:
+            raise ValueError("fixed must be an integer in [0, k) = [0, %d), got %r" % (self.k, fixed))
+        if not np.issubdtype(ids.dtype, np.integer):
+            raise ValueError("ids must be integers")
+        self.ids = np.ascontiguousarray(ids, dtype=np.int64)
+        self.logp0 = np.ascontiguousarray(logp0, dtype=np.float32)
+        self.n_items = None
+        self.check_ids(n_items)
+        srt = np.sort(self.ids, 1)
+        self._refuse((srt[:, 1:] == srt[:, :-1]) & (srt[:, 1:] >= 0), "holds an item twice")
+        self.ids = self.ids.astype(np.int32)
+        pad = self.ids < 0
+        with np.errstate(invalid="ignore"):
+            self._refuse(~(np.isfinite(self.logp0) & (self.logp0 <= 0)), "has a logp0 that is not finite and <= 0")
+        self._refuse(pad & (self.logp0 != 0), "has a logp0 other than 0.0 on padding")
+        self._refuse((self.logp0 != 0)[:, : self.fixed], "has a logp0 other than 0.0 in the fixed head")
+        self.uids = None if uids is None else np.asarray(uids, np.int64).reshape(-1)
+        if self.uids is not None and self.uids.size != self.n:
+            raise ValueError("uids holds %d rows, the log %d" % (self.uids.size, self.n))
+        self.reward = None
+        if reward is not None:
+            self.set_reward(reward)
+
+    @staticmethod
+    def _refuse(bad, what):
+        if bad.any():
+            raise ValueError("row %d %s" % (int(np.nonzero(bad.any(1))[0][0]), what))
+
+    def check_ids(self, n_items):
+        """ids in [0, n_items) or -1 (n_items None: >= -1 only; Replay checks against the catalogue when it is bound)"""
+        self._refuse(self.ids < -1, "has an id below -1")
+        if n_items is not None:
+            self._refuse(self.ids >= int(n_items), "has an id outside [0, %d)" % int(n_items))
+            self.n_items = int(n_items)
+
+    def set_reward(self, reward):
+        reward = np.asarray(reward)
+        if reward.shape != self.ids.shape:
+            raise ValueError("reward must be [n_users, k] = %r, got %r" % (self.ids.shape, reward.shape))
+        reward = np.ascontiguousarray(reward, dtype=np.float32)
+        self._refuse(~np.isfinite(reward), "has a reward that is not finite")
+        self.reward = reward
+        return reward
+
+    @classmethod
+    def from_npz(cls, path, reward=None, fixed=0, n_items=None):
+        """what recommend.py --explore --npz writes: uids [n], ids [n, k], logp [n, k]"""
+        z = np.load(path)
+        for name in ("uids", "ids", "logp"):
+            if name not in z.files:
+                raise ValueError("%s holds no `%s`: not the npz of recommend.py --explore" % (path, name))
+        return cls(z["ids"], z["logp"], reward=reward, fixed=fixed, n_items=n_items, uids=z["uids"])
+
+    @classmethod
+    def from_tsv(cls, path, k, reward=None, fixed=0, n_items=None):
+        """recommend.py's props.tsv: one line per user, `uid<TAB>sid:logp,...` in list order, padded here to k entries"""
+        uids, rows = [], []
+        for n_line, line in enumerate(open(path).read().splitlines()):
+            uid, _, rest = line.partition("\t")
+            cells = [c.split(":") for c in rest.split(",") if c]
+            if len(cells) > int(k) or any(len(c) != 2 for c in cells):
+                raise ValueError("%s line %d: expected at most %d fields sid:logp" % (path, n_line + 1, int(k)))
+            uids.append(int(uid))
+            rows.append(cells)
+        ids = np.full((len(rows), int(k)), -1, np.int64)
+        logp = np.zeros((len(rows), int(k)), np.float32)
+        for r, cells in enumerate(rows):
+            ids[r, : len(cells)] = [int(c[0]) for c in cells]
+            logp[r, : len(cells)] = [float(c[1]) for c in cells]
+        return cls(ids, logp, reward=reward, fixed=fixed, n_items=n_items, uids=uids)
+
+    def rewards_from(self, te):
+        """reward 1.0 where the shown item is a held-out item of the user (te: the split's held-out CSR, rows aligned with the log)"""
+        te = te.tocsr()
+        if te.shape[0] != self.n:
+            raise ValueError("the held-out rows hold %d users, the log %d" % (te.shape[0], self.n))
+        y = np.zeros(self.ids.shape, np.float32)
+        for r in range(self.n):
+            y[r] = np.isin(self.ids[r], te.indices[te.indptr[r]:te.indptr[r + 1]])
+        return self.set_reward(y)
+
+    def rewards_from_file(self, path, uid_start=None):
+        """lines `uid<TAB>sid[,sid...]`: reward 1.0 for the listed items of that user; a user without a line has none.  The uid of row r
+        is uids[r] where the log has them, else uid_start + r"""
+        if self.uids is None and uid_start is None:
+            raise ValueError("the log has no uids: pass uid_start")
+        uids = self.uids if self.uids is not None else np.arange(self.n, dtype=np.int64) + int(uid_start)
+        row_of = {int(u): r for r, u in enumerate(uids.tolist())}
+        y = np.zeros(self.ids.shape, np.float32)
+        for n_line, line in enumerate(open(path).read().splitlines()):
+            if not line.strip():
+                continue
+            uid, _, rest = line.partition("\t")
+            try:
+                u, sids = int(uid), [int(x) for x in rest.split(",") if x.strip()]
+            except ValueError:
+                raise ValueError("%s line %d: expected uid<TAB>sid[,sid...]" % (path, n_line + 1)) from None
+            if u in row_of:
+                y[row_of[u]] = np.maximum(y[row_of[u]], np.isin(self.ids[row_of[u]], sids))
+        return self.set_reward(y)
+
+
+class Replay:
+    """Off-policy estimates from an exploration log, passed as `replay=` to a Recommender / ShardedRecommender: what the
+    logged rewards would have been under the Plackett-Luce policies at `temperatures` (at most 8) behind a fixed head of `fixed` entries
+    (default: the log's; a head shorter than the log's is refused, the log has no support there), under THIS model.  It reads the logits
+    only, so it goes beside any rule and with k = 0.  Per chunk: the target's plain top-`fixed` through the SlabLists (if any),
+    ltg_list_mass on the logged lists of the chunk's users, over item shards four small all-reduces (max of the largest eligible logit,
+    sum of the rescaled rest, max of the entries' logits, max of their states), and ltg_replay_rows into the tables of the whole split.
+    The walk must be the one the log was made with: the same split, keep_prob and RNG step (keep_prob = 1.0 on both sides is the safe
+    choice).  labels / n_groups: the item groups of a LongTailReport (None: one group holding every item).  After run(): table(),
+    logp1 (with keep_logp1=True) and estimates().  Over item shards every rank ends with the same tables."""
+
+    MAX_POLICIES = 8                                  # LTG_REPLAY_MAX_POLICIES
+
+    def __init__(self, log, temperatures, fixed=None, clip=100.0, labels=None, n_groups=None, keep_logp1=False):
+        if log.reward is None:
+            raise ValueError("the log has no rewards: rewards_from / rewards_from_file / set_reward first")
+        self.log = log
+        self.temperatures = [float(t) for t in np.atleast_1d(np.asarray(temperatures, dtype=np.float64)).tolist()]
+        if not 1 <= len(self.temperatures) <= self.MAX_POLICIES:
+            raise ValueError("between 1 and %d temperatures, got %d" % (self.MAX_POLICIES, len(self.temperatures)))
+        self.inv_temps = [inv_temp_of(t) for t in self.temperatures]
+        self.fixed = log.fixed if fixed is None else int(fixed)
+        if (fixed is not None and self.fixed != fixed) or not log.fixed <= self.fixed < log.k:
+            raise ValueError("fixed must be an integer in [the log's head, k) = [%d, %d), got %r: below the logging head the log has no "
+                             "support" % (log.fixed, log.k, fixed))
+        self.clip = float(clip)
+        if not (self.clip > 0.0 and np.isfinite(self.clip)):
+            raise ValueError("clip must be > 0 and finite, got %r" % (clip,))
+        if labels is None:
+            if n_groups is not None:
+                raise ValueError("n_groups needs labels")
+            self.labels_host, self.n_groups = None, 1
+        else:
+            self.n_groups = int(n_groups) if n_groups is not None else int(np.asarray(labels).max()) + 1
+            self.labels_host = group_labels(labels, self.n_groups)
+        self.keep_logp1 = bool(keep_logp1)
+        self.group, self.sharded = None, False
+        self.rows = self.w = self.first_bad = self.logp1 = self.state = self.score = self.top = None
+
+    def bind(self, engine, rows, n_users, group=None, sharded=False):
+        log, dev, P, G = self.log, engine.device, len(self.inv_temps), self.n_groups
+        if log.n != n_users:
+            raise ValueError("the log holds %d users, the split %d" % (log.n, n_users))
+        log.check_ids(engine.I_global)
+        self.group, self.sharded = group, bool(sharded)
+        k, F = log.k, self.fixed
+        labels = self.labels_host if self.labels_host is not None else np.zeros(engine.I_global, np.uint8)
+        self.labels = group_labels(labels, G, engine)
+        to = lambda a: torch.from_numpy(a).to(dev)
+        self.ids_d, self.logp0_d, self.reward_d = to(log.ids), to(log.logp0), to(log.reward)
+        f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+        self.head_s, self.head_i = f32(rows * max(1, F)), torch.empty(rows * max(1, F), dtype=torch.int32, device=dev)
+        self.max, self.rest, self.scale = f32(rows), f32(P * rows), f32(rows)
+        self.score = f32(n_users, k)
+        self.state = torch.zeros(n_users, k, dtype=torch.int32, device=dev)
+        self.top = f32(n_users)
+        self.rows = torch.zeros(n_users, P, G + 1, 2, dtype=torch.float64, device=dev)
+        self.w = torch.zeros(n_users, P, dtype=torch.float64, device=dev)
+        self.first_bad = torch.zeros(n_users, P, dtype=torch.int32, device=dev)
+        self.logp1 = f32(P, n_users, k) if self.keep_logp1 else None
+        self.lp1_chunk = f32(P * rows * k) if self.keep_logp1 else None
+
+    def add(self, lists, acts, tr, n, lo):
+        """users lo .. lo + n, whose logits `acts` holds, into the tables"""
+        eng, F, k, P = lists.eng, self.fixed, self.log.k, len(self.inv_temps)
+        head_i = None
+        if F:                                            # the target's head: the plain top-F'
+            head_s, head_i = self.head_s[: n * F].view(n, F), self.head_i[: n * F].view(n, F)
+            lists.topk(acts, tr, n, F, head_s, head_i)
+        ids, sc, st = self.ids_d[lo:lo + n], self.score[lo:lo + n], self.state[lo:lo + n]
+        mx, rest = self.max[:n], self.rest[: P * n].view(P, n)
+        eng.list_mass(acts, tr, ids, head_i, self.inv_temps, sc, st, mx, rest)
+        top = self.top[lo:lo + n]
+        top.copy_(mx)
+        if lists.parts > 1:                              # the mass of the whole row from the slabs' parts
+            dist.all_reduce(top, op=dist.ReduceOp.MAX, group=lists.group)
+            for p, it in enumerate(self.inv_temps):
+                rest[p].mul_(torch.where(torch.isinf(mx), torch.zeros_like(mx), torch.exp((mx - top) * float(it))))   # (a slab without an eligible item)
+            dist.all_reduce(rest, op=dist.ReduceOp.SUM, group=lists.group)
+            dist.all_reduce(sc, op=dist.ReduceOp.MAX, group=lists.group)
+            dist.all_reduce(st, op=dist.ReduceOp.MAX, group=lists.group)
+        lp1 = self.lp1_chunk[: P * n * k].view(P, n, k) if self.keep_logp1 else None
+        eng.replay_rows(self.inv_temps, head_i, ids, self.logp0_d[lo:lo + n], self.reward_d[lo:lo + n], sc, st, top, rest, self.labels,
+                        self.n_groups, self.clip, self.rows[lo:lo + n], self.w[lo:lo + n], self.first_bad[lo:lo + n], lp1)
+        if lp1 is not None:
+            self.logp1[:, lo:lo + n].copy_(lp1)
+
+    def table(self):
+        """-> dict of host arrays: rows [n_users, n_pol, n_groups + 1, 2] float64 (A, B; slot n_groups = all items), w [n_users, n_pol]
+        float64, first_bad [n_users, n_pol] int32, state / score [n_users, k], M [n_users]; logp1 [n_pol, n_users, k] with keep_logp1"""
+        out = dict(rows=self.rows.cpu().numpy(), w=self.w.cpu().numpy(), first_bad=self.first_bad.cpu().numpy(),
+                   state=self.state.cpu().numpy(), score=self.score.cpu().numpy(), M=self.top.cpu().numpy())
+        if self.logp1 is not None:
+            out["logp1"] = self.logp1.cpu().numpy()
+        return out
+
+    def estimates(self, names=None):
+        """-> {temperature: {group: dict(ips, stderr, snips, exposure, logged, logged_per_slot), ..., "ess", "supported", "n_users"}},
+        group = names[g] (default the group's index) and "all"; on the host in float64 over the per-row table of the whole split"""
+        t = self.table()
+        return replay_estimates(t["rows"], t["w"], t["first_bad"], self.log, self.temperatures, self.labels_host, self.n_groups, names)
+
+
+def replay_estimates(rows, w, first_bad, log, temperatures, labels, n_groups, names=None):
+    """the figures of DESIGN 5.22 from the per-row table (Replay.table(), or the numpy reference's): see Replay.estimates"""
+    rows, w = np.asarray(rows, np.float64), np.asarray(w, np.float64)
+    n, k, G = log.n, log.k, int(n_groups)
+    names = [str(g) for g in range(G)] if names is None else list(names)
+    real = log.ids >= 0
+    lab = (np.zeros(log.ids.shape, np.int64) if labels is None else np.asarray(labels)[np.where(real, log.ids, 0)].astype(np.int64))
+    y = log.reward.astype(np.float64)
+    div = lambda a, b: float(a / b) if b else float("nan")
+    out = {}
+    for p, T in enumerate(temperatures):
+        res = {}
+        for g, name in enumerate(names + ["all"]):
+            A, B = rows[:, p, g, 0], rows[:, p, g, 1]
+            mean = div(A.sum(), n)
+            var = (float((A * A).sum()) / n - mean * mean) * n / (n - 1) if n > 1 else float("nan")
+            in_g = real & ((lab == g) | (g == G))
+            res[name] = dict(ips=mean, stderr=float(np.sqrt(max(var, 0.0) / n)) if n > 1 else float("nan"), snips=div(A.sum(), B.sum()),
+                             exposure=div(B.sum(), n), logged=div(y[in_g].sum(), n), logged_per_slot=div(y[in_g].sum(), int(in_g.sum())))
+        W = w[:, p]
+        res["ess"] = div(W.sum() ** 2, (W * W).sum())
+        res["supported"] = div(int((np.asarray(first_bad)[:, p] == k).sum()), n)
+        res["n_users"] = n
+        out[T] = res
+    return out
+
+
 class Audience:
     """The item audiences a Recommender / ShardedRecommender gathers when it is passed as `audience=`: for every query item (GLOBAL ids,
     any order, repeats allowed) the k users of the split with the largest score -- `logprob`: logit - lse, the log-probability the user's
@@ -1049,12 +1310,13 @@ class Recommender:
     final lists.  A policy over the whole split
     matches after the last chunk, and a second pass over the chunks (no forward) feeds the report and the explanations.  k = 0 walks the
     chunks for the audience alone: run() returns [n_users, 0] arrays, no list kernel is launched, and nothing that needs lists goes
-    with it."""
+    with it.  replay= (a Replay, replay.estimates() after run()) re-weights a logged exploration run under other policies from the
+    chunk's logits; like the audience it changes no list and works with k = 0."""
 
     sharded = False                                  # ShardedRecommender: one rank of `group` per item slab
 
     def __init__(self, engine, ev, k=100, chunk=20000, report=None, rule=None, diversify=None, group=None, audience=None, explain=None,
-                 calibrate=None, cap=None, share=None, floor=None, gate=None, critic=None, explore=None):
+                 calibrate=None, cap=None, share=None, floor=None, gate=None, critic=None, explore=None, replay=None):
         rules = dict(rule=rule, diversify=diversify, calibrate=calibrate, cap=cap, share=share, floor=floor, gate=gate, explore=explore)
         given = [name for name, r in rules.items() if r is not None]
         if len(given) > 1:
@@ -1063,7 +1325,7 @@ class Recommender:
         if int(k) == 0 and (self.policy is not None or report is not None or explain is not None or critic is not None):
             raise ValueError("k = 0 serves no user lists: report=, explain= and every rule need k >= 1")
         self.rule, self.diversify, self.calibrate, self.cap, self.share, self.floor = rule, diversify, calibrate, cap, share, floor
-        self.gate, self.critic, self.explore = gate, critic, explore
+        self.gate, self.critic, self.explore, self.replay = gate, critic, explore, replay
         self.eng, self.ev, self.k, self.report, self.group, self.audience, self.explain = engine, ev, int(k), report, group, audience, explain
         if report is not None:
             report.bind(engine, ev.n, self.k)
@@ -1078,6 +1340,9 @@ class Recommender:
         if critic is not None:
             critic.bind(engine, self.chunk, self.k, ev.n)
             longest = max(longest, critic.top)                       # (its per-slab best anchors are [rows * top, 1])
+        if replay is not None:
+            replay.bind(engine, self.chunk, ev.n, group=group, sharded=self.sharded)
+            longest = max(longest, replay.fixed)                     # (the target's head)
         self.lists = SlabLists(engine, self.chunk, longest, group, dist.get_world_size(group) if self.sharded else 1)
         if audience is not None:
             audience.bind(engine, self.chunk, ev.n, group=group, sharded=self.sharded)
@@ -1120,6 +1385,8 @@ class Recommender:
             self._forward(tr, n, keep_prob, rng_step + lo)
             if self.audience is not None:
                 self.audience.add(eng, self.acts, tr, n, lo)
+            if self.replay is not None:
+                self.replay.add(self.lists, self.acts, tr, n, lo)
             if k == 0:                                   # no user lists: the walk serves the audience alone
                 continue
             if policy is not None and policy.whole:      # the lists depend on every chunk: only what the rule gathers now

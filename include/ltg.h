@@ -1115,6 +1115,41 @@ int ltg_replay_rows(int32_t n_rows, int32_t k, int32_t n_pol, const float* inv_t
                     const uint8_t* item_group, int32_t n_groups, int32_t n_items_global, double clip, double* row_out, double* w_out,
                     int32_t* first_bad_out, float* logp1_out, ltg_stream stream);
 
+/* Posterior-aware scores (additive, ABI v14): lists ranked by the VAE's own uncertainty.  S = n_samples in {1, 4, 8, 16, 32}
+ * samples of z are drawn from the encoder's posterior of every user row, pushed through the decoder, and reduced per (user, item) to
+ * mean, std (population, two-pass) and score = fmaf(beta, std, mean): beta = 0 the posterior mean, beta > 0 UCB, beta < 0 LCB, S = 1 one
+ * Thompson draw (std = 0, score = the sample's logit; beta must be 0).  The [n_rows * S][n_items] logits are never written anywhere.
+ * ltg_posterior_ld: bf16 elements per image row = h_enc rounded up to 32 (608 at 600); 0 for a cfg the calls refuse.
+ * ltg_posterior_image_bytes: the size of the image of n_rows rows; 0 for what the calls refuse.
+ * ltg_posterior_h2: sample s of row r: z = mu + expf(0.5f * logvar) * e from mulv [n_rows][2Z] (mu | logvar, as ltg_gen_acts.mulv holds
+ * them); e = eps[r][s][j] if eps is given, else the counter RNG's normal at (cfg->seed, stream 9, draw, ((row_lo + r) * S + s) * Z + j) -- a
+ * pure function of the seed, the draw, the GLOBAL row, the sample and the column, whatever chunk, row block or rank holds the row.  Then
+ * h2 = tanhf(z . W_p0 + b_p0) in fp32 (gen->p[2], gen->p[6]; one fmaf chain over Z in ascending order), rounded to nearest even into bf16
+ * at image row r * S + s; columns [h_enc, ld) are written as zeros.  z_out (optional) [n_rows * S][Z] receives z.  One kernel.
+ * ltg_posterior_scores: l[r][s][i] = image[r * S + s] . bf16(W_p1t[i]) + b_p1[i] on v_mfma_f32_16x16x32_bf16 with fp32 accumulation.  The
+ * operands are bf16 WHATEVER cfg->precision is.  W_p1t comes from gen->wp1t_bf16 when present (and h_enc <= 608), otherwise gen->p[3] is
+ * rounded on the fly: the same operand values, the same result bit for bit.  score_out [n_rows][cfg->n_items] = fmaf(beta, std, mean);
+ * spread_out (optional, same shape) = std.  An element's bits depend on no tile, workgroup, segment or slab: one MFMA chain over K in
+ * ascending order and one balanced tree over the sample index, no atomics; the slab [lo, hi) of a catalogue gives the whole call's columns
+ * bit for bit, and every call is bit-identical from run to run.  image must be 16-byte aligned.
+ * ltg_posterior_entries: mean_out / std_out [n_rows][k] = the same mean and std for the entries id_in [n_rows][k] (GLOBAL ids) gathered from
+ * the same image, one wave per entry (another K order: equal to ltg_posterior_scores up to fp32 rounding).  An id outside the slab
+ * [cfg->item_lo, cfg->item_lo + cfg->n_items) and padding (-1) get 0.0f in both, so item shards add up under a sum all-reduce.
+ * ltg_row_lse: lse_out [n_rows] = the log-sum-exp of every row of logits [n_rows][cfg->n_items], the kernel ltg_vae_forward runs.
+ * All return LTG_EINVAL before any HIP call for: a NULL required pointer (eps, z_out, spread_out and stream excepted), n_samples outside the
+ * set, beta not finite, n_samples == 1 with beta != 0, row_lo < 0, n_rows < 0, n_rows * n_samples >= 2^31, k outside [1, 1024], an image
+ * that is not 16-byte aligned, n_samples * z_dim * 4 > 64 KiB, a bad cfg.  n_rows == 0 returns LTG_OK and launches nothing. */
+#define LTG_POST_MAX_SAMPLES 32
+int32_t ltg_posterior_ld(const ltg_config* cfg);
+size_t ltg_posterior_image_bytes(const ltg_config* cfg, int32_t n_rows, int32_t n_samples);
+int ltg_posterior_h2(const ltg_config* cfg, const ltg_gen_state* gen, const float* mulv, int32_t n_rows, int32_t row_lo, int32_t n_samples,
+                     uint64_t draw, const float* eps, uint16_t* image_out, float* z_out, ltg_stream stream);
+int ltg_posterior_scores(const ltg_config* cfg, const ltg_gen_state* gen, const uint16_t* image, int32_t n_rows, int32_t n_samples, float beta,
+                         float* score_out, float* spread_out, ltg_stream stream);
+int ltg_posterior_entries(const ltg_config* cfg, const ltg_gen_state* gen, const uint16_t* image, int32_t n_rows, int32_t n_samples,
+                          const int32_t* id_in, int32_t k, float* mean_out, float* std_out, ltg_stream stream);
+int ltg_row_lse(const ltg_config* cfg, const float* logits, int32_t n_rows, float* lse_out, ltg_stream stream);
+
 /* Verification helper of the LTG_PREC_FP8 mode: out[i] = the value the fp8 GEMM operands carry for in[i]
  * (clamp to +-448, round to nearest-even OCP e4m3) -- lets a test pin its CPU model of the rounding to the hardware. */
 int ltg_fp8_roundtrip(const float* in, float* out, int32_t n, ltg_stream stream);

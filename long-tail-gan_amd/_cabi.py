@@ -242,6 +242,13 @@ SYMBOLS = {
                                 C.POINTER(C.c_float), vp, vp, vp, vp, vp]),
     "ltg_replay_rows": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                   C.c_int32, C.c_int32, C.c_double, vp, vp, vp, vp, vp]),
+    "ltg_posterior_ld": (C.c_int32, [C.POINTER(ltg_config)]),
+    "ltg_posterior_image_bytes": (C.c_size_t, [C.POINTER(ltg_config), C.c_int32, C.c_int32]),
+    "ltg_posterior_h2": (C.c_int, [C.POINTER(ltg_config), C.POINTER(ltg_gen_state), vp, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, vp, vp, vp,
+                                   vp]),
+    "ltg_posterior_scores": (C.c_int, [C.POINTER(ltg_config), C.POINTER(ltg_gen_state), vp, C.c_int32, C.c_int32, C.c_float, vp, vp, vp]),
+    "ltg_posterior_entries": (C.c_int, [C.POINTER(ltg_config), C.POINTER(ltg_gen_state), vp, C.c_int32, C.c_int32, vp, C.c_int32, vp, vp, vp]),
+    "ltg_row_lse": (C.c_int, [C.POINTER(ltg_config), vp, C.c_int32, vp, vp]),
     "ltg_topk_diversify": (C.c_int, [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, C.c_float, C.c_int32, vp, vp, vp, vp]),
     "ltg_topk_explain": (C.c_int, [vp, C.c_int32, C.c_int32, C.POINTER(ltg_batch), C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, vp,
                                    vp, vp]),

@@ -174,6 +174,7 @@ __global__ __launch_bounds__(64) void k_gate_set(LtgGate g, LtgGate g2 = LTG_NO_
 #include "ltg_sampler.h"
 #include "ltg_topk.h"
 #include "ltg_explore.h"
+#include "ltg_posterior.h"
 #include "ltg_replay.h"
 #include "ltg_audience.h"
 #include "ltg_cap.h"
@@ -2007,6 +2008,99 @@ int ltg_topk_sample_finish(int32_t n_rows, int32_t k, const float* score, const 
     clear_errors();
     hipLaunchKernelGGL(k_topk_sample_finish, dim3((n_rows + NT / 64 - 1) / (NT / 64)), dim3(NT), 0, (hipStream_t)stream, n_rows, k, score, M, rest,
                        inv_temp, logp_out);
+    return check_launch();
+}
+
+// Posterior-aware scores.  Every refusal comes before the first HIP call.
+static bool post_samples_ok(int32_t s) { return s == 1 || s == 4 || s == 8 || s == 16 || s == 32; }
+static bool post_args_ok(const ltg_config* cfg, const ltg_gen_state* gen, const uint16_t* image, int32_t n_rows, int32_t n_samples) {
+    return cfg_ok(cfg) && cfg->item_lo >= 0 && gen && gen->p[3] && gen->p[7] && image && ((uintptr_t)image % 16) == 0 && n_rows >= 0 &&
+           post_samples_ok(n_samples) && (int64_t)n_rows * n_samples < (int64_t)1 << 31;
+}
+
+int32_t ltg_posterior_ld(const ltg_config* cfg) { return cfg_ok(cfg) ? (cfg->h_enc + 31) / 32 * 32 : 0; }
+
+size_t ltg_posterior_image_bytes(const ltg_config* cfg, int32_t n_rows, int32_t n_samples) {
+    if (!cfg_ok(cfg) || n_rows < 0 || !post_samples_ok(n_samples) || (int64_t)n_rows * n_samples >= (int64_t)1 << 31) return 0;
+    return (size_t)n_rows * n_samples * ltg_posterior_ld(cfg) * sizeof(uint16_t);
+}
+
+int ltg_posterior_h2(const ltg_config* cfg, const ltg_gen_state* gen, const float* mulv, int32_t n_rows, int32_t row_lo, int32_t n_samples,
+                     uint64_t draw, const float* eps, uint16_t* image_out, float* z_out, ltg_stream stream) {
+    if (!cfg_ok(cfg) || !gen || !gen->p[2] || !gen->p[6] || !mulv || !image_out || n_rows < 0 || row_lo < 0 || !post_samples_ok(n_samples) ||
+        (int64_t)n_rows * n_samples >= (int64_t)1 << 31)
+        return LTG_EINVAL;
+    const size_t lds = (size_t)n_samples * cfg->z_dim * sizeof(float);
+    if (lds > 64 * 1024) return LTG_EINVAL;
+    if (n_rows == 0) return LTG_OK;
+    clear_errors();
+#define LTG_POST_H2(SV)                                                                                                                   \
+    hipLaunchKernelGGL(k_post_h2<SV>, dim3(n_rows), dim3(PO_NT), lds, (hipStream_t)stream, cfg->z_dim, cfg->h_enc, ltg_posterior_ld(cfg), \
+                       mulv, eps, cfg->seed, draw, row_lo, gen->p[2], gen->p[6], image_out, z_out)
+    switch (n_samples) {
+        case 1: LTG_POST_H2(1); break;
+        case 4: LTG_POST_H2(4); break;
+        case 8: LTG_POST_H2(8); break;
+        case 16: LTG_POST_H2(16); break;
+        default: LTG_POST_H2(32); break;
+    }
+#undef LTG_POST_H2
+    return check_launch();
+}
+
+int ltg_posterior_scores(const ltg_config* cfg, const ltg_gen_state* gen, const uint16_t* image, int32_t n_rows, int32_t n_samples, float beta,
+                         float* score_out, float* spread_out, ltg_stream stream) {
+    if (!post_args_ok(cfg, gen, image, n_rows, n_samples) || !score_out || !std::isfinite(beta) || (n_samples == 1 && beta != 0.f))
+        return LTG_EINVAL;
+    if (n_rows == 0) return LTG_OK;
+    const int M = n_rows * n_samples, I = cfg->n_items, ld = ltg_posterior_ld(cfg);
+    // item segments: enough workgroups to fill the chip when the row blocks alone do not
+    const int rb = (M + PO_ROWS - 1) / PO_ROWS, steps = (I + PO_STEP - 1) / PO_STEP;
+    int nseg = rb >= 1024 ? 1 : (1024 + rb - 1) / rb;
+    if (nseg > steps) nseg = steps;
+    const int seg_len = (steps + nseg - 1) / nseg * PO_STEP;
+    nseg = (I + seg_len - 1) / seg_len;
+    const size_t lds = (size_t)(ld / 32) * PO_RT * 64 * 16;
+    const bool shadow = gen->wp1t_bf16 != nullptr && cfg->h_enc <= ST_KP;
+    clear_errors();
+#define LTG_POST_SC(SV, SH)                                                                                                           \
+    hipLaunchKernelGGL((k_post_scores<SV, SH>), dim3(rb, nseg), dim3(PO_NT), lds, (hipStream_t)stream, M, I, cfg->h_enc, ld, seg_len, image, \
+                       gen->wp1t_bf16, gen->p[3], gen->p[7], beta, score_out, spread_out)
+#define LTG_POST_SC_S(SV)                                            \
+    do {                                                             \
+        if (shadow) LTG_POST_SC(SV, true); else LTG_POST_SC(SV, false); \
+    } while (0)
+    switch (n_samples) {
+        case 1: LTG_POST_SC_S(1); break;
+        case 4: LTG_POST_SC_S(4); break;
+        case 8: LTG_POST_SC_S(8); break;
+        case 16: LTG_POST_SC_S(16); break;
+        default: LTG_POST_SC_S(32); break;
+    }
+#undef LTG_POST_SC_S
+#undef LTG_POST_SC
+    return check_launch();
+}
+
+int ltg_posterior_entries(const ltg_config* cfg, const ltg_gen_state* gen, const uint16_t* image, int32_t n_rows, int32_t n_samples,
+                          const int32_t* id_in, int32_t k, float* mean_out, float* std_out, ltg_stream stream) {
+    if (!post_args_ok(cfg, gen, image, n_rows, n_samples) || !id_in || !mean_out || !std_out || k < 1 || k > 1024) return LTG_EINVAL;
+    if (n_rows == 0) return LTG_OK;
+    const int64_t n_ent = (int64_t)n_rows * k;
+    if (n_ent >= (int64_t)1 << 31) return LTG_EINVAL;
+    const bool shadow = gen->wp1t_bf16 != nullptr && cfg->h_enc <= ST_KP;
+    clear_errors();
+    hipLaunchKernelGGL(shadow ? k_post_entries<true> : k_post_entries<false>, dim3((unsigned)((n_ent + PO_NT / 64 - 1) / (PO_NT / 64))), dim3(PO_NT),
+                       0, (hipStream_t)stream, (int)n_ent, k, n_samples, cfg->n_items, cfg->h_enc, ltg_posterior_ld(cfg), cfg->item_lo, image,
+                       gen->wp1t_bf16, gen->p[3], gen->p[7], id_in, mean_out, std_out);
+    return check_launch();
+}
+
+int ltg_row_lse(const ltg_config* cfg, const float* logits, int32_t n_rows, float* lse_out, ltg_stream stream) {
+    if (!cfg_ok(cfg) || !logits || !lse_out || n_rows < 0) return LTG_EINVAL;
+    if (n_rows == 0) return LTG_OK;
+    clear_errors();
+    hipLaunchKernelGGL(k_row_lse, dim3(n_rows), dim3(NT), 0, (hipStream_t)stream, cfg->n_items, logits, lse_out);
     return check_launch();
 }
 

@@ -13,6 +13,7 @@
 #define LTG_STREAM_GUMBEL 6
 #define LTG_STREAM_POP_PICK 7
 #define LTG_STREAM_SERVE_GUMBEL 8
+#define LTG_STREAM_POSTERIOR_EPS 9
 
 __device__ __forceinline__ uint64_t ltg_rng_u64(uint64_t seed, uint32_t stream, uint64_t step, uint64_t idx) {
     uint64_t z = (seed ^ ((uint64_t)stream * 0xD6E8FEB86659FD93ull)) + step * 0x94D049BB133111EBull;

@@ -840,6 +840,55 @@ class Engine:
         cabi.check(self.lib.ltg_topk_sample_finish(n, k, _ptr(score), _ptr(M), _ptr(rest), float(inv_temp), _ptr(logp_out), self.stream()),
                    "ltg_topk_sample_finish")
 
+    def posterior_ld(self):
+        """bf16 elements per row of a posterior image (ltg_posterior_ld): H rounded up to 32"""
+        return int(self.lib.ltg_posterior_ld(C.byref(self.cfg)))
+
+    def posterior_image(self, rows, samples):
+        """-> an image buffer [rows * samples, posterior_ld()] int16 (bf16 bits) on the engine's device"""
+        nbytes = int(self.lib.ltg_posterior_image_bytes(C.byref(self.cfg), int(rows), int(samples)))
+        if nbytes == 0 and rows > 0:
+            raise ValueError("no posterior image for %r rows of %r samples (samples in {1, 4, 8, 16, 32})" % (rows, samples))
+        return torch.empty(int(rows) * int(samples), self.posterior_ld(), dtype=torch.int16, device=self.device)
+
+    def posterior_h2(self, mulv, n, row_lo, samples, draw, image_out, eps=None, z_out=None):
+        """image_out [n * samples, ld] <- bf16(tanh(dec-0)) of `samples` draws of z from the posterior of each of the first n rows of mulv
+        [rows, 2Z] (ltg_posterior_h2).  row_lo: the GLOBAL row of the first row; draw: the counter of the draw; eps: injected noise
+        [n, samples, Z] (tests), the counter RNG otherwise; z_out: [n * samples, Z] receives z"""
+        n, S = int(n), int(samples)
+        assert mulv.dtype == torch.float32 and mulv.is_contiguous() and mulv.numel() >= n * 2 * self.Z
+        assert image_out.dtype == torch.int16 and image_out.is_contiguous() and image_out.numel() >= n * S * self.posterior_ld()
+        assert eps is None or (eps.dtype == torch.float32 and eps.is_contiguous() and eps.numel() >= n * S * self.Z)
+        assert z_out is None or (z_out.dtype == torch.float32 and z_out.is_contiguous() and z_out.numel() >= n * S * self.Z)
+        cabi.check(self.lib.ltg_posterior_h2(C.byref(self.cfg), C.byref(self.gen_c), _ptr(mulv), n, int(row_lo), S, int(draw), _ptr(eps),
+                                             _ptr(image_out), _ptr(z_out), self.stream()), "ltg_posterior_h2")
+
+    def posterior_scores(self, image, n, samples, beta, score_out, spread_out=None):
+        """score_out [n, I] <- mean + beta * std over the samples of this slab's logits, from the image posterior_h2 wrote
+        (ltg_posterior_scores; bf16 operands whatever the engine's precision); spread_out [n, I] receives std"""
+        n, S = int(n), int(samples)
+        assert image.dtype == torch.int16 and image.is_contiguous() and image.numel() >= n * S * self.posterior_ld()
+        assert score_out.dtype == torch.float32 and score_out.is_contiguous() and score_out.numel() >= n * self.I
+        assert spread_out is None or (spread_out.dtype == torch.float32 and spread_out.is_contiguous() and spread_out.numel() >= n * self.I)
+        cabi.check(self.lib.ltg_posterior_scores(C.byref(self.cfg), C.byref(self.gen_c), _ptr(image), n, S, float(beta), _ptr(score_out),
+                                                 _ptr(spread_out), self.stream()), "ltg_posterior_scores")
+
+    def posterior_entries(self, image, samples, ids, mean_out, std_out):
+        """mean_out / std_out [n, k] <- the posterior mean and std of the entries ids [n, k] int32 (GLOBAL ids), from the same image
+        (ltg_posterior_entries); an id outside this slab and padding give 0.0 in both"""
+        n, k = (int(x) for x in ids.shape)
+        assert image.dtype == torch.int16 and image.is_contiguous() and image.numel() >= n * int(samples) * self.posterior_ld()
+        assert ids.dtype == torch.int32 and ids.is_contiguous() and tuple(mean_out.shape) == tuple(std_out.shape) == (n, k)
+        assert all(t.is_contiguous() and t.dtype == torch.float32 for t in (mean_out, std_out))
+        cabi.check(self.lib.ltg_posterior_entries(C.byref(self.cfg), C.byref(self.gen_c), _ptr(image), n, int(samples), _ptr(ids), k,
+                                                  _ptr(mean_out), _ptr(std_out), self.stream()), "ltg_posterior_entries")
+
+    def row_lse(self, logits, n, lse_out):
+        """lse_out [n] <- the log-sum-exp of each of the first n rows of logits [rows, I] (ltg_row_lse)"""
+        assert logits.dtype == torch.float32 and logits.is_contiguous() and logits.numel() >= int(n) * self.I
+        assert lse_out.dtype == torch.float32 and lse_out.is_contiguous() and lse_out.numel() >= int(n)
+        cabi.check(self.lib.ltg_row_lse(C.byref(self.cfg), _ptr(logits), int(n), _ptr(lse_out), self.stream()), "ltg_row_lse")
+
     def list_mass(self, logits_or_acts, tr, ids, excl, inv_temps, score_out, state_out, max_out, rest_out):
         """this slab's part of the mass behind the LOGGED lists ids [rows, k] int32 under the target policies inv_temps (a host sequence of
         up to 8 float32(1 / T)) that share the head excl [rows, f] (or None) (ltg_list_mass): state_out [rows, k] int32 1 = eligible / 2 =

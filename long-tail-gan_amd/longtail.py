@@ -7,6 +7,7 @@
         [--cap C|NAME:C[,NAME:C...]] [--cap-candidates N] [--cap-score logprob|logit] [--share NAME[+NAME...]:S]
         [--floor M|NAME:M[,NAME:M...] --floor-reserve R [--floor-candidates N] [--floor-score logprob|logit]]
         [--gate P [--gate-candidates N]] [--critic [TOP]] [--explore T [--explore-fixed F] [--explore-draw N]]
+        [--posterior BETA [--posterior-samples S] [--posterior-draw N]]
 
 restores a checkpoint written by train.py, runs test.py's forward over the users of `<split>_tr.csv` ONCE (chunks of 20 000 users,
 dropout on with keep_prob 0.75 by default: Q3, RNG counter 2*10^9 + first row of the chunk), keeps each user's top-K list on the GPU
@@ -73,6 +74,14 @@ ltg_pair_critic / ltg_critic_finish / ltg_topk_gate): the critic of a niche entr
 logit over the user's popular history items with features, an entry passes iff it has no critic or sigmoid(critic) >= P, and the first K
 passing candidates are the list.  N defaults to min(256, 2 K) and must lie in [K, 256], K = max(100, --k).  The table is then what the gate
 costs each group; the last line is `gate@K: <entries> scored candidates, <entries> rejected, <users> short lists (min_prob P)`.
+
+--posterior BETA (with any rule, or none) replaces every logit, before anything reads it, by mean + BETA * std over --posterior-samples S
+(default 16; one of 1, 4, 8, 16, 32) draws of z from the user's encoder posterior (serving.Posterior: ltg_posterior_h2, ltg_posterior_scores):
+BETA = 0 ranks by the posterior mean, BETA > 0 by an upper confidence bound (what the model is unsure about moves up), BETA < 0 by a lower one,
+S = 1 with BETA = 0 is one Thompson draw.  --posterior-draw N (default 0) numbers the draw.  After the report come one line per group,
+`posterior_std<TAB>name<TAB>entries<TAB>mean std of the served entries of that group`, and the line `posterior@K: beta <B>, samples <S>,
+draw <N>, mean entry std <std>, moved share <share of the served entries outside the plain top-K>`: the model's uncertainty about the
+tail, next to what the bound costs in NDCG@100 and moves in tail share (compare the report with a run without --posterior).
 
 --explore T (T > 0; not together with any rule above) SAMPLES every list before the report reads it (trainer.Explore: ltg_topk_sample,
 ltg_topk_sample_mass, ltg_topk_sample_finish): the first --explore-fixed F entries (default 0, F < K) are the plain top-F, the others are
@@ -150,6 +159,7 @@ def parse_min_slots(spec, names, k):
     return slots
 
 
+POSTERIOR_SAMPLES = (1, 4, 8, 16, 32)     # serving.POSTERIOR_SAMPLES (the parsers import no torch)
 RULE_OPTIONS = ("min_slots", "diversify", "calibrate", "cap", "share", "floor", "gate", "explore")     # at most one of them; a refusal names the later first
 
 
@@ -174,6 +184,9 @@ def add_rule_args(ap):
     ap.add_argument("--explore-fixed", type=int, default=None, metavar="F")
     ap.add_argument("--explore-draw", type=int, default=None, metavar="N")
     ap.add_argument("--critic", type=int, nargs="?", const=0, default=None, metavar="TOP")      # (0: the default, min(k, 256))
+    ap.add_argument("--posterior", type=float, default=None, metavar="BETA")
+    ap.add_argument("--posterior-samples", type=int, default=None, metavar="S")
+    ap.add_argument("--posterior-draw", type=int, default=None, metavar="N")
 
 
 def parse_item_values(opt, v, spec, names):
@@ -296,6 +309,20 @@ def check_rule_args(ap, a, k):
             ap.error("--explore-draw takes N >= 0")
     if a.critic is not None and a.critic != 0 and not 1 <= a.critic <= min(k, 256):
         ap.error("--critic takes TOP in [1, min(k, 256)] = [1, %d]" % min(k, 256))
+    if a.posterior is None:
+        if a.posterior_samples is not None or a.posterior_draw is not None:
+            ap.error("--posterior-samples and --posterior-draw need --posterior")
+    else:
+        with np.errstate(over="ignore"):
+            finite = np.isfinite(a.posterior) and np.isfinite(np.float32(a.posterior))
+        if not finite:
+            ap.error("--posterior takes a finite BETA")
+        if a.posterior_samples is not None and a.posterior_samples not in POSTERIOR_SAMPLES:
+            ap.error("--posterior-samples must be one of %s, got %d" % (", ".join(str(x) for x in POSTERIOR_SAMPLES), a.posterior_samples))
+        if (a.posterior_samples or 16) == 1 and a.posterior != 0.0:
+            ap.error("--posterior-samples 1 is one Thompson draw: it has no std, BETA must be 0")
+        if a.posterior_draw is not None and a.posterior_draw < 0:
+            ap.error("--posterior-draw takes N >= 0")
 
 
 def build_rules(args, dataset_dir, n_items, groups=None):
@@ -357,6 +384,35 @@ def build_critic(args, dataset_dir, n_items):
         return None
     from ltgan.serving import Critic
     return Critic(*critic_sides(dataset_dir, n_items), top=args.critic or None)
+
+
+def build_posterior(args):
+    """the Posterior of --posterior BETA, or None; it composes with every rule (it is not one)"""
+    if getattr(args, "posterior", None) is None:
+        return None
+    from ltgan.serving import Posterior
+    return Posterior(samples=args.posterior_samples or 16, beta=args.posterior, draw=args.posterior_draw or 0, entries=True, stats=True)
+
+
+def posterior_line(post, k):
+    """the line --posterior adds: the mean posterior std of the served entries and the share of them outside the plain top-k"""
+    st = post.stats()
+    return "posterior@%d: beta %.6g, samples %d, draw %d, mean entry std %.6f, moved share %.6f" % (
+        k, post.beta, post.samples, post.draw, st["mean_std"], st["moved_share"])
+
+
+def posterior_group_lines(post, ids, labels, names):
+    """one line per item group: the mean posterior std of the served entries of that group (host arithmetic on Posterior.table())"""
+    _, std = post.table()
+    ids, labels = np.asarray(ids), np.asarray(labels)
+    real = ids >= 0
+    lab = np.where(real, labels[np.where(real, ids, 0)], 255)
+    out = []
+    for g, name in enumerate(names):
+        sel = lab == g
+        n = int(sel.sum())
+        out.append("posterior_std\t%s\t%d\t%s" % (name, n, "%.6f" % float(std[sel].astype(np.float64).mean()) if n else "nan"))
+    return out
 
 
 def gate_line(stats, min_prob, k):
@@ -563,6 +619,9 @@ def longtail(args, h0_size, h1_size, h2_size, h3_size, LEARNING_RATE, precision=
     critic = build_critic(args, d, n_items)
     if critic is not None:
         rule = dict(rule, critic=critic)
+    post = build_posterior(args)
+    if post is not None:
+        rule = dict(rule, posterior=post)
     if world > 1:
         rec = ShardedRecommender(eng, EvalData(tr, te, eng.device, item_lo=lo, item_hi=hi), k=report.k, chunk=batch_size_test, report=report, **rule)
     else:
@@ -577,6 +636,11 @@ def longtail(args, h0_size, h1_size, h2_size, h3_size, LEARNING_RATE, precision=
     if critic is not None:
         rep["critic"] = dict(critic.summary(), top=critic.top)
         print(critic_line(rep["critic"], critic.top))
+    if post is not None:
+        rep["posterior"] = dict(post.stats(), beta=post.beta, samples=post.samples, draw=post.draw)
+        for line in posterior_group_lines(post, ids, labels, names):
+            print(line)
+        print(posterior_line(post, report.k))
     if args.json and rank == 0:
         write_json(rep, args.json)
     close_model(world)

@@ -10,6 +10,7 @@
         [--floor M|NAME:M[,NAME:M...] --floor-reserve R [--floor-candidates N] [--floor-score logprob|logit]]
         [--gate P [--gate-candidates N]] [--critic [TOP] [--critic-out critic.tsv]]
         [--explore T [--explore-fixed F] [--explore-draw N] [--propensities props.tsv]]
+        [--posterior BETA [--posterior-samples S] [--posterior-draw N] [--uncertainty unc.tsv]]
 
 restores a checkpoint written by train.py, runs test.py's forward over the users of `<split>_tr.csv` (chunks of 20 000 users,
 dropout on with keep_prob 0.75 by default: Q3, RNG counter 2*10^9 + first row of the chunk) and keeps each user's k best items, the
@@ -85,6 +86,13 @@ sharding, another N another sample.  The lists are written in draw order.  --pro
 `explore@k: T <T>, fixed <F>, draw <N>, mean list logp <mean log-propensity of a list>, explored share <share>`, explored share = the part
 of the sampled slots whose item is not in the plain top-k of the same user.
 
+--posterior BETA (with any rule, or none) ranks by the VAE's own uncertainty: every logit becomes mean + BETA * std over --posterior-samples S
+(default 16; one of 1, 4, 8, 16, 32) draws of z from the user's encoder posterior (serving.Posterior), before anything else reads it; BETA = 0
+the posterior mean, BETA > 0 an upper confidence bound, BETA < 0 a lower one, S = 1 with BETA = 0 one Thompson draw; --posterior-draw N
+(default 0) numbers the draw.  --uncertainty (default unc.tsv) gets one line per user, `uid<TAB>sid:mean:std,...` (%.6g) in list order;
+--npz also stores post_mean / post_std [users, k].  One more stdout line: `posterior@k: beta <B>, samples <S>, draw <N>, mean entry std
+<std>, moved share <share of the served entries outside the plain top-k>`.
+
 --critic [TOP] scores the first TOP entries (default min(k, 256)) of every list, whichever kind it is, the same way without changing it
 (trainer.Critic: one ltg_pair_critic per chunk).  --critic-out (default critic.tsv) gets one line per scored entry,
 `uid<TAB>sid<TAB>prob<TAB>anchor_sid:prob`: prob = sigmoid(critic), then the popular history item that speaks most for the entry with the
@@ -131,6 +139,7 @@ def parse_args(argv):
     ap.add_argument("--why", default=None)
     ap.add_argument("--critic-out", default=None)
     ap.add_argument("--propensities", default=None)
+    ap.add_argument("--uncertainty", default=None)
     a = ap.parse_args(argv)
     if not 1 <= a.k <= 1024:
         ap.error("--k must be in [1, 1024]")
@@ -158,6 +167,11 @@ def parse_args(argv):
             ap.error("--propensities needs --explore")
     else:
         a.propensities = a.propensities or "props.tsv"
+    if a.posterior is None:
+        if a.uncertainty is not None:
+            ap.error("--uncertainty needs --posterior")
+    else:
+        a.uncertainty = a.uncertainty or "unc.tsv"
     if a.critic is None:
         if a.critic_out is not None:
             ap.error("--critic-out needs --critic")
@@ -166,7 +180,7 @@ def parse_args(argv):
     return a
 
 
-def write_recs(ids, scores, uid_start, tsv_path=None, npz_path=None, why=None, critic=None, logp=None):
+def write_recs(ids, scores, uid_start, tsv_path=None, npz_path=None, why=None, critic=None, logp=None, posterior=None):
     """ids / scores [n_users, k] (padding id -1 dropped from the TSV); row r is uid uid_start + r; the ids are the CSV's sids.
     why: (why_ids, why_scores) of an Explain, critic: the table() of a Critic, logp: the table() of an Explore, stored in the npz as well."""
     ids = np.asarray(ids)
@@ -182,6 +196,8 @@ def write_recs(ids, scores, uid_start, tsv_path=None, npz_path=None, why=None, c
                          anchor_scores=np.asarray(critic["anchor_s"], np.float32), n_anchor=np.asarray(critic["n_anchor"], np.int32))
         if logp is not None:
             extra.update(logp=np.asarray(logp, np.float32))
+        if posterior is not None:                        # (mean, std) of a Posterior's table()
+            extra.update(post_mean=np.asarray(posterior[0], np.float32), post_std=np.asarray(posterior[1], np.float32))
         np.savez(npz_path, uids=uids, ids=ids.astype(np.int32), scores=np.asarray(scores, np.float32), **extra)
     return uids
 
@@ -215,6 +231,18 @@ def write_propensities(logp, ids, uid_start, tsv_path):
             keep = ids[u] >= 0
             f.write("%d\t%s\n" % (int(uid_start) + u, ",".join(
                 "%d:%.6g" % (int(i), float(x)) for i, x in zip(ids[u][keep].tolist(), logp[u][keep].tolist()))))
+    return int(ids.shape[0])
+
+
+def write_uncertainty(mean, std, ids, uid_start, tsv_path):
+    """mean / std [n_users, k] (Posterior.table()), ids [n_users, k] the lists they belong to: one line per user,
+    `uid<TAB>sid:mean:std,...` in list order, padding left out -> lines written"""
+    mean, std, ids = np.asarray(mean), np.asarray(std), np.asarray(ids)
+    with open(tsv_path, "w") as f:
+        for u in range(ids.shape[0]):
+            keep = ids[u] >= 0
+            f.write("%d\t%s\n" % (int(uid_start) + u, ",".join(
+                "%d:%.6g:%.6g" % (int(i), float(m), float(x)) for i, m, x in zip(ids[u][keep].tolist(), mean[u][keep].tolist(), std[u][keep].tolist()))))
     return int(ids.shape[0])
 
 
@@ -273,6 +301,9 @@ def recommend(args, h0_size, h1_size, h2_size, h3_size, LEARNING_RATE, precision
     critic = lt.build_critic(args, d, n_items)
     if critic is not None:
         rule = dict(rule, critic=critic)
+    post = lt.build_posterior(args)
+    if post is not None:
+        rule = dict(rule, posterior=post)
     if world > 1:
         rec = ShardedRecommender(eng, EvalData(tr, te, eng.device, item_lo=lo, item_hi=hi), k=args.k, chunk=batch_size_test, explain=why, **rule)
     else:
@@ -282,10 +313,13 @@ def recommend(args, h0_size, h1_size, h2_size, h3_size, LEARNING_RATE, precision
     why_tab = why.table() if why is not None else None
     critic_tab = critic.table() if critic is not None else None
     logp = rule["explore"].table() if "explore" in rule else None
+    post_tab = post.table() if post is not None else None
     if rank == 0:
-        write_recs(ids, scores, uid0, args.out, args.npz, why=why_tab, critic=critic_tab, logp=logp)
+        write_recs(ids, scores, uid0, args.out, args.npz, why=why_tab, critic=critic_tab, logp=logp, posterior=post_tab)
         if logp is not None:
             write_propensities(logp, ids, uid0, args.propensities)
+        if post is not None:
+            write_uncertainty(post_tab[0], post_tab[1], ids, uid0, args.uncertainty)
     print(summary_line(m, args.k))
     ils_first = "diversify" in rule                      # the ils line stands before the why line, every other rule's line after it
     for line in rule_lines if ils_first else []:
@@ -299,6 +333,8 @@ def recommend(args, h0_size, h1_size, h2_size, h3_size, LEARNING_RATE, precision
         if rank == 0:
             write_critic(critic_tab, ids, uid0, args.critic_out)
         print(lt.critic_line(critic.summary(), critic.top))
+    if post is not None:
+        print(lt.posterior_line(post, args.k))
     close_model(world)
     return ids, scores, m
 

@@ -1221,6 +1221,111 @@ def replay_estimates(rows, w, first_bad, log, temperatures, labels, n_groups, na
     return out
 
 
+POSTERIOR_IMAGE_BYTES = 256 << 20     # the bf16 image of one row block of a Posterior (rows x samples x ld x 2)
+POSTERIOR_SAMPLES = (1, 4, 8, 16, 32)
+
+
+class Posterior:
+    """Posterior-aware scores, passed as `posterior=` to a Recommender / ShardedRecommender.  It is not a Rule: it changes what the
+    logits ARE, and composes with every rule and attachment.  After the plain forward of a chunk, `samples` draws of z from every user's
+    encoder posterior N(mu, exp(logvar)) go through the decoder, and acts.logits becomes mean + beta * std over the draws, acts.lse its
+    row log-sum-exp: beta = 0 the posterior mean, beta > 0 UCB (what the model is unsure about ranks higher), beta < 0 LCB, samples = 1
+    one Thompson draw (beta must be 0).  The noise is the counter RNG at (engine seed, stream 9, draw, ((global user row) * samples + s)
+    * Z + j): the same `draw` gives the same scores whatever the chunk, the row block, the slab or the rank.  A chunk is walked in row
+    blocks whose bf16 image stays within POSTERIOR_IMAGE_BYTES; per block ltg_posterior_h2 and ltg_posterior_scores, then one
+    ltg_row_lse per chunk.  The [rows * samples, I] logits exist nowhere.  Over item shards mu | logvar are replicated, so every rank
+    builds the same image and scores its own slab: the scores are the unsharded run's bit for bit with no new exchange.
+    entries=True: after run(), table() holds the posterior mean and std of every served entry (ltg_posterior_entries on the chunk's
+    final lists; over shards one float all-reduce of the two tables).  stats=True: one extra plain top-k per chunk on the untouched
+    logits, for stats()."""
+
+    def __init__(self, samples=16, beta=1.0, draw=0, entries=True, stats=False):
+        self.samples, self.beta, self.draw = int(samples), float(beta), int(draw)
+        if self.samples != samples or self.samples not in POSTERIOR_SAMPLES:
+            raise ValueError("samples must be one of %s, got %r" % (POSTERIOR_SAMPLES, samples))
+        with np.errstate(over="ignore"):
+            finite = np.isfinite(self.beta) and np.isfinite(np.float32(self.beta))
+        if not finite:
+            raise ValueError("beta must be a finite float32, got %r" % (beta,))
+        if self.samples == 1 and self.beta != 0.0:
+            raise ValueError("samples = 1 is one Thompson draw: it has no std, beta must be 0, got %r" % (beta,))
+        if self.draw != draw or not 0 <= self.draw < 2 ** 64:
+            raise ValueError("draw is an integer >= 0, got %r" % (draw,))
+        self.want_stats = bool(stats)
+        self.want_entries = bool(entries) or self.want_stats
+        self.k = self.block = self.image = self.mulv = self.mean = self.std = self.plain_i = self.outside = self.real = None
+
+    def bind(self, engine, rows, k, n_users):
+        S = self.samples
+        per_row = S * engine.posterior_ld() * 2
+        self.block = int(max(1, min(rows, POSTERIOR_IMAGE_BYTES // per_row)))
+        self.image = engine.posterior_image(self.block, S)
+        self.k = int(k)
+        dev = engine.device
+        if self.want_entries and self.k > 0:
+            if self.k > 1024:
+                raise ValueError("k must be in [1, 1024] for the entry tables, got %d" % k)
+            self.mulv = torch.zeros(n_users, 2 * engine.Z, dtype=torch.float32, device=dev)      # (a whole-split rule reads its lists after the walk)
+            self.table_ms = torch.zeros(2, n_users, self.k, dtype=torch.float32, device=dev)
+            self.mean, self.std = self.table_ms[0], self.table_ms[1]
+            self.ms = torch.empty(2 * rows * self.k, dtype=torch.float32, device=dev)
+        if self.want_stats and self.k > 0:
+            self.plain_s = torch.empty(rows * self.k, dtype=torch.float32, device=dev)
+            self.plain_i = torch.full((n_users, self.k), -1, dtype=torch.int32, device=dev)
+            self.outside = torch.zeros(n_users, dtype=torch.int32, device=dev)
+            self.real = torch.zeros(n_users, dtype=torch.int32, device=dev)
+
+    def rescore(self, engine, acts, n, lo, lists=None, tr=None):
+        """acts.logits [n, I] <- the posterior scores of users lo .. lo + n (this slab's columns), acts.lse <- their row lse"""
+        S = self.samples
+        if self.plain_i is not None and lists is not None:       # the plain lists, from the untouched logits
+            lists.topk(acts, tr, n, self.k, self.plain_s[: n * self.k].view(n, self.k), self.plain_i[lo:lo + n])
+        if self.mulv is not None:
+            self.mulv[lo:lo + n].copy_(acts.mulv[:n])
+        for b0 in range(0, n, self.block):
+            nb = min(self.block, n - b0)
+            engine.posterior_h2(acts.mulv[b0:], nb, lo + b0, S, self.draw, self.image)
+            engine.posterior_scores(self.image, nb, S, self.beta, acts.logits[b0:])
+        engine.row_lse(acts.logits, n, acts.lse)
+
+    def entries(self, lists, lo, hi, ids):
+        """the tables' rows lo .. hi <- the posterior mean and std of the final lists ids [hi - lo, k]"""
+        if self.mean is None:
+            return
+        eng, S, k, n = lists.eng, self.samples, self.k, hi - lo
+        ms = self.ms[: 2 * n * k].view(2, n, k)
+        for b0 in range(0, n, self.block):
+            nb = min(self.block, n - b0)
+            eng.posterior_h2(self.mulv[lo + b0:], nb, lo + b0, S, self.draw, self.image)
+            eng.posterior_entries(self.image, S, ids[b0:b0 + nb], ms[0, b0:b0 + nb], ms[1, b0:b0 + nb])
+        if lists.parts > 1:                              # an entry's slab holds its values, every other slab 0.0
+            dist.all_reduce(ms, op=dist.ReduceOp.SUM, group=lists.group)
+        self.mean[lo:hi].copy_(ms[0])
+        self.std[lo:hi].copy_(ms[1])
+        if self.plain_i is not None:
+            for b0 in range(0, n, 1024):                 # ([rows, k, k] comparisons, a block of rows at a time)
+                a, p = ids[b0:b0 + 1024], self.plain_i[lo + b0:lo + min(n, b0 + 1024)]
+                real = a >= 0
+                inside = (a.unsqueeze(2) == p.unsqueeze(1)).any(2)
+                self.outside[lo + b0:lo + b0 + a.shape[0]].copy_((real & ~inside).sum(1))
+                self.real[lo + b0:lo + b0 + a.shape[0]].copy_(real.sum(1))
+
+    def table(self):
+        """-> (mean, std): [n_users, k] float32 host arrays, the posterior mean and std of every served entry (0.0 for padding)"""
+        if self.mean is None:
+            raise ValueError("this Posterior keeps no entry tables (entries=False, or k = 0)")
+        return self.mean.cpu().numpy(), self.std.cpu().numpy()
+
+    def stats(self):
+        """-> dict: mean_std (the mean posterior std of the served entries), moved_share (the share of the served entries that are not
+        in the same user's plain top-k), entries (the served entries)"""
+        if self.plain_i is None:
+            raise ValueError("stats() needs Posterior(stats=True) and k >= 1")
+        n_e = int(self.real.sum())
+        return dict(mean_std=float(self.std.sum(dtype=torch.float64)) / n_e if n_e else float("nan"),
+                    moved_share=int(self.outside.sum()) / n_e if n_e else float("nan"), entries=n_e)
+
+
 class Audience:
     """The item audiences a Recommender / ShardedRecommender gathers when it is passed as `audience=`: for every query item (GLOBAL ids,
     any order, repeats allowed) the k users of the split with the largest score -- `logprob`: logit - lse, the log-probability the user's
@@ -1311,12 +1416,13 @@ class Recommender:
     matches after the last chunk, and a second pass over the chunks (no forward) feeds the report and the explanations.  k = 0 walks the
     chunks for the audience alone: run() returns [n_users, 0] arrays, no list kernel is launched, and nothing that needs lists goes
     with it.  replay= (a Replay, replay.estimates() after run()) re-weights a logged exploration run under other policies from the
-    chunk's logits; like the audience it changes no list and works with k = 0."""
+    chunk's logits; like the audience it changes no list and works with k = 0.  posterior= (a Posterior) replaces the chunk's logits and
+    their lse by posterior scores right after the forward, before anything above reads them; posterior.table() / .stats() after run()."""
 
     sharded = False                                  # ShardedRecommender: one rank of `group` per item slab
 
     def __init__(self, engine, ev, k=100, chunk=20000, report=None, rule=None, diversify=None, group=None, audience=None, explain=None,
-                 calibrate=None, cap=None, share=None, floor=None, gate=None, critic=None, explore=None, replay=None):
+                 calibrate=None, cap=None, share=None, floor=None, gate=None, critic=None, explore=None, replay=None, posterior=None):
         rules = dict(rule=rule, diversify=diversify, calibrate=calibrate, cap=cap, share=share, floor=floor, gate=gate, explore=explore)
         given = [name for name, r in rules.items() if r is not None]
         if len(given) > 1:
@@ -1325,7 +1431,7 @@ class Recommender:
         if int(k) == 0 and (self.policy is not None or report is not None or explain is not None or critic is not None):
             raise ValueError("k = 0 serves no user lists: report=, explain= and every rule need k >= 1")
         self.rule, self.diversify, self.calibrate, self.cap, self.share, self.floor = rule, diversify, calibrate, cap, share, floor
-        self.gate, self.critic, self.explore, self.replay = gate, critic, explore, replay
+        self.gate, self.critic, self.explore, self.replay, self.posterior = gate, critic, explore, replay, posterior
         self.eng, self.ev, self.k, self.report, self.group, self.audience, self.explain = engine, ev, int(k), report, group, audience, explain
         if report is not None:
             report.bind(engine, ev.n, self.k)
@@ -1346,17 +1452,23 @@ class Recommender:
         self.lists = SlabLists(engine, self.chunk, longest, group, dist.get_world_size(group) if self.sharded else 1)
         if audience is not None:
             audience.bind(engine, self.chunk, ev.n, group=group, sharded=self.sharded)
+        if posterior is not None:
+            posterior.bind(engine, self.chunk, self.k, ev.n)
         self.acts = engine.new_acts(self.chunk)
         dev = engine.device
         self.scores = torch.empty(ev.n, self.k, dtype=torch.float32, device=dev)
         self.ids = torch.empty(ev.n, self.k, dtype=torch.int32, device=dev)
 
-    def _forward(self, tr, n, keep_prob, rng_step):
-        """the logits of the n rows `tr` into self.acts"""
+    def _forward(self, tr, n, keep_prob, rng_step, lo=0):
+        """the logits of the n rows `tr` (users lo .. lo + n) into self.acts; with posterior= the posterior scores in their place"""
         self.eng.forward(tr, self.acts, keep_prob=keep_prob, is_training=0.0, rng_step=rng_step)
+        if self.posterior is not None:
+            self.posterior.rescore(self.eng, self.acts, n, lo, lists=self.lists, tr=tr)
 
     def _read(self, tr, te, lo, hi):
         """the report, the explanations and the critic of users lo .. hi, from their final lists"""
+        if self.posterior is not None:
+            self.posterior.entries(self.lists, lo, hi, self.ids[lo:hi])
         if self.report is not None:
             self.report.add(self.eng, self.ids[lo:hi], te, lo)
         if self.explain is not None:
@@ -1382,7 +1494,7 @@ class Recommender:
         for lo, hi in chunks:
             n = hi - lo
             tr, te = ev.rows(lo, hi)
-            self._forward(tr, n, keep_prob, rng_step + lo)
+            self._forward(tr, n, keep_prob, rng_step + lo, lo)
             if self.audience is not None:
                 self.audience.add(eng, self.acts, tr, n, lo)
             if self.replay is not None:
@@ -1399,7 +1511,7 @@ class Recommender:
             self._read(tr, te, lo, hi)
         if policy is not None and policy.whole:          # its lists exist only now
             policy.match(eng, k, self.scores, self.ids)
-            if self.report is not None or self.explain is not None or self.critic is not None:      # a second pass over the chunks, without a forward
+            if self.report is not None or self.explain is not None or self.critic is not None or self.posterior is not None:      # a second pass over the chunks, without a forward
                 for lo, hi in chunks:
                     self._read(*ev.rows(lo, hi), lo, hi)
         return self.ids.cpu().numpy(), self.scores.cpu().numpy()
@@ -1419,13 +1531,24 @@ class ShardedRecommender(Recommender):
         super().__init__(engine, ev, k=k, group=group, **kw)
         self.rowpart = torch.zeros(self.chunk * 5, dtype=torch.float32, device=engine.device)
         self.rowpart_all = None
-        if any(x is not None and x.needs_lse for x in (self.audience, self.policy)):
+        if any(x is not None and x.needs_lse for x in (self.audience, self.policy)):      # (replay reads no lse)
             self.rowpart_all = torch.zeros(dist.get_world_size(group) * self.chunk * 5, dtype=torch.float32, device=engine.device)
 
-    def _forward(self, tr, n, keep_prob, rng_step):
+    def _forward(self, tr, n, keep_prob, rng_step, lo=0):
         """the slab's logits; with an audience or a policy that needs it (needs_lse) also the FULL-row lse in acts.lse: the slabs' row partials
-        are all-gathered and combined (ltg_rowstats_combine, as ShardedTrainer.create_phase does) -- one more small collective per chunk"""
+        are all-gathered and combined (ltg_rowstats_combine, as ShardedTrainer.create_phase does) -- one more small collective per chunk.
+        With posterior= the slab's posterior scores take the logits' place (mu | logvar are replicated after the h1 all-reduce: nothing new is
+        exchanged), and the full-row lse, where it is needed, is combined from one all-gather of the per-slab lse of the scores"""
         sharded_forward(self.eng, tr, n, self.acts, self.rowpart, keep_prob, rng_step, self.group)
+        if self.posterior is not None:
+            self.posterior.rescore(self.eng, self.acts, n, lo, lists=self.lists, tr=tr)
+            if self.rowpart_all is not None:
+                R = dist.get_world_size(self.group)
+                out = self.rowpart_all[: R * n].view(R, n)
+                dist.all_gather(list(out.unbind(0)), self.acts.lse[:n].contiguous(), group=self.group)
+                m = out.max(0).values
+                self.acts.lse[:n].copy_(m + torch.log(torch.exp(out - m).sum(0)))
+            return
         if self.rowpart_all is not None:
             R, m = dist.get_world_size(self.group), n * 5
             out = self.rowpart_all[: R * m]

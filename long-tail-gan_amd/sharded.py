@@ -30,7 +30,7 @@ import torch
 import torch.distributed as dist
 
 from .engine import Pipe, _ptr
-from .serving import Calibrate, Critic, CriticGate, Explain, Explore, ExposureCap, ExposureFloor, Replay, ReplayLog, ShareTarget, ShardedEvaluator, ShardedItemNeighbors, ShardedPairCompanions, ShardedRecommender  # noqa: F401
+from .serving import Calibrate, Critic, CriticGate, Explain, Explore, ExposureCap, ExposureFloor, Replay, ReplayLog, Posterior, ShareTarget, ShardedEvaluator, ShardedItemNeighbors, ShardedPairCompanions, ShardedRecommender  # noqa: F401
 from .trainer import Trainer
 
 D_SPLIT_MIN_PARAMS = 1_000_000

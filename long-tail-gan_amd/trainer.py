@@ -18,7 +18,7 @@ import torch
 
 from .dataset import DeviceData
 from .engine import Engine, Pipe
-from .serving import EVAL_LOGITS_BYTES, Audience, Calibrate, Critic, CriticGate, Diversify, Evaluator, Explain, Explore, ExposureCap, ExposureFloor, ItemNeighbors, LongTailReport, MinSlots, PairCompanions, Recommender, Replay, ReplayLog, ShareTarget, eval_chunk_rows, group_mask_of, neighbors_ws_bytes  # noqa: F401
+from .serving import EVAL_LOGITS_BYTES, Audience, Calibrate, Critic, CriticGate, Diversify, Evaluator, Explain, Explore, ExposureCap, ExposureFloor, ItemNeighbors, LongTailReport, MinSlots, PairCompanions, Posterior, Recommender, Replay, ReplayLog, ShareTarget, eval_chunk_rows, group_mask_of, neighbors_ws_bytes  # noqa: F401
 
 
 CREATE_LOGITS_BYTES = 1 << 30      # logits of one phase-C span (rows x I x 4)
